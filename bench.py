@@ -37,6 +37,10 @@ The reference-equivalent operand stream (6138 B/hypothesis as the reference re-r
 kept as information only.  `cpu_baseline` times the reference's own C (oracle/_ref, built in place from the reference
 tree) -- or the CPU oracle port when that build is absent -- on a bounded sample.  `tracking` is BASELINE.json's second
 metric, 1000 steps per channel count (N = 1 only).
+
+A plain run times the headline alone: set-up, --warmup steps, --steps timed steps, the line.  `--full` adds everything else --
+the CPU baseline, the secondary legs above and, at N > 1, the parity sample and the configs[3] legs.  `--dump-outputs DIR`
+writes what the last timed step computed to DIR/*.npy (dump_outputs).
 """
 import argparse
 import json
@@ -501,6 +505,27 @@ def _sign_plane(blocks_2bit):
     return np.packbits(bits[..., 0::2], axis=-1, bitorder="little")
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, keys, peaks):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the (search, PRN, Doppler) table of packed
+    peak keys and the (search, PRN, Doppler, bit shift) peak records, one file per field -- as float64 (every value is an
+    integer below 2^53: exact).  Searches beyond the 64 MB budget are left out; those kept are a fixed, seeded sample, listed
+    in search_index.npy.  At N > 1 the keys are the merged table and the peak records rank 0's own shard of them."""
+    records = np.ascontiguousarray(peaks).view(np.uint32)              # [search, PRN, Doppler, shift, (max_val, phase, sum, avr)]
+    n_search = keys.shape[0]
+    per_search = (keys[0].size + records[0].size + 1) * 8
+    keep = min(n_search, (DUMP_LIMIT_BYTES - 6 * 256) // per_search)     # (6 files' .npy headers)
+    index = np.arange(n_search) if keep == n_search else np.sort(np.random.default_rng(0).choice(n_search, keep, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    out = {"keys": keys[index], "search_index": index}
+    for i, field in enumerate(("max_val", "phase", "sum", "avr")):
+        out["peak_" + field] = records[index, ..., i]
+    for name, arr in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def _parity_sample(keys, sign_blocks_of, n_search, n_ms):
     """Rank 0, outside the timed region: cells of the MERGED key table (what the all-reduce left) against the CPU oracle --
     two searches, one from each end of the table (in weak scaling: other ranks' units too), PRNs 3 / 11 / 20 / 30 (one per 8-PRN
@@ -812,6 +837,15 @@ def main():
                          "ten-block searches whatever N: their (search, Doppler, 8-PRN group) units dealt to the N ranks")
     ap.add_argument("--no-parity-check", action="store_true",
                     help="N > 1: skip rank 0's check of the merged key table against the CPU oracle (outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (off by default: a plain run sets up, warms up, times --steps "
+                         "steps and prints the line): at N = 1 the native-grid, ten-block, letter-compliant, weighted two-bit, "
+                         "tracking and pcie_inclusive legs and the CPU baseline; at N > 1 rank 0's oracle parity sample, "
+                         "single_search, configs3_sharded and per_gpu_unsharded.  The --no-* options above apply inside it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- the packed peak keys and the four "
+                         "fields of the peak records -- to DIR/<name>.npy as float64, at most 64 MB in all (a fixed, seeded "
+                         "sample of the searches beyond that; DIR/search_index.npy says which)")
     args = ap.parse_args()
     if args.n_ms is None:
         args.n_ms = 1          # the SAME workload at every N (per-GPU work fixed as N grows: weak scaling from N = 1 on)
@@ -874,7 +908,7 @@ def main():
     n_ms = args.n_ms
     two_bit = args.if_format == "2bit"
     # the sign plane as 2046-byte blocks: the device input in 1-bit mode, and what the CPU leg (rank 0, N = 1) is timed on
-    need_sign_plane = not two_bit or (world == 1 and not args.no_cpu_baseline)
+    need_sign_plane = not two_bit or (world == 1 and args.full and not args.no_cpu_baseline)
     blocks = synth.cold_start_block(n_search * n_ms if not two_bit else 1, seed=11, amp_scale=args.amp_scale) \
         if need_sign_plane else None
     if two_bit:
@@ -942,32 +976,38 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed_s = float(elapsed.item())
 
-    # the secondary legs (N = 1 only; each in a function of its own, each catching its own failure: a secondary leg must
-    # not take the headline line with it)
+    # what the last timed step left in HBM (the merged table at N > 1), read back before a secondary leg reuses the buffers
+    d_keys = key_bufs[(step_no[0] - 1) & 1]
+    keys = d_keys.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, keys, d_peaks.cpu().numpy())
+
+    # the secondary legs (--full, N = 1 only; each in a function of its own, each catching its own failure: a secondary leg
+    # must not take the headline line with it)
     import types
     B = types.SimpleNamespace(args=args, eng=eng, capi=capi, synth=synth, torch=torch, C=C, stream=stream, dev=dev, dev_index=dev_index,
                               prns=prns, n_search=n_search, n_ms=n_ms, two_bit=two_bit, dev_blocks=dev_blocks, d_if=d_if, d_peaks=d_peaks,
                               key_bufs=key_bufs, g=g)
     native = None
-    if world == 1 and n_ms == 1 and not args.no_native:
+    if args.full and world == 1 and n_ms == 1 and not args.no_native:
         native = leg_native_grid(B)
 
     ten_block = None
-    if world == 1 and n_ms == 1 and not args.no_native:
+    if args.full and world == 1 and n_ms == 1 and not args.no_native:
         ten_block = leg_ten_block(B)
 
     letter = None
-    if world == 1 and n_ms == 1 and not args.no_native:
+    if args.full and world == 1 and n_ms == 1 and not args.no_native:
         letter = leg_letter_compliant(B)
 
     weighted = None
-    if world == 1 and n_ms == 1 and not args.no_native:
+    if args.full and world == 1 and n_ms == 1 and not args.no_native:
         weighted = leg_weighted_extension(B)
 
     # the secondary metric first: the legs below leave ~100 MB of page-locked host memory and four contexts' worth of
     # state behind, and the tracking step measured after them is 60 us slower
     tracking = None
-    if not args.no_tracking and world == 1:
+    if args.full and not args.no_tracking and world == 1:
         try:
             tracking = tracking_channels(capi.Engine, dev_index)
         except Exception as exc:   # a secondary leg must not take the headline line with it
@@ -975,17 +1015,15 @@ def main():
             print(f"bench.py: tracking leg failed: {exc!r}", file=sys.stderr, flush=True)
 
     pcie = pcie_serial = None
-    if world == 1 and n_ms == 1 and not args.no_pcie:
+    if args.full and world == 1 and n_ms == 1 and not args.no_pcie:
         pcie, pcie_serial = leg_pcie_inclusive(B)
 
     # sanity outside the timed region: the merged key table must hold the six synthetic satellites' peaks
-    d_keys = key_bufs[(step_no[0] - 1) & 1]
-    keys = d_keys.cpu().numpy()
     energy = keys >> 14
     assert (energy > 0).all() and energy.max() > 1500 * min(1.0, args.amp_scale), "acquisition grid produced no peaks"
 
     parity = None
-    if use_dist and rank == 0 and not args.no_parity_check:
+    if args.full and use_dist and rank == 0 and not args.no_parity_check:
         def sign_blocks_of(s_):
             blk = dev_blocks.reshape(n_search * n_ms, -1)[s_ * n_ms:(s_ + 1) * n_ms]
             return _sign_plane(blk) if two_bit else blk
@@ -1012,7 +1050,7 @@ def main():
     # N ranks, one all-reduce(MAX) of 672 keys; latency per search (outside the headline's timed region)
     single = None
     one_ms = n_ms if n_ms > 1 else 10          # (the headline's own block count, or configs[3]'s ten when the headline is one block)
-    if use_dist and n_search * n_ms >= one_ms:
+    if args.full and use_dist and n_search * n_ms >= one_ms:
         g_one = eng.grid_desc(prns, n_search=1, n_ms=one_ms, search_stride_blocks=one_ms, dopp_min_hz=DOPP_MIN,
                               dopp_step_hz=DOPP_STEP, n_dopp=N_DOPP, phase_mode=capi.PHASES_FINE, win=(0, 2046),
                               shard=(rank, world))
@@ -1042,7 +1080,7 @@ def main():
     # slowest rank): `searches` ten-block searches PER GPU (search s integrates blocks s .. s + 9 of the resident captures,
     # cyclically extended: the N = 1 line's `configs3_one_gpu` is this leg's N = 1 point)
     ten_sharded = None
-    if use_dist and n_ms == 1 and n_search >= 10 and not args.no_native:
+    if args.full and use_dist and n_ms == 1 and n_search >= 10 and not args.no_native:
         try:
             per_block = dev_blocks.reshape(n_search, -1)
             g10 = eng.grid_desc(prns, n_search=n_search, n_ms=10, search_stride_blocks=1, dopp_min_hz=DOPP_MIN,
@@ -1086,7 +1124,7 @@ def main():
     # collective -- so that the sharded, all-reduced job can be compared with N x a single GPU at the SAME configuration
     # (the N = 1 default of this script is configs[2], n_ms = 1: not the series to divide by)
     local_ref = None
-    if use_dist:
+    if args.full and use_dist:
         g_loc = eng.grid_desc(prns, n_search=args.searches, n_ms=n_ms, search_stride_blocks=n_ms, dopp_min_hz=DOPP_MIN,
                               dopp_step_hz=DOPP_STEP, n_dopp=N_DOPP, phase_mode=capi.PHASES_FINE, win=(0, 2046))
         reps_l = max(2, min(args.steps, 10))
@@ -1237,7 +1275,7 @@ def main():
             line["weighted_2bit_extension"] = weighted
         if tracking is not None:
             line["tracking"] = tracking
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 line.update(cpu_baseline(blocks, args.cpu_budget_s))
             except Exception as exc:   # (the reported baseline: its failure is reported, the line still goes out)

@@ -47,7 +47,7 @@ def test_two_ranks_sharded_sweep_equals_unsharded(n_ms, searches, port, ms_mode,
         env["GPSX_USE_LAB_LIBRARY"] = "1"       # forced kernel forms: the lab build of the library reads those knobs
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port(port)), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--searches", str(searches), "--no-cpu-baseline", "--n-ms", str(n_ms)]
+           "--warmup", "1", "--searches", str(searches), "--no-cpu-baseline", "--n-ms", str(n_ms), "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "VERIFY sharded == unsharded" in res.stdout
@@ -87,7 +87,7 @@ def test_plain_python_launch_two_ranks(scaling, port, tmp_path, oracle):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--searches", "6",
-           "--scaling", scaling, "--no-cpu-baseline", "--n-ms", "10"]
+           "--scaling", scaling, "--no-cpu-baseline", "--n-ms", "10", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "VERIFY sharded == unsharded" in res.stdout
@@ -128,7 +128,7 @@ def test_eight_ranks_on_one_device(tmp_path, oracle):
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--searches", str(searches),
-               "--scaling", scaling, "--no-cpu-baseline", "--n-ms", "10"]
+               "--scaling", scaling, "--no-cpu-baseline", "--n-ms", "10", "--full"]
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert res.returncode == 0, res.stderr[-2000:]
         assert "VERIFY sharded == unsharded" in res.stdout
@@ -155,7 +155,7 @@ def test_single_gpu_line_is_compact_strict_and_carries_every_leg(tmp_path):
     from stm32f4_sdr_gps_amd import benchline
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--searches", "16",
-                          "--no-tracking", "--cpu-budget-s", "2"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-tracking", "--cpu-budget-s", "2", "--full"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     last = [l for l in res.stdout.splitlines() if l.strip()][-1]
     line = benchline.check(last)                       # size, strict JSON, contract keys, roofline keys
@@ -176,6 +176,35 @@ def test_single_gpu_line_is_compact_strict_and_carries_every_leg(tmp_path):
     assert detail["configs3_one_gpu"]["roofline"]["algorithmic_bytes"] > 0 and detail["pcie_inclusive"]["serial"] > 1e9
 
 
+def test_plain_single_gpu_run_times_the_headline_only_and_dumps_its_outputs(tmp_path, oracle):
+    """`python bench.py` without --full: the headline alone (no secondary leg in the line), and --dump-outputs leaves what the
+    last timed step computed -- the packed keys and the four peak fields of every search, float64 -- equal to the CPU oracle."""
+    import numpy as np
+    from stm32f4_sdr_gps_amd import benchline, synth
+    out = tmp_path / "outputs"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--searches", "4",
+                          "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = benchline.check([l for l in res.stdout.splitlines() if l.strip()][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 1e9
+    for leg in ("native_grid", "configs3_one_gpu", "letter_compliant", "weighted_2bit_extension", "tracking", "cpu_baseline",
+                "value_pcie_inclusive"):
+        assert leg not in line, leg
+    got = {n: np.load(out / f"{n}.npy") for n in ("keys", "search_index", "peak_max_val", "peak_phase", "peak_sum", "peak_avr")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["keys"].shape == (4, 32, 21) and got["peak_max_val"].shape == (4, 32, 21, 8)
+    assert np.array_equal(got["search_index"], np.arange(4))
+    sign = np.unpackbits(synth.cold_start_block(4, seed=11, amp_scale=0.25, two_bit=True), axis=-1, bitorder="little")
+    blocks = np.packbits(sign[..., 0::2], axis=-1, bitorder="little")           # bench.py's 2-bit captures, sign plane
+    prns = np.array([2, 19, 31], np.uint8)
+    want = oracle.acq_grid(blocks[3:4], 1, prns, -5000, 500, 21, 8, n_threads=max(4, min(32, len(os.sched_getaffinity(0)))), live=True)
+    for f in ("max_val", "phase", "sum", "avr"):
+        assert np.array_equal(got["peak_" + f][3][prns.astype(int) - 1], want[f].astype(np.float64)), f
+    fine = 8 * want["phase"].astype(np.int64) + np.arange(8)[None, None, :]
+    assert np.array_equal(got["keys"][3][prns.astype(int) - 1], ((want["max_val"].astype(np.int64) << 14) | (16383 - fine)).max(axis=2))
+
+
 def test_default_multi_gpu_run_is_the_single_gpu_workload_sharded(tmp_path, oracle):
     """`bench.py --gpus 2` with no --n-ms, as the driver launches it: the SAME workload as N = 1 (BASELINE.json configs[2], one block
     per search, `searches` captures PER GPU: per-GPU work fixed as N grows), its units sharded, one all-reduce(MAX) of the keys per
@@ -188,7 +217,7 @@ def test_default_multi_gpu_run_is_the_single_gpu_workload_sharded(tmp_path, orac
     env = dict(os.environ, GPSX_BENCH_SHARE_DEVICE="1", GPSX_BENCH_BACKEND="gloo", GPSX_BENCH_VERIFY="1", GPSX_BENCH_DUMP_KEYS=dump)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--searches", "12", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--searches", "12", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "VERIFY sharded == unsharded" in res.stdout
@@ -219,7 +248,7 @@ def test_eight_ranks_default_workload(tmp_path):
     env = dict(os.environ, GPSX_BENCH_SHARE_DEVICE="1", GPSX_BENCH_BACKEND="gloo", GPSX_BENCH_VERIFY="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--searches", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--searches", "2", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "VERIFY sharded == unsharded" in res.stdout

@@ -14,14 +14,15 @@ fi
 T=${1:-r04}
 set -x
 mkdir -p gpurun_out
+OUT=$_        # the results directory made on the line above
 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|rror|assert" | head -20 > gpurun_out/${T}_gputests.log
 cat gpurun_out/${T}_gputests.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err
+python bench.py --full > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err"
 tail -c 300 gpurun_out/${T}_bench.err
-python bench.py --searches 64 --no-cpu-baseline --no-tracking > gpurun_out/${T}_bench_64.json 2>> gpurun_out/${T}_bench.err
+python bench.py --full --searches 64 --no-cpu-baseline --no-tracking > "$OUT/${T}_bench_64.json" 2>> "$OUT/${T}_bench.err"
 python bench.py --n-ms 10 --no-cpu-baseline --no-tracking --steps 5 > gpurun_out/${T}_bench_10ms.json 2>> gpurun_out/${T}_bench.err
-python bench.py --amp-scale 1.0 --no-cpu-baseline --no-tracking --steps 10 > gpurun_out/${T}_bench_strong.json 2>> gpurun_out/${T}_bench.err
+python bench.py --full --amp-scale 1.0 --no-cpu-baseline --no-tracking --steps 10 > "$OUT/${T}_bench_strong.json" 2>> "$OUT/${T}_bench.err"
 bash tools/profile_bench.sh ${T} > gpurun_out/${T}_prof.log 2>&1
 BENCH_ARGS="--n-ms 10" bash tools/profile_bench.sh ${T}_10ms > gpurun_out/${T}_prof10.log 2>&1
 bash tools/profile_track.sh ${T}_track > gpurun_out/${T}_proft.log 2>&1

@@ -7,6 +7,7 @@
 set -x
 T=${1:-r06}
 mkdir -p gpurun_out
+OUT=$_        # the results directory made on the line above
 bash tools/profile_bench.sh ${T} > gpurun_out/${T}_prof.log 2>&1
 BENCH_ARGS="--n-ms 10" TRACE_ARGS="--steps 10 --warmup 2" bash tools/profile_bench.sh ${T}_10ms > gpurun_out/${T}_prof10.log 2>&1
 BENCH_ARGS="--acq-path vector" TRACE_ARGS="--steps 10 --warmup 2" bash tools/profile_bench.sh ${T}_poly > gpurun_out/${T}_profpoly.log 2>&1
@@ -15,7 +16,7 @@ python tools/summarize_profile.py $T 256 1 > /dev/null
 python tools/summarize_profile.py ${T}_10ms 256 10 > /dev/null
 python tools/summarize_profile.py ${T}_poly 256 1 k_acq_poly > /dev/null
 python tools/valu_class_rates.py gpurun_out/${T}_valu_rates_microbench.txt $T > /dev/null
-python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err; echo "bench rc=$?"
+python bench.py --full > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err"; echo "bench rc=$?"
 tail -c 400 gpurun_out/${T}_bench.err
 cp bench_detail.json gpurun_out/${T}_bench_detail.json
 head -c 4200 gpurun_out/${T}_bench.json
