@@ -32,8 +32,7 @@ int ensure_grid_tables(gpsx_ctx *ctx, const uint8_t *prns, int n_prn)
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // free + null first: a failed hipMalloc below must not leave dangling members for the next call / gpsx_destroy
     void **members[] = {(void **)&ctx->d_grid_prns, (void **)&ctx->d_grid_chips, (void **)&ctx->d_grid_bits,
-                        (void **)&ctx->d_grid_cw, (void **)&ctx->d_grid_cw8, (void **)&ctx->d_grid_mx_a,
-                        (void **)&ctx->d_grid_mx_t};
+                        (void **)&ctx->d_grid_cw8, (void **)&ctx->d_grid_mx_a, (void **)&ctx->d_grid_mx_t};
     for (void **m : members) {
       if (*m)
         (void)hipFree(*m);
@@ -44,7 +43,6 @@ int ensure_grid_tables(gpsx_ctx *ctx, const uint8_t *prns, int n_prn)
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_grid_prns, slots));
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_grid_chips, (size_t)slots * 1024));
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_grid_bits, (size_t)slots * 32 * 4));
-    HIPCHK(ctx, hipMalloc((void **)&ctx->d_grid_cw, (size_t)slots * kCodeWords * 4));
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_grid_cw8, (size_t)slots * (kCodeWords / 2) * 4));
     const size_t sets = (size_t)(slots + 31) / 32;
     HIPCHK(ctx, hipMalloc((void **)&ctx->d_grid_mx_a, sets * 4096 * 4));
@@ -55,8 +53,7 @@ int ensure_grid_tables(gpsx_ctx *ctx, const uint8_t *prns, int n_prn)
   std::copy(prns, prns + n_prn, padded.begin());
   HIPCHK(ctx, hipMemcpyAsync(ctx->d_grid_prns, padded.data(), slots, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // `padded` goes out of scope
-  launch_build_codes(ctx->stream, ctx->d_grid_prns, slots, kAcqGroup, ctx->d_grid_chips, ctx->d_grid_bits,
-                     ctx->d_grid_cw, ctx->d_grid_cw8);
+  launch_build_codes(ctx->stream, ctx->d_grid_prns, slots, kAcqGroup, ctx->d_grid_chips, ctx->d_grid_bits, ctx->d_grid_cw8);
   LAUNCHCHK(ctx, "k_build_codes");
   launch_build_mx_tables(ctx->stream, ctx->d_grid_bits, slots, ctx->d_grid_mx_a, ctx->d_grid_mx_t);
   LAUNCHCHK(ctx, "k_build_mx_tables");
@@ -170,8 +167,7 @@ int gpsx_create(gpsx_ctx **out, int device, void *stream)
   if (const char *m = std::getenv("GPSX_ACQ_MS_MODE"))
     ctx->ms_mode = std::strcmp(m, "walk") == 0 ? 1 : (std::strcmp(m, "blocks") == 0 ? 2 : 0);
   if (const char *a = std::getenv("GPSX_ACQ_ALGO")) {
-    ctx->algo = std::strcmp(a, "sad") == 0 ? kAlgoSad
-                : std::strcmp(a, "dot8") == 0 ? kAlgoDot8
+    ctx->algo = std::strcmp(a, "dot8") == 0 ? kAlgoDot8
                 : std::strcmp(a, "poly") == 0 ? kAlgoPoly
                                               : kAlgoMx;
   }
@@ -196,7 +192,6 @@ int gpsx_create(gpsx_ctx **out, int device, void *stream)
   bool ok = hipMalloc((void **)&d_prns, slots) == hipSuccess &&
             hipMalloc((void **)&ctx->d_chips_all, (size_t)slots * 1024) == hipSuccess &&
             hipMalloc((void **)&ctx->d_bits_all, (size_t)slots * 32 * 4) == hipSuccess &&
-            hipMalloc((void **)&ctx->d_cw_all, (size_t)slots * kCodeWords * 4) == hipSuccess &&
             hipMalloc((void **)&ctx->d_cw8_all, (size_t)slots * (kCodeWords / 2) * 4) == hipSuccess &&
             hipMalloc((void **)&ctx->d_trk_rep, (size_t)slots * kTrackRepStride * 4) == hipSuccess &&
             hipMemcpyAsync(d_prns, prns.data(), slots, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
@@ -204,7 +199,7 @@ int gpsx_create(gpsx_ctx **out, int device, void *stream)
             hipHostGetDevicePointer((void **)&ctx->d_bad_prn, ctx->h_bad_prn, 0) == hipSuccess;
   if (ok) {
     ctx->h_bad_prn[0] = ctx->h_bad_prn[1] = 0;
-    launch_build_codes(ctx->stream, d_prns, slots, 1, ctx->d_chips_all, ctx->d_bits_all, ctx->d_cw_all, ctx->d_cw8_all);
+    launch_build_codes(ctx->stream, d_prns, slots, 1, ctx->d_chips_all, ctx->d_bits_all, ctx->d_cw8_all);
     launch_build_track_rep(ctx->stream, ctx->d_bits_all, slots, ctx->d_trk_rep);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
   }
@@ -229,8 +224,8 @@ void gpsx_destroy(gpsx_ctx *ctx)
   track_graph_release(ctx);
   if (ctx->stream)
     (void)hipStreamSynchronize(ctx->stream);
-  void *bufs[] = {ctx->d_chips_all, ctx->d_bits_all, ctx->d_cw_all, ctx->d_cw8_all, ctx->d_trk_rep, ctx->d_grid_prns, ctx->d_grid_chips,
-                  ctx->d_grid_bits, ctx->d_grid_cw, ctx->d_grid_cw8, ctx->d_grid_mx_a, ctx->d_grid_mx_t, ctx->d_arena, ctx->d_acc, ctx->d_energy};
+  void *bufs[] = {ctx->d_chips_all, ctx->d_bits_all, ctx->d_cw8_all, ctx->d_trk_rep, ctx->d_grid_prns, ctx->d_grid_chips,
+                  ctx->d_grid_bits, ctx->d_grid_cw8, ctx->d_grid_mx_a, ctx->d_grid_mx_t, ctx->d_arena, ctx->d_acc, ctx->d_energy};
   for (void *p : bufs)
     if (p)
       (void)hipFree(p);
@@ -530,6 +525,29 @@ int ensure_acc(gpsx_ctx *ctx, size_t n_peaks)
   return GPSX_OK;
 }
 
+// ctx->d_energy, the multi-block forms' HBM scratch, grown to `need` bytes: *had = false when that much cannot be had (no more
+// than half of the free memory is taken) -- the caller then runs another form.  Returns an error only if the stream fails.
+int ensure_energy(gpsx_ctx *ctx, size_t need, bool *had)
+{
+  *had = true;
+  if (need <= ctx->energy_bytes)
+    return GPSX_OK;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->d_energy)
+    (void)hipFree(ctx->d_energy);
+  ctx->d_energy = nullptr;
+  ctx->energy_bytes = 0;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2 &&
+      hipMalloc((void **)&ctx->d_energy, need) == hipSuccess)
+    ctx->energy_bytes = need;
+  else {
+    (void)hipGetLastError();
+    *had = false;
+  }
+  return GPSX_OK;
+}
+
 }  // namespace
 
 int gpsx_acq_grid_dev(gpsx_ctx *ctx, const gpsx_acq_grid_t *g, const void *d_if_blocks, int n_blocks,
@@ -571,15 +589,6 @@ int gpsx_acq_grid_dev(gpsx_ctx *ctx, const gpsx_acq_grid_t *g, const void *d_if_
   prm.win_stop = g->win_stop;
   prm.if_format = ctx->if_format;
   prm.if_hz = ctx->if_hz;
-#if defined(GPSX_MX_ABLATIONS) && !defined(GPSX_LAB)
-#error "GPSX_MX_ABLATIONS builds wrong-result timing variants: with -DGPSX_LAB only (tools/build_variant.sh), never into lib/libgpsx.so"
-#endif
-#ifdef GPSX_MX_ABLATIONS   // timing ablations of k_acq_mx (results are then wrong): tools/build_variant.sh -DGPSX_MX_ABLATIONS only
-  {
-    static const char *ex = std::getenv("GPSX_MX_EXPERIMENT");
-    prm.experiment = ex ? std::atoi(ex) : 0;
-  }
-#endif
   prm.jobs = nullptr;
   prm.peaks = d_peaks;
   prm.per_ms = d_per_ms;
@@ -601,21 +610,7 @@ int gpsx_acq_grid_dev(gpsx_ctx *ctx, const gpsx_acq_grid_t *g, const void *d_if_
                                : clusters < ctx->prop.multiProcessorCount &&
                                      acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp) <= ((size_t)8 << 30);
       const size_t need = mx_blocks ? acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp) : acq_mx_energy_bytes(clusters);
-      if (need > ctx->energy_bytes) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_energy)
-          (void)hipFree(ctx->d_energy);
-        ctx->d_energy = nullptr;
-        ctx->energy_bytes = 0;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2 &&
-            hipMalloc((void **)&ctx->d_energy, need) == hipSuccess)
-          ctx->energy_bytes = need;
-        else {
-          (void)hipGetLastError();
-          mx = false;
-        }
-      }
+      if (int rc = ensure_energy(ctx, need, &mx)) return rc;
     }
     if (mx) {
       uint32_t *d_planes = nullptr;
@@ -660,21 +655,7 @@ int gpsx_acq_grid_dev(gpsx_ctx *ctx, const gpsx_acq_grid_t *g, const void *d_if_
                                         acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp) <= ((size_t)8 << 30);
     const size_t need = block_parallel ? acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp)
                                        : acq_poly_energy_bytes(local_units);
-    if (need > ctx->energy_bytes) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      if (ctx->d_energy)
-        (void)hipFree(ctx->d_energy);
-      ctx->d_energy = nullptr;
-      ctx->energy_bytes = 0;
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2 &&
-          hipMalloc((void **)&ctx->d_energy, need) == hipSuccess)
-        ctx->energy_bytes = need;
-      else {
-        (void)hipGetLastError();
-        poly = false;
-      }
-    }
+    if (int rc = ensure_energy(ctx, need, &poly)) return rc;
   }
   if (poly) {
     const size_t n_peaks = gpsx_acq_peaks_count(g);
@@ -687,12 +668,10 @@ int gpsx_acq_grid_dev(gpsx_ctx *ctx, const gpsx_acq_grid_t *g, const void *d_if_
       ctx->acc_entries = 0;     // (as above: stale partial sums must not reach the next call)
     LAUNCHCHK(ctx, "k_acq_poly");
   } else {
-    const int algo = ctx->algo == kAlgoSad ? kAlgoSad : kAlgoDot8;
-    launch_acq(ctx->stream, kAcqGroup, algo, local_units, prm, static_cast<const uint8_t *>(d_if_blocks),
-               algo == kAlgoDot8 ? ctx->d_grid_cw8 : ctx->d_grid_cw, ctx->d_grid_bits);
+    launch_acq(ctx->stream, kAcqGroup, local_units, prm, static_cast<const uint8_t *>(d_if_blocks), ctx->d_grid_cw8,
+               ctx->d_grid_bits);
     LAUNCHCHK(ctx, "k_acq");
-    ctx->last_kernel = algo == kAlgoSad ? (g->n_ms > 1 ? "k_acq<8,true,sad>" : "k_acq<8,false,sad>")
-                                        : (g->n_ms > 1 ? "k_acq<8,true,dot8>" : "k_acq<8,false,dot8>");
+    ctx->last_kernel = g->n_ms > 1 ? "k_acq<8,true,dot8>" : "k_acq<8,false,dot8>";
   }
   if (d_keys) {
     launch_acq_keys(ctx->stream, d_peaks, d_keys, g->n_search, g->n_prn, n_groups, g->n_dopp, n_bits, (int)unit_lo,
@@ -786,9 +765,7 @@ int gpsx_acq_jobs(gpsx_ctx *ctx, const gpsx_acq_job_t *jobs, int n_jobs, const u
   prm.jobs = d_jobs;
   prm.peaks = d_peaks;
   prm.energy = d_energy;
-  const int job_algo = ctx->algo == kAlgoSad ? kAlgoSad : kAlgoDot8;
-  launch_acq(ctx->stream, 1, job_algo, n_jobs, prm, d_if, job_algo == kAlgoDot8 ? ctx->d_cw8_all : ctx->d_cw_all,
-             ctx->d_bits_all);
+  launch_acq(ctx->stream, 1, n_jobs, prm, d_if, ctx->d_cw8_all, ctx->d_bits_all);
   LAUNCHCHK(ctx, "k_acq(jobs)");
   HIPCHK(ctx, hipMemcpyAsync(peaks, d_peaks, n_jobs * sizeof(gpsx_peak_t), hipMemcpyDeviceToHost, ctx->stream));
   if (energy_opt)

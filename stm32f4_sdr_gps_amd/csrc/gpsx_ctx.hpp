@@ -44,7 +44,6 @@ struct gpsx_ctx {
   // tables for every PRN, slot == prn (slot 0 is the empty code): K1 output
   uint8_t *d_chips_all = nullptr;    // [211][1024]
   uint32_t *d_bits_all = nullptr;    // [211][32]
-  uint32_t *d_cw_all = nullptr;      // [211][256] (group of 1)
   uint32_t *d_cw8_all = nullptr;     // [211][128] (group of 1)
   uint32_t *d_trk_rep = nullptr;     // [211][kTrackRepStride]: replica bit streams for the tracking correlators
   int if_format = GPSX_IF_1BIT;
@@ -62,7 +61,7 @@ struct gpsx_ctx {
   gpsx::gpsx_loop_reseed_t *d_loop_cand = nullptr;    // the candidates of one replay pass, uploaded in one piece
   int if_hz = GPSX_IF_HZ;             // gpsx_config_t.if_hz
   int algo = gpsx::kAlgoMx;                // $GPSX_ACQ_ALGO = mx (default: the matrix-core kernel, at every launch size) | poly |
-                                           // dot8 | sad, for A/B measurements and the parity tests of the alternative kernels
+                                           // dot8, for A/B measurements and the parity tests of the alternative kernels
   uint32_t *d_acc = nullptr;         // poly: packed-key and sum planes merged across workgroups
   size_t acc_entries = 0;
   int seg_force = 0;                 // $GPSX_ACQ_SEG = 4 | 8 | 16: the polyphase kernel at that many offsets per workgroup (tests, A/B);
@@ -81,7 +80,6 @@ struct gpsx_ctx {
   uint8_t *d_grid_prns = nullptr;
   uint8_t *d_grid_chips = nullptr;
   uint32_t *d_grid_bits = nullptr;
-  uint32_t *d_grid_cw = nullptr;
   uint32_t *d_grid_cw8 = nullptr;
   uint32_t *d_grid_mx_a = nullptr;   // matrix-core kernel: A fragments per 32-slot cluster
   uint32_t *d_grid_mx_t = nullptr;   //                     transposed chip words

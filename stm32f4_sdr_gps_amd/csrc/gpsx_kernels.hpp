@@ -18,7 +18,6 @@ constexpr int kSuperGroups = 1;   // groups per sharding unit: a unit is (search
                                   // (search, Doppler) pair stay on one GPU (the matrix-core kernel sweeps 32 PRNs at once)
 constexpr int kCodeWords = 256;   // 4-chip code words per PRN (1023 chips + 1 masked pad)
 constexpr int kMaxMs = 128;       // keeps (energy << 11 | phase) and the window sum inside 32 bits
-constexpr int kAlgoSad = 0;       // main loop: v_msad_u8 on 8-bit block sums, 4 chips per instruction
 constexpr int kAlgoDot8 = 1;      // main loop: v_dot8_u32_u4 on 4-bit block sums, 8 chips per instruction
 constexpr int kAlgoPoly = 2;      // fine grid only: polyphase recurrence across the 16 sample offsets, AND + popcount
 constexpr int kAlgoMx = 4;        // the same recurrence as a Toeplitz GEMM on the matrix cores, MX-FP4: the default at every
@@ -49,8 +48,6 @@ struct AcqParams {
   int32_t split_segs;       //   k_acq_mx<5>: workgroups per cluster (2, 4 or 8)
   int32_t n_clusters;       //   k_acq_mx<4>: clusters of the launch (one persistent workgroup per CU walks them)
   uint64_t n_planes;        //   k_acq_mx<5>: entries per result plane (packed keys [0, n), sums [n, 2 n) behind `energy`)
-  int32_t experiment;       // ablations of k_acq_mx for timing (results are then wrong); always 0 unless the library was built
-                            // with -DGPSX_MX_ABLATIONS, which alone makes gpsx_api.hip read $GPSX_MX_EXPERIMENT
   // explicit job list (job mode)
   const AcqJobRec *jobs;
   // outputs (optional ones may be null)
@@ -64,15 +61,14 @@ struct AcqParams {
 // K1: Gold codes + derived tables for `n_slots` code-table slots (padded slots have prn 0 -> all-zero tables).
 //   chips    [n_slots][1024]  0/1 bytes
 //   chipbits [n_slots][32]    packed, bit (i & 31) of word (i >> 5) = chip i
-//   cw       [n_slots/group][256][group]  4 chips per word as SAD reference bytes: 17 (chip 1), 1 (chip 0), 0 (pad)
 //   cw8      [n_slots/group][128][group]  8 chips per word as 0/1 nibbles (pad chip 1023 = 0)
 void launch_build_codes(hipStream_t s, const uint8_t *d_prns, int n_slots, int group, uint8_t *d_chips,
-                        uint32_t *d_chipbits, uint32_t *d_cw, uint32_t *d_cw8);
+                        uint32_t *d_chipbits, uint32_t *d_cw8);
 
 // K2+K3+K4 fused acquisition search.  group = kAcqGroup (grid; local_units = sharding units of this rank) or 1 (job
-// list; local_units = jobs).  d_cw is the table matching `algo` (cw for kAlgoSad, cw8 for kAlgoDot8).
-void launch_acq(hipStream_t s, int group, int algo, long local_units, const AcqParams &prm, const uint8_t *d_if,
-                const uint32_t *d_cw, const uint32_t *d_chipbits);
+// list; local_units = jobs).  d_cw8: the cw8 table of launch_build_codes.
+void launch_acq(hipStream_t s, int group, long local_units, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
+                const uint32_t *d_chipbits);
 // Polyphase variant for phase_mode FINE, no inspection outputs (k_acq_poly.hip).  n_ms > 1 needs d_energy:
 // acq_poly_energy_bytes(local_units) of scratch for the running per-hypothesis sums between blocks.  d_keyacc / d_sumacc: two
 // u32 scratch planes of n_peaks entries, used (zeroed, merged with atomics, converted into d_peaks) only when the launch

@@ -45,10 +45,8 @@
 // for k_acq_vals_search; 4 the byte-phase grid (sample offsets 0 and 8, each started directly from its own block sums; one
 // persistent workgroup per CU runs its clusters as ONE software pipeline: mx_byte_pipe); 5 small launches: 2 / 4 / 8 workgroups per cluster, each started directly
 // at its own sample offset (mx_direct_terms: every quirk term as a start value), results merged through global planes.
-#if !defined(GPSX_LAB) && (defined(WALK_ABL_NO_LOAD) || defined(WALK_ABL_NO_STORE) || defined(GPSX_MX_ABLATIONS) || \
-                           defined(GPSX_MX_NO_PIECES) || defined(GPSX_MX_TIMELINE) || defined(MX_BUILD_BEHIND) || defined(GPSX_MX_NT) || \
-                           defined(MX_VARIANT_B) || defined(WALK_ABL_ALIAS) || defined(MXW_ABL) || defined(GPSX_MX_CYCLES))
-#error "timing ablations / instrumented variants of k_acq_mx (some give wrong results) build with -DGPSX_LAB only: tools/build_variant.sh"
+#if !defined(GPSX_LAB) && defined(MX_VARIANT_B)
+#error "variants of k_acq_mx for same-box A/B timing build with -DGPSX_LAB only: tools/build_variant.sh"
 #endif
 #include <cstdlib>
 
@@ -851,42 +849,8 @@ template <bool S16>
 struct SumRecT {
   u32 w[S16 ? 2 : 3];
 };
-// The records are a stream: written once per block, read once a block later, a megabyte per workgroup in between -- nothing
-// a cache keeps.  GPSX_MX_NT: non-temporal loads / stores for them (A/B: tools/build_variant.sh).
-template <bool S16>
-__device__ __forceinline__ SumRecT<S16> rec_load(const SumRecT<S16> *p)
-{
-#ifdef WALK_ABL_NO_LOAD   // (timing ablation: results are wrong)
-  SumRecT<S16> z{};
-  asm volatile("" : "+v"(z.w[0]), "+v"(z.w[1]));
-  return z;
-#endif
-#ifdef GPSX_MX_NT
-  SumRecT<S16> r;
-#pragma unroll
-  for (int i = 0; i < (S16 ? 2 : 3); i++)
-    r.w[i] = __builtin_nontemporal_load(&p->w[i]);
-  return r;
-#else
-  return *p;
-#endif
-}
-template <bool S16>
-__device__ __forceinline__ void rec_store(SumRecT<S16> *p, const SumRecT<S16> &r)
-{
-#ifdef WALK_ABL_NO_STORE   // (timing ablation: results are wrong)
-  u32 a = r.w[0], b = r.w[1];
-  asm volatile("" : : "v"(a), "v"(b));
-  return;
-#endif
-#ifdef GPSX_MX_NT
-#pragma unroll
-  for (int i = 0; i < (S16 ? 2 : 3); i++)
-    __builtin_nontemporal_store(r.w[i], &p->w[i]);
-#else
-  *p = r;
-#endif
-}
+// (The records are a stream: written once per block, read once a block later, a megabyte per workgroup in between -- nothing
+//  a cache keeps.)
 template <bool S16>
 __device__ __forceinline__ void sums_unpack(const SumRecT<S16> &r, u32 (&s)[4])
 {
@@ -944,9 +908,6 @@ __device__ __forceinline__ void mx_prefetch_sums(const u32 *__restrict__ energy,
   // (first block of a search: the running sums are zero -- read from a small all-zero region, `zero_recs`, instead of being
   //  set by the vector ALU: register writes into the prefetch array made the compiler drain every outstanding store first,
   //  an s_waitcnt vmcnt(0) per step; a load is ordered behind them by the memory system and costs nothing)
-#ifdef WALK_ABL_ALIAS   // (timing ablation, results are wrong: sample offsets t0 and t0 & WALK_ABL_ALIAS share their records -- the same
-  t0 &= WALK_ABL_ALIAS;   //  traffic on 1/2 (7), 1/4 (3) ... of the footprint: does the stream fit the memory-side cache then?)
-#endif
   if constexpr (S16) {
     // 16-bit records: [sample offset][tile][group pair][lane][2] -- a wave's 16-byte loads and stores of a pair cover ONE
     // contiguous kilobyte (whole 128-byte lines per instruction, not half lines twice)
@@ -1079,12 +1040,7 @@ __device__ __forceinline__ void mx_epilogue(MxShared &sh, int lane, int q0_tile,
           both.a = held;
           both.b = nr;
           // ([offset][tile][pair][lane][2]: see mx_prefetch_sums)
-#ifdef WALK_ABL_ALIAS
-          const int t0r = t0 & WALK_ABL_ALIAS;
-#else
-          const int t0r = t0;
-#endif
-          SumRec *e_pair = reinterpret_cast<SumRec *>(energy) + (size_t)(t0r * kMxTiles + j) * 256 + (size_t)(r0 / 8) * 128 + (size_t)lane * 2;
+          SumRec *e_pair = reinterpret_cast<SumRec *>(energy) + (size_t)(t0 * kMxTiles + j) * 256 + (size_t)(r0 / 8) * 128 + (size_t)lane * 2;
           *reinterpret_cast<RecPairT<S16> *>(e_pair) = both;
         } else {
           held = nr;
@@ -1113,7 +1069,7 @@ __device__ __forceinline__ void mx_epilogue(MxShared &sh, int lane, int q0_tile,
 #pragma unroll
         for (int g = 0; g < GS / 4; g++) {
           const u32 o4[4] = {out[4 * g], out[4 * g + 1], out[4 * g + 2], out[4 * g + 3]};
-          rec_store<S16>(&e_rec[g], sums_pack<S16>(o4));
+          e_rec[g] = sums_pack<S16>(o4);
         }
       }
       if (SEARCH && !DIRECT) {   // (pinned in program order: left alone, the compiler sinks all 64 chains to the end and spills)
@@ -1148,8 +1104,7 @@ __device__ __forceinline__ void mx_epilogue(MxShared &sh, int lane, int q0_tile,
 constexpr u32 kRootBias = 0x4B000000u;
 template <int NT>
 __device__ __forceinline__ void mx_epilogue_single(MxShared &sh, int lane, const u32 (&kq)[NT], int t0,
-                                                   const v16f (&acc)[2][NT], bool half_only = false, bool half_atomics = false,
-                                                   int slots = -1)
+                                                   const v16f (&acc)[2][NT], int slots = -1)
 {
   // (slots: which eighth of sh.part takes the results -- the bit shift's own, unless the pipelined byte-phase form says otherwise)
   const int n = lane & 31, h = lane >> 5;
@@ -1170,10 +1125,6 @@ __device__ __forceinline__ void mx_epilogue_single(MxShared &sh, int lane, const
   mx_round_toward_zero();
 #pragma unroll
   for (int jp = 0; jp < NT; jp += 2) {
-#ifdef GPSX_MX_ABLATIONS
-    if (jp >= 2 && half_only)   // (timing ablation 128: half an epilogue)
-      break;
-#endif
 #pragma unroll
     for (int r0 = 0; r0 < 16; r0 += 4) {
       // eight hypotheses: two tiles x four PRNs
@@ -1217,17 +1168,6 @@ __device__ __forceinline__ void mx_epilogue_single(MxShared &sh, int lane, const
     }
   }
   mx_round_to_nearest();
-#ifdef GPSX_MX_ABLATIONS
-  if (half_atomics) {   // (timing ablation 512: half the LDS atomics)
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-      const int p_off = ((r & 3) + 8 * (r >> 2)) * 64;
-      atomicMax(slot + p_off, best[r] | best[r + 8]);
-      atomicAdd(slot + p_off + 32, total[r] + total[r + 8]);
-    }
-    return;
-  }
-#endif
 #pragma unroll
   for (int r = 0; r < 16; r++) {
     const int p_off = ((r & 3) + 8 * (r >> 2)) * 64;   // PRN (r & 3) + 8 (r >> 2) + 4 h: 2 x 32 words per PRN
@@ -1345,15 +1285,7 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
   }
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform values in SGPRs)
-#ifdef GPSX_MX_ABLATIONS
-  const int ex = prm.experiment;
-#else
-  constexpr int ex = 0;            // (production builds carry none of it: its hoisted constants cost the walk form 16 registers)
-#endif
-                                   // timing ablations: 1 = no epilogue, 2 = no MFMA (noise-sized counts instead), 4 = both roles in
-                                   // step, 8 = no vector building, 16 = raised priority for the MFMA passes, 32 = no MFMA pass in
-                                   // role 1, 64 = no epilogue in role 0, 128 = half an epilogue, 256 = no steps, 512 = half the atomics
-  const int role = (ex & 4) ? 0 : wave >> 2;             // waves w and w + 4 share a SIMD: half a step apart
+  const int role = wave >> 2;                            // waves w and w + 4 share a SIMD: half a step apart
   const int q0_tile = 8 * (wave >> 1) + (wave & 1);      // this wave owns q-tiles q0_tile + 2 j
 
   // ---- decode: cluster = (search, Doppler, set of 32 PRN slots); its four 8-PRN groups are sharding units -----------
@@ -1448,69 +1380,34 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
       mx_vector_phase2(sh, 1, tid_p, kMxThreads);
     }
 
-#ifdef GPSX_MX_TIMELINE   // (tools/experiments/single_timeline.py: cycle stamps of workgroup 1000's waves 0 and 4 behind the peaks)
-    unsigned long long *tl1 = (MODE == kMxSingle || (MODE == kMxWalk16 && ms == 5)) && blockIdx.x == 1000 && lane == 0 && (wave & 3) == 0
-                                  ? reinterpret_cast<unsigned long long *>(peaks + (size_t)gridDim.x * 256) + role * 512 : nullptr;
-    int tl1i = 0;
-#define MX_TL1() do { if (tl1 && tl1i < 512) tl1[tl1i++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define MX_TL1() do { } while (0)
-#endif
-    MX_TL1();
     v16f acc[2][kMxTiles];
     mx_init_acc(sh.ones, lane_p, q0_tile, acc, prm.win_start, prm.win_stop);
-    if ((ex & 2) || ((ex & 32) && role)) {   // (timing ablation without MFMAs: noise-sized counts, so that the epilogue takes its usual path)
-#pragma unroll
-      for (int j = 0; j < kMxTiles; j++)
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-          acc[0][j][r] = acc[1][j][r] = (float)(lane + r) * kAccScale;
-    }
     SumRec pre[MULTI ? 16 : 1];
 
     // Steps of two halves: role 0 runs pass p, then the epilogue of sample offset p - 1; role 1 the epilogue of sample
     // offset p - 2, then pass p -- one wave of a SIMD on the matrix pipe while the other has the vector ALU, with nothing
     // but their own pace between the halves: ONE barrier per step, where all eight waves build the vector of pass p + 1
     // into the buffer that both roles read during step p - 1.
-#ifdef GPSX_MX_CYCLES   // (lab: where workgroup 1000's waves spend their cycles -- barrier, vector building, pass, epilogue)
-    unsigned long long cy_bar = 0, cy_build = 0, cy_pass = 0, cy_epi = 0;
-    const unsigned long long cy_begin = __builtin_readcyclecounter();
-#define MX_CY(acc_var) do { const unsigned long long now = __builtin_readcyclecounter(); acc_var += now - cy_last; cy_last = now; } while (0)
-#else
-#define MX_CY(acc_var) do { } while (0)
-#endif
 #pragma unroll 1
-    for (int hs = (ex & 256) ? 2 * n_pass + 1 : 0; hs <= 2 * n_pass; hs++) {   // (timing ablation 256: no steps at all)
-#ifdef GPSX_MX_CYCLES
-      unsigned long long cy_last = __builtin_readcyclecounter();
-#endif
-      MX_TL1();
+    for (int hs = 0; hs <= 2 * n_pass; hs++) {
       if ((hs & 1) == 0)
         __syncthreads();
-      MX_CY(cy_bar);
-      MX_TL1();
       // The vector of the next step: built behind the barrier by everybody (single-block forms), or behind this step's epilogue
       // by the role that just finished one (walk forms: each role's threads own one stream of the vector -- threads 0..255 =
       // waves 0..3 = I, 256..511 = Q --, the buffer it goes into was last read in the previous step, and the barrier that opens
       // the next step publishes it).  Same-box A/B: behind the epilogue is 1.5 % faster for the walk form (whose epilogue waits
       // on HBM anyway) and 1.8 % slower for the single-block form -- the step is bound by the SIMD's issue port, not by the
       // barrier: moving the work does not shorten it.
-#ifdef MX_BUILD_BEHIND
-      constexpr bool kBuildBehindEpilogue = true;
-#else
       constexpr bool kBuildBehindEpilogue = MULTI;
-#endif
       if (!kBuildBehindEpilogue && (hs & 1) == 0) {
         const int p_vec = (hs >> 1) + 1;
-        if (p_vec >= 2 && p_vec < n_pass && !(ex & 8)) {
+        if (p_vec >= 2 && p_vec < n_pass) {
           int tid_v = tid;
           if constexpr (MULTI)
             asm volatile("" : "+v"(tid_v));   // (as above: the builder's addresses are not worth registers across the passes)
           mx_vector_build(sh, pbase + p_vec, tid_v);
         }
       }
-      MX_TL1();
-      MX_CY(cy_build);
       int lane_s = lane;         // (walk forms: opaque per half step, see tid_p -- record addresses are recomputed, not spilled)
       if constexpr (MULTI)
         asm volatile("" : "+v"(lane_s));
@@ -1522,13 +1419,7 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
           if (p >= 1)
             mx_prefetch_sums<0, 8, S16>(e_wave, zero_recs, lane_s, p - 1, ms_first, pre);
         }
-        if (!(ex & 2) && !((ex & 32) && role)) {
-          if (ex & 16)
-            __builtin_amdgcn_s_setprio(3);
-          mx_pass<!MULTI>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne, a_corr, p >= 2 && (SPLIT || p != 9));
-          if (ex & 16)
-            __builtin_amdgcn_s_setprio(0);
-        }
+        mx_pass<!MULTI>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne, a_corr, p >= 2 && (SPLIT || p != 9));
         if constexpr (SPLIT) {
           if (p == 1 && seg) {
             int lane_d = lane;   // (opaque: the terms' per-lane addresses are not worth registers across the step loop)
@@ -1540,26 +1431,23 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
             mx_half_switch(sh, lane_s, q0_tile, acc, prm.win_start, prm.win_stop);
         }
       }
-      MX_TL1();
-      MX_CY(cy_pass);
       if (STORE) {
         if (active && (x & 1) && p >= 1) {
           uint16_t *plane0 = reinterpret_cast<uint16_t *>(energy) +
                              ((size_t)((search * prm.n_ms + ms_store) * prm.n_prn + 32 * set) * prm.n_dopp + dopp) * (16 * 1024);
           mx_epilogue_store(lane, q0_tile, p - 1, acc, group_mask, plane0, (size_t)prm.n_dopp * (16 * 1024), 32 * set, prm.n_prn);
         }
-      } else if (active && (x & 1) && p >= 1 && !(ex & 1) && !((ex & 64) && !role)) {
+      } else if (active && (x & 1) && p >= 1) {
         if (!MULTI)
-          mx_epilogue_single(sh, lane, kq, t0s + p - 1, acc, (ex & 128) != 0, (ex & 512) != 0);
+          mx_epilogue_single(sh, lane, kq, t0s + p - 1, acc);
         else if (!ms_last)
           mx_epilogue<MULTI, false, S16>(sh, lane_s, q0_tile, p - 1, acc, group_mask, e_wave, zero_recs, pre, ms_first, witness);
         else
           mx_epilogue<MULTI, true, S16>(sh, lane_s, q0_tile, p - 1, acc, group_mask, e_wave, zero_recs, pre, ms_first, witness);
       }
-      MX_CY(cy_epi);
       if (kBuildBehindEpilogue && (x & 1) != 0) {
         const int p_vec = (hs >> 1) + 1;
-        if (p_vec >= 2 && p_vec < n_pass && !(ex & 8)) {
+        if (p_vec >= 2 && p_vec < n_pass) {
           int tid_v = tid;
           if constexpr (MULTI)
             asm volatile("" : "+v"(tid_v));
@@ -1567,11 +1455,6 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
         }
       }
     }
-#ifdef GPSX_MX_CYCLES
-    if (blockIdx.x == 1000 && lane == 0 && ms == 0)
-      printf("mode %d wave %d: barrier %llu build %llu pass %llu epilogue %llu, loop %llu cycles\n", MODE, wave, cy_bar, cy_build, cy_pass,
-             cy_epi, __builtin_readcyclecounter() - cy_begin);
-#endif
   }
   if (STORE)
     return;   // k_acq_vals_search sums the blocks and searches
@@ -1944,27 +1827,12 @@ __device__ __forceinline__ void mx_byte_pipe(MxShared &sh, const AcqParams &prm,
   MxBlockRegs next_block = {{0, 0, 0, 0}};
   v16f acc[2][kMxTiles];
   const int n_half = 4 * n_my;
-#ifdef GPSX_MX_TIMELINE   // (tools/experiments/byte_timeline.py: cycle stamps of workgroup 0's waves 0 and 4 behind the peaks)
-  unsigned long long *tl = blockIdx.x == 0 && lane == 0 && (wave & 3) == 0
-                               ? reinterpret_cast<unsigned long long *>(peaks + (size_t)prm.n_clusters * 32) + role * 2048 : nullptr;
-  int tli = 0;
-  int tli2 = 1024;
-#define MX_TL() do { if (tl && tli < 1024) tl[tli++] = __builtin_readcyclecounter(); } while (0)
-#define MX_TL2() do { if (tl && tli2 < 2048) tl[tli2++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define MX_TL() do { } while (0)
-#define MX_TL2() do { } while (0)
-#endif
   // the pieces behind the barrier of even half stage hs_even, thread t's share
   auto piece = [&](int hs_even, int t) {
     asm volatile("" : "+v"(t));   // (per-thread addresses of these pieces are recomputed, not kept across the stages)
     const int c = hs_even >> 2;
     window_to(c);
     const bool steady = c >= 1 && c + 2 < n_my;   // every piece exists: one straight run, their LDS round trips overlap
-#ifdef GPSX_MX_NO_PIECES   // (timing ablation: results are then wrong)
-    if (steady)
-      return;
-#endif
     if ((hs_even & 2) == 0) {
       if (steady) {
         const u32 step = step_of(c + 1);
@@ -2007,16 +1875,13 @@ __device__ __forceinline__ void mx_byte_pipe(MxShared &sh, const AcqParams &prm,
   };
 #pragma unroll 1
   for (int hs = 0; hs <= n_half; hs++) {
-    MX_TL();
     if ((hs & 1) == 0)
       __syncthreads();
-    MX_TL();
     // A stage's pieces only have to be done before the NEXT barrier, and what they write nobody reads before it: role 1 does
     // its threads' share at once (pieces, epilogue, passes), role 0 at the end of its stage (passes, epilogue, pieces) -- the
     // two waves of a SIMD are then on the matrix pipe one after the other from the barrier on.
     if (role == 1 && (hs & 1) == 0)
       piece(hs, tid);
-    MX_TL();
     const int x = hs - role;   // this role's half stage
     if (x >= 0 && x < n_half) {
       const int cc = x >> 2, o = (x >> 1) & 1;   // sample offset 8 o
@@ -2033,7 +1898,7 @@ __device__ __forceinline__ void mx_byte_pipe(MxShared &sh, const AcqParams &prm,
         }
         mx_pass2(sh, lane, q0_tile, acc, va, vb);
       } else {
-        mx_epilogue_single(sh, lane, kq, 8 * o, acc, false, false, cc & 1 ? kSlotsOdd : kSlotsEven);
+        mx_epilogue_single(sh, lane, kq, 8 * o, acc, cc & 1 ? kSlotsOdd : kSlotsEven);
       }
     }
     if (role == 0 && (hs & 1) != 0)
@@ -2192,11 +2057,6 @@ struct MxwShared {
   u32 mplane[16][kPlaneWordsMx];    // polyphase magnitude planes, as s.plane
   int wsum[2];                      // sum over the mixed samples of (2 d - 1) m, per stream
 };
-#ifndef MXW_ABL
-#define MXW_ABL 0   // (lab builds: timing ablations -- 1 no epilogue, 2 no vector building, 4 no MFMA pass, 8 raised priority for the
-                    //  passes, 16 no magnitude test in front of the epilogue, 32 no pass in waves 4-7, 64 no epilogue in waves 0-3;
-                    //  wrong results)
-#endif
 constexpr int kWPasses = 18;                 // 3 for the first offset + 15 recurrence steps
 constexpr u32 kScaleTwo = 0x80808080u;       // E8M0 128 = 2^1
 constexpr u32 kScaleFour = 0x81818181u;      // 2^2
@@ -2408,7 +2268,7 @@ __device__ __forceinline__ void mxw_epilogue(MxShared &sh, int lane, int q0_tile
       lim[j] = mxw_max_abs(lim[j], acc[0][j][r], acc[1][j][r]);
   const float top = __builtin_fmaxf(__builtin_fmaxf(lim[0], lim[1]), __builtin_fmaxf(lim[2], lim[3]));
   bool small[kMxTiles];
-  if (__builtin_amdgcn_ballot_w64(top >= 2896.0f) == 0 || (MXW_ABL & 16)) {
+  if (__builtin_amdgcn_ballot_w64(top >= 2896.0f) == 0) {
     mxw_epilogue_body<true>(sh, lane, q0_tile, t0, acc, small);
   } else {
 #pragma unroll
@@ -2529,49 +2389,18 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mxw(const uint8_t *__rest
   const v4i no_corr = v4i{0, 0, 0, 0};
   // steps of two halves, as mx_unit: role 0 runs pass p, then the epilogue of the offset pass p - 1 finished; role 1 the
   // epilogue first, then the pass; one barrier per step.  The vector of pass p + 1 is built during step p by role 0 alone
-#if MXW_ABL & 256   // (lab: where one workgroup's waves spend their cycles -- barrier, vector building, pass, epilogue)
-  unsigned long long t_bar = 0, t_build = 0, t_pass = 0, t_epi = 0;
-  const unsigned long long t_begin = __builtin_readcyclecounter();
-#define MXW_T(acc_var) do { const unsigned long long now = __builtin_readcyclecounter(); acc_var += now - t_last; t_last = now; } while (0)
-#else
-#define MXW_T(acc_var) do { } while (0)
-#endif
 #pragma unroll 1
   for (int hs = 0; hs <= 2 * kWPasses; hs++) {
-#if MXW_ABL & 256
-    unsigned long long t_last = __builtin_readcyclecounter();
-#endif
-    if ((hs & 1) == 0) {
+    if ((hs & 1) == 0)
       __syncthreads();
-      MXW_T(t_bar);
-    }
-    MXW_T(t_build);
     const int x = hs - role;
     const bool active = x >= 0 && x < 2 * kWPasses;
     const int p = x >> 1;
-    if (active && (x & 1) == 0) {
-      if (!(MXW_ABL & 4) && !((MXW_ABL & 32) && role)) {
-        if (MXW_ABL & 8)
-          __builtin_amdgcn_s_setprio(2);
-        mx_pass<true, kMxTiles, (MXW_ABL & 128) ? kScaleA : kScaleOne>(sh, p & 1, lane, q0_tile, acc, p == 0 ? kScaleOne : p == 1 ? kScaleFour : p == 2 ? kScaleSixteen : kScaleTwo,
-                      no_corr, false);
-        if (MXW_ABL & 8)
-          __builtin_amdgcn_s_setprio(0);
-      } else
-#pragma unroll
-        for (int j = 0; j < kMxTiles; j++)
-          asm volatile("" : "+v"(acc[0][j]), "+v"(acc[1][j]));
-    }
-    MXW_T(t_pass);
-    if (active && (x & 1) && p >= 2) {
-      if (!(MXW_ABL & 1) && !((MXW_ABL & 64) && !role)) {
-        mxw_epilogue(sh, lane, q0_tile, p - 2, acc);
-      } else
-#pragma unroll
-        for (int j = 0; j < kMxTiles; j++)
-          asm volatile("" ::"v"(acc[0][j]), "v"(acc[1][j]));
-    }
-    MXW_T(t_epi);
+    if (active && (x & 1) == 0)
+      mx_pass<true, kMxTiles, kScaleOne>(sh, p & 1, lane, q0_tile, acc, p == 0 ? kScaleOne : p == 1 ? kScaleFour : p == 2 ? kScaleSixteen : kScaleTwo,
+                                         no_corr, false);
+    if (active && (x & 1) && p >= 2)
+      mxw_epilogue(sh, lane, q0_tile, p - 2, acc);
     // the vector of the NEXT step's pass, by the waves of role 0 alone, behind their epilogue: they are the ones that wait at the
     // step's barrier (role 1's epilogue runs beside a pass and takes half as long again); the buffer was last read in the
     // previous step
@@ -2580,17 +2409,12 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mxw(const uint8_t *__rest
       if (p_vec == 2) {
         mxw_build_start(shw, 2, 0, tid);
         mxw_build_start(shw, 2, 0, tid + 256);
-      } else if (p_vec > 2 && p_vec < kWPasses && !(MXW_ABL & 2)) {
+      } else if (p_vec > 2 && p_vec < kWPasses) {
         mxw_build_step(shw, p_vec - 3, p_vec & 1, tid);
         mxw_build_step(shw, p_vec - 3, p_vec & 1, tid + 256);
       }
     }
   }
-#if MXW_ABL & 256
-  if (blockIdx.x == 1000 && lane == 0)
-    printf("wave %d: barrier %llu build %llu pass %llu epilogue %llu, loop %llu cycles\n", wave, t_bar, t_build, t_pass, t_epi,
-           __builtin_readcyclecounter() - t_begin);
-#endif
   __syncthreads();
   // ---- one triplet per (search, PRN, Doppler): the eight bit shifts' slots (32 lanes each) meet here --------------------------
   {

@@ -9,7 +9,7 @@
 namespace gpsx {
 
 __global__ void k_build_codes(const uint8_t *__restrict__ prns, int n_slots, int group, uint8_t *__restrict__ chips,
-                              u32 *__restrict__ chipbits, u32 *__restrict__ cw, u32 *__restrict__ cw8)
+                              u32 *__restrict__ chipbits, u32 *__restrict__ cw8)
 {
   const int slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= n_slots)
@@ -48,19 +48,6 @@ __global__ void k_build_codes(const uint8_t *__restrict__ prns, int n_slots, int
   uint8_t *row = chips + (size_t)slot * 1024;
   for (int i = 0; i < 1024; i++)
     row[i] = i < kChips ? (uint8_t)((bits[i >> 5] >> (i & 31)) & 1u) : (uint8_t)0;
-  if (cw) {
-    const bool live = prn >= 1 && prn <= GPSX_MAX_PRN;
-    u32 *base = cw + (size_t)(slot / group) * kCodeWords * group + (slot % group);
-    for (int jw = 0; jw < kCodeWords; jw++) {
-      u32 word = 0;
-      for (int e = 0; e < 4; e++) {
-        const int c = 4 * jw + e;
-        if (live && c < kChips)
-          word |= (((bits[c >> 5] >> (c & 31)) & 1u) ? 17u : 1u) << (8 * e);
-      }
-      base[(size_t)jw * group] = word;
-    }
-  }
   if (cw8) {
     const bool live = prn >= 1 && prn <= GPSX_MAX_PRN;
     u32 *base = cw8 + (size_t)(slot / group) * (kCodeWords / 2) * group + (slot % group);
@@ -77,12 +64,12 @@ __global__ void k_build_codes(const uint8_t *__restrict__ prns, int n_slots, int
 }
 
 void launch_build_codes(hipStream_t s, const uint8_t *d_prns, int n_slots, int group, uint8_t *d_chips,
-                        uint32_t *d_chipbits, uint32_t *d_cw, uint32_t *d_cw8)
+                        uint32_t *d_chipbits, uint32_t *d_cw8)
 {
   if (n_slots <= 0)
     return;
   hipLaunchKernelGGL(k_build_codes, dim3((n_slots + 63) / 64), dim3(64), 0, s, d_prns, n_slots, group, d_chips,
-                     d_chipbits, d_cw, d_cw8);
+                     d_chipbits, d_cw8);
 }
 
 }  // namespace gpsx

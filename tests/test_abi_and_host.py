@@ -251,8 +251,8 @@ def test_loop_state_conversion_round_trips_and_touches_only_the_loops_fields(lib
 
 def test_product_and_lab_builds_and_no_register_spills(lib_path):
     """lib/libgpsx.so is the product: built without GPSX_LAB, it reads none of the $GPSX_ACQ_* / $GPSX_TRACK_WAVE_FROM knobs that
-    force a kernel form (the getenv block is not compiled into it) and cannot carry the wrong-result timing ablations
-    (k_acq_mx.hip / gpsx_api.hip refuse those macros without GPSX_LAB).  lib/libgpsx_lab.so is the same sources with the knobs.
+    force a kernel form (the getenv block is not compiled into it) and cannot carry an A/B variant of the matrix-core kernel
+    (k_acq_mx.hip refuses MX_VARIANT_B without GPSX_LAB).  lib/libgpsx_lab.so is the same sources with the knobs.
     And no instance of the matrix-core grid kernel spills registers (k_acq_mx<3> sits at 255 VGPRs)."""
     import ctypes as C
     import os
@@ -276,9 +276,9 @@ def test_product_and_lab_builds_and_no_register_spills(lib_path):
     # the device tracking loops: no spills, and the two xorshift instantiations (the ones that run at scale) at three waves per SIMD
     assert len(loops) == 4 and all(v["scratch_bytes"] == 0 for v in loops.values())
     assert sorted(v["vgprs"] for v in loops.values())[:2] <= [168, 168]
-    # the ablation macros do not compile into a product object
+    # the A/B variant macro does not compile into a product object
     src = os.path.join(os.path.dirname(os.path.dirname(lib_path)), "csrc", "k_acq_mx.hip")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-DGPSX_MX_NO_PIECES", src],
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-DMX_VARIANT_B", src],
                        capture_output=True, text=True)
     assert r.returncode != 0 and "GPSX_LAB" in r.stderr
 

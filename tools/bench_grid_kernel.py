@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The grid kernel alone (device-resident captures, HIP events on the engine's stream), no result checks: for timing
-ablations ($GPSX_MX_EXPERIMENT) and A/B runs ($GPSX_ACQ_ALGO).  tools/bench_grid_kernel.py [searches [n_ms [reps]]]"""
+"""The grid kernel alone (device-resident captures, HIP events on the engine's stream), no result checks: for A/B runs
+($GPSX_ACQ_ALGO, $GPSX_LIB).  tools/bench_grid_kernel.py [searches [n_ms [reps]]]"""
 import ctypes as C
 import json
 import os
@@ -45,8 +45,7 @@ def main():
     eng.synchronize()
     ms = eng.elapsed_ms(e0, e1) / reps
     hyp = searches * n_ms * 32 * 21 * 16368
-    print(json.dumps({"kernel": eng.lib.gpsx_last_kernel(eng.h).decode(), "searches": searches, "n_ms": n_ms,
-                      "experiment": os.environ.get("GPSX_MX_EXPERIMENT", "0"), "ms": round(ms, 4),
+    print(json.dumps({"kernel": eng.lib.gpsx_last_kernel(eng.h).decode(), "searches": searches, "n_ms": n_ms, "ms": round(ms, 4),
                       "hyp_per_s": hyp / (ms * 1e-3)}))
 
 
