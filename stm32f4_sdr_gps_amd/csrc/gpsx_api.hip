@@ -153,26 +153,24 @@ int gpsx_create(gpsx_ctx **out, int device, void *stream)
 #ifdef GPSX_LAB
   // lib/libgpsx_lab.so only (csrc/Makefile; the product library is built without GPSX_LAB and reads none of these): forced
   // kernel forms for the parity tests of the alternative kernels and for A/B measurements
+  AcqKnobs &k = ctx->acq_knobs;
   if (const char *sg = std::getenv("GPSX_ACQ_SEG")) {
     const int v = std::atoi(sg);
-    ctx->seg_force = (v == 4 || v == 8 || v == 16) ? v : 0;
+    k.seg = (v == 4 || v == 8 || v == 16) ? v : 0;
   }
-  ctx->no_split = std::getenv("GPSX_ACQ_NO_SPLIT") != nullptr;
+  k.no_split = std::getenv("GPSX_ACQ_NO_SPLIT") != nullptr;
   if (const char *sp = std::getenv("GPSX_ACQ_SPLIT")) {
     const int v = std::atoi(sp);
-    ctx->split_force = v == 8 ? 8 : v == 4 ? 4 : 2;
+    k.split = v == 8 ? 8 : v == 4 ? 4 : 2;
   }
   if (const char *w = std::getenv("GPSX_TRACK_WAVE_FROM"))
     ctx->track_wave_from = std::atoi(w) > 0 ? std::atoi(w) : 1;
   if (const char *m = std::getenv("GPSX_ACQ_MS_MODE"))
-    ctx->ms_mode = std::strcmp(m, "walk") == 0 ? 1 : (std::strcmp(m, "blocks") == 0 ? 2 : 0);
-  if (const char *a = std::getenv("GPSX_ACQ_ALGO")) {
-    ctx->algo = std::strcmp(a, "dot8") == 0 ? kAlgoDot8
-                : std::strcmp(a, "poly") == 0 ? kAlgoPoly
-                                              : kAlgoMx;
-  }
-  if (ctx->seg_force && ctx->algo == kAlgoMx)
-    ctx->algo = kAlgoPoly;   // $GPSX_ACQ_SEG names a form of the polyphase kernel: it selects that kernel too
+    k.ms_mode = std::strcmp(m, "walk") == 0 ? 1 : (std::strcmp(m, "blocks") == 0 ? 2 : 0);
+  if (const char *a = std::getenv("GPSX_ACQ_ALGO"))
+    k.algo = std::strcmp(a, "dot8") == 0 ? kAlgoDot8 : std::strcmp(a, "poly") == 0 ? kAlgoPoly : kAlgoMx;
+  if (k.seg && k.algo == kAlgoMx)
+    k.algo = kAlgoPoly;   // $GPSX_ACQ_SEG names a form of the polyphase kernel: it selects that kernel too
 #endif
   if (stream) {
     ctx->stream = reinterpret_cast<hipStream_t>(stream);
@@ -559,123 +557,58 @@ int gpsx_acq_grid_dev(gpsx_ctx *ctx, const gpsx_acq_grid_t *g, const void *d_if_
     return fail(ctx, GPSX_EINVAL, "null device pointer");
   if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
 
-  const int shard_count = g->shard_count > 0 ? g->shard_count : 1;
-  const int shard_index = g->shard_count > 0 ? g->shard_index : 0;
+  // which kernels serve the call, with what grids and scratch: plan_acq (gpsx_acq_plan.hpp).  Scratch that cannot be had
+  // passes the form that needs it over: matrix -> polyphase -> dot8; no planes -> the unsplit matrix form.
   const int n_bits = gpsx_acq_bits(g->phase_mode);
-  const int n_groups = (g->n_prn + kAcqGroup - 1) / kAcqGroup;
-  const long n_units = (long)g->n_search * n_groups * g->n_dopp;
-  const long unit_lo = n_units * shard_index / shard_count, unit_hi = n_units * (shard_index + 1) / shard_count;
-  const long local_units = unit_hi - unit_lo;
-  if (local_units * n_bits * kSuperGroups > 0x7FFFFFFFL)
+  const AcqShape shape{g->n_search, g->n_ms, g->n_prn, g->n_dopp, n_bits, g->shard_index, g->shard_count,
+                       d_per_ms || d_energy || d_cnt};
+  const int n_cus = ctx->prop.multiProcessorCount;
+  int refused = 0;
+  AcqPlan plan = plan_acq(shape, ctx->acq_knobs, n_cus, refused);
+  const long local_units = plan.unit_hi - plan.unit_lo;
+  if (local_units * n_bits > 0x7FFFFFFFL)
     return fail(ctx, GPSX_EINVAL, "grid too large for one launch");
-
-  if (shard_count > 1) {
+  if (g->shard_count > 1) {
     // entries owned by other shards must read as zero
-    HIPCHK(ctx, hipMemsetAsync(d_peaks, 0, gpsx_acq_peaks_count(g) * sizeof(gpsx_peak_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_peaks, 0, plan.n_peaks * sizeof(gpsx_peak_t), ctx->stream));
   }
-  AcqParams prm{};
-  prm.split_segs = ctx->split_force;   // 0: launch_acq_mx picks by launch size
-  prm.n_ms = g->n_ms;
-  prm.search_stride_blocks = g->search_stride_blocks;
-  prm.n_prn = g->n_prn;
-  prm.n_groups = n_groups;
-  prm.n_dopp = g->n_dopp;
-  prm.dopp_min_hz = g->dopp_min_hz;
-  prm.dopp_step_hz = g->dopp_step_hz;
-  prm.n_bits = n_bits;
-  prm.unit_lo = (int32_t)unit_lo;
-  prm.unit_hi = (int32_t)unit_hi;
-  prm.win_start = g->win_start;
-  prm.win_stop = g->win_stop;
-  prm.if_format = ctx->if_format;
-  prm.if_hz = ctx->if_hz;
-  prm.jobs = nullptr;
-  prm.peaks = d_peaks;
-  prm.per_ms = d_per_ms;
-  prm.energy = d_energy;
-  prm.cnt = d_cnt;
-  const bool inspect = d_per_ms || d_energy || d_cnt;
-  const bool fine = (ctx->algo == kAlgoPoly || ctx->algo == kAlgoMx) && n_bits == 8 && !inspect;
-  // The matrix-core kernel (one 512-thread workgroup per (search, Doppler, 32 PRNs), one per CU) is the faster one at
-  // every launch size measured, a single capture included (0.155 ms against 0.166 ms, profiles/r02_launch_size_sweep.json).
-  // (and serves the byte-phase grid as sample offsets 0 and 8 of the fine one: ten of its seventeen passes, two epilogues)
-  bool mx = ctx->algo == kAlgoMx && !inspect && (n_bits == 8 || g->n_ms == 1);
-  if (mx) {
-    const long clusters = acq_mx_clusters(prm);
-    // n_ms > 1, few searches: a workgroup per (cluster, block) instead of a workgroup walking its cluster's blocks -- a lone
-    // ten-block search is 210 workgroups (one round of the chip) instead of 21 doing ten blocks each
-    bool mx_blocks = false;
-    if (g->n_ms > 1) {
-      mx_blocks = ctx->ms_mode ? ctx->ms_mode == 2
-                               : clusters < ctx->prop.multiProcessorCount &&
-                                     acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp) <= ((size_t)8 << 30);
-      const size_t need = mx_blocks ? acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp) : acq_mx_energy_bytes(clusters);
-      if (int rc = ensure_energy(ctx, need, &mx)) return rc;
-    }
-    if (mx) {
-      uint32_t *d_planes = nullptr;
-      // the split form's result planes: launches of at most half a round of the chip, and launches of whole rounds plus a
-      // last one that fills at most half of it (launch_acq_mx hands that tail to the split form)
-      const long cus = ctx->prop.multiProcessorCount, tail = clusters % cus;
-      if (g->n_ms == 1 && n_bits == 8 && shard_count == 1 && !ctx->no_split &&
-          (2 * clusters <= cus || (clusters > cus && tail > 0 && 2 * tail <= cus))) {
-        if (ensure_acc(ctx, gpsx_acq_peaks_count(g)) == GPSX_OK)
-          d_planes = ctx->d_acc;
-        else
-          (void)hipGetLastError();   // (no memory for the planes: the unsplit form runs; the error must not stick to its launch)
-      }
-      bool keys_done = false;
-      prm.keys = shard_count == 1 ? d_keys : nullptr;   // (a shard's foreign units must read as zero: k_acq_keys sees to that)
-      ctx->last_kernel = launch_acq_mx(ctx->stream, prm, static_cast<const uint8_t *>(d_if_blocks), ctx->d_grid_mx_a,
-                                       ctx->d_grid_mx_t, d_peaks, ctx->d_energy, mx_blocks, gpsx_acq_peaks_count(g), d_planes,
-                                       ctx->prop.multiProcessorCount, &keys_done);
-      if (d_planes && hipPeekAtLastError() != hipSuccess)
-        ctx->acc_entries = 0;   // a launch between the split and finalize kernels failed: the planes may hold partial sums --
-                                // the next use allocates and zeroes them afresh (ensure_acc)
-      LAUNCHCHK(ctx, "k_acq_mx");
-      if (d_keys && !keys_done) {
-        launch_acq_keys(ctx->stream, d_peaks, d_keys, g->n_search, g->n_prn, n_groups, g->n_dopp, n_bits, (int)unit_lo,
-                        (int)unit_hi);
-        LAUNCHCHK(ctx, "k_acq_keys");
-      }
-      return GPSX_OK;
+  while (plan.energy_bytes) {
+    bool had;
+    if (int rc = ensure_energy(ctx, plan.energy_bytes, &had)) return rc;
+    if (had)
+      break;
+    refused |= plan.mx ? kNoMxScratch : kNoPolyScratch;
+    plan = plan_acq(shape, ctx->acq_knobs, n_cus, refused);
+  }
+  if (plan.planes) {
+    if (int rc = ensure_acc(ctx, plan.n_peaks)) {
+      if (!plan.mx)
+        return rc;
+      (void)hipGetLastError();   // (no memory for the split form's planes: the unsplit form runs; the error must not stick to its launch)
+      plan = plan_acq(shape, ctx->acq_knobs, n_cus, refused | kNoPlanes);
     }
   }
-  bool poly = fine;
-  bool block_parallel = false;
-  if (poly && g->n_ms > 1) {
-    // Scratch in HBM between blocks.  Many searches: each workgroup walks the blocks of its unit and keeps 64 KB of
-    // running sums per (PRN, Doppler) pair of this shard (2.7 GB for 64 simultaneous cold-start searches).  Fewer
-    // searches (fewer workgroups than six rounds of the chip's 768 slots): a workgroup per (unit, block) instead, all
-    // blocks' magnitudes as u16 (32 KB per pair and block), summed and searched by a second small kernel -- a single
-    // 10-block cold-start search then takes 0.84 ms instead of 2.8, and the form stays ahead up to ~40 searches.
-    // When the scratch cannot be had, the register-resident dot8 kernel does the job.
-    block_parallel = ctx->ms_mode ? ctx->ms_mode == 2
-                                  : local_units * kSuperGroups < 6 * 768 &&
-                                        acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp) <= ((size_t)8 << 30);
-    const size_t need = block_parallel ? acq_poly_vals_bytes(g->n_search, g->n_ms, g->n_prn, g->n_dopp)
-                                       : acq_poly_energy_bytes(local_units);
-    if (int rc = ensure_energy(ctx, need, &poly)) return rc;
-  }
-  if (poly) {
-    const size_t n_peaks = gpsx_acq_peaks_count(g);
-    if (int rc = ensure_acc(ctx, n_peaks))   // (zeroed when allocated, kept zero by k_acq_finalize)
-      return rc;
-    ctx->last_kernel = launch_acq_poly(ctx->stream, local_units, prm, static_cast<const uint8_t *>(d_if_blocks), ctx->d_grid_cw8,
-                    ctx->d_grid_bits, ctx->d_acc, ctx->d_acc + n_peaks, n_peaks, d_peaks, shard_count > 1,
-                    ctx->d_energy, block_parallel, ctx->seg_force);
-    if (hipPeekAtLastError() != hipSuccess)
-      ctx->acc_entries = 0;     // (as above: stale partial sums must not reach the next call)
-    LAUNCHCHK(ctx, "k_acq_poly");
-  } else {
-    launch_acq(ctx->stream, kAcqGroup, local_units, prm, static_cast<const uint8_t *>(d_if_blocks), ctx->d_grid_cw8,
-               ctx->d_grid_bits);
-    LAUNCHCHK(ctx, "k_acq");
-    ctx->last_kernel = g->n_ms > 1 ? "k_acq<8,true,dot8>" : "k_acq<8,false,dot8>";
-  }
-  if (d_keys) {
-    launch_acq_keys(ctx->stream, d_peaks, d_keys, g->n_search, g->n_prn, n_groups, g->n_dopp, n_bits, (int)unit_lo,
-                    (int)unit_hi);
+  const AcqParams prm{.n_ms = g->n_ms, .search_stride_blocks = g->search_stride_blocks, .n_prn = g->n_prn, .n_groups = plan.n_groups,
+                      .n_dopp = g->n_dopp, .dopp_min_hz = g->dopp_min_hz, .dopp_step_hz = g->dopp_step_hz, .n_bits = n_bits,
+                      .unit_lo = (int32_t)plan.unit_lo, .unit_hi = (int32_t)plan.unit_hi, .win_start = g->win_start,
+                      .win_stop = g->win_stop, .if_format = ctx->if_format, .if_hz = ctx->if_hz, .split_segs = plan.split_segs,
+                      .n_clusters = plan.c_hi - plan.c_lo, .n_planes = plan.n_peaks, .jobs = nullptr, .peaks = d_peaks,
+                      .keys = plan.keys_in_kernels ? d_keys : nullptr, .per_ms = d_per_ms, .energy = d_energy, .cnt = d_cnt};
+  const uint8_t *d_if = static_cast<const uint8_t *>(d_if_blocks);
+  ctx->last_kernel = plan.name;
+  if (plan.mx)
+    launch_acq_mx(ctx->stream, plan, prm, d_if, ctx->d_grid_mx_a, ctx->d_grid_mx_t, ctx->d_acc, ctx->d_energy);
+  else if (plan.form == AcqForm::kDot8)
+    launch_acq(ctx->stream, kAcqGroup, local_units, prm, d_if, ctx->d_grid_cw8, ctx->d_grid_bits);
+  else
+    launch_acq_poly(ctx->stream, plan, prm, d_if, ctx->d_grid_cw8, ctx->d_grid_bits, ctx->d_acc, ctx->d_energy);
+  if (plan.planes && hipPeekAtLastError() != hipSuccess)
+    ctx->acc_entries = 0;   // a launch between the merging kernels and finalize failed: the planes may hold partial sums --
+                            // the next use allocates and zeroes them afresh (ensure_acc)
+  LAUNCHCHK(ctx, plan.mx ? "k_acq_mx" : plan.form == AcqForm::kDot8 ? "k_acq" : "k_acq_poly");
+  if (d_keys && plan.keys_kernel) {
+    launch_acq_keys(ctx->stream, d_peaks, d_keys, g->n_search, g->n_prn, plan.n_groups, g->n_dopp, n_bits, (int)plan.unit_lo,
+                    (int)plan.unit_hi);
     LAUNCHCHK(ctx, "k_acq_keys");
   }
   return GPSX_OK;
@@ -1095,7 +1028,7 @@ int gpsx_acq_grid_weighted_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, cons
   if (int rc = check_weighted(ctx, g, n_blocks)) return rc;
   if (!d_if_blocks_2bit || !d_peaks)
     return fail(ctx, GPSX_EINVAL, "null device pointer");
-  if (ctx->algo == kAlgoMx) {
+  if (ctx->acq_knobs.algo == kAlgoMx) {
     // the matrix-core form (GPSX_ACQ_PATH_MATRIX, the default): chips from the sign-only grid's tables
     if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
     launch_acq_mxw(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), g->n_search, g->search_stride_blocks, g->n_prn,
@@ -1170,7 +1103,7 @@ int gpsx_set_acq_path(gpsx_ctx *ctx, int path)
     return GPSX_EINVAL;
   if (path != GPSX_ACQ_PATH_MATRIX && path != GPSX_ACQ_PATH_VECTOR)
     return fail(ctx, GPSX_EINVAL, "unknown acquisition path");
-  ctx->algo = path == GPSX_ACQ_PATH_VECTOR ? kAlgoPoly : kAlgoMx;
+  ctx->acq_knobs.algo = path == GPSX_ACQ_PATH_VECTOR ? kAlgoPoly : kAlgoMx;
   return GPSX_OK;
 }
 

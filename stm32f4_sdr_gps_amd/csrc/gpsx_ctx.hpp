@@ -60,19 +60,13 @@ struct gpsx_ctx {
   uint32_t *d_loop_n_events = nullptr;          // the kernel's event counter: DEVICE memory (copied back with the event list)
   gpsx::gpsx_loop_reseed_t *d_loop_cand = nullptr;    // the candidates of one replay pass, uploaded in one piece
   int if_hz = GPSX_IF_HZ;             // gpsx_config_t.if_hz
-  int algo = gpsx::kAlgoMx;                // $GPSX_ACQ_ALGO = mx (default: the matrix-core kernel, at every launch size) | poly |
-                                           // dot8, for A/B measurements and the parity tests of the alternative kernels
-  uint32_t *d_acc = nullptr;         // poly: packed-key and sum planes merged across workgroups
+  gpsx::AcqKnobs acq_knobs;          // the acquisition path (gpsx_set_acq_path) and the lab knobs that force a kernel form
+  uint32_t *d_acc = nullptr;         // the planes of a plan: packed-key and sum planes merged across workgroups
   size_t acc_entries = 0;
-  int seg_force = 0;                 // $GPSX_ACQ_SEG = 4 | 8 | 16: the polyphase kernel at that many offsets per workgroup (tests, A/B);
-                                     // implies $GPSX_ACQ_ALGO=poly unless another algorithm was named
   int track_wave_from = 1;           // $GPSX_TRACK_WAVE_FROM: channels from which k_track_epl_wave serves the step (default: always;
                                      // a large value selects the workgroup-per-channel kernel: tests, A/B)
   bool in_chunk_callback = false;    // set around the on_chunk calls of gpsx_track_epl_batch_chunked: entry points refuse re-entry
-  int split_force = 0;               // $GPSX_ACQ_SPLIT: workgroups per cluster of the split form (2, 4, 8; 0 = by launch size)
-  bool no_split = false;             // $GPSX_ACQ_NO_SPLIT: small single-block fine grids stay one workgroup per cluster (tests, A/B)
-  int ms_mode = 0;                   // $GPSX_ACQ_MS_MODE = walk | blocks: force one multi-block form (tests, A/B); 0 = by size
-  uint32_t *d_energy = nullptr;      // poly, n_ms > 1: running per-hypothesis sums between blocks (grow-only)
+  uint32_t *d_energy = nullptr;      // a plan's energy_bytes: the multi-block forms' scratch between blocks (grow-only)
   size_t energy_bytes = 0;
   // grouped tables for the PRN list of the last grid call
   std::vector<uint8_t> grid_prns;

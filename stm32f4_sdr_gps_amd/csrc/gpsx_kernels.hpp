@@ -7,21 +7,11 @@
 #include <vector>
 
 #include "../../include/gpsx.h"
+#include "gpsx_acq_plan.hpp"
 
 namespace gpsx {
 
-constexpr int kAcqGroup = 8;      // PRNs per accumulator set (one main-loop pass) in the grid kernel
-constexpr int kSuperGroups = 1;   // groups per sharding unit: a unit is (search, Doppler bin, 8-PRN group) -- 84 units per
-                                  // 32 PRN x 21 Doppler search, SURVEY.md 8(e).  Unit index u = (search * n_dopp + dopp) *
-                                  // n_groups + group (group fastest); shard r of W owns the contiguous run
-                                  // [r * U / W, (r + 1) * U / W) -- balanced to one unit, and the four groups of a
-                                  // (search, Doppler) pair stay on one GPU (the matrix-core kernel sweeps 32 PRNs at once)
 constexpr int kCodeWords = 256;   // 4-chip code words per PRN (1023 chips + 1 masked pad)
-constexpr int kMaxMs = 128;       // keeps (energy << 11 | phase) and the window sum inside 32 bits
-constexpr int kAlgoDot8 = 1;      // main loop: v_dot8_u32_u4 on 4-bit block sums, 8 chips per instruction
-constexpr int kAlgoPoly = 2;      // fine grid only: polyphase recurrence across the 16 sample offsets, AND + popcount
-constexpr int kAlgoMx = 4;        // the same recurrence as a Toeplitz GEMM on the matrix cores, MX-FP4: the default at every
-                                  // launch size, for fine grids and single-block byte-phase grids without inspection outputs
 
 // One search = one workgroup pass: `count` (<= group size) consecutive code-table slots, one carrier frequency,
 // one replica bit shift, n_ms consecutive blocks.
@@ -44,7 +34,7 @@ struct AcqParams {
   int32_t win_start, win_stop;
   int32_t if_format;        // GPSX_IF_1BIT / GPSX_IF_2BIT_SM
   int32_t if_hz;            // gpsx_config_t.if_hz: centre of the Doppler axis
-  // set by launch_acq_mx for its own forms:
+  // from the plan (gpsx_acq_plan.hpp), read by the k_acq_mx forms named:
   int32_t split_segs;       //   k_acq_mx<5>: workgroups per cluster (2, 4 or 8)
   int32_t n_clusters;       //   k_acq_mx<4>: clusters of the launch (one persistent workgroup per CU walks them)
   uint64_t n_planes;        //   k_acq_mx<5>: entries per result plane (packed keys [0, n), sums [n, 2 n) behind `energy`)
@@ -69,46 +59,20 @@ void launch_build_codes(hipStream_t s, const uint8_t *d_prns, int n_slots, int g
 // list; local_units = jobs).  d_cw8: the cw8 table of launch_build_codes.
 void launch_acq(hipStream_t s, int group, long local_units, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
                 const uint32_t *d_chipbits);
-// Polyphase variant for phase_mode FINE, no inspection outputs (k_acq_poly.hip).  n_ms > 1 needs d_energy:
-// acq_poly_energy_bytes(local_units) of scratch for the running per-hypothesis sums between blocks.  d_keyacc / d_sumacc: two
-// u32 scratch planes of n_peaks entries, used (zeroed, merged with atomics, converted into d_peaks) only when the launch
-// is split into two 8-offset workgroups per chip; the one-workgroup-per-chip form writes d_peaks directly.
-// Returns the name of the dominant kernel it launched (for gpsx_last_kernel / bench reports).
-const char *launch_acq_poly(hipStream_t s, long local_units, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
-                     const uint32_t *d_chipbits, uint32_t *d_keyacc, uint32_t *d_sumacc, size_t n_peaks,
-                     gpsx_peak_t *d_peaks, bool peaks_are_zero, uint32_t *d_energy, bool block_parallel,
-                     int seg_force);
-// scratch of the block-parallel multi-block form: every block's magnitudes, u16 per hypothesis
-inline size_t acq_poly_vals_bytes(int n_search, int n_ms, int n_prn, int n_dopp)
-{
-  return (size_t)n_search * n_ms * n_prn * n_dopp * 16 * 1024 * sizeof(uint16_t);
-}
-inline size_t acq_poly_energy_bytes(long local_units)
-{
-  return (size_t)local_units * kSuperGroups * kAcqGroup * 16 * 1024 * sizeof(uint32_t);
-}
-// Matrix-core variant (k_acq_mx.hip): phase_mode FINE, no inspection outputs; one 512-thread workgroup per (search, Doppler,
-// 32 PRN slots).  Tables: mx_a [sets][4096] A fragments, mx_t [sets][1032] transposed chip words (launch_build_mx_tables).
-// n_ms > 1 needs d_energy = acq_mx_energy_bytes(clusters) of scratch.
+// The fine grid (and k_acq_mx's byte-phase grid) without inspection outputs: plan_acq (gpsx_acq_plan.hpp) decides the form, its
+// grids and scratch; these launchers issue the plan's launch sequence.  d_planes: 2 * plan.n_peaks u32 (keys, then sums; all-zero
+// between launches: k_acq_finalize* puts back what it reads), d_energy: plan.energy_bytes.  d_peaks = prm.peaks.
+// Polyphase variant (k_acq_poly.hip): AND + popcount recurrence across the 16 sample offsets.
+void launch_acq_poly(hipStream_t s, const AcqPlan &plan, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
+                     const uint32_t *d_chipbits, uint32_t *d_planes, uint32_t *d_energy);
+// Matrix-core variant (k_acq_mx.hip): one 512-thread workgroup per (search, Doppler, 32 PRN slots).  Tables: mx_a [sets][4096]
+// A fragments, mx_t [sets][1032] transposed chip words (launch_build_mx_tables).
 void launch_build_mx_tables(hipStream_t s, const uint32_t *d_chipbits, int n_slots, uint32_t *d_mx_a, uint32_t *d_mx_t);
-long acq_mx_clusters(const AcqParams &prm);
-constexpr size_t kMxZeroRecBytes = 16384;          // a tile-row's worth of all-zero records in front of the flags: what the walk
-                                                   // forms "read back" in the first block of a search (16 offsets x ... of the
-                                                   // same addresses: 4 tiles x 64 lanes x 4 groups x 12 B = 12 KB, rounded up)
-inline size_t acq_mx_energy_bytes(long clusters)   // per workgroup: 8 waves x 16 offsets x 4 tiles x 4 groups x 64 lanes x 12 B
-{                                                  // (the 24-bit records of the fallback form), + the zero records + one overflow flag
-  return (size_t)clusters * 8 * (16 * 4 * 4 * 64) * 12 + kMxZeroRecBytes + (size_t)clusters * 4;
-}
-// block_parallel (n_ms > 1): a workgroup per (cluster, block) writes magnitudes into d_energy (acq_poly_vals_bytes of it, u16),
-// k_acq_vals_search sums and searches -- the form for a handful of multi-block searches
-// d_planes (may be null): 2 * n_peaks u32 of scratch; with it, single-block fine grids of at most n_cus / 2 clusters run as two
-// workgroups per cluster (sample offsets 0..7 / 8..15) that merge through the planes + k_acq_finalize ("k_acq_mx<5>")
+void launch_acq_mx(hipStream_t s, const AcqPlan &plan, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_mx_a,
+                   const uint32_t *d_mx_t, uint32_t *d_planes, uint32_t *d_energy);
 void launch_acq_finalize_from(hipStream_t s, uint32_t *d_keyacc, uint32_t *d_sumacc, size_t first, size_t n_peaks,
                               gpsx_peak_t *d_peaks, int n_prn, int n_dopp, int n_bits, int n_sets, int cluster_from,
                               int64_t *d_keys_opt = nullptr);   // d_keys_opt (n_bits = 8): the packed keys as well
-const char *launch_acq_mx(hipStream_t s, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_mx_a,
-                          const uint32_t *d_mx_t, gpsx_peak_t *d_peaks, uint32_t *d_energy, bool block_parallel, size_t n_peaks,
-                          uint32_t *d_planes, int n_cus, bool *keys_done);
 void launch_acq_vals_search(hipStream_t s, const AcqParams &prm, const uint16_t *d_vals, gpsx_peak_t *d_peaks, size_t n_peaks);
 void launch_acq_finalize(hipStream_t s, uint32_t *d_keyacc, uint32_t *d_sumacc, size_t n_peaks,
                          gpsx_peak_t *d_peaks, int64_t *d_keys_opt = nullptr);

@@ -103,7 +103,6 @@ __global__ __launch_bounds__(kThreads, MULTI ? 2 : 3) void k_acq(const AcqParams
                                                            const u32 *__restrict__ cw8, const u32 *__restrict__ chipbits)
 {
   constexpr int kSteps = kCodeWords / 2;   // 8 chips per main-loop step
-  static_assert(kSuperGroups == 1, "a workgroup serves one G-PRN group: the sharding unit");
   __shared__ AcqShared<G> sh;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -548,7 +547,7 @@ void launch_acq(hipStream_t s, int group, long local_units, const AcqParams &prm
   if (local_units <= 0)
     return;
   if (group == kAcqGroup)
-    launch_acq_t<kAcqGroup>(s, (int)(local_units * prm.n_bits * kSuperGroups), prm, d_if, d_cw8, d_chipbits);
+    launch_acq_t<kAcqGroup>(s, (int)(local_units * prm.n_bits), prm, d_if, d_cw8, d_chipbits);
   else   // job list: one PRN, one workgroup per job
     launch_acq_t<1>(s, (int)local_units, prm, d_if, d_cw8, d_chipbits);
 }

@@ -1929,109 +1929,45 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mx(const AcqParams prm, i
   }
 }
 
-// clusters that intersect this shard's run of units
-static void mx_cluster_range(const AcqParams &prm, int *c_lo, int *c_hi)
+// plan_acq (gpsx_acq_plan.hpp) decides the form, its grids and split_segs (in prm); this issues its launch sequence
+void launch_acq_mx(hipStream_t s, const AcqPlan &p, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_mx_a,
+                   const uint32_t *d_mx_t, uint32_t *d_planes, uint32_t *d_energy)
 {
-  const int n_sets = (prm.n_groups + 3) / 4;
-  auto cluster_of = [&](int unit) { return (unit / prm.n_groups) * n_sets + (unit % prm.n_groups) / 4; };
-  *c_lo = cluster_of(prm.unit_lo);
-  *c_hi = cluster_of(prm.unit_hi - 1) + 1;
-}
-
-long acq_mx_clusters(const AcqParams &prm)
-{
-  if (prm.unit_hi <= prm.unit_lo)
-    return 0;
-  int c_lo, c_hi;
-  mx_cluster_range(prm, &c_lo, &c_hi);
-  return c_hi - c_lo;
-}
-
-const char *launch_acq_mx(hipStream_t s, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_mx_a,
-                          const uint32_t *d_mx_t, gpsx_peak_t *d_peaks, uint32_t *d_energy, bool block_parallel, size_t n_peaks,
-                          uint32_t *d_planes, int n_cus, bool *keys_done)
-{
-  *keys_done = false;   // true: every key of the launch was written by the kernels themselves (prm.keys)
-  if (prm.unit_hi <= prm.unit_lo)
-    return "";
-  int c_lo, c_hi;
-  mx_cluster_range(prm, &c_lo, &c_hi);
-  if (prm.n_ms > 1 && block_parallel) {
-    hipLaunchKernelGGL(k_acq_mx<kMxStore>, dim3((unsigned)((c_hi - c_lo) * prm.n_ms)), dim3(kMxThreads), 0, s, prm, c_lo, d_if,
-                       d_mx_a, d_mx_t, d_peaks, d_energy, (u32 *)nullptr);
-    launch_acq_vals_search(s, prm, reinterpret_cast<const uint16_t *>(d_energy), d_peaks, n_peaks);
-    return "k_acq_mx<2>";
-  }
-  if (prm.n_ms > 1) {
-    // 16-bit running sums first; where they cannot overflow (n_ms x 11573 < 2^16) that is all, otherwise the 24-bit form
-    // follows and redoes the clusters whose flag went up.  The flags sit behind the records.
-    const unsigned n_wg = (unsigned)(c_hi - c_lo);
-    u32 *d_flags = d_energy + acq_mx_energy_bytes(n_wg) / sizeof(u32) - n_wg;
+  if (p.c_hi <= p.c_lo)
+    return;
+  const dim3 grid((unsigned)p.grid), block(kMxThreads);
+  gpsx_peak_t *d_peaks = prm.peaks;
+  switch (p.form) {
+  case AcqForm::kMxStore:
+    hipLaunchKernelGGL(k_acq_mx<kMxStore>, grid, block, 0, s, prm, p.c_lo, d_if, d_mx_a, d_mx_t, d_peaks, d_energy, (u32 *)nullptr);
+    launch_acq_vals_search(s, prm, reinterpret_cast<const uint16_t *>(d_energy), d_peaks, p.n_peaks);
+    break;
+  case AcqForm::kMxWalk: {
+    u32 *d_flags = d_energy + acq_mx_energy_bytes(p.grid) / sizeof(u32) - p.grid;   // (the flags sit behind the records)
     (void)hipMemsetAsync(d_flags - kMxZeroRecBytes / sizeof(u32), 0, kMxZeroRecBytes, s);   // the first block's "previous sums"
-    hipLaunchKernelGGL(k_acq_mx<kMxWalk16>, dim3(n_wg), dim3(kMxThreads), 0, s, prm, c_lo, d_if, d_mx_a, d_mx_t, d_peaks,
-                       d_energy, d_flags);
-    if (prm.n_ms * 11573 > 65535)
-      hipLaunchKernelGGL(k_acq_mx<kMxWalk>, dim3(n_wg), dim3(kMxThreads), 0, s, prm, c_lo, d_if, d_mx_a, d_mx_t, d_peaks,
-                         d_energy, d_flags);
-    *keys_done = prm.keys != nullptr;
-    return "k_acq_mx<3>";
+    hipLaunchKernelGGL(k_acq_mx<kMxWalk16>, grid, block, 0, s, prm, p.c_lo, d_if, d_mx_a, d_mx_t, d_peaks, d_energy, d_flags);
+    if (p.walk24)   // redoes the clusters whose flag went up
+      hipLaunchKernelGGL(k_acq_mx<kMxWalk>, grid, block, 0, s, prm, p.c_lo, d_if, d_mx_a, d_mx_t, d_peaks, d_energy, d_flags);
+    break;
   }
-  if (prm.n_bits == 1) {   // byte-phase grid: sample offsets 0 and 8, each started from its own block sums
-    AcqParams bp = prm;
-    bp.n_clusters = c_hi - c_lo;
-    // one software pipeline per persistent workgroup; a workgroup keeps ONE PRN set's tables: the grid is a multiple of n_sets
-    const int n_sets = (prm.n_groups + 3) / 4;
-    const int grid = bp.n_clusters < n_cus ? bp.n_clusters : n_cus - n_cus % n_sets;
-    hipLaunchKernelGGL(k_acq_mx<kMxByte>, dim3((unsigned)grid), dim3(kMxThreads), 0, s, bp, c_lo, d_if, d_mx_a, d_mx_t, d_peaks,
-                       (u32 *)nullptr, (u32 *)nullptr);
-    *keys_done = prm.keys != nullptr;
-    return "k_acq_mx<4>";
+  case AcqForm::kMxByte:
+    hipLaunchKernelGGL(k_acq_mx<kMxByte>, grid, block, 0, s, prm, p.c_lo, d_if, d_mx_a, d_mx_t, d_peaks, (u32 *)nullptr,
+                       (u32 *)nullptr);
+    break;
+  case AcqForm::kMxSplit:
+    hipLaunchKernelGGL(k_acq_mx<kMxSplit>, grid, block, 0, s, prm, p.c_lo, d_if, d_mx_a, d_mx_t, d_peaks, d_planes, (u32 *)nullptr);
+    launch_acq_finalize(s, d_planes, d_planes + p.n_peaks, p.n_peaks, d_peaks, prm.keys);
+    break;
+  default:   // kMxSingle, and kMxTail's full rounds (their workgroups write their keys in their folds, k_acq_finalize_from the tail's)
+    hipLaunchKernelGGL(k_acq_mx<kMxSingle>, grid, block, 0, s, prm, p.c_lo, d_if, d_mx_a, d_mx_t, d_peaks, (u32 *)nullptr,
+                       (u32 *)nullptr);
+    if (p.form != AcqForm::kMxTail)
+      break;
+    hipLaunchKernelGGL(k_acq_mx<kMxSplit>, dim3((unsigned)p.grid_tail), block, 0, s, prm, p.c_tail, d_if, d_mx_a, d_mx_t, d_peaks,
+                       d_planes, (u32 *)nullptr);
+    launch_acq_finalize_from(s, d_planes, d_planes + p.n_peaks, p.first_peak, p.n_peaks, d_peaks, prm.n_prn, prm.n_dopp,
+                             prm.n_bits, (prm.n_groups + 3) / 4, p.c_tail, prm.keys);
   }
-  if (d_planes && 2 * (c_hi - c_lo) <= n_cus) {
-    // fewer clusters than half the chip (a lone cold start is 21): two workgroups per cluster with eight sample offsets each,
-    // four with four each from a quarter of the chip down
-    AcqParams sp = prm;
-    const int nc = c_hi - c_lo;
-    sp.split_segs = 8 * nc <= n_cus ? 8 : 4 * nc <= n_cus ? 4 : 2;   // (a lone cold start: 21 clusters -> 168 workgroups)
-    if (prm.split_segs)   // ($GPSX_ACQ_SPLIT, read when the context was created: 2, 4 or 8 whatever the launch size -- tests, A/B)
-      sp.split_segs = prm.split_segs;
-    sp.n_planes = n_peaks;   // (the planes are all-zero between launches: k_acq_finalize puts back what it reads)
-    hipLaunchKernelGGL(k_acq_mx<kMxSplit>, dim3((unsigned)(sp.split_segs * (c_hi - c_lo))), dim3(kMxThreads), 0, s, sp, c_lo, d_if,
-                       d_mx_a, d_mx_t, d_peaks, d_planes, (u32 *)nullptr);
-    launch_acq_finalize(s, d_planes, d_planes + n_peaks, n_peaks, d_peaks, prm.n_bits == 8 ? prm.keys : nullptr);
-    *keys_done = prm.n_bits == 8 && prm.keys != nullptr;
-    return "k_acq_mx<5>";
-  }
-  // One workgroup per cluster and CU: a launch is rounds of n_cus clusters, and a last round that fills at most half of the
-  // chip takes as long as a full one.  Then the full rounds go out as they are and the leftover clusters in the split form
-  // behind them -- 2, 4 or 8 workgroups per cluster, as many as still fit ONE round, each with a run of sample offsets it
-  // starts directly (16 captures = 336 clusters: 256 + 80 x 2; 64 captures = 1344: 1280 + 64 x 4).
-  const int nc = c_hi - c_lo, tail = nc % n_cus;
-  if (d_planes && nc > n_cus && tail > 0 && 2 * tail <= n_cus) {
-    const int c_tail = c_hi - tail;
-    hipLaunchKernelGGL(k_acq_mx<kMxSingle>, dim3((unsigned)(nc - tail)), dim3(kMxThreads), 0, s, prm, c_lo, d_if, d_mx_a, d_mx_t,
-                       d_peaks, (u32 *)nullptr, (u32 *)nullptr);
-    AcqParams sp = prm;
-    sp.split_segs = 8 * tail <= n_cus ? 8 : 4 * tail <= n_cus ? 4 : 2;
-    if (prm.split_segs && prm.split_segs * tail <= n_cus)   // $GPSX_ACQ_SPLIT here too, as long as the tail still fits one round
-      sp.split_segs = prm.split_segs;
-    sp.n_planes = n_peaks;
-    // the planes of the tail's peaks only: from the first peak of the search the tail begins in
-    const int n_sets = (prm.n_groups + 3) / 4;
-    const size_t per_search = (size_t)prm.n_prn * prm.n_dopp * prm.n_bits;
-    const size_t first = (size_t)(c_tail / (n_sets * prm.n_dopp)) * per_search;
-    // (no memset: the planes are all-zero between launches, k_acq_finalize* puts back what it reads)
-    hipLaunchKernelGGL(k_acq_mx<kMxSplit>, dim3((unsigned)(sp.split_segs * tail)), dim3(kMxThreads), 0, s, sp, c_tail, d_if,
-                       d_mx_a, d_mx_t, d_peaks, d_planes, (u32 *)nullptr);
-    launch_acq_finalize_from(s, d_planes, d_planes + n_peaks, first, n_peaks, d_peaks, prm.n_prn, prm.n_dopp, prm.n_bits, n_sets,
-                             c_tail, prm.n_bits == 8 ? prm.keys : nullptr);
-    *keys_done = prm.n_bits == 8 && prm.keys != nullptr;   // (the full rounds' workgroups wrote theirs in their folds)
-    return "k_acq_mx<0>";
-  }
-  hipLaunchKernelGGL(k_acq_mx<kMxSingle>, dim3((unsigned)(c_hi - c_lo)), dim3(kMxThreads), 0, s, prm, c_lo, d_if, d_mx_a, d_mx_t,
-                     d_peaks, (u32 *)nullptr, (u32 *)nullptr);
-  *keys_done = prm.keys != nullptr;
-  return "k_acq_mx<0>";
 }
 
 // =============================================================================================================================

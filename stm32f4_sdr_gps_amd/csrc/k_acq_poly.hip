@@ -235,15 +235,13 @@ __global__ __launch_bounds__(kThreads, MODE == kPolyMulti ? 2 : 3) void k_acq_po
   int id = blockIdx.x;
   const int seg = id % kSegs;
   id /= kSegs;
-  const int gsel = id % kSuperGroups;
-  id /= kSuperGroups;
   const int ms_store = STORE ? id % prm.n_ms : 0;
   const int unit_local = STORE ? id / prm.n_ms : id;
   const int unit = prm.unit_lo + unit_local;
   const int t = unit / prm.n_groups;
   const int dopp = t % prm.n_dopp;
   const int search = t / prm.n_dopp;
-  const int group = unit % prm.n_groups + gsel;
+  const int group = unit % prm.n_groups;
   if (group >= prm.n_groups)
     return;
   const int slot0 = group * G;
@@ -664,57 +662,38 @@ void launch_acq_finalize_from(hipStream_t s, uint32_t *d_keyacc, uint32_t *d_sum
                      first, n_peaks, d_peaks, n_prn, n_dopp, n_bits, n_sets, cluster_from, d_keys_opt);
 }
 
-const char *launch_acq_poly(hipStream_t s, long local_units, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
-                     const uint32_t *d_chipbits, uint32_t *d_keyacc, uint32_t *d_sumacc, size_t n_peaks,
-                     gpsx_peak_t *d_peaks, bool peaks_are_zero, uint32_t *d_energy, bool block_parallel,
-                     int seg_force)
+// plan_acq (gpsx_acq_plan.hpp) decides the form, its offsets per workgroup and its grid; this issues its launch sequence
+void launch_acq_poly(hipStream_t s, const AcqPlan &p, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
+                     const uint32_t *d_chipbits, uint32_t *d_planes, uint32_t *d_energy)
 {
-  if (local_units <= 0 || n_peaks == 0)
-    return "";
-  if (prm.n_ms > 1 && block_parallel) {
-    // Few multi-block searches: a workgroup per (unit, block) instead of per unit walking its blocks, the blocks'
-    // magnitudes through HBM (d_energy holds them as u16), one more small kernel to sum and search them.  Eight-offset
-    // workgroups when that is still a small launch: no merge is needed here, every hypothesis is stored on its own.
-    const long wg16 = local_units * kSuperGroups * prm.n_ms;
-    if (wg16 >= 6 * 768)
-      hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 16, kPolyStore>), dim3((unsigned)wg16), dim3(kThreads), 0, s, prm, d_if, d_cw8,
-                         d_chipbits, d_keyacc, d_sumacc, d_peaks, d_energy);
+  if (p.unit_hi <= p.unit_lo || p.n_peaks == 0)
+    return;
+  const dim3 grid((unsigned)p.grid), block(kThreads);
+  uint32_t *d_keyacc = d_planes, *d_sumacc = d_planes + p.n_peaks;
+  gpsx_peak_t *d_peaks = prm.peaks;
+  if (p.form == AcqForm::kPolyStore) {
+    if (p.seg == 16)
+      hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 16, kPolyStore>), grid, block, 0, s, prm, d_if, d_cw8, d_chipbits, d_keyacc,
+                         d_sumacc, d_peaks, d_energy);
     else
-      hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 8, kPolyStore>), dim3((unsigned)(wg16 * 2)), dim3(kThreads), 0, s, prm, d_if,
-                         d_cw8, d_chipbits, d_keyacc, d_sumacc, d_peaks, d_energy);
-    hipLaunchKernelGGL(k_acq_vals_search, dim3((unsigned)(n_peaks / 8)), dim3(kThreads), 0, s, prm,
-                       reinterpret_cast<const uint16_t *>(d_energy), d_peaks);
-    return wg16 >= 6 * 768 ? "k_acq_poly<8,16,2>" : "k_acq_poly<8,8,2>";
+      hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 8, kPolyStore>), grid, block, 0, s, prm, d_if, d_cw8, d_chipbits, d_keyacc,
+                         d_sumacc, d_peaks, d_energy);
+    launch_acq_vals_search(s, prm, reinterpret_cast<const uint16_t *>(d_energy), d_peaks, p.n_peaks);
+  } else if (p.form == AcqForm::kPolyWalk) {
+    hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 16, kPolyMulti>), grid, block, 0, s, prm, d_if, d_cw8, d_chipbits, d_keyacc,
+                       d_sumacc, d_peaks, d_energy);
+  } else if (p.seg == 16) {
+    hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 16, kPolySingle>), grid, block, 0, s, prm, d_if, d_cw8, d_chipbits, d_keyacc,
+                       d_sumacc, d_peaks, (u32 *)nullptr);
+  } else {
+    if (p.seg == 4)
+      hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 4, kPolySingle>), grid, block, 0, s, prm, d_if, d_cw8, d_chipbits, d_keyacc,
+                         d_sumacc, d_peaks, (u32 *)nullptr);
+    else
+      hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 8, kPolySingle>), grid, block, 0, s, prm, d_if, d_cw8, d_chipbits, d_keyacc,
+                         d_sumacc, d_peaks, (u32 *)nullptr);
+    launch_acq_finalize(s, d_keyacc, d_sumacc, p.n_peaks, d_peaks);
   }
-  if (prm.n_ms > 1) {
-    // Non-coherent integration: always one workgroup per chip -- the energies of a (PRN, Doppler) pair then have one
-    // owner, which walks the blocks itself and keeps the running sums in its own 64 KB-per-PRN slice of d_energy.
-    hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 16, kPolyMulti>), dim3((unsigned)(local_units * kSuperGroups)), dim3(kThreads), 0,
-                       s, prm, d_if, d_cw8, d_chipbits, d_keyacc, d_sumacc, d_peaks, d_energy);
-    return "k_acq_poly<8,16,1>";
-  }
-  // One workgroup per chip (16 offsets: one direct step + 15 recurrence steps; results merged in LDS and written once)
-  // when that still leaves several waves of workgroups per CU slot; otherwise two (8 offsets each) or, for launches of
-  // a capture or two, four (4 offsets each), merged through global atomics on two scratch planes and converted by
-  // k_acq_finalize -- balance and latency against the extra direct steps.
-  const long wg16 = local_units * kSuperGroups;
-  const int seg = seg_force ? seg_force : (wg16 >= 6 * 768 ? 16 : (wg16 >= 768 ? 8 : 4));   // ($GPSX_ACQ_SEG forces one)
-  if (seg == 16) {
-    (void)peaks_are_zero;   // units of other shards keep whatever the caller zeroed
-    hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 16, kPolySingle>), dim3((unsigned)wg16), dim3(kThreads), 0, s, prm, d_if, d_cw8,
-                       d_chipbits, d_keyacc, d_sumacc, d_peaks, (u32 *)nullptr);
-    return "k_acq_poly<8,16,0>";
-  }
-  // (d_sumacc = d_keyacc + n_peaks; the planes are all-zero between launches: k_acq_finalize puts back what it reads)
-  if (seg == 4)
-    hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 4, kPolySingle>), dim3((unsigned)(wg16 * 4)), dim3(kThreads), 0, s, prm, d_if, d_cw8,
-                       d_chipbits, d_keyacc, d_sumacc, d_peaks, (u32 *)nullptr);
-  else
-    hipLaunchKernelGGL((k_acq_poly<kAcqGroup, 8, kPolySingle>), dim3((unsigned)(wg16 * 2)), dim3(kThreads), 0, s, prm, d_if, d_cw8,
-                       d_chipbits, d_keyacc, d_sumacc, d_peaks, (u32 *)nullptr);
-  hipLaunchKernelGGL(k_acq_finalize, dim3((unsigned)((n_peaks + 255) / 256)), dim3(256), 0, s, d_keyacc, d_sumacc, n_peaks,
-                     d_peaks, (int64_t *)nullptr);
-  return seg == 4 ? "k_acq_poly<8,4,0>" : "k_acq_poly<8,8,0>";
 }
 
 }  // namespace gpsx
