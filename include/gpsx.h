@@ -27,7 +27,8 @@ extern "C" {
 #define GPSX_VERSION            110        /* 0.1.1: gpsx_loop_state_t is 120 bytes (96 up to 0.1.0), flag bit 7 = "served" is new and
                                             * gps_tracking_words_batch skips flag bytes without it, the product library reads no
                                             * $GPSX_ACQ_* / $GPSX_TRACK_WAVE_FROM knobs (lib/libgpsx_lab.so does).  A host built against an
-                                            * older header must not run on this library: call gpsx_abi_check once at start-up. */
+                                            * older header must not run on this library: call gpsx_abi_check once at start-up.
+                                            * gpsx_acq_grid_weighted_ms(_dev) came later in 0.1.1: new entry points, no layout change. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -283,6 +284,25 @@ int gpsx_acq_grid_weighted_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, cons
                                gpsx_peak_t *d_peaks);
 int gpsx_acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const uint8_t *if_blocks_2bit, int n_blocks,
                            gpsx_peak_t *peaks);
+/* The same grid over n_ms blocks per search, summed NON-coherently:
+ *   search s reads blocks s * search_stride_blocks + b for b = 0 .. n_ms-1 (4092-byte blocks whatever the context's IF format;
+ *                  stride 0 and overlapping searches are legal); the call needs (n_search-1)*stride + n_ms <= n_blocks
+ *   m_b(tau)       = floor(sqrt(I_b(tau)^2 + Q_b(tau)^2)) for every fine phase tau in [0, 16368): the one-block definition above
+ *                  applied to block b -- the reference's NCO on the sign plane with phase 0 at EACH block's start, the sixteen
+ *                  unmixed samples at weight 0, the replica circular, both GPSX_WEIGHTS_* modes
+ *   E(tau)         = sum_b m_b(tau), exact (at most 128 x 69375 < 2^24; one block's m is at most floor(sqrt(2) 49056) = 69375)
+ *   record         max_val = max_tau E(tau); phase = the SMALLEST tau reaching max_val; sum = sum_tau E(tau) mod 2^32 (what u32
+ *                  adds give in any order); avr = sum / 16368 -- peaks[n_search][n_prn][n_dopp], as the one-block call
+ * n_ms runs from 1 to 128; n_ms out of range, too few blocks and whatever the one-block call refuses return GPSX_EINVAL (with a
+ * gpsx_last_error text) and write nothing.  n_ms == 1 gives records byte-identical to gpsx_acq_grid_weighted (and runs its
+ * kernels).  Matrix cores (k_acq_wmx_ms: k_acq_mxw's passes per block, running sums in a grow-only HBM scratch of the context,
+ * 2 MB per cluster of 32 PRNs in flight, launched in chunks of clusters; GPSX_ENOMEM if not even one cluster's scratch can be
+ * had) or, under GPSX_ACQ_PATH_VECTOR, the vector ALU (k_acq_weighted_ms: running sums in registers, no scratch): the same
+ * records, bit for bit. */
+int gpsx_acq_grid_weighted_ms_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_ms,
+                                  const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks);
+int gpsx_acq_grid_weighted_ms(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_ms,
+                              const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks);
 
 /* ---- K2+K3+K5: Early/Prompt/Late tracking correlators  (replaces the correlator part of
  *      gps_tracking_data_process, PM/GPS/tracking.c:115-138, for n_ch channels at once) ------------------------- */

@@ -58,16 +58,24 @@ def check_no_scratch() -> dict:
     instance spills to scratch memory is refused here, not discovered as a slow kernel on the GPU box."""
     res = kernel_resources()
     mx = {k: v for k, v in res.items() if "k_acq_mx" in k}
+    # ... the weighted grid's multi-block matrix-core kernel beside them (its own name: the counts above are k_acq_mx's)
+    wmx = {k: v for k, v in res.items() if "k_acq_wmx" in k}
+    if len(wmx) != 1:
+        raise RuntimeError(f"expected k_acq_wmx_ms in build/k_acq_mx.o, found {sorted(wmx)}")
     if not mx:
         raise RuntimeError("no k_acq_mx kernels found in build/k_acq_mx.o's code object metadata")
     # ... and the device tracking loops, whose occupancy (three waves per SIMD: 168 VGPRs) is asked for by __launch_bounds__
     loops = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop.o")).items() if "k_track_loop" in k}
     if len(loops) != 4:
         raise RuntimeError(f"expected four k_track_loop instances, found {sorted(loops)}")
-    bad = {k: v for k, v in {**mx, **loops}.items() if v["scratch_bytes"] != 0}
+    # ... and the weighted grid's vector-ALU kernels (k_acq_weighted_ms keeps 32 running sums per thread in registers)
+    wv = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_acq_weighted.o")).items() if "k_acq_weighted" in k}
+    if len(wv) != 2:
+        raise RuntimeError(f"expected k_acq_weighted and k_acq_weighted_ms, found {sorted(wv)}")
+    bad = {k: v for k, v in {**mx, **wmx, **loops, **wv}.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")
-    return {**mx, **loops}
+    return {**mx, **wmx, **loops, **wv}
 
 
 if __name__ == "__main__":

@@ -41,6 +41,7 @@ struct AcqKnobs {
   int split = 0;          // $GPSX_ACQ_SPLIT: workgroups per cluster of the split form (2, 4, 8; 0 = by launch size)
   bool no_split = false;  // $GPSX_ACQ_NO_SPLIT: small single-block fine grids stay one workgroup per cluster
   int ms_mode = 0;        // $GPSX_ACQ_MS_MODE = walk (1) | blocks (2): force one multi-block form; 0 = by size
+  int wms_scratch_mb = 0; // $GPSX_ACQ_WMS_SCRATCH_MB: cap on the weighted multi-block walk's scratch per launch (0 = the default)
 };
 
 struct AcqShape {
@@ -189,6 +190,78 @@ inline AcqPlan plan_acq(const AcqShape &g, const AcqKnobs &k, int n_cus, int ref
   }
   if (units <= 0 && p.form != AcqForm::kDot8)
     p.name = "";   // (nothing of the grid is this shard's: nothing is launched)
+  return p;
+}
+
+// ---- the weighted two-bit grid (gpsx_acq_grid_weighted_ms; n_ms = 1 is gpsx_acq_grid_weighted) ------------------------------
+// The matrix-core walk (k_acq_wmx_ms): a workgroup per cluster (search, Doppler bin, 32-PRN set) walks the search's blocks and keeps
+// its running sums E(tau) as u32 in HBM between them: 16 sample offsets x 8 waves x 16 (tile, quad of PRN rows) x 64 lanes x 16 B.
+constexpr size_t kMxwMsClusterBytes = (size_t)16 * 8 * 16 * 64 * 16;   // 2 MB per cluster in flight
+constexpr int kWmsScratchMbDefault = 2048;                               // 1024 clusters per launch: four rounds of 256 CUs
+
+struct AcqWShape {
+  int n_search, n_ms, n_prn, n_dopp;
+  bool vector;                 // GPSX_ACQ_PATH_VECTOR
+};
+
+enum class AcqWForm {
+  kMxw,        // k_acq_mxw: one block (n_ms = 1), a workgroup per cluster
+  kMxwWalk,    // k_acq_wmx_ms: a workgroup per cluster walks n_ms blocks, running sums through HBM scratch, in chunks of clusters
+  kVec,        // k_acq_weighted: one block, a workgroup per (search, Doppler, 8 PRNs)
+  kVecMs,      // k_acq_weighted_ms: the same workgroups, running sums in registers (no scratch)
+};
+
+struct AcqWPlan {
+  AcqWForm form;
+  bool mx;
+  bool enomem;           // not even one cluster's scratch could be had: GPSX_ENOMEM
+  long units;            // clusters (matrix) or workgroups (vector) of the whole call
+  long chunk;            // units per launch (the last launch takes the rest)
+  int n_chunks;
+  long grid;             // workgroups of a full chunk's launch
+  size_t scratch_bytes;  // HBM scratch (gpsx_ctx::d_energy) of one chunk, 0: none
+  const char *name;      // gpsx_last_kernel
+};
+
+// `refused`: how many scratch requests of this call were refused so far -- each halves the chunk.
+inline AcqWPlan plan_acq_weighted(const AcqWShape &g, const AcqKnobs &k, int n_cus, int refused)
+{
+  AcqWPlan p{};
+  p.mx = !g.vector;
+  if (!p.mx) {
+    // vector ALU: the running sums of a thread's 4 chip offsets x 8 PRNs stay in registers; blocks inner, sample offsets outer
+    p.form = g.n_ms == 1 ? AcqWForm::kVec : AcqWForm::kVecMs;
+    p.units = (long)g.n_search * g.n_dopp * ((g.n_prn + 7) / 8);
+    p.chunk = p.grid = p.units;
+    p.n_chunks = 1;
+    p.name = g.n_ms == 1 ? "k_acq_weighted" : "k_acq_weighted_ms";
+    return p;
+  }
+  p.units = (long)g.n_search * g.n_dopp * ((g.n_prn + 31) / 32);
+  if (g.n_ms == 1) {
+    p.form = AcqWForm::kMxw;
+    p.chunk = p.grid = p.units;
+    p.n_chunks = 1;
+    p.name = "k_acq_mxw";
+    return p;
+  }
+  p.form = AcqWForm::kMxwWalk;
+  p.name = "k_acq_wmx_ms";
+  // a chunk: as many clusters as the cap holds, whole rounds of the chip when that is at least one (a launch is rounds of one
+  // workgroup per CU), never more than the call has; every refusal halves it
+  const size_t cap = (size_t)(k.wms_scratch_mb > 0 ? k.wms_scratch_mb : kWmsScratchMbDefault) << 20;
+  long chunk = (long)(cap / kMxwMsClusterBytes);
+  if (chunk >= n_cus)
+    chunk -= chunk % n_cus;
+  chunk = chunk < p.units ? chunk : p.units;
+  chunk = refused < 62 ? chunk >> refused : 0;
+  if (chunk < 1) {
+    p.enomem = true;
+    return p;
+  }
+  p.chunk = p.grid = chunk;
+  p.n_chunks = (int)((p.units + chunk - 1) / chunk);
+  p.scratch_bytes = (size_t)chunk * kMxwMsClusterBytes;
   return p;
 }
 

@@ -107,6 +107,14 @@ int launch_acq_weighted(hipStream_t s, const uint8_t *d_if_blocks, int n_search,
 // the same grid on the matrix cores (k_acq_mx.hip: k_acq_mxw): d_mx_a = the chip tables of the sign-only grid (launch_build_mx_tables)
 void launch_acq_mxw(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_prn, const uint32_t *d_mx_a,
                     int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp, int use_magnitude, gpsx_peak_t *d_peaks);
+// gpsx_acq_grid_weighted_ms (plan_acq_weighted): clusters [cluster_lo, + n_clusters) walk n_ms blocks each, d_scratch = n_clusters x
+// kMxwMsClusterBytes (k_acq_wmx_ms) / the vector-ALU form, running sums in registers (k_acq_weighted_ms; -1: LDS size refused)
+void launch_acq_mxw_ms(hipStream_t s, const uint8_t *d_if_blocks, int stride_blocks, int n_ms, int n_prn, const uint32_t *d_mx_a, int if_hz,
+                       int dopp_min_hz, int dopp_step_hz, int n_dopp, int use_magnitude, int cluster_lo, int n_clusters, void *d_scratch,
+                       gpsx_peak_t *d_peaks);
+int launch_acq_weighted_ms(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_ms, int n_prn,
+                           const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                           int use_magnitude, gpsx_peak_t *d_peaks);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -2214,6 +2214,82 @@ __device__ __forceinline__ void mxw_epilogue(MxShared &sh, int lane, int q0_tile
   }
 }
 
+// one block into the workgroup: the two bit planes, the wipe-off, the magnitude planes, the streams' totals, the first two vectors --
+// k_acq_wmx_ms's per-block preamble, k_acq_mxw's own written out (a shared helper changed k_acq_mxw's register allocation: the
+// single-block kernel keeps its instructions); the caller's LDS writes before it are ordered by its first barrier
+__device__ __forceinline__ void mxw_block_start(MxwShared &shw, const uint8_t *blk, int use_magnitude, u32 step_word, int tid, int lane)
+{
+  MxShared &sh = shw.s;
+  mx_load_block(sh, blk, GPSX_IF_2BIT_SM, tid);
+  for (int w = tid; w < 514; w += kMxThreads) {
+    u32 m = 0;
+    if (use_magnitude && w < 512) {
+#pragma unroll
+      for (int hh = 0; hh < 2; hh++) {
+        const int w16 = 2 * w + hh;
+        if (w16 < kWords16) {
+          const uint16_t *p = reinterpret_cast<const uint16_t *>(blk) + 2 * w16;
+          m |= even_bits16(((u32)p[0] | ((u32)p[1] << 16)) >> 1) << (16 * hh);
+        }
+      }
+    }
+    shw.mag[w] = m;
+  }
+  if (tid < 2)
+    shw.wsum[tid] = 0;
+  __syncthreads();
+  if (tid == 0)
+    shw.mag[511] |= shw.mag[0] << 16;                    // the stream wraps to sample 0 (as s.d's word 511)
+  mx_wipe_block(sh, step_word, tid, lane);
+  // ---- magnitude planes (first period), the weighted part of the streams' totals, the first two vectors -----------------------
+  for (int m = tid; m < 32 * 16; m += kMxThreads) {
+    const int t0 = m & 15, w = m >> 4;
+    const u32 *src = &shw.mag[16 * w];
+    u32 bits = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const u32 sk = src[k];
+      bits |= ((sk >> t0) & 1u) << (2 * k);
+      bits |= ((sk >> (16 + t0)) & 1u) << (2 * k + 1);
+    }
+    shw.mplane[t0][w] = bits;
+  }
+  {
+    int part_i = 0, part_q = 0;
+    for (int w = tid; w < kWords32; w += kMxThreads) {
+      const u32 m = shw.mag[w];
+      part_i += 2 * (int)__popc(sh.d[0][w] & m) - (int)__popc(m);
+      part_q += 2 * (int)__popc(sh.d[1][w] & m) - (int)__popc(m);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      part_i += __shfl_xor(part_i, off);
+      part_q += __shfl_xor(part_q, off);
+    }
+    if (lane == 0) {
+      atomicAdd(&shw.wsum[0], part_i);
+      atomicAdd(&shw.wsum[1], part_q);
+    }
+  }
+  mxw_build_start(shw, 0, 0, tid);
+  mxw_build_start(shw, 1, 1, tid);
+  __syncthreads();
+  for (int m = tid; m < 16 * (kPlaneWordsMx - 32); m += kMxThreads) {   // circular extension, as mx_wipe_block's
+    const int w = 32 + m % (kPlaneWordsMx - 32);
+    const int r = m / (kPlaneWordsMx - 32);
+    const u32 *pl = shw.mplane[r];
+    const int pos = 32 * w - (w >= 64 ? 2 * kChips : kChips);
+    const int lo = pos >> 5;
+    u32 v = __builtin_amdgcn_alignbit(lo < 31 ? pl[lo + 1] : 0u, pl[lo], (u32)(pos & 31));
+    if (pos + 32 > kChips) {
+      const int k = kChips - pos;
+      v = (v & ((1u << k) - 1u)) | (pl[0] << k);
+    }
+    shw.mplane[r][w] = v;
+  }
+
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mxw(const uint8_t *__restrict__ if_blocks, int stride_blocks, int n_prn,
@@ -2391,6 +2467,212 @@ void launch_acq_mxw(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int
   const int n_sets = (n_prn + 31) / 32;
   hipLaunchKernelGGL(k_acq_mxw, dim3((unsigned)(n_search * n_dopp * n_sets)), dim3(kMxThreads), 0, s, d_if_blocks, stride_blocks,
                      n_prn, d_mx_a, if_hz, dopp_min_hz, dopp_step_hz, n_dopp, use_magnitude, d_peaks);
+}
+
+// =============================================================================================================================
+// EXTENSION, not in the reference: the weighted grid over n_ms blocks summed non-coherently (include/gpsx.h
+// gpsx_acq_grid_weighted_ms):  E(tau) = sum_b floor(sqrt(I_b(tau)^2 + Q_b(tau)^2)),  then max / first phase / sum of E.
+// Form: k_acq_mxw's workgroup (a cluster: search, Doppler bin, 32 PRNs) walks the search's blocks -- per block the same
+// preamble (mxw_block_start), passes and exact roots as the single-block kernel.  A block's roots go into running sums E kept
+// in HBM (u32: 128 x 69375 < 2^24): record layout per wave [sample offset][tile][quad of PRN rows][lane] as uint4, one
+// contiguous kilobyte per wave instruction; the first block reads none, the last writes none and folds E instead -- into
+// 64-bit keys (E << 14 | 16383 - tau: E needs up to 24 bits, the single-block kernel's 32-bit keys hold 21) and u32 sums, one
+// slot per (PRN, lane) in the LDS of the single-block kernel's result slots.  Records are requested half a tile ahead.
+namespace {
+
+constexpr int kWmsRecsPerWave = 16 * 64;    // uint4 per (sample offset, wave): 4 tiles x 4 quads x 64 lanes
+
+// half a tile's records (quads 2 hh, 2 hh + 1 of tile j: eight PRN rows) of this lane
+__device__ __forceinline__ void wmxms_request(const uint4 *__restrict__ rec, int half, int lane, uint4 (&r)[2])
+{
+#pragma unroll
+  for (int c = 0; c < 2; c++)
+    r[c] = rec[(half * 2 + c) * 64 + lane];
+}
+
+// the epilogue of sample offset t0 in halves of a tile (eight PRN rows): the next half's records are requested before this
+// one's roots (nothing is held across the MFMA pass: 8 more registers there spilled)
+__device__ __forceinline__ void wmxms_epilogue(MxShared &sh, int lane, int q0_tile, int t0, const v16f (&acc)[2][kMxTiles],
+                                               uint4 *__restrict__ rec, bool first, bool last)
+{
+  asm volatile("" : "+v"(lane));   // (its addresses are worked out here, not hoisted into registers held across the passes)
+  uint4 pre[2];
+  if (!first)
+    wmxms_request(rec, 0, lane, pre);
+  const int n = lane & 31, h = lane >> 5;
+  const bool last_exists = 32 * (q0_tile + 2 * (kMxTiles - 1)) + n < kChips;   // chip offset 1023 does not exist
+  // result slots (last block): u64 keys [32 PRNs][32 lanes] in the first 8 KB of s.part, u32 sums behind them
+  unsigned long long *key_slot = reinterpret_cast<unsigned long long *>(&sh.part[0][0][0][0]) + 4 * h * 32 + n;
+  u32 *sum_slot = &sh.part[0][0][0][0] + 2048 + 4 * h * 32 + n;
+#pragma unroll
+  for (int hf = 0; hf < 2 * kMxTiles; hf++) {
+    const int j = hf >> 1, r0 = 8 * (hf & 1);
+    uint4 nxt[2];
+    if (!first && hf + 1 < 2 * kMxTiles)
+      wmxms_request(rec, hf + 1, lane, nxt);
+    float lim = 0.0f;
+#pragma unroll
+    for (int r = r0; r < r0 + 8; r++)
+      lim = mxw_max_abs(lim, acc[0][j][r], acc[1][j][r]);
+    const bool small = __builtin_amdgcn_ballot_w64(lim >= 2896.0f) == 0;
+    u32 e[8];
+    if (small) {
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        e[i] = mxw_root_small(acc[0][j][r0 + i], acc[1][j][r0 + i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        e[i] = mxw_root_exact((int)acc[0][j][r0 + i], (int)acc[1][j][r0 + i]);
+    }
+    const bool exists = j < kMxTiles - 1 || last_exists;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+      e[i] = exists ? e[i] : 0u;
+    if (!first) {
+#pragma unroll
+      for (int c = 0; c < 2; c++) {
+        e[4 * c + 0] += pre[c].x;
+        e[4 * c + 1] += pre[c].y;
+        e[4 * c + 2] += pre[c].z;
+        e[4 * c + 3] += pre[c].w;
+      }
+    }
+    if (!last) {
+#pragma unroll
+      for (int c = 0; c < 2; c++)
+        rec[(hf * 2 + c) * 64 + lane] = make_uint4(e[4 * c], e[4 * c + 1], e[4 * c + 2], e[4 * c + 3]);
+    } else {
+      const int q = 32 * (q0_tile + 2 * j) + n;
+      const unsigned long long low = exists ? (unsigned long long)(16383 - (16 * q + t0)) : 0ull;
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const int r = r0 + i, p = (r & 3) + 8 * (r >> 2);  // PRN p + 4 h of the cluster
+        const unsigned long long key = exists ? ((unsigned long long)e[i] << 14) | low : 0ull;
+        atomicMax(&key_slot[p * 32], key);
+        atomicAdd(&sum_slot[p * 32], e[i]);
+      }
+    }
+    if (!first && hf + 1 < 2 * kMxTiles) {
+#pragma unroll
+      for (int c = 0; c < 2; c++)
+        pre[c] = nxt[c];
+    }
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kMxThreads, 1) void k_acq_wmx_ms(const uint8_t *__restrict__ if_blocks, int stride_blocks, int n_ms, int n_prn,
+                                                              const u32 *__restrict__ mx_a, int if_hz, int dopp_min_hz, int dopp_step_hz,
+                                                              int n_dopp, int use_magnitude, int cluster_lo, uint4 *__restrict__ scratch,
+                                                              gpsx_peak_t *__restrict__ peaks)
+{
+  __shared__ MxwShared shw;
+  MxShared &sh = shw.s;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int role = wave >> 2;
+  const int q0_tile = 8 * (wave >> 1) + (wave & 1);
+  const int n_sets = (n_prn + 31) / 32;
+  const int cluster = cluster_lo + (int)blockIdx.x;
+  const int set = cluster % n_sets, sd = cluster / n_sets, dopp = sd % n_dopp, search = sd / n_dopp;
+  const u32 step_word = nco_step_per_word((float)(if_hz + dopp_min_hz + dopp * dopp_step_hz));
+  // this workgroup's running sums: [sample offset][wave] slices of kWmsRecsPerWave records
+  uint4 *const recs = scratch + (size_t)blockIdx.x * (16 * 8 * kWmsRecsPerWave) + (size_t)wave * kWmsRecsPerWave;
+
+  {
+    const u32 *src_a = mx_a + (size_t)set * (16 * 2 * 32 * 4);
+    u32 *dst_a = reinterpret_cast<u32 *>(&sh.chips_a[0][0][0]);
+    for (int i = tid; i < 16 * 2 * 32 * 4; i += kMxThreads)
+      dst_a[i] = src_a[i];
+  }
+  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
+    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
+  mxw_fill_table(sh, tid);
+  const v4i no_corr = v4i{0, 0, 0, 0};
+#pragma unroll 1
+  for (int b = 0; b < n_ms; b++) {
+    const bool first = b == 0, last = b == n_ms - 1;
+    if (!first)
+      __syncthreads();   // (the previous block's passes and vectors are done with the planes)
+    // (the preamble's addresses derive from an opaque copy of the thread index: hoisted out of the block loop they stayed live
+    //  across every pass and spilled)
+    int tid_b = tid, lane_b = lane;
+    asm volatile("" : "+v"(tid_b), "+v"(lane_b));
+    mxw_block_start(shw, if_blocks + ((size_t)search * stride_blocks + b) * GPSX_BYTES_PER_MS_2BIT, use_magnitude, step_word, tid_b, lane_b);
+    v16f acc[2][kMxTiles];
+    {
+      const float t_i = (float)(2 * (int)sh.ones[0] - 32 * kWords32 + 2 * shw.wsum[0]);
+      const float t_q = (float)(2 * (int)sh.ones[1] - 32 * kWords32 + 2 * shw.wsum[1]);
+#pragma unroll
+      for (int j = 0; j < kMxTiles; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          acc[0][j][r] = t_i;
+          acc[1][j][r] = t_q;
+        }
+    }
+    // k_acq_mxw's schedule of passes, epilogues and vector builds
+#pragma unroll 1
+    for (int hs = 0; hs <= 2 * kWPasses; hs++) {
+      if ((hs & 1) == 0)
+        __syncthreads();
+      const int x = hs - role;
+      const bool active = x >= 0 && x < 2 * kWPasses;
+      const int p = x >> 1;
+      if (active && (x & 1) == 0)
+        mx_pass<true, kMxTiles, kScaleOne>(sh, p & 1, lane, q0_tile, acc, p == 0 ? kScaleOne : p == 1 ? kScaleFour : p == 2 ? kScaleSixteen : kScaleTwo,
+                                           no_corr, false);
+      if (active && (x & 1) && p >= 2)
+        wmxms_epilogue(sh, lane, q0_tile, p - 2, acc, recs + (size_t)(p - 2) * 8 * kWmsRecsPerWave, first, last);
+      if (role == 0 && (hs & 1)) {
+        const int p_vec = (hs >> 1) + 1;
+        int tv = tid;
+        asm volatile("" : "+v"(tv));
+        if (p_vec == 2) {
+          mxw_build_start(shw, 2, 0, tv);
+          mxw_build_start(shw, 2, 0, tv + 256);
+        } else if (p_vec > 2 && p_vec < kWPasses) {
+          mxw_build_step(shw, p_vec - 3, p_vec & 1, tv);
+          mxw_build_step(shw, p_vec - 3, p_vec & 1, tv + 256);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // ---- one record per (search, PRN, Doppler): the 32 lanes' slots of each PRN ------------------------------------------------
+  {
+    const int p = tid >> 4, i = tid & 15;                  // 16 threads per PRN, two slots each
+    const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(&sh.part[0][0][0][0]) + p * 32;
+    const u32 *sums = &sh.part[0][0][0][0] + 2048 + p * 32;
+    unsigned long long k = keys[i] > keys[i + 16] ? keys[i] : keys[i + 16];
+    u32 t = sums[i] + sums[i + 16];
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      const u32 lo = __shfl_xor((u32)k, off), hi = __shfl_xor((u32)(k >> 32), off);
+      const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+      k = o > k ? o : k;
+      t += __shfl_xor(t, off);
+    }
+    const int slot = 32 * set + p;
+    if (i == 0 && slot < n_prn) {
+      gpsx_peak_t pk;
+      pk.max_val = (u32)(k >> 14);
+      pk.phase = pk.max_val ? 16383u - (u32)(k & 16383u) : 0u;
+      pk.sum = t;
+      pk.avr = t / (u32)kSamples;
+      peaks[((size_t)search * n_prn + slot) * n_dopp + dopp] = pk;
+    }
+  }
+}
+
+void launch_acq_mxw_ms(hipStream_t s, const uint8_t *d_if_blocks, int stride_blocks, int n_ms, int n_prn, const uint32_t *d_mx_a, int if_hz,
+                       int dopp_min_hz, int dopp_step_hz, int n_dopp, int use_magnitude, int cluster_lo, int n_clusters, void *d_scratch,
+                       gpsx_peak_t *d_peaks)
+{
+  hipLaunchKernelGGL(k_acq_wmx_ms, dim3((unsigned)n_clusters), dim3(kMxThreads), 0, s, d_if_blocks, stride_blocks, n_ms, n_prn, d_mx_a,
+                     if_hz, dopp_min_hz, dopp_step_hz, n_dopp, use_magnitude, cluster_lo, static_cast<uint4 *>(d_scratch), d_peaks);
 }
 
 }  // namespace gpsx

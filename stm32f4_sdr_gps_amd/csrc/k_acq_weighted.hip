@@ -235,4 +235,226 @@ int launch_acq_weighted(hipStream_t s, const uint8_t *d_if_blocks, int n_search,
   return 0;
 }
 
+// ---- EXTENSION: n_ms blocks summed non-coherently (include/gpsx.h gpsx_acq_grid_weighted_ms) ---------------------------------
+//   E(tau) = sum_b floor(sqrt(I_b(tau)^2 + Q_b(tau)^2)),  per record: max of E, the first tau reaching it, the sum of E.
+// The same workgroups and correlation loop as k_acq_weighted, with the loops turned round: sample offset t0 outer, blocks inner.
+// A thread's running sums -- its four chip offsets x eight PRNs, 32 u32 -- stay in registers across the blocks of one t0, and
+// a step builds only that t0's two chip-sum rows of block b (its planes from L2, wiped again: 4 KB and 2 x 1023 windows against
+// 64 v_dot4 x 256 chip words per thread).  No scratch.  Keys are 64-bit: E reaches 128 x 69375 < 2^24.
+namespace {
+
+struct WMsShared {
+  u32 mag[512];                     // the block's magnitude plane (zero in the sign-only mode)
+  u32 d[2][512];                    // its wiped sign planes I / Q
+  u32 sums[2][kSumDwords];          // [stream][k]: int8 chip sums of this step's t0, k = 0 .. 2045
+  u32 chips[kWG][256];
+  unsigned long long best[kWG];
+  u32 total[kWG];
+};
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const u32 lo = __shfl_xor((u32)v, off), hi = __shfl_xor((u32)(v >> 32), off);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kWThreads) void k_acq_weighted_ms(const uint8_t *__restrict__ if_blocks, int stride_blocks, int n_ms, int n_prn,
+                                                               const uint8_t *__restrict__ chips_all, const uint8_t *__restrict__ prns,
+                                                               int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                                                               int use_magnitude, gpsx_peak_t *__restrict__ peaks)
+{
+  extern __shared__ u32 w_smem[];
+  WMsShared &sh = *reinterpret_cast<WMsShared *>(w_smem);
+  const int tid = threadIdx.x;
+  const int n_groups = (n_prn + kWG - 1) / kWG;
+  const int group = (int)blockIdx.x % n_groups, dopp = ((int)blockIdx.x / n_groups) % n_dopp, search = (int)blockIdx.x / (n_groups * n_dopp);
+  const uint8_t *blk0 = if_blocks + (size_t)search * stride_blocks * GPSX_BYTES_PER_MS_2BIT;
+  const u32 step_word = nco_step_per_word((float)(if_hz + dopp_min_hz + dopp * dopp_step_hz));
+
+  for (int i = tid; i < kWG * 256; i += kWThreads) {
+    const int g = i >> 8, c4 = i & 255, p = group * kWG + g;
+    u32 word = 0;
+    if (p < n_prn) {
+      const uint8_t *ch = chips_all + (size_t)prns[p] * 1024;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int c = 4 * c4 + k;
+        const u32 v = c < kChips ? (ch[c] ? 0xFFu : 0x01u) : 0u;
+        word |= v << (8 * k);
+      }
+    }
+    sh.chips[g][c4] = word;
+  }
+  if (tid < kWG) {
+    sh.best[tid] = 0;
+    sh.total[tid] = 0;
+  }
+
+  unsigned long long best[kWG];
+  u32 total[kWG];
+#pragma unroll
+  for (int g = 0; g < kWG; g++) {
+    best[g] = 0;
+    total[g] = 0;
+  }
+#pragma unroll 1
+  for (int t0 = 0; t0 < 16; t0++) {
+    u32 e_sum[4][kWG];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int g = 0; g < kWG; g++)
+        e_sum[j][g] = 0;
+#pragma unroll 1
+    for (int b = 0; b < n_ms; b++) {
+      const uint8_t *blk = blk0 + (size_t)b * GPSX_BYTES_PER_MS_2BIT;
+      __syncthreads();              // (the previous step is done with the planes and rows)
+      // ---- block b's planes, wiped as k_acq_weighted's (word 511: the sixteen unmixed samples, sign zero) -------------------
+      for (int w = tid; w < 512; w += kWThreads) {
+        u32 sg = 0, m = 0;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int w16 = 2 * w + h;
+          if (w16 < kWords16) {
+            const uint16_t *p = reinterpret_cast<const uint16_t *>(blk) + 2 * w16;
+            const u32 pairs = (u32)p[0] | ((u32)p[1] << 16);
+            sg |= even_bits16(pairs) << (16 * h);
+            m |= even_bits16(pairs >> 1) << (16 * h);
+          }
+        }
+        const u32 quad = (step_word * (u32)w) >> 30;
+        sh.mag[w] = use_magnitude ? m : 0u;
+        sh.d[0][w] = w < kWords32 ? sg ^ carrier_i(quad) : 0u;
+        sh.d[1][w] = w < kWords32 ? sg ^ carrier_q(quad) : 0u;
+      }
+      __syncthreads();
+      // ---- this t0's rows of chip sums (as k_acq_weighted's) ---------------------------------------------------------------
+      for (int i = tid; i < 2 * kChips; i += kWThreads) {
+        const int stream = i / kChips, k = i % kChips;
+        const int p = 16 * k + t0;
+        const u32 x = win16(sh.d[stream], p), m = win16(sh.mag, p);
+        u32 v = 0xFFFFu;
+        if (p + 16 > kSamples - 16) {
+          v = 0;
+#pragma unroll
+          for (int j = 0; j < 16; j++) {
+            int n = p + j;
+            n = n >= kSamples ? n - kSamples : n;
+            v |= (n < kSamples - 16 ? 1u : 0u) << j;
+          }
+        }
+        const int s = (2 * (int)__popc(x & v) - (int)__popc(v)) + 2 * (2 * (int)__popc(x & m & v) - (int)__popc(m & v));
+        uint8_t *row = reinterpret_cast<uint8_t *>(sh.sums[stream]);
+        row[k] = (uint8_t)(int8_t)s;
+        row[k + kChips] = (uint8_t)(int8_t)s;
+      }
+      if (tid < 2)
+        reinterpret_cast<uint8_t *>(sh.sums[tid])[2 * kChips] = reinterpret_cast<uint8_t *>(sh.sums[tid])[2 * kChips + 1] = 0;
+      __syncthreads();
+      // ---- the correlations of block b at this t0 ------------------------------------------------------------------------
+      int acc[4][2][kWG];
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int st = 0; st < 2; st++)
+#pragma unroll
+          for (int g = 0; g < kWG; g++)
+            acc[j][st][g] = 0;
+      const u32 *row_i = sh.sums[0], *row_q = sh.sums[1];
+      u32 prev[4][2];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int q = min(tid + 256 * j, kChips - 1);
+        prev[j][0] = row_i[q >> 2];
+        prev[j][1] = row_q[q >> 2];
+      }
+#pragma unroll 2
+      for (int c4 = 0; c4 < 256; c4++) {
+        u32 win[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int q = min(tid + 256 * j, kChips - 1);
+          const u32 nxt_i = row_i[(q >> 2) + c4 + 1], nxt_q = row_q[(q >> 2) + c4 + 1];
+          win[j][0] = __builtin_amdgcn_alignbyte(nxt_i, prev[j][0], (u32)(q & 3));
+          win[j][1] = __builtin_amdgcn_alignbyte(nxt_q, prev[j][1], (u32)(q & 3));
+          prev[j][0] = nxt_i;
+          prev[j][1] = nxt_q;
+        }
+#pragma unroll
+        for (int g = 0; g < kWG; g++) {
+          const u32 cw = sh.chips[g][c4];
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            acc[j][0][g] = __builtin_amdgcn_sdot4((int)win[j][0], (int)cw, acc[j][0][g], false);
+            acc[j][1][g] = __builtin_amdgcn_sdot4((int)win[j][1], (int)cw, acc[j][1][g], false);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int g = 0; g < kWG; g++) {
+          const long long ai = acc[j][0][g], aq = acc[j][1][g];
+          e_sum[j][g] += isqrt_u64((u64)(ai * ai) + (u64)(aq * aq));
+        }
+    }
+    // ---- this offset's sums into the PRNs' running best / sum (tau = 16 q + t0; key = E << 14 | 16383 - tau) ----------------
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int q = tid + 256 * j;
+      if (q >= kChips)
+        continue;
+      const unsigned long long low = 16383u - (u32)(16 * q + t0);
+#pragma unroll
+      for (int g = 0; g < kWG; g++) {
+        const unsigned long long key = ((unsigned long long)e_sum[j][g] << 14) | low;
+        best[g] = key > best[g] ? key : best[g];
+        total[g] += e_sum[j][g];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int g = 0; g < kWG; g++) {
+    const unsigned long long b = wave_max_u64(best[g]);
+    const u32 t = wave_sum_to_lane63(total[g]);
+    if ((tid & 63) == 63) {
+      atomicMax(&sh.best[g], b);
+      atomicAdd(&sh.total[g], t);
+    }
+  }
+  __syncthreads();
+  if (tid < kWG && group * kWG + tid < n_prn) {
+    const unsigned long long key = sh.best[tid];
+    const u32 sum = sh.total[tid];
+    gpsx_peak_t pk;
+    pk.max_val = (u32)(key >> 14);
+    pk.phase = pk.max_val ? 16383u - (u32)(key & 0x3FFFu) : 0u;
+    pk.sum = sum;
+    pk.avr = sum / (u32)kSamples;
+    peaks[((size_t)search * n_prn + group * kWG + tid) * n_dopp + dopp] = pk;
+  }
+}
+
+int launch_acq_weighted_ms(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_ms, int n_prn,
+                           const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                           int use_magnitude, gpsx_peak_t *d_peaks)
+{
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_acq_weighted_ms), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)sizeof(WMsShared)) != hipSuccess)
+    return -1;
+  const int n_groups = (n_prn + kWG - 1) / kWG;
+  hipLaunchKernelGGL(k_acq_weighted_ms, dim3((unsigned)(n_search * n_dopp * n_groups)), dim3(kWThreads), sizeof(WMsShared), s,
+                     d_if_blocks, stride_blocks, n_ms, n_prn, d_chips_all, d_prns, if_hz, dopp_min_hz, dopp_step_hz, n_dopp,
+                     use_magnitude, d_peaks);
+  return 0;
+}
+
 }  // namespace gpsx

@@ -2,7 +2,9 @@
 """The weighted two-bit acquisition extension's kernels alone (device-resident captures, HIP events on the engine's stream):
 searches x 32 PRN x 21 Doppler x 16368 phases per launch, first on the matrix cores (k_acq_mxw), then on the vector ALU
 (k_acq_weighted), and the sign-only fine grid (k_acq_mx<0>) on the same captures' sign plane beside them.
-usage: bench_weighted_kernel.py [searches [reps]]"""
+--n-ms N: the multi-block call instead (gpsx_acq_grid_weighted_ms_dev: k_acq_wmx_ms / k_acq_weighted_ms), N blocks per search, on
+both paths, beside N single-block calls on the same captures (block b of every search: the same hypothesis-blocks), in one process.
+usage: bench_weighted_kernel.py [--n-ms N] [searches [reps]]"""
 import ctypes as C
 import json
 import os
@@ -16,8 +18,14 @@ sys.path.insert(0, ROOT)
 
 def main():
     from stm32f4_sdr_gps_amd import capi, synth
-    searches = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    argv = list(sys.argv[1:])
+    n_ms = 0
+    if "--n-ms" in argv:
+        at = argv.index("--n-ms")
+        n_ms = int(argv[at + 1])
+        del argv[at:at + 2]
+    searches = int(argv[0]) if len(argv) > 0 else 16
+    reps = int(argv[1]) if len(argv) > 1 else 5
     if os.environ.get("GPSX_LIB"):   # A/B runs against another build of the library (tools/build_variant.sh)
         capi.LIB_PATH = capi.LAB_LIB_PATH = os.environ["GPSX_LIB"]
     eng = capi.Engine(0, lab=bool(os.environ.get("GPSX_LIB")))
@@ -43,6 +51,8 @@ def main():
         eng.synchronize()
         return eng.elapsed_ms(e0, e1) / reps
     hyp = searches * 32 * 21 * 16368
+    if n_ms:
+        return multi_block(eng, capi, synth, searches, n_ms, reps, timed)
     for path in (capi.ACQ_PATH_MATRIX, capi.ACQ_PATH_VECTOR):
         eng.set_acq_path(path)
         ms = timed(run)
@@ -70,6 +80,43 @@ def main():
     ms = timed(run_sign)
     print(json.dumps({"kernel": "gpsx::" + eng.lib.gpsx_last_kernel(eng.h).decode(), "searches": searches, "ms": round(ms, 3), "hyp_per_s": hyp / (ms * 1e-3),
                       "note": "the sign-only fine grid, same shape"}))
+
+
+def multi_block(eng, capi, synth, searches, n_ms, reps, timed):
+    blocks = synth.cold_start_block(searches * n_ms, seed=11, amp_scale=0.25, two_bit=True)
+    prns = np.arange(1, 33, dtype=np.uint8)
+    g = capi.AcqWeightedT(searches, n_ms, 32, prns.ctypes.data_as(C.POINTER(C.c_uint8)), -5000, 500, 21, 1)
+    d_if = eng.malloc(blocks.size + 2)
+    eng.h2d(d_if, np.concatenate([blocks.reshape(-1), np.zeros(2, np.uint8)]))
+    d_pk = eng.malloc(searches * 32 * 21 * 16)
+    n_blocks = searches * n_ms
+
+    def run_ms():
+        rc = eng.lib.gpsx_acq_grid_weighted_ms_dev(eng.h, C.byref(g), n_ms, C.c_void_p(d_if), n_blocks, C.c_void_p(d_pk))
+        assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+
+    def run_sweeps():   # block b of every search: the single-block call from byte offset b x 4092, stride n_ms
+        for b in range(n_ms):
+            rc = eng.lib.gpsx_acq_grid_weighted_dev(eng.h, C.byref(g), C.c_void_p(d_if + b * capi.BYTES_PER_MS_2BIT), n_blocks - b,
+                                                    C.c_void_p(d_pk))
+            assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+    hyp_blocks = searches * 32 * 21 * 16368 * n_ms
+    for path in (capi.ACQ_PATH_MATRIX, capi.ACQ_PATH_VECTOR):
+        eng.set_acq_path(path)
+        ms_sweeps = timed(run_sweeps)
+        k_one = eng.lib.gpsx_last_kernel(eng.h).decode()
+        ms_multi = timed(run_ms)
+        k_ms = eng.lib.gpsx_last_kernel(eng.h).decode()
+        line = {"kernel": "gpsx::" + k_ms, "searches": searches, "n_ms": n_ms, "ms": round(ms_multi, 3),
+                "hyp_blocks_per_s": hyp_blocks / (ms_multi * 1e-3), "sweeps_kernel": "gpsx::" + k_one, "sweeps_ms": round(ms_sweeps, 3),
+                "sweeps_hyp_blocks_per_s": hyp_blocks / (ms_sweeps * 1e-3), "ratio": round(ms_multi / ms_sweeps, 3)}
+        if path == capi.ACQ_PATH_MATRIX:
+            # running sums: u32 read and written per hypothesis-block but for the first (no read) and last (no write) block
+            scratch = searches * 32 * 21 * 16384 * 4 * 2 * (n_ms - 1)
+            line.update({"scratch_bytes": scratch, "scratch_bytes_per_hyp_block": scratch / hyp_blocks,
+                         "scratch_tb_per_s": scratch / (ms_multi * 1e-3) / 1e12})
+        print(json.dumps(line))
+    eng.set_acq_path(capi.ACQ_PATH_MATRIX)
 
 
 if __name__ == "__main__":
