@@ -1006,25 +1006,9 @@ int gpsx_track_epl_batch(gpsx_ctx *ctx, const uint8_t *if_block, gpsx_trk_state_
 /* ---- extension: weighted two-bit acquisition grid ------------------------------------------------------------------------ */
 
 namespace {
-int check_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_blocks)
-{
-  if (!g || !g->prns)
-    return fail(ctx, GPSX_EINVAL, "null descriptor");
-  if (g->n_search < 1 || g->n_prn < 1 || g->n_dopp < 1 || g->search_stride_blocks < 0 || g->n_prn > 255)
-    return fail(ctx, GPSX_EINVAL, "bad grid shape");
-  if (g->weights != GPSX_WEIGHTS_SIGN_ONLY && g->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
-    return fail(ctx, GPSX_EINVAL, "unknown weights");
-  if ((long)(g->n_search - 1) * g->search_stride_blocks + 1 > n_blocks)
-    return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
-  for (int i = 0; i < g->n_prn; i++)
-    if (g->prns[i] < 1 || g->prns[i] > GPSX_MAX_PRN)
-      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
-  return GPSX_OK;
-}
-
 // the PRN list behind the vector-ALU kernels: a few bytes through the arena's tail would collide with a host-pointer caller's
 // buffers -- its own small allocation, grow-only
-static int stage_weighted_prns(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g)
+int stage_weighted_prns(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g)
 {
   if (ctx->weighted_prns_cap < g->n_prn) {
     if (ctx->d_weighted_prns) (void)hipFree(ctx->d_weighted_prns);
@@ -1037,124 +1021,119 @@ static int stage_weighted_prns(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g)
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's PRN array is the caller's again)
   return GPSX_OK;
 }
+
+// The four entry points in one.  `ms`: a multi-block call -- n_ms and the block count are checked before the descriptor (the
+// one-block calls pass n_ms = 1 and start with the descriptor); search s reads blocks s * stride .. + n_ms - 1.  `host`: the
+// capture and the records are host memory, staged through the arena.
+int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int n_ms, const void *if_blocks_2bit, int n_blocks,
+                      void *peaks, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (ms && (n_ms < 1 || n_ms > kMaxMs))
+    return fail(ctx, GPSX_EINVAL, "n_ms outside 1..128");
+  if (ms && n_blocks < n_ms)
+    return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
+  if (!g || !g->prns)
+    return fail(ctx, GPSX_EINVAL, "null descriptor");
+  if (g->n_search < 1 || g->n_prn < 1 || g->n_dopp < 1 || g->search_stride_blocks < 0 || g->n_prn > 255)
+    return fail(ctx, GPSX_EINVAL, "bad grid shape");
+  if (g->weights != GPSX_WEIGHTS_SIGN_ONLY && g->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
+    return fail(ctx, GPSX_EINVAL, "unknown weights");
+  if ((long)(g->n_search - 1) * g->search_stride_blocks + n_ms > n_blocks)
+    return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
+  for (int i = 0; i < g->n_prn; i++)
+    if (g->prns[i] < 1 || g->prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+  if (!if_blocks_2bit || !peaks)
+    return fail(ctx, GPSX_EINVAL, host ? "null host pointer" : "null device pointer");
+
+  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, n_peaks = (size_t)g->n_search * g->n_prn * g->n_dopp;
+  const uint8_t *d_if = static_cast<const uint8_t *>(if_blocks_2bit);
+  gpsx_peak_t *d_peaks = static_cast<gpsx_peak_t *>(peaks);
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(n_peaks * sizeof(gpsx_peak_t))))
+      return rc;
+    uint8_t *staged = arena_take<uint8_t>(ctx, if_bytes + 2);
+    d_peaks = arena_take<gpsx_peak_t>(ctx, n_peaks);
+    HIPCHK(ctx, hipMemcpyAsync(staged, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_if = staged;
+  }
+  const int use_magnitude = g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;
+  const int n_cus = ctx->prop.multiProcessorCount;
+  const AcqWShape shape{g->n_search, n_ms, g->n_prn, g->n_dopp, ctx->acq_knobs.algo != kAlgoMx};
+  AcqWPlan plan = plan_acq_weighted(shape, ctx->acq_knobs, n_cus, 0);
+  switch (plan.form) {
+  case AcqWForm::kMxw:
+    // chips from the sign-only grid's tables
+    if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
+    launch_acq_mxw(ctx->stream, d_if, g->n_search, g->search_stride_blocks, g->n_prn, ctx->d_grid_mx_a, ctx->if_hz, g->dopp_min_hz,
+                   g->dopp_step_hz, g->n_dopp, use_magnitude, d_peaks);
+    LAUNCHCHK(ctx, plan.name);
+    break;
+  case AcqWForm::kVec:
+  case AcqWForm::kVecMs: {
+    if (int rc = stage_weighted_prns(ctx, g)) return rc;
+    const int lds_refused =
+        plan.form == AcqWForm::kVec
+            ? launch_acq_weighted(ctx->stream, d_if, g->n_search, g->search_stride_blocks, g->n_prn, ctx->d_chips_all,
+                                  ctx->d_weighted_prns, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, use_magnitude, d_peaks)
+            : launch_acq_weighted_ms(ctx->stream, d_if, g->n_search, g->search_stride_blocks, n_ms, g->n_prn, ctx->d_chips_all,
+                                     ctx->d_weighted_prns, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, use_magnitude, d_peaks);
+    if (lds_refused)
+      return fail(ctx, GPSX_EIO, std::string(plan.name) + ": the kernel's LDS size was refused");
+    LAUNCHCHK(ctx, plan.name);
+    break;
+  }
+  case AcqWForm::kMxwWalk:
+    // running sums in the context's scratch, a chunk of clusters per launch; refused scratch halves the chunk
+    for (int refused = 1;; refused++) {
+      if (plan.enomem)
+        return fail(ctx, GPSX_ENOMEM, "k_acq_wmx_ms: not even one cluster's scratch (2 MB) could be had");
+      bool had = false;
+      if (int rc = ensure_energy(ctx, plan.scratch_bytes, &had)) return rc;
+      if (had)
+        break;
+      plan = plan_acq_weighted(shape, ctx->acq_knobs, n_cus, refused);
+    }
+    if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
+    for (long lo = 0; lo < plan.units; lo += plan.chunk) {
+      const long n = plan.units - lo < plan.chunk ? plan.units - lo : plan.chunk;
+      launch_acq_mxw_ms(ctx->stream, d_if, g->search_stride_blocks, n_ms, g->n_prn, ctx->d_grid_mx_a, ctx->if_hz, g->dopp_min_hz,
+                        g->dopp_step_hz, g->n_dopp, use_magnitude, (int)lo, (int)n, ctx->d_energy, d_peaks);
+      LAUNCHCHK(ctx, plan.name);
+    }
+    break;
+  }
+  ctx->last_kernel = plan.name;
+  if (host) {
+    HIPCHK(ctx, hipMemcpyAsync(peaks, d_peaks, n_peaks * sizeof(gpsx_peak_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GPSX_OK;
+}
 }  // namespace
 
 int gpsx_acq_grid_weighted_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const void *d_if_blocks_2bit, int n_blocks,
                                gpsx_peak_t *d_peaks)
 {
-  if (int rc = use_device(ctx)) return rc;
-  if (int rc = check_weighted(ctx, g, n_blocks)) return rc;
-  if (!d_if_blocks_2bit || !d_peaks)
-    return fail(ctx, GPSX_EINVAL, "null device pointer");
-  if (ctx->acq_knobs.algo == kAlgoMx) {
-    // the matrix-core form (GPSX_ACQ_PATH_MATRIX, the default): chips from the sign-only grid's tables
-    if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
-    launch_acq_mxw(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), g->n_search, g->search_stride_blocks, g->n_prn,
-                   ctx->d_grid_mx_a, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp,
-                   g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, d_peaks);
-    LAUNCHCHK(ctx, "k_acq_mxw");
-    ctx->last_kernel = "k_acq_mxw";
-    return GPSX_OK;
-  }
-  // the vector-ALU form (GPSX_ACQ_PATH_VECTOR)
-  if (int rc = stage_weighted_prns(ctx, g)) return rc;
-  if (launch_acq_weighted(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), g->n_search, g->search_stride_blocks, g->n_prn,
-                          ctx->d_chips_all, ctx->d_weighted_prns, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp,
-                          g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, d_peaks))
-    return fail(ctx, GPSX_EIO, "k_acq_weighted: the kernel's LDS size was refused");
-  LAUNCHCHK(ctx, "k_acq_weighted");
-  ctx->last_kernel = "k_acq_weighted";
-  return GPSX_OK;
+  return acq_grid_weighted(ctx, g, false, 1, d_if_blocks_2bit, n_blocks, d_peaks, false);
 }
 
 int gpsx_acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks)
 {
-  if (int rc = use_device(ctx)) return rc;
-  if (int rc = check_weighted(ctx, g, n_blocks)) return rc;
-  if (!if_blocks_2bit || !peaks)
-    return fail(ctx, GPSX_EINVAL, "null host pointer");
-  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, n_peaks = (size_t)g->n_search * g->n_prn * g->n_dopp;
-  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(n_peaks * sizeof(gpsx_peak_t))))
-    return rc;
-  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
-  gpsx_peak_t *d_peaks = arena_take<gpsx_peak_t>(ctx, n_peaks);
-  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = gpsx_acq_grid_weighted_dev(ctx, g, d_if, n_blocks, d_peaks)) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(peaks, d_peaks, n_peaks * sizeof(gpsx_peak_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return GPSX_OK;
+  return acq_grid_weighted(ctx, g, false, 1, if_blocks_2bit, n_blocks, peaks, true);
 }
 
 int gpsx_acq_grid_weighted_ms_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_ms, const void *d_if_blocks_2bit, int n_blocks,
                                   gpsx_peak_t *d_peaks)
 {
-  if (int rc = use_device(ctx)) return rc;
-  if (n_ms < 1 || n_ms > kMaxMs)
-    return fail(ctx, GPSX_EINVAL, "n_ms outside 1..128");
-  if (n_blocks < n_ms)
-    return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
-  // search s reads blocks s * stride .. + n_ms - 1: the single-block check on the blocks a search can start at
-  if (int rc = check_weighted(ctx, g, n_blocks - (n_ms - 1))) return rc;
-  if (!d_if_blocks_2bit || !d_peaks)
-    return fail(ctx, GPSX_EINVAL, "null device pointer");
-  if (n_ms == 1)
-    return gpsx_acq_grid_weighted_dev(ctx, g, d_if_blocks_2bit, n_blocks, d_peaks);
-  const uint8_t *d_if = static_cast<const uint8_t *>(d_if_blocks_2bit);
-  const int use_magnitude = g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;
-  const int n_cus = ctx->prop.multiProcessorCount;
-  const AcqWShape shape{g->n_search, n_ms, g->n_prn, g->n_dopp, ctx->acq_knobs.algo != kAlgoMx};
-  AcqWPlan plan = plan_acq_weighted(shape, ctx->acq_knobs, n_cus, 0);
-  if (!plan.mx) {
-    if (int rc = stage_weighted_prns(ctx, g)) return rc;
-    if (launch_acq_weighted_ms(ctx->stream, d_if, g->n_search, g->search_stride_blocks, n_ms, g->n_prn, ctx->d_chips_all,
-                               ctx->d_weighted_prns, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, use_magnitude, d_peaks))
-      return fail(ctx, GPSX_EIO, "k_acq_weighted_ms: the kernel's LDS size was refused");
-    LAUNCHCHK(ctx, plan.name);
-    ctx->last_kernel = plan.name;
-    return GPSX_OK;
-  }
-  // the matrix-core walk: running sums in the context's scratch, a chunk of clusters per launch; refused scratch halves the chunk
-  for (int refused = 1;; refused++) {
-    if (plan.enomem)
-      return fail(ctx, GPSX_ENOMEM, "k_acq_wmx_ms: not even one cluster's scratch (2 MB) could be had");
-    bool had = false;
-    if (int rc = ensure_energy(ctx, plan.scratch_bytes, &had)) return rc;
-    if (had)
-      break;
-    plan = plan_acq_weighted(shape, ctx->acq_knobs, n_cus, refused);
-  }
-  if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
-  ctx->last_kernel = plan.name;
-  for (long lo = 0; lo < plan.units; lo += plan.chunk) {
-    const long n = plan.units - lo < plan.chunk ? plan.units - lo : plan.chunk;
-    launch_acq_mxw_ms(ctx->stream, d_if, g->search_stride_blocks, n_ms, g->n_prn, ctx->d_grid_mx_a, ctx->if_hz, g->dopp_min_hz,
-                      g->dopp_step_hz, g->n_dopp, use_magnitude, (int)lo, (int)n, ctx->d_energy, d_peaks);
-    LAUNCHCHK(ctx, plan.name);
-  }
-  return GPSX_OK;
+  return acq_grid_weighted(ctx, g, true, n_ms, d_if_blocks_2bit, n_blocks, d_peaks, false);
 }
 
 int gpsx_acq_grid_weighted_ms(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_ms, const uint8_t *if_blocks_2bit, int n_blocks,
                               gpsx_peak_t *peaks)
 {
-  if (int rc = use_device(ctx)) return rc;
-  if (n_ms < 1 || n_ms > kMaxMs)
-    return fail(ctx, GPSX_EINVAL, "n_ms outside 1..128");
-  if (n_blocks < n_ms)
-    return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
-  if (int rc = check_weighted(ctx, g, n_blocks - (n_ms - 1))) return rc;
-  if (!if_blocks_2bit || !peaks)
-    return fail(ctx, GPSX_EINVAL, "null host pointer");
-  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, n_peaks = (size_t)g->n_search * g->n_prn * g->n_dopp;
-  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(n_peaks * sizeof(gpsx_peak_t))))
-    return rc;
-  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
-  gpsx_peak_t *d_peaks = arena_take<gpsx_peak_t>(ctx, n_peaks);
-  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (int rc = gpsx_acq_grid_weighted_ms_dev(ctx, g, n_ms, d_if, n_blocks, d_peaks)) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(peaks, d_peaks, n_peaks * sizeof(gpsx_peak_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return GPSX_OK;
+  return acq_grid_weighted(ctx, g, true, n_ms, if_blocks_2bit, n_blocks, peaks, true);
 }
 
 /* ---- the tracking loops on the device ---------------------------------------------------------------------------------- */

@@ -2214,9 +2214,20 @@ __device__ __forceinline__ void mxw_epilogue(MxShared &sh, int lane, int q0_tile
   }
 }
 
-// one block into the workgroup: the two bit planes, the wipe-off, the magnitude planes, the streams' totals, the first two vectors --
-// k_acq_wmx_ms's per-block preamble, k_acq_mxw's own written out (a shared helper changed k_acq_mxw's register allocation: the
-// single-block kernel keeps its instructions); the caller's LDS writes before it are ordered by its first barrier
+// a cluster's start, before its first block: the 32 PRNs' chips, the result slots zeroed, the difference table
+__device__ __forceinline__ void mxw_cluster_start(MxShared &sh, const u32 *__restrict__ mx_a, int set, int tid)
+{
+  const u32 *src_a = mx_a + (size_t)set * (16 * 2 * 32 * 4);
+  u32 *dst_a = reinterpret_cast<u32 *>(&sh.chips_a[0][0][0]);
+  for (int i = tid; i < 16 * 2 * 32 * 4; i += kMxThreads)
+    dst_a[i] = src_a[i];
+  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
+    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
+  mxw_fill_table(sh, tid);
+}
+
+// one block into the workgroup: the two bit planes, the wipe-off, the magnitude planes, the streams' totals, the first two vectors
+// (the preamble of every block, in both kernels); the caller's LDS writes before it are ordered by its first barrier
 __device__ __forceinline__ void mxw_block_start(MxwShared &shw, const uint8_t *blk, int use_magnitude, u32 step_word, int tid, int lane)
 {
   MxShared &sh = shw.s;
@@ -2287,7 +2298,6 @@ __device__ __forceinline__ void mxw_block_start(MxwShared &shw, const uint8_t *b
     }
     shw.mplane[r][w] = v;
   }
-
 }
 
 }  // namespace
@@ -2308,84 +2318,8 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mxw(const uint8_t *__rest
   const u32 step_word = nco_step_per_word((float)(if_hz + dopp_min_hz + dopp * dopp_step_hz));
   const uint8_t *blk = if_blocks + (size_t)search * stride_blocks * GPSX_BYTES_PER_MS_2BIT;
 
-  // ---- the cluster's chips, the capture's two bit planes -----------------------------------------------------------------
-  {
-    const u32 *src_a = mx_a + (size_t)set * (16 * 2 * 32 * 4);
-    u32 *dst_a = reinterpret_cast<u32 *>(&sh.chips_a[0][0][0]);
-    for (int i = tid; i < 16 * 2 * 32 * 4; i += kMxThreads)
-      dst_a[i] = src_a[i];
-  }
-  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
-    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
-  mxw_fill_table(sh, tid);
-  mx_load_block(sh, blk, GPSX_IF_2BIT_SM, tid);
-  for (int w = tid; w < 514; w += kMxThreads) {
-    u32 m = 0;
-    if (use_magnitude && w < 512) {
-#pragma unroll
-      for (int hh = 0; hh < 2; hh++) {
-        const int w16 = 2 * w + hh;
-        if (w16 < kWords16) {
-          const uint16_t *p = reinterpret_cast<const uint16_t *>(blk) + 2 * w16;
-          m |= even_bits16(((u32)p[0] | ((u32)p[1] << 16)) >> 1) << (16 * hh);
-        }
-      }
-    }
-    shw.mag[w] = m;
-  }
-  if (tid < 2)
-    shw.wsum[tid] = 0;
-  __syncthreads();
-  if (tid == 0)
-    shw.mag[511] |= shw.mag[0] << 16;                    // the stream wraps to sample 0 (as s.d's word 511)
-  mx_wipe_block(sh, step_word, tid, lane);
-  // ---- magnitude planes (first period), the weighted part of the streams' totals, the first two vectors -----------------------
-  for (int m = tid; m < 32 * 16; m += kMxThreads) {
-    const int t0 = m & 15, w = m >> 4;
-    const u32 *src = &shw.mag[16 * w];
-    u32 bits = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const u32 sk = src[k];
-      bits |= ((sk >> t0) & 1u) << (2 * k);
-      bits |= ((sk >> (16 + t0)) & 1u) << (2 * k + 1);
-    }
-    shw.mplane[t0][w] = bits;
-  }
-  {
-    int part_i = 0, part_q = 0;
-    for (int w = tid; w < kWords32; w += kMxThreads) {
-      const u32 m = shw.mag[w];
-      part_i += 2 * (int)__popc(sh.d[0][w] & m) - (int)__popc(m);
-      part_q += 2 * (int)__popc(sh.d[1][w] & m) - (int)__popc(m);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      part_i += __shfl_xor(part_i, off);
-      part_q += __shfl_xor(part_q, off);
-    }
-    if (lane == 0) {
-      atomicAdd(&shw.wsum[0], part_i);
-      atomicAdd(&shw.wsum[1], part_q);
-    }
-  }
-  mxw_build_start(shw, 0, 0, tid);
-  mxw_build_start(shw, 1, 1, tid);
-  __syncthreads();
-  for (int m = tid; m < 16 * (kPlaneWordsMx - 32); m += kMxThreads) {   // circular extension, as mx_wipe_block's
-    const int w = 32 + m % (kPlaneWordsMx - 32);
-    const int r = m / (kPlaneWordsMx - 32);
-    const u32 *pl = shw.mplane[r];
-    const int pos = 32 * w - (w >= 64 ? 2 * kChips : kChips);
-    const int lo = pos >> 5;
-    u32 v = __builtin_amdgcn_alignbit(lo < 31 ? pl[lo + 1] : 0u, pl[lo], (u32)(pos & 31));
-    if (pos + 32 > kChips) {
-      const int k = kChips - pos;
-      v = (v & ((1u << k) - 1u)) | (pl[0] << k);
-    }
-    shw.mplane[r][w] = v;
-  }
-
+  mxw_cluster_start(sh, mx_a, set, tid);
+  mxw_block_start(shw, blk, use_magnitude, step_word, tid, lane);
   v16f acc[2][kMxTiles];
   {
     const float t_i = (float)(2 * (int)sh.ones[0] - 32 * kWords32 + 2 * shw.wsum[0]);
@@ -2401,6 +2335,7 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mxw(const uint8_t *__rest
   const v4i no_corr = v4i{0, 0, 0, 0};
   // steps of two halves, as mx_unit: role 0 runs pass p, then the epilogue of the offset pass p - 1 finished; role 1 the
   // epilogue first, then the pass; one barrier per step.  The vector of pass p + 1 is built during step p by role 0 alone
+  // (k_acq_wmx_ms runs this schedule with its own epilogue: one shared loop changed both kernels' main loops, EXPERIMENTS.md)
 #pragma unroll 1
   for (int hs = 0; hs <= 2 * kWPasses; hs++) {
     if ((hs & 1) == 0)
@@ -2581,15 +2516,7 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_wmx_ms(const uint8_t *__r
   // this workgroup's running sums: [sample offset][wave] slices of kWmsRecsPerWave records
   uint4 *const recs = scratch + (size_t)blockIdx.x * (16 * 8 * kWmsRecsPerWave) + (size_t)wave * kWmsRecsPerWave;
 
-  {
-    const u32 *src_a = mx_a + (size_t)set * (16 * 2 * 32 * 4);
-    u32 *dst_a = reinterpret_cast<u32 *>(&sh.chips_a[0][0][0]);
-    for (int i = tid; i < 16 * 2 * 32 * 4; i += kMxThreads)
-      dst_a[i] = src_a[i];
-  }
-  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
-    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
-  mxw_fill_table(sh, tid);
+  mxw_cluster_start(sh, mx_a, set, tid);
   const v4i no_corr = v4i{0, 0, 0, 0};
 #pragma unroll 1
   for (int b = 0; b < n_ms; b++) {
@@ -2605,15 +2532,15 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_wmx_ms(const uint8_t *__r
     {
       const float t_i = (float)(2 * (int)sh.ones[0] - 32 * kWords32 + 2 * shw.wsum[0]);
       const float t_q = (float)(2 * (int)sh.ones[1] - 32 * kWords32 + 2 * shw.wsum[1]);
-#pragma unroll
+  #pragma unroll
       for (int j = 0; j < kMxTiles; j++)
-#pragma unroll
+  #pragma unroll
         for (int r = 0; r < 16; r++) {
           acc[0][j][r] = t_i;
           acc[1][j][r] = t_q;
         }
     }
-    // k_acq_mxw's schedule of passes, epilogues and vector builds
+    // k_acq_mxw's schedule of passes, epilogues and vector builds (its own copy: one shared loop changed both kernels' main loops)
 #pragma unroll 1
     for (int hs = 0; hs <= 2 * kWPasses; hs++) {
       if ((hs & 1) == 0)

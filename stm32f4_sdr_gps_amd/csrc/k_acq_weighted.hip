@@ -53,6 +53,117 @@ __device__ __forceinline__ u32 isqrt_u64(u64 e)
   return (u32)r;
 }
 
+// the chip signs of the workgroup's eight PRNs: chips 4 i .. 4 i + 3 as int8 x 4, -1 / +1 (chip 1023 does not exist: 0)
+__device__ __forceinline__ void load_chip_words(u32 (&chips)[kWG][256], const uint8_t *chips_all, const uint8_t *prns, int n_prn,
+                                                int group, int tid)
+{
+  for (int i = tid; i < kWG * 256; i += kWThreads) {
+    const int g = i >> 8, c4 = i & 255, p = group * kWG + g;
+    u32 word = 0;
+    if (p < n_prn) {
+      const uint8_t *ch = chips_all + (size_t)prns[p] * 1024;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int c = 4 * c4 + k;
+        const u32 v = c < kChips ? (ch[c] ? 0xFFu : 0x01u) : 0u;
+        word |= v << (8 * k);
+      }
+    }
+    chips[g][c4] = word;
+  }
+}
+
+// word w of the block's sign and magnitude planes (word 511: the last sixteen samples in its low half)
+__device__ __forceinline__ void unpack_planes(const uint8_t *blk, int w, u32 &s, u32 &m)
+{
+  s = 0, m = 0;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int w16 = 2 * w + h;
+    if (w16 < kWords16) {
+      const uint16_t *p = reinterpret_cast<const uint16_t *>(blk) + 2 * w16;
+      const u32 pairs = (u32)p[0] | ((u32)p[1] << 16);
+      s |= even_bits16(pairs) << (16 * h);
+      m |= even_bits16(pairs >> 1) << (16 * h);
+    }
+  }
+}
+
+// chip sum k of sample offset t0 into both copies of its row: S = the sum of the window's sixteen values
+//   = (2 pop(X & V) - pop(V)) + 2 (2 pop(X & M & V) - pop(M & V)),  V = the samples the NCO mixed (bit positions below 16352)
+__device__ __forceinline__ void put_chip_sum(u32 *row, const u32 *d, const u32 *mag, int t0, int k)
+{
+  const int p = 16 * k + t0;                              // < 16368
+  const u32 x = win16(d, p), m = win16(mag, p);
+  // valid bits of the window: positions (p + j) mod 16368 < 16352
+  u32 v = 0xFFFFu;
+  if (p + 16 > kSamples - 16) {
+    v = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      int n = p + j;
+      n = n >= kSamples ? n - kSamples : n;
+      v |= (n < kSamples - 16 ? 1u : 0u) << j;
+    }
+  }
+  const int s = (2 * (int)__popc(x & v) - (int)__popc(v)) + 2 * (2 * (int)__popc(x & m & v) - (int)__popc(m & v));
+  uint8_t *r = reinterpret_cast<uint8_t *>(row);
+  r[k] = (uint8_t)(int8_t)s;
+  r[k + kChips] = (uint8_t)(int8_t)s;
+}
+
+// one sample offset's correlations from its two rows of chip sums (thread tid: chip offsets q = tid + 256 j)
+__device__ __forceinline__ void correlate(int (&acc)[4][2][kWG], const u32 *row_i, const u32 *row_q, const u32 (&chips)[kWG][256], int tid)
+{
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int st = 0; st < 2; st++)
+#pragma unroll
+      for (int g = 0; g < kWG; g++)
+        acc[j][st][g] = 0;
+  u32 prev[4][2];                   // the dword below the window's upper one, per q and stream
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int q = min(tid + 256 * j, kChips - 1);
+    prev[j][0] = row_i[q >> 2];
+    prev[j][1] = row_q[q >> 2];
+  }
+#pragma unroll 2
+  for (int c4 = 0; c4 < 256; c4++) {
+    u32 win[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int q = min(tid + 256 * j, kChips - 1);
+      const u32 nxt_i = row_i[(q >> 2) + c4 + 1], nxt_q = row_q[(q >> 2) + c4 + 1];
+      win[j][0] = __builtin_amdgcn_alignbyte(nxt_i, prev[j][0], (u32)(q & 3));
+      win[j][1] = __builtin_amdgcn_alignbyte(nxt_q, prev[j][1], (u32)(q & 3));
+      prev[j][0] = nxt_i;
+      prev[j][1] = nxt_q;
+    }
+#pragma unroll
+    for (int g = 0; g < kWG; g++) {
+      const u32 cw = chips[g][c4];   // (wave-uniform address: one broadcast read)
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        acc[j][0][g] = __builtin_amdgcn_sdot4((int)win[j][0], (int)cw, acc[j][0][g], false);
+        acc[j][1][g] = __builtin_amdgcn_sdot4((int)win[j][1], (int)cw, acc[j][1][g], false);
+      }
+    }
+  }
+}
+
+// a (search, PRN, Doppler) record from its key (value << 14 | 16383 - tau, the first tau reaching the maximum) and its sum
+__device__ __forceinline__ void put_record(gpsx_peak_t *peak, unsigned long long key, u32 sum)
+{
+  gpsx_peak_t pk;
+  pk.max_val = (u32)(key >> 14);
+  pk.phase = pk.max_val ? 16383u - (u32)(key & 0x3FFFu) : 0u;
+  pk.sum = sum;
+  pk.avr = sum / (u32)kSamples;
+  *peak = pk;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(kWThreads) void k_acq_weighted(const uint8_t *__restrict__ if_blocks, int stride_blocks, int n_prn,
@@ -69,34 +180,12 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted(const uint8_t *__res
 
   // ---- the capture's two bit planes; the PRNs' chip signs ---------------------------------------------------------------
   for (int w = tid; w < 512; w += kWThreads) {
-    u32 s = 0, m = 0;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int w16 = 2 * w + h;
-      if (w16 < kWords16) {
-        const uint16_t *p = reinterpret_cast<const uint16_t *>(blk) + 2 * w16;
-        const u32 pairs = (u32)p[0] | ((u32)p[1] << 16);
-        s |= even_bits16(pairs) << (16 * h);
-        m |= even_bits16(pairs >> 1) << (16 * h);
-      }
-    }
+    u32 s, m;
+    unpack_planes(blk, w, s, m);
     sh.sign[w] = s;
     sh.mag[w] = use_magnitude ? m : 0u;
   }
-  for (int i = tid; i < kWG * 256; i += kWThreads) {
-    const int g = i >> 8, c4 = i & 255, p = group * kWG + g;
-    u32 word = 0;
-    if (p < n_prn) {
-      const uint8_t *ch = chips_all + (size_t)prns[p] * 1024;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int c = 4 * c4 + k;
-        const u32 v = c < kChips ? (ch[c] ? 0xFFu : 0x01u) : 0u;   // -1 / +1 as int8; chip 1023 does not exist
-        word |= v << (8 * k);
-      }
-    }
-    sh.chips[g][c4] = word;
-  }
+  load_chip_words(sh.chips, chips_all, prns, n_prn, group, tid);
   if (tid < kWG) {
     sh.best[tid] = 0;
     sh.total[tid] = 0;
@@ -110,27 +199,10 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted(const uint8_t *__res
     sh.d[1][w] = w < kWords32 ? sh.sign[w] ^ carrier_q(quad) : 0u;
   }
   __syncthreads();
-  // ---- chip sums: S = sum of the window's sixteen values = (2 pop(X & V) - pop(V)) + 2 (2 pop(X & M & V) - pop(M & V)),
-  //      V = the samples the NCO mixed (bit positions below 16352) ---------------------------------------------------------
+  // ---- the 2 x 16 rows of chip sums ----------------------------------------------------------------------------------------
   for (int i = tid; i < 2 * 16 * kChips; i += kWThreads) {
     const int stream = i / (16 * kChips), rest = i % (16 * kChips), t0 = rest / kChips, k = rest % kChips;
-    const int p = 16 * k + t0;                              // < 16368
-    const u32 x = win16(sh.d[stream], p), m = win16(sh.mag, p);
-    // valid bits of the window: positions (p + j) mod 16368 < 16352
-    u32 v = 0xFFFFu;
-    if (p + 16 > kSamples - 16) {
-      v = 0;
-#pragma unroll
-      for (int j = 0; j < 16; j++) {
-        int n = p + j;
-        n = n >= kSamples ? n - kSamples : n;
-        v |= (n < kSamples - 16 ? 1u : 0u) << j;
-      }
-    }
-    const int s = (2 * (int)__popc(x & v) - (int)__popc(v)) + 2 * (2 * (int)__popc(x & m & v) - (int)__popc(m & v));
-    uint8_t *row = reinterpret_cast<uint8_t *>(sh.sums[stream][t0]);
-    row[k] = (uint8_t)(int8_t)s;
-    row[k + kChips] = (uint8_t)(int8_t)s;
+    put_chip_sum(sh.sums[stream][t0], sh.d[stream], sh.mag, t0, k);
   }
   for (int i = tid; i < 2 * 16; i += kWThreads)              // the two pad bytes of every row
     reinterpret_cast<uint8_t *>(sh.sums[i >> 4][i & 15])[2 * kChips] = reinterpret_cast<uint8_t *>(sh.sums[i >> 4][i & 15])[2 * kChips + 1] = 0;
@@ -146,43 +218,7 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted(const uint8_t *__res
 #pragma unroll 1
   for (int t0 = 0; t0 < 16; t0++) {
     int acc[4][2][kWG];
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-      for (int st = 0; st < 2; st++)
-#pragma unroll
-        for (int g = 0; g < kWG; g++)
-          acc[j][st][g] = 0;
-    const u32 *row_i = sh.sums[0][t0], *row_q = sh.sums[1][t0];
-    u32 prev[4][2];                 // the dword below the window's upper one, per q and stream
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int q = min(tid + 256 * j, kChips - 1);
-      prev[j][0] = row_i[q >> 2];
-      prev[j][1] = row_q[q >> 2];
-    }
-#pragma unroll 2
-    for (int c4 = 0; c4 < 256; c4++) {
-      u32 win[4][2];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int q = min(tid + 256 * j, kChips - 1);
-        const u32 nxt_i = row_i[(q >> 2) + c4 + 1], nxt_q = row_q[(q >> 2) + c4 + 1];
-        win[j][0] = __builtin_amdgcn_alignbyte(nxt_i, prev[j][0], (u32)(q & 3));
-        win[j][1] = __builtin_amdgcn_alignbyte(nxt_q, prev[j][1], (u32)(q & 3));
-        prev[j][0] = nxt_i;
-        prev[j][1] = nxt_q;
-      }
-#pragma unroll
-      for (int g = 0; g < kWG; g++) {
-        const u32 cw = sh.chips[g][c4];   // (wave-uniform address: one broadcast read)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          acc[j][0][g] = __builtin_amdgcn_sdot4((int)win[j][0], (int)cw, acc[j][0][g], false);
-          acc[j][1][g] = __builtin_amdgcn_sdot4((int)win[j][1], (int)cw, acc[j][1][g], false);
-        }
-      }
-    }
+    correlate(acc, sh.sums[0][t0], sh.sums[1][t0], sh.chips, tid);
     // ---- this offset's magnitudes into the PRNs' running best / sum (tau = 16 q + t0; key = magnitude << 14 | 16383 - tau) --
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -209,15 +245,8 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted(const uint8_t *__res
     }
   }
   __syncthreads();
-  if (tid < kWG && group * kWG + tid < n_prn) {
-    const u32 key = sh.best[tid], sum = sh.total[tid];
-    gpsx_peak_t pk;
-    pk.max_val = key >> 14;
-    pk.phase = pk.max_val ? 16383u - (key & 0x3FFFu) : 0u;
-    pk.sum = sum;
-    pk.avr = sum / (u32)kSamples;
-    peaks[((size_t)search * n_prn + group * kWG + tid) * n_dopp + dopp] = pk;
-  }
+  if (tid < kWG && group * kWG + tid < n_prn)
+    put_record(&peaks[((size_t)search * n_prn + group * kWG + tid) * n_dopp + dopp], sh.best[tid], sh.total[tid]);
 }
 
 int launch_acq_weighted(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_prn,
@@ -237,7 +266,7 @@ int launch_acq_weighted(hipStream_t s, const uint8_t *d_if_blocks, int n_search,
 
 // ---- EXTENSION: n_ms blocks summed non-coherently (include/gpsx.h gpsx_acq_grid_weighted_ms) ---------------------------------
 //   E(tau) = sum_b floor(sqrt(I_b(tau)^2 + Q_b(tau)^2)),  per record: max of E, the first tau reaching it, the sum of E.
-// The same workgroups and correlation loop as k_acq_weighted, with the loops turned round: sample offset t0 outer, blocks inner.
+// The same workgroups and helpers as k_acq_weighted, with the loops turned round: sample offset t0 outer, blocks inner.
 // A thread's running sums -- its four chip offsets x eight PRNs, 32 u32 -- stay in registers across the blocks of one t0, and
 // a step builds only that t0's two chip-sum rows of block b (its planes from L2, wiped again: 4 KB and 2 x 1023 windows against
 // 64 v_dot4 x 256 chip words per thread).  No scratch.  Keys are 64-bit: E reaches 128 x 69375 < 2^24.
@@ -278,20 +307,7 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted_ms(const uint8_t *__
   const uint8_t *blk0 = if_blocks + (size_t)search * stride_blocks * GPSX_BYTES_PER_MS_2BIT;
   const u32 step_word = nco_step_per_word((float)(if_hz + dopp_min_hz + dopp * dopp_step_hz));
 
-  for (int i = tid; i < kWG * 256; i += kWThreads) {
-    const int g = i >> 8, c4 = i & 255, p = group * kWG + g;
-    u32 word = 0;
-    if (p < n_prn) {
-      const uint8_t *ch = chips_all + (size_t)prns[p] * 1024;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int c = 4 * c4 + k;
-        const u32 v = c < kChips ? (ch[c] ? 0xFFu : 0x01u) : 0u;
-        word |= v << (8 * k);
-      }
-    }
-    sh.chips[g][c4] = word;
-  }
+  load_chip_words(sh.chips, chips_all, prns, n_prn, group, tid);
   if (tid < kWG) {
     sh.best[tid] = 0;
     sh.total[tid] = 0;
@@ -318,85 +334,25 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted_ms(const uint8_t *__
       __syncthreads();              // (the previous step is done with the planes and rows)
       // ---- block b's planes, wiped as k_acq_weighted's (word 511: the sixteen unmixed samples, sign zero) -------------------
       for (int w = tid; w < 512; w += kWThreads) {
-        u32 sg = 0, m = 0;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const int w16 = 2 * w + h;
-          if (w16 < kWords16) {
-            const uint16_t *p = reinterpret_cast<const uint16_t *>(blk) + 2 * w16;
-            const u32 pairs = (u32)p[0] | ((u32)p[1] << 16);
-            sg |= even_bits16(pairs) << (16 * h);
-            m |= even_bits16(pairs >> 1) << (16 * h);
-          }
-        }
+        u32 sg, m;
+        unpack_planes(blk, w, sg, m);
         const u32 quad = (step_word * (u32)w) >> 30;
         sh.mag[w] = use_magnitude ? m : 0u;
         sh.d[0][w] = w < kWords32 ? sg ^ carrier_i(quad) : 0u;
         sh.d[1][w] = w < kWords32 ? sg ^ carrier_q(quad) : 0u;
       }
       __syncthreads();
-      // ---- this t0's rows of chip sums (as k_acq_weighted's) ---------------------------------------------------------------
+      // ---- this t0's rows of chip sums ---------------------------------------------------------------------------------------
       for (int i = tid; i < 2 * kChips; i += kWThreads) {
         const int stream = i / kChips, k = i % kChips;
-        const int p = 16 * k + t0;
-        const u32 x = win16(sh.d[stream], p), m = win16(sh.mag, p);
-        u32 v = 0xFFFFu;
-        if (p + 16 > kSamples - 16) {
-          v = 0;
-#pragma unroll
-          for (int j = 0; j < 16; j++) {
-            int n = p + j;
-            n = n >= kSamples ? n - kSamples : n;
-            v |= (n < kSamples - 16 ? 1u : 0u) << j;
-          }
-        }
-        const int s = (2 * (int)__popc(x & v) - (int)__popc(v)) + 2 * (2 * (int)__popc(x & m & v) - (int)__popc(m & v));
-        uint8_t *row = reinterpret_cast<uint8_t *>(sh.sums[stream]);
-        row[k] = (uint8_t)(int8_t)s;
-        row[k + kChips] = (uint8_t)(int8_t)s;
+        put_chip_sum(sh.sums[stream], sh.d[stream], sh.mag, t0, k);
       }
       if (tid < 2)
         reinterpret_cast<uint8_t *>(sh.sums[tid])[2 * kChips] = reinterpret_cast<uint8_t *>(sh.sums[tid])[2 * kChips + 1] = 0;
       __syncthreads();
       // ---- the correlations of block b at this t0 ------------------------------------------------------------------------
       int acc[4][2][kWG];
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int st = 0; st < 2; st++)
-#pragma unroll
-          for (int g = 0; g < kWG; g++)
-            acc[j][st][g] = 0;
-      const u32 *row_i = sh.sums[0], *row_q = sh.sums[1];
-      u32 prev[4][2];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int q = min(tid + 256 * j, kChips - 1);
-        prev[j][0] = row_i[q >> 2];
-        prev[j][1] = row_q[q >> 2];
-      }
-#pragma unroll 2
-      for (int c4 = 0; c4 < 256; c4++) {
-        u32 win[4][2];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const int q = min(tid + 256 * j, kChips - 1);
-          const u32 nxt_i = row_i[(q >> 2) + c4 + 1], nxt_q = row_q[(q >> 2) + c4 + 1];
-          win[j][0] = __builtin_amdgcn_alignbyte(nxt_i, prev[j][0], (u32)(q & 3));
-          win[j][1] = __builtin_amdgcn_alignbyte(nxt_q, prev[j][1], (u32)(q & 3));
-          prev[j][0] = nxt_i;
-          prev[j][1] = nxt_q;
-        }
-#pragma unroll
-        for (int g = 0; g < kWG; g++) {
-          const u32 cw = sh.chips[g][c4];
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            acc[j][0][g] = __builtin_amdgcn_sdot4((int)win[j][0], (int)cw, acc[j][0][g], false);
-            acc[j][1][g] = __builtin_amdgcn_sdot4((int)win[j][1], (int)cw, acc[j][1][g], false);
-          }
-        }
-      }
+      correlate(acc, sh.sums[0], sh.sums[1], sh.chips, tid);
 #pragma unroll
       for (int j = 0; j < 4; j++)
 #pragma unroll
@@ -431,16 +387,8 @@ __global__ __launch_bounds__(kWThreads) void k_acq_weighted_ms(const uint8_t *__
     }
   }
   __syncthreads();
-  if (tid < kWG && group * kWG + tid < n_prn) {
-    const unsigned long long key = sh.best[tid];
-    const u32 sum = sh.total[tid];
-    gpsx_peak_t pk;
-    pk.max_val = (u32)(key >> 14);
-    pk.phase = pk.max_val ? 16383u - (u32)(key & 0x3FFFu) : 0u;
-    pk.sum = sum;
-    pk.avr = sum / (u32)kSamples;
-    peaks[((size_t)search * n_prn + group * kWG + tid) * n_dopp + dopp] = pk;
-  }
+  if (tid < kWG && group * kWG + tid < n_prn)
+    put_record(&peaks[((size_t)search * n_prn + group * kWG + tid) * n_dopp + dopp], sh.best[tid], sh.total[tid]);
 }
 
 int launch_acq_weighted_ms(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_ms, int n_prn,
