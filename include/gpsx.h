@@ -28,7 +28,8 @@ extern "C" {
                                             * gps_tracking_words_batch skips flag bytes without it, the product library reads no
                                             * $GPSX_ACQ_* / $GPSX_TRACK_WAVE_FROM knobs (lib/libgpsx_lab.so does).  A host built against an
                                             * older header must not run on this library: call gpsx_abi_check once at start-up.
-                                            * gpsx_acq_grid_weighted_ms(_dev) came later in 0.1.1: new entry points, no layout change. */
+                                            * gpsx_acq_grid_weighted_ms(_dev) came later in 0.1.1: new entry points, no layout change;
+                                            * so did gpsx_acq_grid_weighted_coh(_dev). */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -303,6 +304,33 @@ int gpsx_acq_grid_weighted_ms_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, i
                                   const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks);
 int gpsx_acq_grid_weighted_ms(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_ms,
                               const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks);
+/* The same grid over n_coh blocks per search integrated COHERENTLY (I and Q added over the blocks before the magnitude):
+ *   blocks         search s reads blocks s * search_stride_blocks + b for b = 0 .. n_coh-1, as the _ms call (stride 0 and
+ *                  overlapping searches are legal); the call needs (n_search-1)*stride + n_coh <= n_blocks
+ *   carrier        f = (float)(if_hz + dopp_min_hz + d * dopp_step_hz), as the one-block call.  Block b is wiped by the reference's
+ *                  NCO on its sign plane starting from acc_b, acc_0 = 0 and acc_{b+1} = the accumulator block b leaves (the
+ *                  511-word loop: acc_b = b * 511 * step32 mod 2^32, step32 = (uint32)((uint64)nco_step(f) * 32)) -- what
+ *                  consecutive gps_shift_to_zero_freq_track calls on one channel do (PM/GPS/gps_misc.c:244-274); the sixteen
+ *                  unmixed samples of every block: weight 0
+ *   samples        vI_b[n], vQ_b[n] in {0, +-1, +-3} ({0, +-1} under GPSX_WEIGHTS_SIGN_ONLY)
+ *   correlation    I(tau) = sum_b sum_n vI_b[n] c[((n - tau) mod 16368) / 16], Q likewise, c the +-1 replica, tau in [0, 16368):
+ *                  signed and exact, |I| <= 3 x 16352 x 20 = 981 120
+ *   magnitude      m(tau) = floor(sqrt(I^2 + Q^2)), exact (I^2 + Q^2 < 2^41)
+ *   record         the _ms call's: max_val = max m, phase = the smallest tau reaching it, sum = sum m mod 2^32, avr = sum / 16368
+ * n_coh runs from 1 to 20: twenty blocks are one navigation-data bit.  n_coh out of range, too few blocks and whatever the
+ * one-block call refuses return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.  n_coh == 1 gives records
+ * byte-identical to gpsx_acq_grid_weighted (and runs its kernels).
+ * Caller guidance: a coherent window of n ms narrows a Doppler bin to about 1/n kHz -- step the grid by about 500/n Hz.  A window
+ * that spans a data-bit edge loses signal; with n_coh <= 10, two consecutive searches (stride = n_coh) always include one window
+ * without an edge: take the better record of the two.
+ * The C/A code repeats every block, so the n_coh blocks' correlation is ONE correlation of their wiped sum: a workgroup adds the
+ * blocks sample by sample in LDS and correlates once -- on the matrix cores (k_acq_coh_mx: v_mfma_i32_32x32x32_i8, a workgroup per
+ * cluster of 32 PRNs) or, under GPSX_ACQ_PATH_VECTOR, the vector ALU (k_acq_coh_vec: v_dot2_i32_i16): the same records, bit for
+ * bit.  No HBM scratch (no GPSX_ENOMEM). */
+int gpsx_acq_grid_weighted_coh_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh,
+                                   const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks);
+int gpsx_acq_grid_weighted_coh(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh,
+                               const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks);
 
 /* ---- K2+K3+K5: Early/Prompt/Late tracking correlators  (replaces the correlator part of
  *      gps_tracking_data_process, PM/GPS/tracking.c:115-138, for n_ch channels at once) ------------------------- */

@@ -72,10 +72,14 @@ def check_no_scratch() -> dict:
     wv = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_acq_weighted.o")).items() if "k_acq_weighted" in k}
     if len(wv) != 2:
         raise RuntimeError(f"expected k_acq_weighted and k_acq_weighted_ms, found {sorted(wv)}")
-    bad = {k: v for k, v in {**mx, **wmx, **loops, **wv}.items() if v["scratch_bytes"] != 0}
+    # ... and the coherent weighted grid's two kernels (no scratch by design: the pre-summed blocks live in LDS)
+    coh = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_acq_coh.o")).items() if "k_acq_coh" in k}
+    if len(coh) != 2 or not all(any(k in name for name in coh) for k in ("k_acq_coh_mx", "k_acq_coh_vec")):
+        raise RuntimeError(f"expected k_acq_coh_mx and k_acq_coh_vec in build/k_acq_coh.o, found {sorted(coh)}")
+    bad = {k: v for k, v in {**mx, **wmx, **loops, **wv, **coh}.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")
-    return {**mx, **wmx, **loops, **wv}
+    return {**mx, **wmx, **loops, **wv, **coh}
 
 
 if __name__ == "__main__":

@@ -209,6 +209,8 @@ enum class AcqWForm {
   kMxwWalk,    // k_acq_wmx_ms: a workgroup per cluster walks n_ms blocks, running sums through HBM scratch, in chunks of clusters
   kVec,        // k_acq_weighted: one block, a workgroup per (search, Doppler, 8 PRNs)
   kVecMs,      // k_acq_weighted_ms: the same workgroups, running sums in registers (no scratch)
+  kCohMx,      // k_acq_coh_mx: n_coh blocks summed sample by sample, one correlation; a workgroup per cluster (no scratch)
+  kCohVec,     // k_acq_coh_vec: the same on the vector ALU, a workgroup per (search, Doppler, 8 PRNs) (no scratch)
 };
 
 struct AcqWPlan {
@@ -262,6 +264,26 @@ inline AcqWPlan plan_acq_weighted(const AcqWShape &g, const AcqKnobs &k, int n_c
   p.chunk = p.grid = chunk;
   p.n_chunks = (int)((p.units + chunk - 1) / chunk);
   p.scratch_bytes = (size_t)chunk * kMxwMsClusterBytes;
+  return p;
+}
+
+// ---- the weighted grid over n_coh blocks integrated coherently (gpsx_acq_grid_weighted_coh; g.n_ms = n_coh) -----------------
+// Twenty blocks are one navigation-data bit, and the limit of the pre-summed samples' int8 differences (|dM| <= 6 n_coh <= 120).
+constexpr int kMaxCoh = 20;
+
+// One launch, no scratch: a workgroup adds its search's blocks in LDS and correlates the sum once.  n_coh = 1 is the one-block
+// call's plan (its kernels: byte-identical records by construction).
+inline AcqWPlan plan_acq_coherent(const AcqWShape &g)
+{
+  if (g.n_ms == 1)
+    return plan_acq_weighted(g, AcqKnobs{}, 1, 0);
+  AcqWPlan p{};
+  p.mx = !g.vector;
+  p.form = p.mx ? AcqWForm::kCohMx : AcqWForm::kCohVec;
+  p.units = (long)g.n_search * g.n_dopp * (p.mx ? (g.n_prn + 31) / 32 : (g.n_prn + 7) / 8);
+  p.chunk = p.grid = p.units;
+  p.n_chunks = 1;
+  p.name = p.mx ? "k_acq_coh_mx" : "k_acq_coh_vec";
   return p;
 }
 

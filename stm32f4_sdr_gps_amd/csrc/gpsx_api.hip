@@ -1022,15 +1022,17 @@ int stage_weighted_prns(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g)
   return GPSX_OK;
 }
 
-// The four entry points in one.  `ms`: a multi-block call -- n_ms and the block count are checked before the descriptor (the
+// The six entry points in one.  `ms`: a multi-block call -- n_ms and the block count are checked before the descriptor (the
 // one-block calls pass n_ms = 1 and start with the descriptor); search s reads blocks s * stride .. + n_ms - 1.  `host`: the
-// capture and the records are host memory, staged through the arena.
+// capture and the records are host memory, staged through the arena.  `coh`: the blocks are integrated coherently (n_ms = n_coh).
 int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int n_ms, const void *if_blocks_2bit, int n_blocks,
-                      void *peaks, bool host)
+                      void *peaks, bool host, bool coh = false)
 {
   if (int rc = use_device(ctx)) return rc;
-  if (ms && (n_ms < 1 || n_ms > kMaxMs))
+  if (ms && !coh && (n_ms < 1 || n_ms > kMaxMs))
     return fail(ctx, GPSX_EINVAL, "n_ms outside 1..128");
+  if (coh && (n_ms < 1 || n_ms > kMaxCoh))
+    return fail(ctx, GPSX_EINVAL, "n_coh outside 1..20");
   if (ms && n_blocks < n_ms)
     return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
   if (!g || !g->prns)
@@ -1061,7 +1063,7 @@ int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int 
   const int use_magnitude = g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;
   const int n_cus = ctx->prop.multiProcessorCount;
   const AcqWShape shape{g->n_search, n_ms, g->n_prn, g->n_dopp, ctx->acq_knobs.algo != kAlgoMx};
-  AcqWPlan plan = plan_acq_weighted(shape, ctx->acq_knobs, n_cus, 0);
+  AcqWPlan plan = coh ? plan_acq_coherent(shape) : plan_acq_weighted(shape, ctx->acq_knobs, n_cus, 0);
   switch (plan.form) {
   case AcqWForm::kMxw:
     // chips from the sign-only grid's tables
@@ -1084,6 +1086,13 @@ int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int 
     LAUNCHCHK(ctx, plan.name);
     break;
   }
+  case AcqWForm::kCohMx:
+  case AcqWForm::kCohVec:
+    if (int rc = stage_weighted_prns(ctx, g)) return rc;
+    launch_acq_coh(ctx->stream, plan.mx, d_if, g->n_search, g->search_stride_blocks, n_ms, g->n_prn, ctx->d_chips_all,
+                   ctx->d_weighted_prns, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, use_magnitude, d_peaks);
+    LAUNCHCHK(ctx, plan.name);
+    break;
   case AcqWForm::kMxwWalk:
     // running sums in the context's scratch, a chunk of clusters per launch; refused scratch halves the chunk
     for (int refused = 1;; refused++) {
@@ -1134,6 +1143,18 @@ int gpsx_acq_grid_weighted_ms(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n
                               gpsx_peak_t *peaks)
 {
   return acq_grid_weighted(ctx, g, true, n_ms, if_blocks_2bit, n_blocks, peaks, true);
+}
+
+int gpsx_acq_grid_weighted_coh_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh, const void *d_if_blocks_2bit, int n_blocks,
+                                   gpsx_peak_t *d_peaks)
+{
+  return acq_grid_weighted(ctx, g, true, n_coh, d_if_blocks_2bit, n_blocks, d_peaks, false, true);
+}
+
+int gpsx_acq_grid_weighted_coh(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh, const uint8_t *if_blocks_2bit, int n_blocks,
+                               gpsx_peak_t *peaks)
+{
+  return acq_grid_weighted(ctx, g, true, n_coh, if_blocks_2bit, n_blocks, peaks, true, true);
 }
 
 /* ---- the tracking loops on the device ---------------------------------------------------------------------------------- */

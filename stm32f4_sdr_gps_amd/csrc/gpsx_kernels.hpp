@@ -115,6 +115,11 @@ void launch_acq_mxw_ms(hipStream_t s, const uint8_t *d_if_blocks, int stride_blo
 int launch_acq_weighted_ms(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_ms, int n_prn,
                            const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
                            int use_magnitude, gpsx_peak_t *d_peaks);
+// gpsx_acq_grid_weighted_coh (plan_acq_coherent, n_coh >= 2): k_acq_coh_mx (mx: a workgroup per 32-PRN cluster) or k_acq_coh_vec
+// (a workgroup per 8 PRNs); neither needs scratch
+void launch_acq_coh(hipStream_t s, bool mx, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_coh, int n_prn,
+                    const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                    int use_magnitude, gpsx_peak_t *d_peaks);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

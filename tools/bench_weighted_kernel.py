@@ -4,7 +4,9 @@ searches x 32 PRN x 21 Doppler x 16368 phases per launch, first on the matrix co
 (k_acq_weighted), and the sign-only fine grid (k_acq_mx<0>) on the same captures' sign plane beside them.
 --n-ms N: the multi-block call instead (gpsx_acq_grid_weighted_ms_dev: k_acq_wmx_ms / k_acq_weighted_ms), N blocks per search, on
 both paths, beside N single-block calls on the same captures (block b of every search: the same hypothesis-blocks), in one process.
-usage: bench_weighted_kernel.py [--n-ms N] [searches [reps]]"""
+--coh N: the coherent call (gpsx_acq_grid_weighted_coh_dev: k_acq_coh_mx / k_acq_coh_vec), N blocks per search, on both paths,
+alternating with the non-coherent call over the same N blocks (n_ms = N) on the same captures, in one process.
+usage: bench_weighted_kernel.py [--n-ms N | --coh N] [searches [reps]]"""
 import ctypes as C
 import json
 import os
@@ -19,10 +21,14 @@ sys.path.insert(0, ROOT)
 def main():
     from stm32f4_sdr_gps_amd import capi, synth
     argv = list(sys.argv[1:])
-    n_ms = 0
+    n_ms = n_coh = 0
     if "--n-ms" in argv:
         at = argv.index("--n-ms")
         n_ms = int(argv[at + 1])
+        del argv[at:at + 2]
+    if "--coh" in argv:
+        at = argv.index("--coh")
+        n_coh = int(argv[at + 1])
         del argv[at:at + 2]
     searches = int(argv[0]) if len(argv) > 0 else 16
     reps = int(argv[1]) if len(argv) > 1 else 5
@@ -51,6 +57,8 @@ def main():
         eng.synchronize()
         return eng.elapsed_ms(e0, e1) / reps
     hyp = searches * 32 * 21 * 16368
+    if n_coh:
+        return coherent(eng, capi, synth, searches, n_coh, reps, timed)
     if n_ms:
         return multi_block(eng, capi, synth, searches, n_ms, reps, timed)
     for path in (capi.ACQ_PATH_MATRIX, capi.ACQ_PATH_VECTOR):
@@ -116,6 +124,48 @@ def multi_block(eng, capi, synth, searches, n_ms, reps, timed):
             line.update({"scratch_bytes": scratch, "scratch_bytes_per_hyp_block": scratch / hyp_blocks,
                          "scratch_tb_per_s": scratch / (ms_multi * 1e-3) / 1e12})
         print(json.dumps(line))
+    eng.set_acq_path(capi.ACQ_PATH_MATRIX)
+
+
+def coherent(eng, capi, synth, searches, n_coh, reps, timed, rounds=3):
+    blocks = synth.cold_start_block(searches * n_coh, seed=11, amp_scale=0.25, two_bit=True)
+    prns = np.arange(1, 33, dtype=np.uint8)
+    g = capi.AcqWeightedT(searches, n_coh, 32, prns.ctypes.data_as(C.POINTER(C.c_uint8)), -5000, 500, 21, 1)
+    d_if = eng.malloc(blocks.size + 2)
+    eng.h2d(d_if, np.concatenate([blocks.reshape(-1), np.zeros(2, np.uint8)]))
+    d_pk = eng.malloc(searches * 32 * 21 * 16)
+    n_blocks = searches * n_coh
+
+    def run_coh():
+        rc = eng.lib.gpsx_acq_grid_weighted_coh_dev(eng.h, C.byref(g), n_coh, C.c_void_p(d_if), n_blocks, C.c_void_p(d_pk))
+        assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+
+    def run_ms():
+        rc = eng.lib.gpsx_acq_grid_weighted_ms_dev(eng.h, C.byref(g), n_coh, C.c_void_p(d_if), n_blocks, C.c_void_p(d_pk))
+        assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+    hyp = searches * 32 * 21 * 16368
+    for path in (capi.ACQ_PATH_MATRIX, capi.ACQ_PATH_VECTOR):
+        eng.set_acq_path(path)
+        t_coh, t_ms = [], []
+        for _ in range(rounds):        # alternating: the two calls see the same clocks
+            t_coh.append(timed(run_coh))
+            k_coh = eng.lib.gpsx_last_kernel(eng.h).decode()
+            t_ms.append(timed(run_ms))
+            k_ms = eng.lib.gpsx_last_kernel(eng.h).decode()
+        ms_coh, ms_nc = float(np.median(t_coh)), float(np.median(t_ms))
+        line = {"kernel": "gpsx::" + k_coh, "searches": searches, "n_coh": n_coh, "ms": round(ms_coh, 3), "hyp_per_s": hyp / (ms_coh * 1e-3),
+                "noncoherent_kernel": "gpsx::" + k_ms, "noncoherent_ms": round(ms_nc, 3), "ratio": round(ms_coh / ms_nc, 3),
+                "ms_runs": [round(t, 3) for t in t_coh], "noncoherent_ms_runs": [round(t, 3) for t in t_ms]}
+        if k_coh == "k_acq_coh_mx":
+            # per hypothesis 2 streams x 17 passes x 1024 chips x 2 (multiply, add) on int8 operands, against ~5 x 10^15 dense I8
+            ops = hyp / 16 * 2 * 17 * 1024 * 2
+            line.update({"mfma_tops": ops / (ms_coh * 1e-3) / 1e12, "frac_of_i8_dense_peak": ops / (ms_coh * 1e-3) / 5.0e15,
+                         "note": "MFMA int8 ops as issued (17 passes per 16 sample offsets) against the ~5 POP/s dense I8 peak (2x BF16)"})
+        elif k_coh == "k_acq_coh_vec":
+            dot2 = hyp * 2 * 512            # per hypothesis two streams x 512 two-chip steps
+            line.update({"dot2_lane_ops_per_s": dot2 / (ms_coh * 1e-3), "frac_of_valu_issue_peak": dot2 / (ms_coh * 1e-3) / (256 * 64 * 2.4e9),
+                         "note": "algorithmic v_dot2_i32_i16 lane-ops (1024 per hypothesis) against one wave64 op per 4 cycles per SIMD at 2.4 GHz"})
+        print(json.dumps(line), flush=True)
     eng.set_acq_path(capi.ACQ_PATH_MATRIX)
 
 
