@@ -331,6 +331,32 @@ int gpsx_acq_grid_weighted_coh_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, 
                                    const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks);
 int gpsx_acq_grid_weighted_coh(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh,
                                const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks);
+/* The product of the two multi-block calls: n_seg COHERENT windows ("segments") of n_coh blocks each per search, the windows'
+ * magnitudes summed NON-COHERENTLY -- what a weak-signal search runs once one data bit is too short:
+ *   blocks         search s, segment j, block b reads block s * search_stride_blocks + j * n_coh + b, j in [0, n_seg), b in
+ *                  [0, n_coh) (stride 0 and overlapping searches are legal); the call needs
+ *                  (n_search-1)*stride + n_coh*n_seg <= n_blocks
+ *   a segment      exactly what gpsx_acq_grid_weighted_coh computes for a search starting at the segment's first block: the NCO
+ *                  accumulator starts at 0 at the segment's first block and is chained through its n_coh blocks
+ *                  (acc_b = b * 511 * step32 mod 2^32), the sixteen unmixed samples weigh 0, v in {0, +-1, +-3} (or {0, +-1}),
+ *                  I_j(tau), Q_j(tau) signed and exact, m_j(tau) = floor(sqrt(I_j^2 + Q_j^2)) exact (< 2^21 at n_coh = 20)
+ *   sum            E(tau) = sum_j m_j(tau)  (n_seg <= 128: E <= 128 x 1 387 513 < 2^28)
+ *   record         the _ms call's: max_val = max E, phase = the smallest tau reaching it, sum = sum_tau E mod 2^32, avr = sum / 16368
+ * n_coh runs from 1 to 20, n_seg from 1 to 128.  Checked in this order: n_coh, n_seg, n_blocks < n_coh * n_seg, then whatever the
+ * one-block call refuses: each returns GPSX_EINVAL (with a gpsx_last_error text) and writes nothing.  n_seg == 1 gives records
+ * byte-identical to gpsx_acq_grid_weighted_coh and n_coh == 1 to gpsx_acq_grid_weighted_ms with n_ms = n_seg (and runs their
+ * kernels, with the latter's chunking and GPSX_ENOMEM): the call covers every legal argument of the two older ones.
+ * Caller guidance: step the grid by about 500 / n_coh Hz.  With n_coh <= 10 no alignment to the data-bit edge is needed (at least
+ * every second window is free of one).  Code Doppler slides the peak by about 3 samples per 100 ms at 5 kHz, so n_coh * n_seg much
+ * beyond ~150 ms smears it unless the Doppler is small.  n_search = 20, stride = 1, n_coh = 20 scans the bit-edge alignment.
+ * Matrix cores (k_acq_hyb_mx: per segment k_acq_coh_mx's pre-sum and passes, the roots added into u32 running sums in the
+ * context's grow-only HBM scratch, 2 MB per cluster of 32 PRNs in flight, launched in chunks of clusters; GPSX_ENOMEM if not even
+ * one cluster's scratch can be had) or, under GPSX_ACQ_PATH_VECTOR, the vector ALU (k_acq_hyb_vec: running sums in registers, no
+ * scratch): the same records, bit for bit. */
+int gpsx_acq_grid_weighted_hyb_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh, int n_seg,
+                                   const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks);
+int gpsx_acq_grid_weighted_hyb(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh, int n_seg,
+                               const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks);
 
 /* ---- K2+K3+K5: Early/Prompt/Late tracking correlators  (replaces the correlator part of
  *      gps_tracking_data_process, PM/GPS/tracking.c:115-138, for n_ch channels at once) ------------------------- */

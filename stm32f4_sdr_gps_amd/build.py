@@ -76,10 +76,15 @@ def check_no_scratch() -> dict:
     coh = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_acq_coh.o")).items() if "k_acq_coh" in k}
     if len(coh) != 2 or not all(any(k in name for name in coh) for k in ("k_acq_coh_mx", "k_acq_coh_vec")):
         raise RuntimeError(f"expected k_acq_coh_mx and k_acq_coh_vec in build/k_acq_coh.o, found {sorted(coh)}")
-    bad = {k: v for k, v in {**mx, **wmx, **loops, **wv, **coh}.items() if v["scratch_bytes"] != 0}
+    # ... and the hybrid (coherent windows summed non-coherently) grid's two, in an object and under names of their own
+    hyb = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_acq_hyb.o")).items() if "k_acq_hyb" in k}
+    if len(hyb) != 2 or not all(any(k in name for name in hyb) for k in ("k_acq_hyb_mx", "k_acq_hyb_vec")):
+        raise RuntimeError(f"expected k_acq_hyb_mx and k_acq_hyb_vec in build/k_acq_hyb.o, found {sorted(hyb)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb}
+    bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")
-    return {**mx, **wmx, **loops, **wv, **coh}
+    return every
 
 
 if __name__ == "__main__":

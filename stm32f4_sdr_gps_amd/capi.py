@@ -134,6 +134,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_acq_grid_weighted_ms_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_acq_grid_weighted_coh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_acq_grid_weighted_coh_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_acq_grid_weighted_hyb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_acq_grid_weighted_hyb_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -464,6 +466,22 @@ class Engine:
         peaks = np.zeros((n_search, len(prns), n_dopp), PEAK_DTYPE)
         self._chk(self.lib.gpsx_acq_grid_weighted_coh(self.h, C.byref(g), n_coh, blocks.ctypes.data, len(blocks), peaks.ctypes.data),
                   "gpsx_acq_grid_weighted_coh")
+        return peaks
+
+    def acq_grid_weighted_hyb(self, blocks_2bit: np.ndarray, prns, n_search: int, n_coh: int, n_seg: int, dopp_min_hz: int,
+                              dopp_step_hz: int, n_dopp: int, use_magnitude: bool = True, stride_blocks: int | None = None) -> np.ndarray:
+        """EXTENSION: the weighted grid over n_seg coherent windows of n_coh blocks each (1 .. 20 x 1 .. 128), the windows'
+        magnitudes summed non-coherently (search s, window j: blocks s * stride_blocks + j * n_coh .. + n_coh - 1, the carrier
+        NCO started from 0 at the window's first block; the stride defaults to n_coh * n_seg)
+        -> PEAK_DTYPE [n_search, n_prn, n_dopp]"""
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        prns = np.ascontiguousarray(prns, np.uint8)
+        stride = n_coh * n_seg if stride_blocks is None else stride_blocks
+        g = AcqWeightedT(n_search, stride, len(prns), prns.ctypes.data_as(C.POINTER(C.c_uint8)), dopp_min_hz, dopp_step_hz, n_dopp,
+                         1 if use_magnitude else 0)
+        peaks = np.zeros((n_search, len(prns), n_dopp), PEAK_DTYPE)
+        self._chk(self.lib.gpsx_acq_grid_weighted_hyb(self.h, C.byref(g), n_coh, n_seg, blocks.ctypes.data, len(blocks),
+                                                      peaks.ctypes.data), "gpsx_acq_grid_weighted_hyb")
         return peaks
 
     def set_loop_schedule(self, schedule: int) -> None:

@@ -211,6 +211,8 @@ enum class AcqWForm {
   kVecMs,      // k_acq_weighted_ms: the same workgroups, running sums in registers (no scratch)
   kCohMx,      // k_acq_coh_mx: n_coh blocks summed sample by sample, one correlation; a workgroup per cluster (no scratch)
   kCohVec,     // k_acq_coh_vec: the same on the vector ALU, a workgroup per (search, Doppler, 8 PRNs) (no scratch)
+  kHybMx,      // k_acq_hyb_mx: a workgroup per cluster walks n_seg coherent windows, running sums through HBM scratch, in chunks
+  kHybVec,     // k_acq_hyb_vec: a workgroup per (search, Doppler, 8 PRNs), running sums in registers (no scratch)
 };
 
 struct AcqWPlan {
@@ -224,6 +226,26 @@ struct AcqWPlan {
   size_t scratch_bytes;  // HBM scratch (gpsx_ctx::d_energy) of one chunk, 0: none
   const char *name;      // gpsx_last_kernel
 };
+
+// The chunks of a walk whose clusters keep kMxwMsClusterBytes of running sums each: as many clusters per launch as the cap holds,
+// whole rounds of the chip when that is at least one (a launch is rounds of one workgroup per CU), never more than the call has;
+// every refusal halves it.  p.units is set; p.enomem if not even one cluster is left.
+inline void plan_wms_chunks(AcqWPlan &p, const AcqKnobs &k, int n_cus, int refused)
+{
+  const size_t cap = (size_t)(k.wms_scratch_mb > 0 ? k.wms_scratch_mb : kWmsScratchMbDefault) << 20;
+  long chunk = (long)(cap / kMxwMsClusterBytes);
+  if (chunk >= n_cus)
+    chunk -= chunk % n_cus;
+  chunk = chunk < p.units ? chunk : p.units;
+  chunk = refused < 62 ? chunk >> refused : 0;
+  if (chunk < 1) {
+    p.enomem = true;
+    return;
+  }
+  p.chunk = p.grid = chunk;
+  p.n_chunks = (int)((p.units + chunk - 1) / chunk);
+  p.scratch_bytes = (size_t)chunk * kMxwMsClusterBytes;
+}
 
 // `refused`: how many scratch requests of this call were refused so far -- each halves the chunk.
 inline AcqWPlan plan_acq_weighted(const AcqWShape &g, const AcqKnobs &k, int n_cus, int refused)
@@ -249,21 +271,7 @@ inline AcqWPlan plan_acq_weighted(const AcqWShape &g, const AcqKnobs &k, int n_c
   }
   p.form = AcqWForm::kMxwWalk;
   p.name = "k_acq_wmx_ms";
-  // a chunk: as many clusters as the cap holds, whole rounds of the chip when that is at least one (a launch is rounds of one
-  // workgroup per CU), never more than the call has; every refusal halves it
-  const size_t cap = (size_t)(k.wms_scratch_mb > 0 ? k.wms_scratch_mb : kWmsScratchMbDefault) << 20;
-  long chunk = (long)(cap / kMxwMsClusterBytes);
-  if (chunk >= n_cus)
-    chunk -= chunk % n_cus;
-  chunk = chunk < p.units ? chunk : p.units;
-  chunk = refused < 62 ? chunk >> refused : 0;
-  if (chunk < 1) {
-    p.enomem = true;
-    return p;
-  }
-  p.chunk = p.grid = chunk;
-  p.n_chunks = (int)((p.units + chunk - 1) / chunk);
-  p.scratch_bytes = (size_t)chunk * kMxwMsClusterBytes;
+  plan_wms_chunks(p, k, n_cus, refused);
   return p;
 }
 
@@ -284,6 +292,35 @@ inline AcqWPlan plan_acq_coherent(const AcqWShape &g)
   p.chunk = p.grid = p.units;
   p.n_chunks = 1;
   p.name = p.mx ? "k_acq_coh_mx" : "k_acq_coh_vec";
+  return p;
+}
+
+// ---- n_seg coherent windows of n_coh blocks each, their magnitudes summed (gpsx_acq_grid_weighted_hyb) ------------------------
+struct AcqHShape {
+  int n_search, n_coh, n_seg, n_prn, n_dopp;
+  bool vector;                 // GPSX_ACQ_PATH_VECTOR
+};
+
+// One window is the coherent call's plan, windows of one block are the non-coherent call's (n_ms = n_seg): their kernels, their
+// records.  Otherwise the matrix form keeps a cluster's running sums in k_acq_wmx_ms's scratch layout and is chunked by its rule;
+// the vector form keeps them in registers: one launch, no scratch.
+inline AcqWPlan plan_acq_hybrid(const AcqHShape &g, const AcqKnobs &k, int n_cus, int refused)
+{
+  if (g.n_seg == 1)
+    return plan_acq_coherent(AcqWShape{g.n_search, g.n_coh, g.n_prn, g.n_dopp, g.vector});
+  if (g.n_coh == 1)
+    return plan_acq_weighted(AcqWShape{g.n_search, g.n_seg, g.n_prn, g.n_dopp, g.vector}, k, n_cus, refused);
+  AcqWPlan p{};
+  p.mx = !g.vector;
+  p.form = p.mx ? AcqWForm::kHybMx : AcqWForm::kHybVec;
+  p.name = p.mx ? "k_acq_hyb_mx" : "k_acq_hyb_vec";
+  p.units = (long)g.n_search * g.n_dopp * (p.mx ? (g.n_prn + 31) / 32 : (g.n_prn + 7) / 8);
+  if (p.mx) {
+    plan_wms_chunks(p, k, n_cus, refused);
+    return p;
+  }
+  p.chunk = p.grid = p.units;
+  p.n_chunks = 1;
   return p;
 }
 

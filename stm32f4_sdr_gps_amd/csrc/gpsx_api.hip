@@ -1022,18 +1022,23 @@ int stage_weighted_prns(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g)
   return GPSX_OK;
 }
 
-// The six entry points in one.  `ms`: a multi-block call -- n_ms and the block count are checked before the descriptor (the
+// The eight entry points in one.  `ms`: a multi-block call -- n_ms and the block count are checked before the descriptor (the
 // one-block calls pass n_ms = 1 and start with the descriptor); search s reads blocks s * stride .. + n_ms - 1.  `host`: the
 // capture and the records are host memory, staged through the arena.  `coh`: the blocks are integrated coherently (n_ms = n_coh).
+// `n_seg` > 0: the hybrid call -- n_seg coherent windows of n_ms = n_coh blocks each, a search spans n_coh * n_seg blocks.
 int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int n_ms, const void *if_blocks_2bit, int n_blocks,
-                      void *peaks, bool host, bool coh = false)
+                      void *peaks, bool host, bool coh = false, int n_seg = 0)
 {
   if (int rc = use_device(ctx)) return rc;
+  const bool hyb = n_seg != 0;
   if (ms && !coh && (n_ms < 1 || n_ms > kMaxMs))
     return fail(ctx, GPSX_EINVAL, "n_ms outside 1..128");
   if (coh && (n_ms < 1 || n_ms > kMaxCoh))
     return fail(ctx, GPSX_EINVAL, "n_coh outside 1..20");
-  if (ms && n_blocks < n_ms)
+  if (hyb && (n_seg < 1 || n_seg > kMaxMs))
+    return fail(ctx, GPSX_EINVAL, "n_seg outside 1..128");
+  const int span = hyb ? n_ms * n_seg : n_ms;   // blocks a search reads
+  if (ms && n_blocks < span)
     return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
   if (!g || !g->prns)
     return fail(ctx, GPSX_EINVAL, "null descriptor");
@@ -1041,7 +1046,7 @@ int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int 
     return fail(ctx, GPSX_EINVAL, "bad grid shape");
   if (g->weights != GPSX_WEIGHTS_SIGN_ONLY && g->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
     return fail(ctx, GPSX_EINVAL, "unknown weights");
-  if ((long)(g->n_search - 1) * g->search_stride_blocks + n_ms > n_blocks)
+  if ((long)(g->n_search - 1) * g->search_stride_blocks + span > n_blocks)
     return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
   for (int i = 0; i < g->n_prn; i++)
     if (g->prns[i] < 1 || g->prns[i] > GPSX_MAX_PRN)
@@ -1063,7 +1068,14 @@ int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int 
   const int use_magnitude = g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;
   const int n_cus = ctx->prop.multiProcessorCount;
   const AcqWShape shape{g->n_search, n_ms, g->n_prn, g->n_dopp, ctx->acq_knobs.algo != kAlgoMx};
-  AcqWPlan plan = coh ? plan_acq_coherent(shape) : plan_acq_weighted(shape, ctx->acq_knobs, n_cus, 0);
+  const AcqHShape hshape{g->n_search, n_ms, n_seg, g->n_prn, g->n_dopp, shape.vector};
+  auto make_plan = [&](int refused) {
+    return hyb ? plan_acq_hybrid(hshape, ctx->acq_knobs, n_cus, refused)
+               : coh ? plan_acq_coherent(shape) : plan_acq_weighted(shape, ctx->acq_knobs, n_cus, refused);
+  };
+  AcqWPlan plan = make_plan(0);
+  if (hyb && n_ms == 1)
+    n_ms = n_seg;   // windows of one block: the non-coherent call's plan walks n_seg blocks
   switch (plan.form) {
   case AcqWForm::kMxw:
     // chips from the sign-only grid's tables
@@ -1102,13 +1114,38 @@ int acq_grid_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, bool ms, int 
       if (int rc = ensure_energy(ctx, plan.scratch_bytes, &had)) return rc;
       if (had)
         break;
-      plan = plan_acq_weighted(shape, ctx->acq_knobs, n_cus, refused);
+      plan = make_plan(refused);
     }
     if (int rc = ensure_grid_tables(ctx, g->prns, g->n_prn)) return rc;
     for (long lo = 0; lo < plan.units; lo += plan.chunk) {
       const long n = plan.units - lo < plan.chunk ? plan.units - lo : plan.chunk;
       launch_acq_mxw_ms(ctx->stream, d_if, g->search_stride_blocks, n_ms, g->n_prn, ctx->d_grid_mx_a, ctx->if_hz, g->dopp_min_hz,
                         g->dopp_step_hz, g->n_dopp, use_magnitude, (int)lo, (int)n, ctx->d_energy, d_peaks);
+      LAUNCHCHK(ctx, plan.name);
+    }
+    break;
+  case AcqWForm::kHybVec:
+    if (int rc = stage_weighted_prns(ctx, g)) return rc;
+    launch_acq_hyb_vec(ctx->stream, d_if, g->n_search, g->search_stride_blocks, n_ms, n_seg, g->n_prn, ctx->d_chips_all,
+                       ctx->d_weighted_prns, ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, use_magnitude, d_peaks);
+    LAUNCHCHK(ctx, plan.name);
+    break;
+  case AcqWForm::kHybMx:
+    // k_acq_wmx_ms's scratch loop: a chunk of clusters per launch, refused scratch halves the chunk
+    for (int refused = 1;; refused++) {
+      if (plan.enomem)
+        return fail(ctx, GPSX_ENOMEM, "k_acq_hyb_mx: not even one cluster's scratch (2 MB) could be had");
+      bool had = false;
+      if (int rc = ensure_energy(ctx, plan.scratch_bytes, &had)) return rc;
+      if (had)
+        break;
+      plan = make_plan(refused);
+    }
+    if (int rc = stage_weighted_prns(ctx, g)) return rc;
+    for (long lo = 0; lo < plan.units; lo += plan.chunk) {
+      const long n = plan.units - lo < plan.chunk ? plan.units - lo : plan.chunk;
+      launch_acq_hyb_mx(ctx->stream, d_if, g->search_stride_blocks, n_ms, n_seg, g->n_prn, ctx->d_chips_all, ctx->d_weighted_prns,
+                        ctx->if_hz, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, use_magnitude, (int)lo, (int)n, ctx->d_energy, d_peaks);
       LAUNCHCHK(ctx, plan.name);
     }
     break;
@@ -1155,6 +1192,19 @@ int gpsx_acq_grid_weighted_coh(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int 
                                gpsx_peak_t *peaks)
 {
   return acq_grid_weighted(ctx, g, true, n_coh, if_blocks_2bit, n_blocks, peaks, true, true);
+}
+
+int gpsx_acq_grid_weighted_hyb_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh, int n_seg, const void *d_if_blocks_2bit,
+                                   int n_blocks, gpsx_peak_t *d_peaks)
+{
+  // (a window count of 0 must be refused as out of range, not read as "not the hybrid call")
+  return acq_grid_weighted(ctx, g, true, n_coh, d_if_blocks_2bit, n_blocks, d_peaks, false, true, n_seg ? n_seg : -1);
+}
+
+int gpsx_acq_grid_weighted_hyb(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, int n_coh, int n_seg, const uint8_t *if_blocks_2bit,
+                               int n_blocks, gpsx_peak_t *peaks)
+{
+  return acq_grid_weighted(ctx, g, true, n_coh, if_blocks_2bit, n_blocks, peaks, true, true, n_seg ? n_seg : -1);
 }
 
 /* ---- the tracking loops on the device ---------------------------------------------------------------------------------- */

@@ -120,6 +120,15 @@ int launch_acq_weighted_ms(hipStream_t s, const uint8_t *d_if_blocks, int n_sear
 void launch_acq_coh(hipStream_t s, bool mx, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_coh, int n_prn,
                     const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
                     int use_magnitude, gpsx_peak_t *d_peaks);
+// gpsx_acq_grid_weighted_hyb (plan_acq_hybrid, n_coh >= 2 and n_seg >= 2; k_acq_hyb.hip): k_acq_hyb_mx -- clusters [cluster_lo,
+// + n_clusters) walk n_seg windows of n_coh blocks each, d_scratch = n_clusters x kMxwMsClusterBytes -- or k_acq_hyb_vec, running
+// sums in registers, no scratch
+void launch_acq_hyb_mx(hipStream_t s, const uint8_t *d_if_blocks, int stride_blocks, int n_coh, int n_seg, int n_prn,
+                       const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                       int use_magnitude, int cluster_lo, int n_clusters, void *d_scratch, gpsx_peak_t *d_peaks);
+void launch_acq_hyb_vec(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_coh, int n_seg, int n_prn,
+                        const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                        int use_magnitude, gpsx_peak_t *d_peaks);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -6,7 +6,11 @@ searches x 32 PRN x 21 Doppler x 16368 phases per launch, first on the matrix co
 both paths, beside N single-block calls on the same captures (block b of every search: the same hypothesis-blocks), in one process.
 --coh N: the coherent call (gpsx_acq_grid_weighted_coh_dev: k_acq_coh_mx / k_acq_coh_vec), N blocks per search, on both paths,
 alternating with the non-coherent call over the same N blocks (n_ms = N) on the same captures, in one process.
-usage: bench_weighted_kernel.py [--n-ms N | --coh N] [searches [reps]]"""
+--hyb N S: the hybrid call (gpsx_acq_grid_weighted_hyb_dev: k_acq_hyb_mx / k_acq_hyb_vec), S coherent windows of N blocks per search,
+on both paths (--matrix-only: that path alone), alternating with (a) the coherent call over the same windows as searches x S searches
+of stride N -- what a caller without the hybrid call has to run, and still cannot add up -- and (b) the non-coherent call over the
+same N x S blocks (at most its 128), in one process.
+usage: bench_weighted_kernel.py [--n-ms N | --coh N | --hyb N S [--matrix-only]] [searches [reps]]"""
 import ctypes as C
 import json
 import os
@@ -30,6 +34,14 @@ def main():
         at = argv.index("--coh")
         n_coh = int(argv[at + 1])
         del argv[at:at + 2]
+    hyb = None
+    if "--hyb" in argv:
+        at = argv.index("--hyb")
+        hyb = (int(argv[at + 1]), int(argv[at + 2]))
+        del argv[at:at + 3]
+    matrix_only = "--matrix-only" in argv
+    if matrix_only:
+        argv.remove("--matrix-only")
     searches = int(argv[0]) if len(argv) > 0 else 16
     reps = int(argv[1]) if len(argv) > 1 else 5
     if os.environ.get("GPSX_LIB"):   # A/B runs against another build of the library (tools/build_variant.sh)
@@ -57,6 +69,8 @@ def main():
         eng.synchronize()
         return eng.elapsed_ms(e0, e1) / reps
     hyp = searches * 32 * 21 * 16368
+    if hyb:
+        return hybrid(eng, capi, synth, searches, hyb[0], hyb[1], timed, matrix_only)
     if n_coh:
         return coherent(eng, capi, synth, searches, n_coh, reps, timed)
     if n_ms:
@@ -165,6 +179,67 @@ def coherent(eng, capi, synth, searches, n_coh, reps, timed, rounds=3):
             dot2 = hyp * 2 * 512            # per hypothesis two streams x 512 two-chip steps
             line.update({"dot2_lane_ops_per_s": dot2 / (ms_coh * 1e-3), "frac_of_valu_issue_peak": dot2 / (ms_coh * 1e-3) / (256 * 64 * 2.4e9),
                          "note": "algorithmic v_dot2_i32_i16 lane-ops (1024 per hypothesis) against one wave64 op per 4 cycles per SIMD at 2.4 GHz"})
+        print(json.dumps(line), flush=True)
+    eng.set_acq_path(capi.ACQ_PATH_MATRIX)
+
+
+def hybrid(eng, capi, synth, searches, n_coh, n_seg, timed, matrix_only, rounds=3):
+    span = n_coh * n_seg
+    n_blocks = searches * span
+    blocks = synth.cold_start_block(n_blocks, seed=11, amp_scale=0.25, two_bit=True)
+    prns = np.arange(1, 33, dtype=np.uint8)
+    p_prns = prns.ctypes.data_as(C.POINTER(C.c_uint8))
+    g = capi.AcqWeightedT(searches, span, 32, p_prns, -5000, 500, 21, 1)
+    g_win = capi.AcqWeightedT(searches * n_seg, n_coh, 32, p_prns, -5000, 500, 21, 1)    # every window a search of its own
+    n_ms = min(span, 128)
+    d_if = eng.malloc(blocks.size + 2)
+    eng.h2d(d_if, np.concatenate([blocks.reshape(-1), np.zeros(2, np.uint8)]))
+    d_pk = eng.malloc(searches * n_seg * 32 * 21 * 16)
+
+    def run_hyb():
+        rc = eng.lib.gpsx_acq_grid_weighted_hyb_dev(eng.h, C.byref(g), n_coh, n_seg, C.c_void_p(d_if), n_blocks, C.c_void_p(d_pk))
+        assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+
+    def run_windows():
+        rc = eng.lib.gpsx_acq_grid_weighted_coh_dev(eng.h, C.byref(g_win), n_coh, C.c_void_p(d_if), n_blocks, C.c_void_p(d_pk))
+        assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+
+    def run_ms():
+        rc = eng.lib.gpsx_acq_grid_weighted_ms_dev(eng.h, C.byref(g), n_ms, C.c_void_p(d_if), n_blocks, C.c_void_p(d_pk))
+        assert rc == 0, eng.lib.gpsx_last_error(eng.h)
+    hyp_win = searches * n_seg * 32 * 21 * 16368          # hypotheses x windows
+    for path in (capi.ACQ_PATH_MATRIX,) if matrix_only else (capi.ACQ_PATH_MATRIX, capi.ACQ_PATH_VECTOR):
+        eng.set_acq_path(path)
+        t_hyb, t_win, t_ms = [], [], []
+        for _ in range(rounds):        # alternating: the three calls see the same clocks
+            t_hyb.append(timed(run_hyb))
+            k_hyb = eng.lib.gpsx_last_kernel(eng.h).decode()
+            t_win.append(timed(run_windows))
+            k_win = eng.lib.gpsx_last_kernel(eng.h).decode()
+            t_ms.append(timed(run_ms))
+            k_ms = eng.lib.gpsx_last_kernel(eng.h).decode()
+        ms_hyb, ms_win, ms_nc = float(np.median(t_hyb)), float(np.median(t_win)), float(np.median(t_ms))
+        line = {"kernel": "gpsx::" + k_hyb, "searches": searches, "n_coh": n_coh, "n_seg": n_seg, "ms": round(ms_hyb, 3),
+                "hyp_windows_per_s": hyp_win / (ms_hyb * 1e-3),
+                "windows_kernel": "gpsx::" + k_win, "windows_searches": searches * n_seg, "windows_ms": round(ms_win, 3),
+                "ratio_to_windows": round(ms_hyb / ms_win, 3),
+                "noncoherent_kernel": "gpsx::" + k_ms, "noncoherent_n_ms": n_ms, "noncoherent_ms": round(ms_nc, 3),
+                "ratio_to_noncoherent": round(ms_hyb / ms_nc, 3), "ms_runs": [round(t, 3) for t in t_hyb],
+                "windows_ms_runs": [round(t, 3) for t in t_win], "noncoherent_ms_runs": [round(t, 3) for t in t_ms]}
+        if k_hyb == "k_acq_hyb_mx":
+            # per hypothesis and window 2 streams x 17 passes x 1024 chips x 2 (multiply, add) on int8 operands; running sums: 2 MB
+            # per cluster, read by every window but the first and written by every window but the last
+            ops = hyp_win / 16 * 2 * 17 * 1024 * 2
+            scratch = searches * 21 * (2 << 20) * 2 * (n_seg - 1)
+            line.update({"mfma_tops": ops / (ms_hyb * 1e-3) / 1e12, "frac_of_i8_dense_peak": ops / (ms_hyb * 1e-3) / 5.0e15,
+                         "scratch_bytes": scratch, "scratch_gb_per_s": scratch / (ms_hyb * 1e-3) / 1e9,
+                         "note": "MFMA int8 ops as issued (17 passes per 16 sample offsets and window) against the ~5 POP/s dense I8 "
+                                 "peak (2x BF16); scratch: the u32 running sums' reads and writes over the call's time"})
+        elif k_hyb == "k_acq_hyb_vec":
+            dot2 = hyp_win * 2 * 512            # per hypothesis and window two streams x 512 two-chip steps
+            line.update({"dot2_lane_ops_per_s": dot2 / (ms_hyb * 1e-3), "frac_of_valu_issue_peak": dot2 / (ms_hyb * 1e-3) / (256 * 64 * 2.4e9),
+                         "note": "algorithmic v_dot2_i32_i16 lane-ops (1024 per hypothesis and window) against one wave64 op per 4 cycles "
+                                 "per SIMD at 2.4 GHz"})
         print(json.dumps(line), flush=True)
     eng.set_acq_path(capi.ACQ_PATH_MATRIX)
 
