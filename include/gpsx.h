@@ -29,7 +29,8 @@ extern "C" {
                                             * $GPSX_ACQ_* / $GPSX_TRACK_WAVE_FROM knobs (lib/libgpsx_lab.so does).  A host built against an
                                             * older header must not run on this library: call gpsx_abi_check once at start-up.
                                             * gpsx_acq_grid_weighted_ms(_dev) came later in 0.1.1: new entry points, no layout change;
-                                            * so did gpsx_acq_grid_weighted_coh(_dev). */
+                                            * so did gpsx_acq_grid_weighted_coh(_dev).
+                                            * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -387,6 +388,50 @@ int gpsx_track_epl_batch_dev(gpsx_ctx *ctx, const void *d_if_block, gpsx_trk_sta
 typedef void (*gpsx_track_chunk_fn)(void *user, int first_channel, int n_channels);
 int gpsx_track_epl_batch_chunked(gpsx_ctx *ctx, const uint8_t *if_block, gpsx_trk_state_t *st, int n_ch, int16_t *iq_out,
                                  int n_chunks, gpsx_track_chunk_fn on_chunk, void *user);
+
+/* ---- EXTENSION, not in the reference: Early / Prompt / Late on WEIGHTED two-bit samples, K blocks per launch ---------------
+ * The per-millisecond building block of a weak-signal receiver behind the weighted grids above: E/P/L I and Q on both bits, for
+ * n_ch channels and n_blocks consecutive blocks in one launch, with the weighted grids' sample, carrier and replica definitions,
+ * so that a grid record hands over to a channel state exactly (code_phase_fine = the record's phase, if_freq_offset_hz = its
+ * Doppler bin, if_freq_accum = 0 at the window's first block: the sum of the prompts over the window's blocks is the record's I, Q).
+ *   blocks         n_blocks consecutive 1 ms blocks of 4092 bytes each (GPSX_IF_2BIT_SM layout) whatever the context's IF format,
+ *                  shared by all channels; 1 <= n_blocks <= 4096
+ *   channel state  the gpsx_trk_state_t of gpsx_track_epl_batch (one state array serves the sign-only and the weighted step):
+ *                  tau = (int)code_phase_fine (C truncation towards zero) reduced to [0, 16368) with a non-negative remainder,
+ *                  constant over the call's blocks (code Doppler moves the peak about 3 samples per 100 ms at 5 kHz: the host
+ *                  updates it between calls); f = (float)if_hz + if_freq_offset_hz, as gpsx_track_epl_batch forms it -- for
+ *                  integer-valued offsets the weighted grids' (float)(if_hz + doppler)
+ *   carrier        block b's sign plane is wiped by the reference's NCO starting from acc_b = if_freq_accum + b * 511 * step32
+ *                  mod 2^32, step32 = (uint32)((uint64)nco_step(f) * 32): gpsx_acq_grid_weighted_coh's chaining, started from the
+ *                  channel's accumulator instead of 0.  After the call if_freq_accum = acc_{n_blocks} is written back.  The
+ *                  sixteen unmixed samples of every block: weight 0
+ *   samples        vI_b[n], vQ_b[n] in {0, +-1, +-3} ({0, +-1} under GPSX_WEIGHTS_SIGN_ONLY): exactly the weighted grids' values
+ *   correlators    for k = E, P, L with tau_E = tau - spacing, tau_P = tau, tau_L = tau + spacing (mod 16368):
+ *                  I_k = sum_n vI_b[n] c[((n - tau_k) mod 16368) / 16], Q likewise, c the +-1 replica, circular;
+ *                  |I|, |Q| <= 3 x 16352 = 49 056
+ *   output         iq_out[n_blocks][n_ch][6] = IE, QE, IP, QP, IL, QL as int32, exact
+ *   sign           (|E| - |L|) / (|E| + |L|) > 0 means tau is too large (magnitudes summed over 40 blocks of a satellite at
+ *                  amplitude 0.1: a +3 sample error gives +0.36 at spacing 8, +0.14 at spacing 2, +0.40 at spacing 15; -3 gives
+ *                  -0.32, -0.12, -0.45)
+ * This is NOT gpsx_track_epl_batch on the sign plane: no reference quirks.  GPSX_WEIGHTS_SIGN_ONLY differs from that call by its
+ * quirk terms (the replica's zeroed first samples, the words odd byte offsets skip, the half-chip tap spacing in bytes) and by
+ * the int16 centring of its accumulators.
+ * Errors: a NULL cfg, blocks, state or output pointer, weights or spacing out of range, n_blocks out of range, n_ch < 1 and a
+ * size product that overflows return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.  PRNs are validated BY THE
+ * KERNEL, with gpsx_track_epl_batch(_dev)'s policy: a channel whose prn is outside 1..210 -- or whose code_phase_fine is not
+ * finite or has magnitude >= 2^24 -- gets six zeros per block, its accumulator IS advanced, and the call then returns
+ * GPSX_EINVAL: gpsx_track_epl_weighted after its wait, gpsx_track_epl_weighted_dev from the next gpsx_synchronize().
+ * Vector ALU (k_track_epl_weighted: a wave per channel and block; three taps are no contraction, so there is no matrix-core form
+ * and gpsx_set_acq_path does not apply).  The host variant copies blocks and states in, states and iq_out out, and does not
+ * recognise capture-ring pointers. */
+typedef struct {
+  int32_t weights;   /* GPSX_WEIGHTS_SIGN_MAGNITUDE or GPSX_WEIGHTS_SIGN_ONLY                              */
+  int32_t spacing;   /* Early and Late sit `spacing` samples before / after Prompt: 1 .. 15; 8 = half a chip */
+} gpsx_trk_weighted_t;
+int gpsx_track_epl_weighted_dev(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                gpsx_trk_state_t *d_st, int n_ch, int32_t *d_iq_out);
+int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                            gpsx_trk_state_t *st, int n_ch, int32_t *iq_out);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

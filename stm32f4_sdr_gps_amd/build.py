@@ -80,7 +80,11 @@ def check_no_scratch() -> dict:
     hyb = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_acq_hyb.o")).items() if "k_acq_hyb" in k}
     if len(hyb) != 2 or not all(any(k in name for name in hyb) for k in ("k_acq_hyb_mx", "k_acq_hyb_vec")):
         raise RuntimeError(f"expected k_acq_hyb_mx and k_acq_hyb_vec in build/k_acq_hyb.o, found {sorted(hyb)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb}
+    # ... and the weighted E/P/L correlators (twelve counters and sixteen plane words per lane: no spill by a wide margin)
+    trw = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_weighted.o")).items() if "k_track_epl_weighted" in k}
+    if len(trw) != 1:
+        raise RuntimeError(f"expected k_track_epl_weighted in build/k_track_weighted.o, found {sorted(trw)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

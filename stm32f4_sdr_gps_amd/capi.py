@@ -136,6 +136,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_acq_grid_weighted_coh_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_acq_grid_weighted_hyb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_acq_grid_weighted_hyb_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_track_epl_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_track_epl_weighted_dev.argtypes = lib.gpsx_track_epl_weighted.argtypes
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -483,6 +485,20 @@ class Engine:
         self._chk(self.lib.gpsx_acq_grid_weighted_hyb(self.h, C.byref(g), n_coh, n_seg, blocks.ctypes.data, len(blocks),
                                                       peaks.ctypes.data), "gpsx_acq_grid_weighted_hyb")
         return peaks
+
+    def track_epl_weighted(self, blocks_2bit: np.ndarray, states: np.ndarray, use_magnitude: bool = True, spacing: int = 8) -> np.ndarray:
+        """EXTENSION: Early / Prompt / Late on weighted two-bit samples over the n_blocks consecutive 4092-byte blocks given, with
+        the weighted grids' sample, carrier and replica definitions (a grid record hands over exactly: phase -> code_phase_fine,
+        Doppler bin -> if_freq_offset_hz, accumulator 0 at the window's first block).  states: TRK_DTYPE array, updated in place
+        (if_freq_accum advanced by n_blocks blocks).  Early and Late sit `spacing` samples (1 .. 15) around Prompt.
+        -> int32 [n_blocks, n_ch, 6] = IE, QE, IP, QP, IL, QL"""
+        assert states.dtype == TRK_DTYPE and states.flags.c_contiguous
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        cfg = np.array([1 if use_magnitude else 0, spacing], np.int32)
+        iq = np.zeros((len(blocks), len(states), 6), np.int32)
+        self._chk(self.lib.gpsx_track_epl_weighted(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), states.ctypes.data,
+                                                   len(states), iq.ctypes.data), "gpsx_track_epl_weighted")
+        return iq
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

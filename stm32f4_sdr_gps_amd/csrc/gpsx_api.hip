@@ -1003,6 +1003,69 @@ int gpsx_track_epl_batch(gpsx_ctx *ctx, const uint8_t *if_block, gpsx_trk_state_
   return track_prn_verdict(ctx);
 }
 
+/* ---- extension: E/P/L on weighted two-bit samples, K blocks per launch ----------------------------------------------------- */
+
+namespace {
+// every refusal of gpsx_track_epl_weighted(_dev), before anything is written; *iq_bytes = the records' size
+int track_weighted_check(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *blocks, int n_blocks, const void *st, int n_ch,
+                         const void *iq_out, size_t *iq_bytes)
+{
+  if (!cfg || !blocks || !st || !iq_out)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->weights != GPSX_WEIGHTS_SIGN_ONLY && cfg->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
+    return fail(ctx, GPSX_EINVAL, "unknown weights");
+  if (cfg->spacing < 1 || cfg->spacing > 15)
+    return fail(ctx, GPSX_EINVAL, "spacing must be 1..15 samples");
+  if (n_blocks < 1 || n_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
+  if (n_ch < 1)
+    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
+  size_t recs = 0;
+  if (__builtin_mul_overflow((size_t)n_blocks, (size_t)n_ch, &recs) || __builtin_mul_overflow(recs, 6 * sizeof(int32_t), iq_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_blocks x n_ch records overflow a size");
+  return GPSX_OK;
+}
+}  // namespace
+
+int gpsx_track_epl_weighted_dev(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                gpsx_trk_state_t *d_st, int n_ch, int32_t *d_iq_out)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t iq_bytes = 0;
+  if (int rc = track_weighted_check(ctx, cfg, d_if_blocks_2bit, n_blocks, d_st, n_ch, d_iq_out, &iq_bytes)) return rc;
+  launch_track_epl_weighted(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), n_blocks, ctx->if_hz,
+                            cfg->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, cfg->spacing, d_st, n_ch, ctx->d_trk_rep, d_iq_out,
+                            ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize, as gpsx_track_epl_batch_dev)
+  LAUNCHCHK(ctx, "k_track_epl_weighted");
+  ctx->last_kernel = "k_track_epl_weighted";
+  return GPSX_OK;
+}
+
+int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                            gpsx_trk_state_t *st, int n_ch, int32_t *iq_out)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t iq_bytes = 0;
+  if (int rc = track_weighted_check(ctx, cfg, if_blocks_2bit, n_blocks, st, n_ch, iq_out, &iq_bytes)) return rc;
+  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, st_bytes = (size_t)n_ch * sizeof(gpsx_trk_state_t);
+  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(st_bytes) + arena_size(iq_bytes)))
+    return rc;
+  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
+  gpsx_trk_state_t *d_st = arena_take<gpsx_trk_state_t>(ctx, n_ch);
+  int32_t *d_iq = arena_take<int32_t>(ctx, iq_bytes / sizeof(int32_t));
+  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernels, as gpsx_track_epl_batch does)
+  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_st, st, st_bytes, hipMemcpyHostToDevice, ctx->stream));
+  launch_track_epl_weighted(ctx->stream, d_if, n_blocks, ctx->if_hz, cfg->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, cfg->spacing, d_st,
+                            n_ch, ctx->d_trk_rep, d_iq, ctx->d_bad_prn);
+  LAUNCHCHK(ctx, "k_track_epl_weighted");
+  ctx->last_kernel = "k_track_epl_weighted";
+  HIPCHK(ctx, hipMemcpyAsync(st, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(iq_out, d_iq, iq_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return track_prn_verdict(ctx);
+}
+
 /* ---- extension: weighted two-bit acquisition grid ------------------------------------------------------------------------ */
 
 namespace {

@@ -129,6 +129,11 @@ void launch_acq_hyb_mx(hipStream_t s, const uint8_t *d_if_blocks, int stride_blo
 void launch_acq_hyb_vec(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_coh, int n_seg, int n_prn,
                         const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
                         int use_magnitude, gpsx_peak_t *d_peaks);
+// extension: gpsx_track_epl_weighted (k_track_weighted.hip) -- E/P/L on weighted two-bit samples, n_blocks 4092-byte blocks x n_ch
+// channels in one launch, d_iq [n_blocks][n_ch][6] int32; every channel's accumulator is advanced by n_blocks blocks (at
+// n_blocks >= 2 by k_track_weighted_advance behind the correlators).  d_bad_prn as launch_track_epl's.
+void launch_track_epl_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, int use_magnitude, int spacing,
+                               gpsx_trk_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, int32_t *d_iq, uint32_t *d_bad_prn);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)
