@@ -19,6 +19,7 @@
 //    block.  The state is read by every block's unit, so the accumulator a call leaves is written where nothing else can be reading
 //    it: by the kernel itself at K = 1, by k_track_weighted_advance behind it on the stream otherwise.
 #include "gpsx_track_wave.hpp"
+#include "gpsx_track_weighted_plan.hpp"
 
 namespace gpsx {
 
@@ -212,15 +213,9 @@ void launch_track_epl_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, i
 {
   if (n_ch <= 0 || n_blocks <= 0)
     return;
-  // channels per wave: as many as leave ~4 workgroups per CU over the (block, channel group) units, 16 at most (lanes 4 c + k
-  // carry the per-channel values), and no more than spread the channels over a workgroup's four waves
-  long cpw = (long)n_ch * n_blocks / (4 * 256 * 4);
-  const long spread = ((long)n_ch + 3) / 4;
-  cpw = cpw > spread ? spread : cpw;
-  cpw = cpw < 1 ? 1 : (cpw > 16 ? 16 : cpw);
-  const unsigned groups = (unsigned)(((long)n_ch + 4 * cpw - 1) / (4 * cpw));
-  hipLaunchKernelGGL(k_track_epl_weighted, dim3(groups, (unsigned)n_blocks), dim3(256), 0, s, d_if_blocks_2bit, if_hz, use_magnitude,
-                     spacing, d_st, n_ch, (int)cpw, d_trk_rep, d_iq, d_bad_prn, n_blocks == 1 ? 1 : 0);
+  const TrackWeightedPlan p = plan_track_weighted(n_ch, n_blocks);   // channels per wave and workgroups: gpsx_track_weighted_plan.hpp
+  hipLaunchKernelGGL(k_track_epl_weighted, dim3(p.groups, (unsigned)n_blocks), dim3(256), 0, s, d_if_blocks_2bit, if_hz, use_magnitude,
+                     spacing, d_st, n_ch, p.cpw, d_trk_rep, d_iq, d_bad_prn, n_blocks == 1 ? 1 : 0);
   if (n_blocks > 1)
     hipLaunchKernelGGL(k_track_weighted_advance, dim3((unsigned)(((long)n_ch + 255) / 256)), dim3(256), 0, s, if_hz, d_st, n_ch,
                        (u32)n_blocks);

@@ -64,6 +64,32 @@ def test_accumulator_left_after_k_blocks(oracle):
             assert int(acc[ch]) == (a0 + k * 511 * step32) % (1 << 32)
 
 
+@pytest.mark.parametrize("use_mag", [True, False])
+def test_selected_blocks_equal_the_full_computation(oracle, use_mag):
+    """track(blocks=...) starts block b from acc + b x 511 x step32: the selected records are the full computation's bit for
+    bit, the others stay zero, the accumulators are the whole call's; with a channel selection on top, and counted"""
+    blocks = _blocks(7, seed=9)
+    st = _states([(7, 4321.0, 1310.0, 0), (19, 16367.2, -2240.5, 0xFEDCBA98), (150, 3.0, 4999.75, 77), (0, 5.0, 10.0, 1),
+                  (33, float("nan"), -8.0, 2)])
+    full, acc_full = T.track(oracle, blocks, st, use_mag, 5)
+    assert full[:, :3, :].any(axis=2).all() and not full[:, 3:, :].any()
+    for pick in ([0], [6], [2, 5], [6, 0, 3, 3], range(7)):
+        n = [0]
+        got, acc = T.track(oracle, blocks, st, use_mag, 5, blocks=pick, count=n)
+        assert got.dtype == np.int32 and acc.dtype == np.uint32 and np.array_equal(acc, acc_full)
+        sel = sorted(set(pick))
+        rest = [b for b in range(7) if b not in sel]
+        assert np.array_equal(got[sel], full[sel]) and not got[rest].any()
+        assert n[0] == 3 * len(sel)                                        # the bad channels are not restated
+    n = [0]
+    got, acc = T.track(oracle, blocks, st, use_mag, 5, channels=[1, 3], blocks=[4, 1], count=n)
+    assert np.array_equal(acc, acc_full) and np.array_equal(got[[1, 4], 1], full[[1, 4], 1]) and n[0] == 2
+    got[[1, 4], 1] = 0
+    assert not got.any()
+    with pytest.raises(AssertionError):
+        T.track(oracle, blocks, st, use_mag, 5, blocks=[7])
+
+
 def test_tau_truncates_towards_zero_and_wraps():
     for phase, tau in ((0.0, 0), (7.9, 7), (16367.99, 16367), (-3.5, 16365), (16370.2, 2), (-0.9, 0), (16368.0, 0),
                        (-16368.0, 0), (16777215.0, 16777215 % 16368)):
