@@ -30,7 +30,8 @@ extern "C" {
                                             * older header must not run on this library: call gpsx_abi_check once at start-up.
                                             * gpsx_acq_grid_weighted_ms(_dev) came later in 0.1.1: new entry points, no layout change;
                                             * so did gpsx_acq_grid_weighted_coh(_dev).
-                                            * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change. */
+                                            * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change;
+                                            * gpsx_track_loop_weighted(_dev) too (new structs of their own). */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -432,6 +433,70 @@ int gpsx_track_epl_weighted_dev(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, c
                                 gpsx_trk_state_t *d_st, int n_ch, int32_t *d_iq_out);
 int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
                             gpsx_trk_state_t *st, int n_ch, int32_t *iq_out);
+
+/* ---- EXTENSION, not in the reference: a closed DLL / Costas PLL / FLL on WEIGHTED two-bit samples, state resident in HBM -------
+ * gpsx_track_epl_weighted with the loop behind it on the device: n_blocks consecutive 1 ms blocks per launch, the six correlator
+ * sums of every coherent window of n_coh blocks (1 .. 20) fed to the discriminators, code phase and carrier updated once per
+ * window, one 36-byte record per (window, channel) and nothing else back to the host.  cfg is per launch: a pull-in launch with
+ * fll_c set and a small n_coh, then steady-state launches, on the same state array.  A grid record hands over by filling the
+ * first four fields of a zeroed state (they ARE a gpsx_trk_state_t); the alignment of a 20 ms window with the data bit edge stays
+ * the caller's business (the _hyb grid's guidance above).  No carrier aiding of the code loop.
+ *
+ * Definition, for window u of a channel.  Every float operation is one IEEE single operation in the order written: no
+ * contraction, correctly rounded division.
+ *   correlators    for the window's blocks b = 0 .. n_coh - 1 the six int32 values gpsx_track_epl_weighted returns for the state at
+ *                  the window's start: tau, f = (float)if_hz + if_freq_offset_hz and step32 constant over the window,
+ *                  acc_b = if_freq_accum + b * 511 * step32; summed over b (|sum| <= 20 x 49 056).  if_freq_accum then advances by
+ *                  n_coh * 511 * step32 (the step of the window just processed)
+ *   DLL            e2 = IE^2 + QE^2, l2 = IL^2 + QL^2 in int64; d = (e2 + l2 == 0) ? 0 : (float)(e2 - l2) / (float)(e2 + l2)
+ *                  (int64 -> float rounds to nearest even); d > 0: tau is too large.  T = (float)n_coh * 0.001f;
+ *                  code_phase_fine = code_phase_fine - (dll_c1 * (d - dll_err) + (dll_c2 * T) * d); one wrap into [0, 16368):
+ *                  + 16368.0f if negative, - 16368.0f if >= 16368.0f; dll_err = d
+ *   Costas PLL     IP == 0: p = QP > 0 ? 0.25f : QP < 0 ? -0.25f : 0; else p = atanf((float)QP / (float)IP) * 0.15915494f
+ *                  (cycles; atanf is glibc <= 2.40's fdlibm one, operation by operation); insensitive to data bits
+ *   FLL            only if fll_c != 0 and n_updates > 0: cross = prev_ip * QP - prev_qp * IP, dot = prev_ip * IP + prev_qp * QP in
+ *                  int64; fe = (dot == 0) ? 0 : atanf((float)cross / (float)dot) * 0.15915494f / T (Hz); otherwise fe = 0
+ *   carrier        if_freq_offset_hz = if_freq_offset_hz - ((pll_c1 * (p - pll_err) + (pll_c2 * T) * p) + fll_c * fe)
+ *   end of window  pll_err = p; prev_ip = IP; prev_qp = QP; n_updates++; then the record is written
+ * The loop rests at if_freq_offset_hz ~ fd (1 + 1/1022): the NCO mixes 16 352 of a block's 16 368 samples, so the accumulator loses
+ * 16 samples of phase per block (as in the grids) and the loop makes that up in frequency.
+ * Errors: NULL pointers, weights / spacing / n_coh out of range, n_blocks outside 1 .. 4096 or not a multiple of n_coh, n_ch < 1 and
+ * a gain that is not finite return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.  Channels are validated BY THE
+ * KERNEL with gpsx_track_epl_weighted's policy, window by window: while a channel's prn is outside 1 .. 210 or its code_phase_fine is
+ * not finite or has magnitude >= 2^24, its window's iq is zero, its floats and loop memory stay as they were, its accumulator IS
+ * advanced, and GPSX_EINVAL comes from gpsx_track_loop_weighted after its wait / from the next gpsx_synchronize() after _dev.
+ * The host variant takes blocks and records in host memory and the state on the device, as gpsx_track_loop does. */
+typedef struct {                 /* 40 bytes, device resident */
+  int32_t  prn;                  /* the first 16 bytes ARE a gpsx_trk_state_t: a grid record hands over by filling these four */
+  float    code_phase_fine;
+  float    if_freq_offset_hz;
+  uint32_t if_freq_accum;
+  float    dll_err, pll_err;     /* the previous window's discriminator outputs */
+  int32_t  prev_ip, prev_qp;     /* the previous window's summed prompt (FLL) */
+  uint32_t n_updates;            /* windows processed so far; 0 = no previous prompt */
+  uint32_t reserved;             /* 0 */
+} gpsx_wloop_state_t;
+
+typedef struct {
+  int32_t weights;               /* GPSX_WEIGHTS_SIGN_MAGNITUDE or GPSX_WEIGHTS_SIGN_ONLY */
+  int32_t spacing;               /* 1 .. 15, as gpsx_trk_weighted_t */
+  int32_t n_coh;                 /* blocks summed coherently before each loop update, 1 .. 20 */
+  float   dll_c1, dll_c2;        /* the reference's PI form; its values are 1, 300 */
+  float   pll_c1, pll_c2;        /* the reference's are 4, 3000 (8, 5000 after bit sync) */
+  float   fll_c;                 /* 0 = no frequency loop */
+} gpsx_wloop_cfg_t;
+
+typedef struct {                 /* 36 bytes, one per (window, channel) */
+  int32_t  iq[6];                /* IE, QE, IP, QP, IL, QL summed over the window's n_coh blocks, exact */
+  float    code_phase_fine, if_freq_offset_hz;   /* AFTER this window's update */
+  uint32_t if_freq_accum;        /* after the window's last block */
+} gpsx_wloop_rec_t;
+
+/* d_rec / rec: [n_blocks / n_coh][n_ch] */
+int gpsx_track_loop_weighted_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                 gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec);
+int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                             gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

@@ -84,7 +84,11 @@ def check_no_scratch() -> dict:
     trw = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_weighted.o")).items() if "k_track_epl_weighted" in k}
     if len(trw) != 1:
         raise RuntimeError(f"expected k_track_epl_weighted in build/k_track_weighted.o, found {sorted(trw)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw}
+    # ... and the closed loop behind them (k_track_wloop: the same correlator body, ten state words and the loop's floats on top)
+    wloop = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted.o")).items() if "k_track_wloop" in k}
+    if len(wloop) != 1:
+        raise RuntimeError(f"expected k_track_wloop in build/k_track_loop_weighted.o, found {sorted(wloop)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

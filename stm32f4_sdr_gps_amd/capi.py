@@ -45,6 +45,23 @@ LOOP_TRACE_DTYPE = np.dtype([("iq", "<i2", 6), ("code_phase_fine", "<f4"), ("if_
 assert LOOP_DTYPE.itemsize == 120 and LOOP_TRACE_DTYPE.itemsize == 24
 PEAK_DTYPE = np.dtype([("max_val", "<u4"), ("phase", "<u4"), ("sum", "<u4"), ("avr", "<u4")])
 TRACK_CHUNK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)   # gpsx_track_chunk_fn
+# gpsx_wloop_state_t / gpsx_wloop_cfg_t / gpsx_wloop_rec_t (the closed loop on weighted two-bit samples)
+WLOOP_STATE_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"), ("if_freq_accum", "<u4"),
+                              ("dll_err", "<f4"), ("pll_err", "<f4"), ("prev_ip", "<i4"), ("prev_qp", "<i4"), ("n_updates", "<u4"),
+                              ("reserved", "<u4")])
+WLOOP_CFG_DTYPE = np.dtype([("weights", "<i4"), ("spacing", "<i4"), ("n_coh", "<i4"), ("dll_c1", "<f4"), ("dll_c2", "<f4"),
+                            ("pll_c1", "<f4"), ("pll_c2", "<f4"), ("fll_c", "<f4")])
+WLOOP_REC_DTYPE = np.dtype([("iq", "<i4", 6), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"), ("if_freq_accum", "<u4")])
+assert WLOOP_STATE_DTYPE.itemsize == 40 and WLOOP_CFG_DTYPE.itemsize == 32 and WLOOP_REC_DTYPE.itemsize == 36
+
+
+def wloop_cfg(n_coh, use_magnitude=True, spacing=8, dll=(1.0, 300.0), pll=(4.0, 3000.0), fll=0.0) -> np.ndarray:
+    """a gpsx_wloop_cfg_t as a one-element WLOOP_CFG_DTYPE array"""
+    cfg = np.zeros(1, WLOOP_CFG_DTYPE)
+    cfg[0] = (1 if use_magnitude else 0, spacing, n_coh, dll[0], dll[1], pll[0], pll[1], fll)
+    return cfg
+
+
 TRK_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"),
                       ("if_freq_accum", "<u4")])
 JOB_DTYPE = np.dtype([("block", "<i4"), ("n_ms", "<i4"), ("prn", "<i4"), ("freq_hz", "<f4"), ("offset_bits", "<i4"),
@@ -138,6 +155,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_acq_grid_weighted_hyb_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_track_epl_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_track_epl_weighted_dev.argtypes = lib.gpsx_track_epl_weighted.argtypes
+    lib.gpsx_track_loop_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_track_loop_weighted_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -499,6 +518,19 @@ class Engine:
         self._chk(self.lib.gpsx_track_epl_weighted(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), states.ctypes.data,
                                                    len(states), iq.ctypes.data), "gpsx_track_epl_weighted")
         return iq
+
+    def track_loop_weighted(self, blocks_2bit: np.ndarray, d_state: int, n_ch: int, n_coh: int, use_magnitude: bool = True,
+                            spacing: int = 8, dll=(1.0, 300.0), pll=(4.0, 3000.0), fll: float = 0.0) -> np.ndarray:
+        """EXTENSION: the closed DLL / Costas PLL / FLL on weighted two-bit samples over the n_blocks consecutive 4092-byte blocks
+        given (a multiple of n_coh), on the n_ch WLOOP_STATE_DTYPE states at device address d_state: the loop is updated once per
+        coherent window of n_coh blocks (1 .. 20).  dll / pll: the (c1, c2) gains of the PI forms, fll: the frequency loop's gain
+        (0: none).  -> WLOOP_REC_DTYPE [n_blocks / n_coh, n_ch]"""
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        cfg = wloop_cfg(n_coh, use_magnitude, spacing, dll, pll, fll)
+        rec = np.zeros((len(blocks) // max(n_coh, 1), n_ch), WLOOP_REC_DTYPE)
+        self._chk(self.lib.gpsx_track_loop_weighted(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), C.c_void_p(d_state), n_ch,
+                                                    rec.ctypes.data), "gpsx_track_loop_weighted")
+        return rec
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -134,6 +134,12 @@ void launch_acq_hyb_vec(hipStream_t s, const uint8_t *d_if_blocks, int n_search,
 // n_blocks >= 2 by k_track_weighted_advance behind the correlators).  d_bad_prn as launch_track_epl's.
 void launch_track_epl_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, int use_magnitude, int spacing,
                                gpsx_trk_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, int32_t *d_iq, uint32_t *d_bad_prn);
+// extension: gpsx_track_loop_weighted (k_track_loop_weighted.hip: k_track_wloop) -- the closed DLL / PLL / FLL on weighted two-bit
+// samples: n_blocks 4092-byte blocks (a multiple of cfg.n_coh) one after the other inside one launch, d_rec [n_blocks / n_coh][n_ch];
+// the states are read once and written once.  d_bad_prn as launch_track_epl's.
+void launch_track_loop_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wloop_cfg_t &cfg,
+                                gpsx_wloop_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wloop_rec_t *d_rec,
+                                uint32_t *d_bad_prn);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -1,0 +1,25 @@
+// gpsx_track_loop_weighted_plan.hpp -- the launch shape of k_track_wloop (k_track_loop_weighted.hip): how many channels a wave
+// serves one after the other and how many workgroups that takes.  The blocks run one after the other inside the kernel (the loop
+// is a recurrence in time), so there is no block dimension to spread over: the shape depends on n_ch alone.  Pure host C++ (no
+// HIP): tests/test_track_loop_weighted_plan.py compiles it with g++ and checks the shapes the GPU tests run.
+#pragma once
+
+namespace gpsx {
+
+constexpr int kTrackLoopWeightedMaxCpw = 16;   // lanes 4 c + k carry channel c's values: sixteen channels fill a wave
+
+struct TrackLoopWeightedPlan {
+  int cpw;           // channels per wave, 1 .. 16; wave w of workgroup g serves channels (4 g + w) cpw .. + cpw - 1 below n_ch
+  unsigned groups;   // workgroups of four waves
+};
+
+// channels per wave: as many as leave ~4 workgroups per CU (launch_track_loop's rule), 16 at most
+inline TrackLoopWeightedPlan plan_track_loop_weighted(int n_ch)
+{
+  long cpw = (long)n_ch / (4 * 256 * 4);
+  cpw = cpw < 1 ? 1 : (cpw > kTrackLoopWeightedMaxCpw ? kTrackLoopWeightedMaxCpw : cpw);
+  const unsigned groups = (unsigned)(((long)n_ch + 4 * cpw - 1) / (4 * cpw));
+  return TrackLoopWeightedPlan{(int)cpw, groups};
+}
+
+}  // namespace gpsx

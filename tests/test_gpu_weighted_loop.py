@@ -1,0 +1,358 @@
+"""The closed DLL / Costas PLL / FLL on weighted two-bit samples (EXTENSION, not in the reference: include/gpsx.h
+gpsx_track_loop_weighted; k_track_wloop on the vector ALU) against its exact CPU restatement (tests/weighted_loop_ref.py, pinned in
+tests/test_weighted_loop_reference.py).  Every comparison is for equality, byte for byte, on records and final states: channel
+counts that fill waves partly and fully and leave waves of a workgroup idle, every channels-per-wave value the plan can choose
+(tests/weighted_loop_cases.py, asserted without a GPU in tests/test_track_loop_weighted_plan.py), n_coh 1 / 4 / 10 / 20, both
+weights, spacings 1 / 8 / 15, a non-default IF, a few hundred blocks; with gains 0 the window sums against
+gpsx_track_epl_weighted_dev on every channel (GPU against GPU); split launches against one; the device against the host variant;
+the exact handover from a coherent grid's record; bad channels and refusals, with canaries; and the pull-in scenario, truncated."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import weighted_loop_cases as S
+import weighted_loop_ref as L
+
+pytestmark = pytest.mark.gpu
+
+EINVAL = -22
+GUARD = 4096
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from stm32f4_sdr_gps_amd import capi
+    e = capi.Engine(0)
+    yield e
+    e.close()
+
+
+def _blocks(n, amp=0.3, seed=3):
+    from stm32f4_sdr_gps_amd import synth
+    sats = [synth.Sat(7, 1310.0, 4321.0, amp, 0.4), synth.Sat(19, -2240.0, 12007.0, amp, 2.0), synth.Sat(30, 2018.0, 13000.0, amp, 4.0)]
+    return synth.make_if_static(n, sats, noise_amp=1.0, seed=seed, two_bit=True)
+
+
+# code phases on the seam (tau -+ spacing wraps on either side for every spacing; an update can carry them across either end)
+PHASES = [4321.0, 0.0, 7.9, 16367.99, 3.0, 16365.0, 0.5, 14.0, 16353.0, 12007.25, 1.0, 16367.0, 15.0, 16352.5, 0.25, 16366.5]
+PRNS = [7, 19, 30, 1, 33, 64, 150, 210, 32, 209, 5, 100]
+
+
+def _states(n, seed):
+    rng = np.random.default_rng(seed)
+    st = np.zeros(n, L.STATE_DTYPE)
+    idx = np.arange(n)
+    st["prn"] = np.where(idx < 3 * len(PRNS), np.array(PRNS)[idx % len(PRNS)], rng.integers(1, 211, n))
+    st["code_phase_fine"] = np.where(idx < 2 * len(PHASES), np.array(PHASES, np.float32)[idx % len(PHASES)], rng.uniform(0.0, 16367.0, n).astype(np.float32))
+    st["if_freq_offset_hz"] = np.where(idx % 3 == 0, rng.integers(-5000, 5001, n), rng.uniform(-5000.0, 5000.0, n))
+    st["if_freq_offset_hz"][:3] = [1310.0, -2240.0, 2018.0][:n]
+    st["if_freq_accum"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    st["if_freq_accum"][::5] = 0
+    half = idx % 2 == 1                                   # every other channel arrives with a loop memory
+    st["dll_err"] = np.where(half, rng.uniform(-0.5, 0.5, n), 0.0)
+    st["pll_err"] = np.where(half, rng.uniform(-0.2, 0.2, n), 0.0)
+    st["prev_ip"] = np.where(half, rng.integers(-30000, 30001, n), 0)
+    st["prev_qp"] = np.where(half, rng.integers(-30000, 30001, n), 0)
+    st["n_updates"] = np.where(half, rng.integers(1, 1000, n), 0)
+    return st
+
+
+def _cfg(c):
+    from stm32f4_sdr_gps_amd import capi
+    return capi.wloop_cfg(c["n_coh"], c["use_magnitude"], c["spacing"], (c["dll_c1"], c["dll_c2"]), (c["pll_c1"], c["pll_c2"]), c["fll_c"])
+
+
+def _gpu(eng, blocks, st, cfg, dev=False, pieces=None):
+    """the library on a copy of `st` in device memory -> (records, states after); dev: blocks and records in device memory too"""
+    blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 4092)
+    n_ch, n_coh = len(st), cfg["n_coh"]
+    after = st.copy()
+    d_st = eng.malloc(st.nbytes)
+    recs = []
+    try:
+        eng.h2d(d_st, st)
+        at = 0
+        for k in pieces or [len(blocks)]:
+            part = blocks[at:at + k]
+            at += k
+            if not dev:
+                recs.append(eng.track_loop_weighted(part, d_st, n_ch, n_coh, cfg["use_magnitude"], cfg["spacing"], (cfg["dll_c1"], cfg["dll_c2"]),
+                                                    (cfg["pll_c1"], cfg["pll_c2"]), cfg["fll_c"]))
+                assert eng.lib.gpsx_last_kernel(eng.h) == b"k_track_wloop"
+                continue
+            rec = np.zeros((k // n_coh, n_ch), L.REC_DTYPE)
+            d_if, d_rec = eng.malloc(part.nbytes), eng.malloc(rec.nbytes)
+            try:
+                eng.h2d(d_if, part)
+                c = _cfg(cfg)
+                eng._chk(eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st), n_ch,
+                                                              C.c_void_p(d_rec)), "gpsx_track_loop_weighted_dev")
+                eng.synchronize()
+                eng.d2h(rec, d_rec)
+            finally:
+                eng.free(d_if)
+                eng.free(d_rec)
+            recs.append(rec)
+        eng.d2h(after, d_st)
+    finally:
+        eng.free(d_st)
+    return np.concatenate(recs), after
+
+
+def _same(rec, after, want_rec, want_st, channels, what):
+    ch = list(channels)
+    assert rec.dtype == L.REC_DTYPE and rec.shape == want_rec.shape, what
+    bad = [c for c in ch if rec[:, c].tobytes() != want_rec[:, c].tobytes()]
+    assert not bad, (what, "records", bad[:4], rec[:, bad[0]][:2], want_rec[:, bad[0]][:2])
+    bad = [c for c in ch if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
+    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+
+
+MOVING = dict(dll=(1.0, 100.0), pll=(56.0, 1600.0), fll=0.1)
+
+# (channels, blocks, n_coh, use_magnitude, spacing, gains): every channel is restated
+SMALL = [(1, 1, 1, True, 8, MOVING), (3, 8, 4, False, 1, MOVING), (5, 20, 10, True, 15, S.STEADY), (64, 40, 20, True, 8, S.STEADY),
+         (257, 12, 4, False, 15, MOVING), (64, 6, 1, True, 1, S.REFERENCE_1MS), (3, 40, 20, False, 8, S.STEADY), (5, 30, 10, False, 1, MOVING)]
+
+
+@pytest.mark.parametrize("n_ch,n_blocks,n_coh,use_mag,spacing,gains", SMALL)
+def test_records_and_states_match_the_restatement(eng, oracle, n_ch, n_blocks, n_coh, use_mag, spacing, gains):
+    assert S.tabled(n_ch) == 1
+    blocks = _blocks(40)[:n_blocks]
+    st = _states(n_ch, 100 * n_ch + n_blocks)
+    cfg = L.make_cfg(n_coh, use_mag, spacing, gains["dll"], gains["pll"], gains["fll"])
+    want_st = st.copy()
+    want = L.run(oracle, blocks, want_st, cfg)
+    rec, after = _gpu(eng, blocks, st, cfg)
+    _same(rec, after, want, want_st, range(n_ch), (n_ch, n_blocks, n_coh, use_mag, spacing))
+    assert not np.array_equal(after["code_phase_fine"], st["code_phase_fine"])
+
+
+@pytest.mark.parametrize("n_ch", [r[0] for r in S.SHAPES if r[0] > 257])
+def test_every_channels_per_wave_value(eng, oracle, n_ch):
+    """cpw 2 .. 16 through the device entry point, canaries around records and states: 24 sampled channels (the first, the last,
+    the ragged last wave's and the wave boundaries among them) against the restatement over 8 blocks in windows of 4, all of them
+    against gpsx_track_epl_weighted_dev's sums with gains 0"""
+    from stm32f4_sdr_gps_amd import capi
+    cpw = S.tabled(n_ch)
+    k, n_coh = 8, 4
+    use_mag, spacing = cpw % 2 == 0, (1, 8, 15)[cpw % 3]
+    blocks = _blocks(8, seed=cpw)
+    st = _states(n_ch, n_ch)
+    rng = np.random.default_rng(n_ch)
+    last = S.ROWS[n_ch][2]
+    sample = sorted({0, 1, cpw - 1, cpw, 4 * cpw - 1, 4 * cpw, n_ch - 1, n_ch - last, max(0, n_ch - last - 1)} | {int(c) for c in rng.integers(0, n_ch, 15)})
+    for gains in (MOVING, dict(dll=(0.0, 0.0), pll=(0.0, 0.0), fll=0.0)):
+        cfg = L.make_cfg(n_coh, use_mag, spacing, gains["dll"], gains["pll"], gains["fll"])
+        rec_bytes = (k // n_coh) * n_ch * 36
+        h_rec = np.full(GUARD + rec_bytes + GUARD, 0xA5, np.uint8)
+        h_st = np.full(GUARD + st.nbytes + GUARD, 0xA5, np.uint8)
+        h_st[GUARD:GUARD + st.nbytes] = st.view(np.uint8)
+        trk = np.zeros(n_ch, capi.TRK_DTYPE)
+        for f in trk.dtype.names:
+            trk[f] = st[f]
+        iq = np.zeros((k, n_ch, 6), np.int32)
+        d_if, d_rec, d_st, d_trk, d_iq = (eng.malloc(x.nbytes) for x in (blocks, h_rec, h_st, trk, iq))
+        try:
+            eng.h2d(d_if, blocks)
+            eng.h2d(d_rec, h_rec)
+            eng.h2d(d_st, h_st)
+            eng.h2d(d_trk, trk)
+            c = _cfg(cfg)
+            eng._chk(eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st + GUARD), n_ch,
+                                                          C.c_void_p(d_rec + GUARD)), "gpsx_track_loop_weighted_dev")
+            ocfg = np.array([1 if use_mag else 0, spacing], np.int32)
+            eng._chk(eng.lib.gpsx_track_epl_weighted_dev(eng.h, ocfg.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_trk), n_ch,
+                                                         C.c_void_p(d_iq)), "gpsx_track_epl_weighted_dev")
+            eng.synchronize()
+            eng.d2h(h_rec, d_rec)
+            eng.d2h(h_st, d_st)
+            eng.d2h(iq, d_iq)
+            eng.d2h(trk, d_trk)
+        finally:
+            for p in (d_if, d_rec, d_st, d_trk, d_iq):
+                eng.free(p)
+        for h, size in ((h_rec, rec_bytes), (h_st, st.nbytes)):
+            assert (h[:GUARD] == 0xA5).all() and (h[GUARD + size:] == 0xA5).all(), (n_ch, "canary")
+        rec = h_rec[GUARD:GUARD + rec_bytes].view(L.REC_DTYPE).reshape(k // n_coh, n_ch)
+        after = h_st[GUARD:GUARD + st.nbytes].view(L.STATE_DTYPE)
+        want_st = st.copy()
+        want = L.run(oracle, blocks, want_st, cfg, channels=sample)
+        _same(rec, after, want, want_st, sample, (n_ch, cpw, gains is MOVING))
+        if gains is not MOVING:      # GPU against GPU, every channel: the open-loop correlators' sums, floats untouched, accumulators
+            sums = iq.astype(np.int64).reshape(k // n_coh, n_coh, n_ch, 6).sum(axis=1)
+            assert np.array_equal(rec["iq"], sums) and np.count_nonzero(sums) > 0.9 * sums.size
+            assert np.array_equal(after["if_freq_accum"], trk["if_freq_accum"])
+            for f in ("prn", "code_phase_fine", "if_freq_offset_hz", "reserved"):
+                assert after[f].tobytes() == st[f].tobytes(), f
+            assert np.array_equal(after["n_updates"], st["n_updates"] + k // n_coh)
+
+
+def test_non_default_if(oracle):
+    from stm32f4_sdr_gps_amd import capi
+    blocks = _blocks(8, seed=8)
+    st = _states(5, 5)
+    cfg = L.make_cfg(4, True, 8, **MOVING)
+    want_st = st.copy()
+    want = L.run(oracle, blocks, want_st, cfg, if_hz=4_100_000)
+    e = capi.Engine(0)
+    try:
+        e.set_config(if_hz=4_100_000)
+        rec, after = _gpu(e, blocks, st, cfg)
+    finally:
+        e.close()
+    _same(rec, after, want, want_st, range(5), "if_hz")
+
+
+def test_a_few_hundred_blocks_split_launches_and_both_variants(eng, oracle):
+    """240 blocks, 3 channels: one launch = launches of 40 / 120 / 80 = the device variant, all equal to the restatement"""
+    blocks = _blocks(240, seed=6)
+    st = _states(3, 42)
+    for n_coh, gains in ((20, S.STEADY), (4, MOVING), (1, S.REFERENCE_1MS)):
+        cfg = L.make_cfg(n_coh, True, 8, gains["dll"], gains["pll"], gains["fll"])
+        want_st = st.copy()
+        want = L.run(oracle, blocks, want_st, cfg)
+        one = _gpu(eng, blocks, st, cfg)
+        _same(*one, want, want_st, range(3), ("one launch", n_coh))
+        for what, got in (("split", _gpu(eng, blocks, st, cfg, pieces=[40, 120, 80])), ("device", _gpu(eng, blocks, st, cfg, dev=True)),
+                          ("device, split", _gpu(eng, blocks, st, cfg, dev=True, pieces=[100, 140]))):
+            assert got[0].tobytes() == one[0].tobytes() and got[1].tobytes() == one[1].tobytes(), (what, n_coh)
+
+
+def test_a_coherent_grid_record_hands_over_exactly(eng):
+    """GPU against GPU: the best record of the coherent grid (n_coh = 10) fills the first four fields of a zeroed state -- phase ->
+    code_phase_fine, bin -> if_freq_offset_hz, accumulator 0 -- and the first window's floor(sqrt(IP^2 + QP^2)) IS the record's
+    max_val, whatever the gains (the record is written after the update, its sums were formed before)"""
+    from stm32f4_sdr_gps_amd import synth
+    blocks = synth.cold_start_block(20, seed=11, amp_scale=0.03, two_bit=True)
+    pk = eng.acq_grid_weighted_coh(blocks[:10], np.array([14], np.uint8), 1, 10, 3800, 50, 11)
+    d = int(pk[0, 0, :]["max_val"].argmax())
+    max_val, phase, dopp = int(pk[0, 0, d]["max_val"]), int(pk[0, 0, d]["phase"]), 3800 + 50 * d
+    st = L.handover(14, float(phase), float(dopp))
+    rec, after = _gpu(eng, blocks, st, L.make_cfg(10, True, 8, **MOVING))
+    ip, qp = int(rec["iq"][0, 0, 2]), int(rec["iq"][0, 0, 3])
+    print("coherent record", max_val, "at phase", phase, "bin", dopp, "Hz; first window's prompt", ip, qp)
+    assert math.isqrt(ip * ip + qp * qp) == max_val and max_val > 3000
+    assert after["n_updates"][0] == 2 and (after["prev_ip"][0], after["prev_qp"][0]) == (rec["iq"][1, 0, 2], rec["iq"][1, 0, 3])
+
+
+def test_argument_checks_write_nothing(eng):
+    from stm32f4_sdr_gps_amd import capi
+    blocks = _blocks(8)
+    st0 = _states(4, 9)
+    good = dict(cfg=dict(n_coh=4), null_cfg=False, null_if=False, null_st=False, null_out=False, n_blocks=8, n_ch=4)
+    nan, inf = float("nan"), float("inf")
+    refusals = [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(cfg=dict(n_coh=4, weights=2)),
+                dict(cfg=dict(n_coh=4, weights=-1)), dict(cfg=dict(n_coh=4, spacing=0)), dict(cfg=dict(n_coh=4, spacing=16)),
+                dict(cfg=dict(n_coh=0)), dict(cfg=dict(n_coh=-4)), dict(cfg=dict(n_coh=21)), dict(cfg=dict(n_coh=3)), dict(cfg=dict(n_coh=16)),
+                dict(n_blocks=0), dict(n_blocks=-4), dict(n_blocks=4100), dict(n_blocks=6), dict(n_ch=0), dict(n_ch=-3),
+                dict(cfg=dict(n_coh=4, dll=(nan, 1.0))), dict(cfg=dict(n_coh=4, dll=(1.0, inf))), dict(cfg=dict(n_coh=4, pll=(-inf, 1.0))),
+                dict(cfg=dict(n_coh=4, pll=(1.0, nan))), dict(cfg=dict(n_coh=4, fll=inf))]
+    d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(2 * 4 * 36)
+    try:
+        eng.h2d(d_if, blocks)
+        for dev, fn in ((False, eng.lib.gpsx_track_loop_weighted), (True, eng.lib.gpsx_track_loop_weighted_dev)):
+            for change in refusals:
+                a = {**good, **change}
+                c = a["cfg"]
+                cfg = capi.wloop_cfg(c["n_coh"], True, c.get("spacing", 8), c.get("dll", (1.0, 100.0)), c.get("pll", (56.0, 1600.0)), c.get("fll", 0.1))
+                if "weights" in c:
+                    cfg["weights"] = c["weights"]
+                rec = np.full((2, 4), 0xA5, np.uint8).repeat(36, axis=1).view(np.uint8)
+                eng.h2d(d_st, st0)
+                eng.h2d(d_rec, rec)
+                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (C.c_void_p(d_if) if dev else blocks.ctypes.data),
+                        a["n_blocks"], None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
+                        None if a["null_out"] else (C.c_void_p(d_rec) if dev else rec.ctypes.data))
+                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h), (dev, change)
+                eng.synchronize()   # nothing was enqueued, nothing is pending
+                st, dr = st0.copy(), np.zeros_like(rec)
+                eng.d2h(st, d_st)
+                eng.d2h(dr, d_rec)
+                assert (rec == 0xA5).all() and (dr == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
+    finally:
+        for p in (d_st, d_if, d_rec):
+            eng.free(p)
+
+
+def test_bad_channels(eng, oracle):
+    """PRN 0, 211 and -7, a NaN code phase and one of magnitude 2^24 among good channels, canaries around states and records: the
+    good channels are the restatement's, the bad ones get zero sums, keep floats and loop memory and have their accumulator
+    advanced; GPSX_EINVAL comes from the host variant itself and from the next synchronize after the device variant"""
+    blocks = _blocks(12)
+    st0 = _states(12, 4)
+    bad = {2: ("prn", 0), 5: ("prn", 211), 7: ("code_phase_fine", np.nan), 11: ("code_phase_fine", -16777216.0), 8: ("prn", -7)}
+    for ch, (field, value) in bad.items():
+        st0[field][ch] = value
+    good = [c for c in range(12) if c not in bad]
+    cfg = L.make_cfg(4, True, 8, **MOVING)
+    want_st = st0.copy()
+    want = L.run(oracle, blocks, want_st, cfg)
+    assert not want["iq"][:, sorted(bad)].any() and want["iq"][:, good].any(axis=(0, 2)).all()
+    for ch in bad:
+        for f in ("code_phase_fine", "if_freq_offset_hz", "dll_err", "pll_err", "prev_ip", "prev_qp", "n_updates"):
+            assert want_st[f][ch:ch + 1].tobytes() == st0[f][ch:ch + 1].tobytes()
+        assert want_st["if_freq_accum"][ch] != st0["if_freq_accum"][ch]
+    c = _cfg(cfg)
+    rec_bytes = 3 * 12 * 36
+    for dev in (False, True):
+        h_st = np.full(GUARD + st0.nbytes + GUARD, 0xA5, np.uint8)
+        h_st[GUARD:GUARD + st0.nbytes] = st0.view(np.uint8)
+        h_rec = np.full(GUARD + rec_bytes + GUARD, 0x5A, np.uint8)
+        d_st, d_if, d_rec = eng.malloc(h_st.nbytes), eng.malloc(blocks.nbytes), eng.malloc(h_rec.nbytes)
+        try:
+            eng.h2d(d_st, h_st)
+            eng.h2d(d_if, blocks)
+            eng.h2d(d_rec, h_rec)
+            eng.synchronize()
+            if dev:
+                rc = eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), 12, C.c_void_p(d_st + GUARD), 12,
+                                                          C.c_void_p(d_rec + GUARD))
+                assert rc == 0
+                assert eng.lib.gpsx_synchronize(eng.h) == EINVAL
+                assert eng.lib.gpsx_synchronize(eng.h) == 0
+                eng.d2h(h_rec, d_rec)
+            else:
+                rc = eng.lib.gpsx_track_loop_weighted(eng.h, c.ctypes.data, blocks.ctypes.data, 12, C.c_void_p(d_st + GUARD), 12,
+                                                      h_rec[GUARD:].ctypes.data)
+                assert rc == EINVAL and b"prn" in eng.lib.gpsx_last_error(eng.h)
+            eng.d2h(h_st, d_st)
+        finally:
+            for p in (d_st, d_if, d_rec):
+                eng.free(p)
+        for h, size, v in ((h_rec, rec_bytes, 0x5A), (h_st, st0.nbytes, 0xA5)):
+            assert (h[:GUARD] == v).all() and (h[GUARD + size:] == v).all(), dev
+        rec = h_rec[GUARD:GUARD + rec_bytes].view(L.REC_DTYPE).reshape(3, 12)
+        after = h_st[GUARD:GUARD + st0.nbytes].view(L.STATE_DTYPE)
+        _same(rec, after, want, want_st, range(12), ("device" if dev else "host"))
+    rec, after = _gpu(eng, blocks, st0[good].copy(), cfg)      # the same channels without the bad ones: no error
+    assert rec.tobytes() == np.ascontiguousarray(want[:, good]).tobytes() and after.tobytes() == want_st[good].tobytes()
+
+
+def test_the_pull_in_scenario_truncated(eng, oracle):
+    """tests/test_weighted_loop_reference.py's scenario at its amplitude, the three seeds' handovers as three channels on seed 1's
+    blocks: 200 ms of pull-in (n_coh = 4, frequency loop) and 400 ms of steady state (n_coh = 20) on the same state array, equal to
+    the restatement, and the 20 bits after pull-in are read on every channel"""
+    n_ms = 600
+    blocks, bits = S.scenario(S.AMPLITUDE, 1, n_ms)
+    st = np.concatenate([S.handover_state(seed) for seed in S.SEEDS])
+    want_st = st.copy()
+    want = [L.run(oracle, blocks[:S.PULL_IN_MS], want_st, L.make_cfg(**S.PULL_IN)), L.run(oracle, blocks[S.PULL_IN_MS:], want_st, L.make_cfg(**S.STEADY))]
+    d_st = eng.malloc(st.nbytes)
+    try:
+        eng.h2d(d_st, st)
+        got = [eng.track_loop_weighted(blocks[:S.PULL_IN_MS], d_st, 3, **S.PULL_IN), eng.track_loop_weighted(blocks[S.PULL_IN_MS:], d_st, 3, **S.STEADY)]
+        after = st.copy()
+        eng.d2h(after, d_st)
+    finally:
+        eng.free(d_st)
+    for g, w in zip(got, want):
+        assert g.tobytes() == w.tobytes()
+    assert after.tobytes() == want_st.tobytes()
+    for ch in range(3):
+        recs = [(0, 4, got[0][:, ch:ch + 1]), (S.PULL_IN_MS, 20, got[1][:, ch:ch + 1])]
+        errors, n_bits = S.bit_errors(recs, bits, S.PULL_IN_MS // 20, n_ms)
+        print("channel", ch, "bit errors", errors, "of", n_bits, "code phase", after["code_phase_fine"][ch], "carrier", after["if_freq_offset_hz"][ch])
+        assert errors == 0 and n_bits == 20

@@ -6,7 +6,16 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
   bench_track_kernel.py --weighted [K] [channels ...] gpsx_track_epl_weighted_dev (EXTENSION: both bits, K blocks per launch, K = 1
                                                       and the K given) beside gpsx_track_epl_batch_dev: the calls take turns in one
                                                       process, WINDOWS timed windows each, every window some tenths of a second
-                                                      long (--window-s S: another length); median, minimum and maximum per launch (one JSON line per row)"""
+                                                      long (--window-s S: another length); median, minimum and maximum per launch (one JSON line per row)
+  bench_track_kernel.py --weighted-loop [n_coh] [channels ...]
+                                                      gpsx_track_loop_weighted_dev (EXTENSION: the closed loop on both bits, K = 200
+                                                      blocks per launch, n_coh = 1, 20 and the n_coh given) beside what it is made of
+                                                      and measured against: gpsx_track_epl_weighted_dev at K = 20 (the same correlators,
+                                                      open loop), and the sign plane's pair gpsx_track_loop_dev (K = 200) /
+                                                      gpsx_track_epl_batch_dev -- time per channel-millisecond and the two
+                                                      closed-over-open ratios; then the host-driven alternative: one K = 200,
+                                                      n_coh = 10 launch against twenty gpsx_track_epl_weighted calls of K = 10 with the
+                                                      records copied back and the states rewritten by the host (wall clock)"""
 import ctypes as C
 import json
 import os
@@ -79,15 +88,125 @@ def weighted(k_blocks, counts):
             eng.free(p)
 
 
-def main():
+def _timed_rows(eng, calls, extra):
+    """calls: {name: (blocks per launch, fn)} taking turns, WINDOWS windows each -> {name: median us per launch}, one JSON line each"""
+    e0, e1 = eng.event(), eng.event()
+
+    def window(fn, reps):
+        eng.record(e0)
+        for _ in range(reps):
+            fn()
+        eng.record(e1)
+        eng.synchronize()
+        return eng.elapsed_ms(e0, e1) / reps * 1e3
+
+    reps = {}
+    for name, (_, fn) in calls.items():   # warm-up, then as many launches as fill a window
+        eng._chk(fn(), name)
+        window(fn, 3)
+        reps[name] = max(3, int(WINDOW_S * 1e6 / window(fn, 5)))
+    us = {name: [] for name in calls}
+    for _ in range(WINDOWS):
+        for name, (_, fn) in calls.items():
+            us[name].append(window(fn, reps[name]))
+    med = {}
+    for name, (k, _) in calls.items():
+        med[name] = float(np.median(us[name]))
+        print(json.dumps({"call": name, **extra, "blocks": k, "windows": WINDOWS, "launches_per_window": reps[name],
+                          "us_median": round(med[name], 3), "us_min": round(min(us[name]), 3), "us_max": round(max(us[name]), 3),
+                          "ns_per_channel_ms": round(med[name] / k / extra["channels"] * 1e3, 4)}), flush=True)
+    return med
+
+
+def weighted_loop(n_coh_arg, counts, k_loop=200, k_open=20):
+    import time
     from stm32f4_sdr_gps_amd import capi, synth
+    eng = capi.Engine(0)
+    blk = synth.default_four_sv(k_loop, seed=7)
+    d_if = eng.malloc(blk.nbytes + 2)
+    eng.h2d(d_if, np.concatenate([blk.reshape(-1), np.zeros(2, np.uint8)]))
+    blocks2 = np.random.default_rng(7).integers(0, 256, (k_loop, 4092), dtype=np.uint8)
+    d_if2 = eng.malloc(blocks2.nbytes)
+    eng.h2d(d_if2, blocks2)
+    ocfg = np.array([1, 8], np.int32)
+    for n in counts:
+        trk = _bench_states(n)
+        loop = np.zeros(n, capi.LOOP_DTYPE)
+        wst = np.zeros(n, capi.WLOOP_STATE_DTYPE)
+        for f in ("prn", "code_phase_fine", "if_freq_offset_hz"):
+            loop[f] = trk[f]
+            wst[f] = trk[f]
+        loop["found_freq_offset_hz"] = loop["if_freq_offset_hz"].astype(np.int16)
+        loop["rng"] = np.arange(n) + 1
+        d_trk, d_iq, d_iqw = eng.malloc(trk.nbytes), eng.malloc(n * 12), eng.malloc(k_open * n * 24)
+        d_loop, d_fl, d_wst, d_rec = eng.malloc(loop.nbytes), eng.malloc(n * k_loop), eng.malloc(wst.nbytes), eng.malloc(k_loop * n * 36)
+        eng.h2d(d_trk, trk)
+        eng.h2d(d_loop, loop)
+        eng.h2d(d_wst, wst)
+        tick = [0]
+
+        def sign_loop():
+            tick[0] += k_loop
+            return eng.lib.gpsx_track_loop_dev(eng.h, C.c_void_p(d_if), k_loop, C.c_void_p(d_loop), n, tick[0], C.c_void_p(d_fl), None)
+
+        calls = {"sign_epl_k1": (1, lambda: eng.lib.gpsx_track_epl_batch_dev(eng.h, C.c_void_p(d_if), C.c_void_p(d_trk), n, C.c_void_p(d_iq))),
+                 f"sign_loop_k{k_loop}": (k_loop, sign_loop),
+                 f"weighted_epl_k{k_open}": (k_open, lambda: eng.lib.gpsx_track_epl_weighted_dev(eng.h, ocfg.ctypes.data, C.c_void_p(d_if2), k_open,
+                                                                                                C.c_void_p(d_trk), n, C.c_void_p(d_iqw)))}
+        cfgs = {}
+        for n_coh in sorted({1, 20, n_coh_arg}):
+            cfgs[n_coh] = capi.wloop_cfg(n_coh, True, 8, (1.0, 300.0), (4.0, 3000.0), 0.1)
+            calls[f"weighted_loop_k{k_loop}_ncoh{n_coh}"] = (k_loop, lambda c=cfgs[n_coh]: eng.lib.gpsx_track_loop_weighted_dev(
+                eng.h, c.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d_wst), n, C.c_void_p(d_rec)))
+        med = _timed_rows(eng, calls, {"channels": n})
+        per = {name: med[name] / calls[name][0] for name in calls}
+        sign_ratio = per[f"sign_loop_k{k_loop}"] / per["sign_epl_k1"]
+        for n_coh in cfgs:
+            ratio = per[f"weighted_loop_k{k_loop}_ncoh{n_coh}"] / per[f"weighted_epl_k{k_open}"]
+            print(json.dumps({"ratio": "closed over open, per channel-ms", "channels": n, "n_coh": n_coh, "weighted": round(ratio, 4),
+                              "sign_plane": round(sign_ratio, 4), "bound_sign_plane_x_1.10": round(1.1 * sign_ratio, 4),
+                              "within_bound": bool(ratio <= 1.1 * sign_ratio)}), flush=True)
+        for p in (d_trk, d_iq, d_iqw, d_loop, d_fl, d_rec):
+            eng.free(p)
+
+        # the host-driven alternative (wall clock, blocks in host memory either way)
+        if n <= 65536:
+            cfg10 = dict(n_coh=10, dll=(1.0, 300.0), pll=(4.0, 3000.0), fll=0.1)
+            walls = {"device_loop_1x200": [], "host_loop_20x10": []}
+            for _ in range(WINDOWS):
+                t0 = time.perf_counter()
+                eng.track_loop_weighted(blocks2, d_wst, n, **cfg10)
+                walls["device_loop_1x200"].append(time.perf_counter() - t0)
+                st = trk.copy()
+                t0 = time.perf_counter()
+                for w in range(k_loop // 10):
+                    iq = eng.track_epl_weighted(blocks2[10 * w:10 * w + 10], st)
+                    iq.sum(axis=0, dtype=np.int64)       # (the window sums a host loop would start from; its arithmetic is not counted)
+                walls["host_loop_20x10"].append(time.perf_counter() - t0)
+            print(json.dumps({"host_driven_alternative": True, "channels": n, "blocks": k_loop, "n_coh": 10,
+                              **{k: round(float(np.median(v)) * 1e3, 3) for k, v in walls.items()}, "unit": "ms wall clock, median of %d" % WINDOWS}), flush=True)
+        eng.free(d_wst)
+
+
+def main():
+    global WINDOW_S
+    from stm32f4_sdr_gps_amd import capi, synth
+    if "--weighted-loop" in sys.argv[1:]:
+        args = sys.argv[1:]
+        at = args.index("--weighted-loop")
+        n_coh = int(args.pop(at + 1)) if at + 1 < len(args) and args[at + 1].isdigit() and int(args[at + 1]) <= 20 else 20
+        args.pop(at)
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_loop(n_coh, [int(a) for a in args] or [65536, 212992])
     if "--weighted" in sys.argv[1:]:
         args = sys.argv[1:]
         at = args.index("--weighted")
         k = int(args.pop(at + 1)) if at + 1 < len(args) and args[at + 1].isdigit() else 1
         args.pop(at)
         if "--window-s" in args:   # (a profiler run wants short windows)
-            global WINDOW_S
             at = args.index("--window-s")
             WINDOW_S = float(args.pop(at + 1))
             args.pop(at)
