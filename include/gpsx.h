@@ -31,7 +31,8 @@ extern "C" {
                                             * gpsx_acq_grid_weighted_ms(_dev) came later in 0.1.1: new entry points, no layout change;
                                             * so did gpsx_acq_grid_weighted_coh(_dev).
                                             * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change;
-                                            * gpsx_track_loop_weighted(_dev) too (new structs of their own). */
+                                            * gpsx_track_loop_weighted(_dev) and gpsx_track_loop_weighted_sync(_dev) too (new
+                                            * structs of their own). */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -497,6 +498,111 @@ int gpsx_track_loop_weighted_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, con
                                  gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec);
 int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
                              gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec);
+
+/* ---- EXTENSION, not in the reference: the weighted loop with a per-channel 20 ms bit synchroniser and bit-aligned windows ------
+ * gpsx_track_loop_weighted with what it leaves to the caller done on the device, channel by channel: every channel runs short
+ * coherent windows (n_coh_search blocks, the `search` gains) while a bit synchroniser looks for the position of its data bit edge
+ * in a 20 ms grid; once two consecutive rounds agree it waits for that edge and from then on runs windows of n_coh_lock blocks (the
+ * `lock` gains) that never straddle a bit edge, and reports the sum of the prompts over every bit.  The open window lives in the
+ * state, so a launch may be cut anywhere: n_blocks is 1 .. 4096 and no multiple of anything, and launches of any lengths give the
+ * states and records of one launch over the same blocks.  gpsx_track_loop_weighted, its structs and its kernel are unchanged.
+ *
+ * Bit sync is NOT a presence detector: on noise alone two rounds agree with probability 1 / 20 and the energy ratio reaches what
+ * weak signals give.  The caller decides whether a satellite is there (acquisition, the records' prompt energy) and re-arms a
+ * search by writing mode = 0 into the state (search_n = 0 and prev_best_p1 = 0 with it for a fresh one).
+ *
+ * Definition, per channel and block b = 0 .. n_blocks - 1 of the launch, in this order.  Float operations as above: one IEEE
+ * single operation each in the order written.  "The mode's" n_coh and gains: n_coh_search / `search` in SEARCH, n_coh_lock /
+ * `lock` in LOCKED.
+ *   1 validation   at the launch's start and after every window's end the channel is checked: prn in 1 .. 210, code_phase_fine
+ *                  finite with magnitude < 2^24 (gpsx_track_loop_weighted's policy), and -- at the launch's start, where they
+ *                  come from the caller -- mode in 0 .. 2, ms_count and edge in 0 .. 19, win_n in 0 .. 20, search_n in 0 .. 4020.
+ *                  A channel that fails is BAD for the rest of the launch: per block only if_freq_accum += 511 * step32 happens;
+ *                  it gets no window record (its slots are the empty pattern: zero sums), its floats, loop memory, window and
+ *                  sync words stay as they were, and GPSX_EINVAL comes from gpsx_track_loop_weighted_sync after its wait / from
+ *                  the next gpsx_synchronize() after _dev.  Steps 2 .. 7 are those of a good channel.
+ *   2 leaving WAIT if mode == WAIT and ms_count == edge: mode = LOCKED (this block is the first of a data bit)
+ *   3 correlators  if mode != WAIT: the six int32 values of gpsx_track_epl_weighted for this block, with tau, f = (float)if_hz +
+ *                  if_freq_offset_hz and step32 those of the state's floats -- which change at a window's end only, so a window
+ *                  that continues over launches sees the same values -- and acc = if_freq_accum; they are added to win_iq and
+ *                  win_n++.  In every mode if_freq_accum += 511 * step32
+ *   4 counter      ms_count = (ms_count + 1) % 20
+ *   5 search       in SEARCH only: p_i += IP_b, p_q += QP_b (this block's prompt; int32, wrapping); c = ms_count;
+ *                  if search_n >= 20: e[c] += (int64)di * di + (int64)dq * dq with di = p_i - base[c][0], dq = p_q - base[c][1]
+ *                  (int32, wrapping; the sum wraps modulo 2^64 -- neither happens from a zeroed search); base[c] = p; search_n++.
+ *                  e[c] is the energy of the 20-block sums that START where ms_count == c
+ *   6 window end   if mode != WAIT and (win_n >= the mode's n_coh, or mode == LOCKED and ms_count == edge -- which keeps bits
+ *                  aligned whatever cfg did between launches): the DLL / Costas PLL / FLL / carrier / end-of-window arithmetic of
+ *                  gpsx_track_loop_weighted above, verbatim, on win_iq with the mode's gains and T = (float)win_n * 0.001f.
+ *                  In LOCKED bit_ip += IP (the window's), and if ms_count == edge the record gets GPSX_WSYNC_BIT and bit_ip, then
+ *                  bit_ip = 0.  The record is written with GPSX_WSYNC_WINDOW (and GPSX_WSYNC_LOCKED in LOCKED), its first 36
+ *                  bytes formed as gpsx_track_loop_weighted forms them; win_iq = 0, win_n = 0
+ *   7 decision     in SEARCH when search_n >= 20 * (sync_bits + 1) (== in a run with one sync_bits): best = the lowest index of
+ *                  the maximum of e[], opp = e[(best + 10) % 20]; accept iff best + 1 == prev_best_p1 and e[best] * sync_den >=
+ *                  opp * sync_num (int64; from a zeroed search below 2^63 by the bounds on sync_bits and sync_num).  Always:
+ *                  last_best_e = e[best], last_opp_e = opp, prev_best_p1 = best + 1, sync_rounds++, e[] = 0, p = 0, search_n = 0
+ *                  (base[] is overwritten before it is read again).  On accept: edge = best, mode = WAIT, the open window is
+ *                  discarded (win_iq = 0, win_n = 0, bit_ip = 0) and loop.n_updates = 0, so that the first locked window has no
+ *                  FLL term from a window of another length; dll_err and pll_err stay.
+ * prev_best_p1 holds the previous round's best + 1 and 0 for "none", so that a zeroed state has no predecessor and its first
+ * decision is always a rejection: agreement of two consecutive rounds is the gate, the ratio only refuses flat rounds.
+ * Records: rec[n_slots][n_ch] with span = min(n_coh_search, n_coh_lock) and n_slots = ceil(n_blocks / span); a window that ends at
+ * block b goes to slot b / span.  Window ends of a channel are at least span blocks apart (from states this call wrote, under one
+ * cfg; should a caller's state make two fall into one slot, the later one stays), a slot in which none ended is zero with
+ * end_block = -1: every byte of rec is written.
+ * Errors: NULL pointers, weights / spacing out of range, n_coh_search or n_coh_lock not in {1, 2, 4, 5, 10, 20}, sync_bits
+ * outside 1 .. 200, sync_num or sync_den outside 1 .. 1024 or sync_num < sync_den, a gain that is not finite, n_blocks outside
+ * 1 .. 4096, n_ch < 1 and a size that overflows return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.
+ * Vector ALU (k_track_wsync: k_track_wloop's shape with per-lane window ends).  The host variant takes blocks and records in host
+ * memory and the state on the device, as gpsx_track_loop_weighted does. */
+#define GPSX_WSYNC_SEARCH 0
+#define GPSX_WSYNC_WAIT   1
+#define GPSX_WSYNC_LOCKED 2
+#define GPSX_WSYNC_WINDOW 1u     /* flags: the slot holds a window's record */
+#define GPSX_WSYNC_LOCKED_FLAG 2u   /* the window ran in LOCKED */
+#define GPSX_WSYNC_BIT    4u     /* the window's last block was a data bit's last: bit_ip is the bit's prompt sum */
+
+typedef struct { float dll_c1, dll_c2, pll_c1, pll_c2, fll_c; } gpsx_wsync_gains_t;   /* as gpsx_wloop_cfg_t's */
+
+typedef struct {                 /* 68 bytes */
+  int32_t weights, spacing;      /* as gpsx_wloop_cfg_t */
+  int32_t n_coh_search;          /* blocks per window in SEARCH: 1, 2, 4, 5, 10 or 20 */
+  int32_t n_coh_lock;            /* blocks per window in LOCKED: 1, 2, 4, 5, 10 or 20 */
+  gpsx_wsync_gains_t search, lock;
+  int32_t sync_bits;             /* 20-block sums per candidate and round: 1 .. 200 */
+  int32_t sync_num, sync_den;    /* accept needs e[best] / e[best + 10] >= sync_num / sync_den: 1 .. 1024, sync_num >= sync_den */
+} gpsx_wsync_cfg_t;
+
+typedef struct {                 /* 448 bytes, device resident; zeroed with loop's first four fields filled: a handover */
+  gpsx_wloop_state_t loop;       /*   0  (reserved: 0) */
+  int32_t  win_iq[6];            /*  40  the open window's sums IE, QE, IP, QP, IL, QL */
+  int32_t  win_n;                /*  64  blocks in the open window */
+  int32_t  ms_count;             /*  68  0 .. 19: the 20 ms grid the edge is counted in */
+  int32_t  mode;                 /*  72  GPSX_WSYNC_SEARCH / _WAIT / _LOCKED */
+  int32_t  edge;                 /*  76  0 .. 19: ms_count at a bit's first block; meaningful when mode != 0 */
+  int32_t  bit_ip;               /*  80  the prompt sum of the open bit (LOCKED) */
+  int32_t  search_n;             /*  84  blocks this search round has seen */
+  int32_t  prev_best_p1;         /*  88  the previous round's best + 1; 0: none */
+  int32_t  sync_rounds;          /*  92  decisions taken so far */
+  int32_t  p_i, p_q;             /*  96  the round's running prompt sum */
+  int64_t  last_best_e, last_opp_e;   /* 104  what the last decision compared */
+  int32_t  zero[2];              /* 120  0 */
+  int32_t  base[20][2];          /* 128  p when ms_count was c, 20 blocks ago */
+  int64_t  e[20];                /* 288  per candidate: the energy of its 20-block sums this round */
+} gpsx_wsync_state_t;
+
+typedef struct {                 /* 48 bytes, one per (slot, channel) */
+  gpsx_wloop_rec_t w;            /*  0  as gpsx_track_loop_weighted's record for this window */
+  int32_t  end_block;            /* 36  the window's last block, counted from the launch's first; -1: no window ended in this slot */
+  uint32_t flags;                /* 40  GPSX_WSYNC_WINDOW | GPSX_WSYNC_LOCKED_FLAG | GPSX_WSYNC_BIT */
+  int32_t  bit_ip;               /* 44  with GPSX_WSYNC_BIT: the bit's prompt sum, its sign the data bit up to one polarity */
+} gpsx_wsync_rec_t;
+
+/* d_rec / rec: [ceil(n_blocks / min(n_coh_search, n_coh_lock))][n_ch] */
+int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                      gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec);
+int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                                  gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

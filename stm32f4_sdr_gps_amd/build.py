@@ -88,7 +88,11 @@ def check_no_scratch() -> dict:
     wloop = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted.o")).items() if "k_track_wloop" in k}
     if len(wloop) != 1:
         raise RuntimeError(f"expected k_track_wloop in build/k_track_loop_weighted.o, found {sorted(wloop)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop}
+    # ... and the loop with the bit synchroniser (k_track_wsync: the open window and the synchroniser's words on top of that)
+    wsync = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted_sync.o")).items() if "k_track_wsync" in k}
+    if len(wsync) != 1:
+        raise RuntimeError(f"expected k_track_wsync in build/k_track_loop_weighted_sync.o, found {sorted(wsync)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

@@ -62,6 +62,38 @@ def wloop_cfg(n_coh, use_magnitude=True, spacing=8, dll=(1.0, 300.0), pll=(4.0, 
     return cfg
 
 
+# gpsx_wsync_state_t / gpsx_wsync_cfg_t / gpsx_wsync_rec_t (the weighted loop with a per-channel bit synchroniser)
+WSYNC_SEARCH, WSYNC_WAIT, WSYNC_LOCKED = 0, 1, 2
+WSYNC_FLAG_WINDOW, WSYNC_FLAG_LOCKED, WSYNC_FLAG_BIT = 1, 2, 4
+WSYNC_GAINS_DTYPE = np.dtype([("dll_c1", "<f4"), ("dll_c2", "<f4"), ("pll_c1", "<f4"), ("pll_c2", "<f4"), ("fll_c", "<f4")])
+WSYNC_CFG_DTYPE = np.dtype([("weights", "<i4"), ("spacing", "<i4"), ("n_coh_search", "<i4"), ("n_coh_lock", "<i4"),
+                            ("search", WSYNC_GAINS_DTYPE), ("lock", WSYNC_GAINS_DTYPE), ("sync_bits", "<i4"), ("sync_num", "<i4"),
+                            ("sync_den", "<i4")])
+WSYNC_STATE_DTYPE = np.dtype([("loop", WLOOP_STATE_DTYPE), ("win_iq", "<i4", 6), ("win_n", "<i4"), ("ms_count", "<i4"), ("mode", "<i4"),
+                              ("edge", "<i4"), ("bit_ip", "<i4"), ("search_n", "<i4"), ("prev_best_p1", "<i4"), ("sync_rounds", "<i4"),
+                              ("p_i", "<i4"), ("p_q", "<i4"), ("last_best_e", "<i8"), ("last_opp_e", "<i8"), ("zero", "<i4", 2),
+                              ("base", "<i4", (20, 2)), ("e", "<i8", 20)])
+WSYNC_REC_DTYPE = np.dtype([("w", WLOOP_REC_DTYPE), ("end_block", "<i4"), ("flags", "<u4"), ("bit_ip", "<i4")])
+assert WSYNC_CFG_DTYPE.itemsize == 68 and WSYNC_STATE_DTYPE.itemsize == 448 and WSYNC_REC_DTYPE.itemsize == 48
+
+
+def wsync_cfg(n_coh_search, n_coh_lock, search, lock, sync_bits=20, sync_ratio=(5, 4), use_magnitude=True, spacing=8) -> np.ndarray:
+    """a gpsx_wsync_cfg_t as a one-element WSYNC_CFG_DTYPE array.  search / lock: dict(dll=(c1, c2), pll=(c1, c2), fll=c), the gains
+    of the windows before and after bit sync; sync_ratio: (sync_num, sync_den)"""
+    cfg = np.zeros(1, WSYNC_CFG_DTYPE)
+    cfg["weights"], cfg["spacing"], cfg["n_coh_search"], cfg["n_coh_lock"] = (1 if use_magnitude else 0), spacing, n_coh_search, n_coh_lock
+    for name, g in (("search", search), ("lock", lock)):
+        cfg[name][0] = (g["dll"][0], g["dll"][1], g["pll"][0], g["pll"][1], g.get("fll", 0.0))
+    cfg["sync_bits"], cfg["sync_num"], cfg["sync_den"] = sync_bits, sync_ratio[0], sync_ratio[1]
+    return cfg
+
+
+def wsync_slots(n_blocks, n_coh_search, n_coh_lock) -> int:
+    """record slots of a launch: ceil(n_blocks / min(n_coh_search, n_coh_lock))"""
+    span = max(1, min(n_coh_search, n_coh_lock))
+    return (n_blocks + span - 1) // span
+
+
 TRK_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"),
                       ("if_freq_accum", "<u4")])
 JOB_DTYPE = np.dtype([("block", "<i4"), ("n_ms", "<i4"), ("prn", "<i4"), ("freq_hz", "<f4"), ("offset_bits", "<i4"),
@@ -157,6 +189,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_track_epl_weighted_dev.argtypes = lib.gpsx_track_epl_weighted.argtypes
     lib.gpsx_track_loop_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_track_loop_weighted_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
+    lib.gpsx_track_loop_weighted_sync.argtypes = lib.gpsx_track_loop_weighted.argtypes
+    lib.gpsx_track_loop_weighted_sync_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -530,6 +564,18 @@ class Engine:
         rec = np.zeros((len(blocks) // max(n_coh, 1), n_ch), WLOOP_REC_DTYPE)
         self._chk(self.lib.gpsx_track_loop_weighted(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), C.c_void_p(d_state), n_ch,
                                                     rec.ctypes.data), "gpsx_track_loop_weighted")
+        return rec
+
+    def track_loop_weighted_sync(self, blocks_2bit: np.ndarray, d_state: int, n_ch: int, cfg: np.ndarray) -> np.ndarray:
+        """EXTENSION: the weighted loop with a 20 ms bit synchroniser per channel and bit-aligned windows over the n_blocks
+        consecutive 4092-byte blocks given (any number from 1 to 4096: the open window lives in the state), on the n_ch
+        WSYNC_STATE_DTYPE states at device address d_state.  cfg: wsync_cfg(...).  -> WSYNC_REC_DTYPE [slots, n_ch], slots =
+        wsync_slots(n_blocks, n_coh_search, n_coh_lock); a slot without a window has end_block -1 and flags 0"""
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        assert cfg.dtype == WSYNC_CFG_DTYPE and cfg.size == 1
+        rec = np.zeros((wsync_slots(len(blocks), int(cfg["n_coh_search"][0]), int(cfg["n_coh_lock"][0])), n_ch), WSYNC_REC_DTYPE)
+        self._chk(self.lib.gpsx_track_loop_weighted_sync(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), C.c_void_p(d_state),
+                                                         n_ch, rec.ctypes.data), "gpsx_track_loop_weighted_sync")
         return rec
 
     def set_loop_schedule(self, schedule: int) -> None:

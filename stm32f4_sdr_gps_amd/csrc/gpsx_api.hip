@@ -1132,6 +1132,79 @@ int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const u
   return track_prn_verdict(ctx);
 }
 
+/* ---- extension: the weighted loop with a per-channel bit synchroniser and bit-aligned windows ------------------------------- */
+
+namespace {
+// every refusal of gpsx_track_loop_weighted_sync(_dev), before anything is written; *rec_bytes = the records' size
+int track_loop_weighted_sync_check(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *blocks, int n_blocks, const void *st, int n_ch,
+                                   const void *rec, size_t *rec_bytes)
+{
+  if (!cfg || !blocks || !st || !rec)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->weights != GPSX_WEIGHTS_SIGN_ONLY && cfg->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
+    return fail(ctx, GPSX_EINVAL, "unknown weights");
+  if (cfg->spacing < 1 || cfg->spacing > 15)
+    return fail(ctx, GPSX_EINVAL, "spacing must be 1..15 samples");
+  for (int n : {cfg->n_coh_search, cfg->n_coh_lock})
+    if (n < 1 || n > 20 || 20 % n != 0)
+      return fail(ctx, GPSX_EINVAL, "n_coh_search and n_coh_lock must be 1, 2, 4, 5, 10 or 20 blocks");
+  if (cfg->sync_bits < 1 || cfg->sync_bits > 200)
+    return fail(ctx, GPSX_EINVAL, "sync_bits must be 1..200");
+  if (cfg->sync_num < 1 || cfg->sync_num > 1024 || cfg->sync_den < 1 || cfg->sync_den > 1024)
+    return fail(ctx, GPSX_EINVAL, "sync_num and sync_den must be 1..1024");
+  if (cfg->sync_num < cfg->sync_den)
+    return fail(ctx, GPSX_EINVAL, "sync_num must not be below sync_den");
+  if (n_blocks < 1 || n_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
+  if (n_ch < 1)
+    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
+  for (const gpsx_wsync_gains_t *g : {&cfg->search, &cfg->lock})
+    for (float v : {g->dll_c1, g->dll_c2, g->pll_c1, g->pll_c2, g->fll_c})
+      if (!(__builtin_fabsf(v) <= 3.402823466e+38f))
+        return fail(ctx, GPSX_EINVAL, "a loop gain is not finite");
+  const int span = cfg->n_coh_search < cfg->n_coh_lock ? cfg->n_coh_search : cfg->n_coh_lock;
+  size_t recs = 0;
+  if (__builtin_mul_overflow((size_t)((n_blocks + span - 1) / span), (size_t)n_ch, &recs) ||
+      __builtin_mul_overflow(recs, sizeof(gpsx_wsync_rec_t), rec_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  return GPSX_OK;
+}
+}  // namespace
+
+int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                      gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t rec_bytes = 0;
+  if (int rc = track_loop_weighted_sync_check(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, &rec_bytes)) return rc;
+  launch_track_loop_weighted_sync(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), n_blocks, ctx->if_hz, *cfg, d_state, n_ch,
+                                  ctx->d_trk_rep, d_rec, ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
+  LAUNCHCHK(ctx, "k_track_wsync");
+  ctx->last_kernel = "k_track_wsync";
+  return GPSX_OK;
+}
+
+int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                                  gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t rec_bytes = 0;
+  if (int rc = track_loop_weighted_sync_check(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, &rec_bytes)) return rc;
+  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT;
+  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(rec_bytes)))
+    return rc;
+  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
+  gpsx_wsync_rec_t *d_rec = arena_take<gpsx_wsync_rec_t>(ctx, rec_bytes / sizeof(gpsx_wsync_rec_t));
+  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel, as gpsx_track_loop_weighted does)
+  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+  launch_track_loop_weighted_sync(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, ctx->d_bad_prn);
+  LAUNCHCHK(ctx, "k_track_wsync");
+  ctx->last_kernel = "k_track_wsync";
+  HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return track_prn_verdict(ctx);
+}
+
 /* ---- extension: weighted two-bit acquisition grid ------------------------------------------------------------------------ */
 
 namespace {

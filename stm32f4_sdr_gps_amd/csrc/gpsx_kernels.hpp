@@ -140,6 +140,12 @@ void launch_track_epl_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, i
 void launch_track_loop_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wloop_cfg_t &cfg,
                                 gpsx_wloop_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wloop_rec_t *d_rec,
                                 uint32_t *d_bad_prn);
+// extension: gpsx_track_loop_weighted_sync (k_track_loop_weighted_sync.hip: k_track_wsync) -- the same loop with a 20 ms bit
+// synchroniser per channel and bit-aligned windows: any n_blocks, the open window in the state (448 bytes per channel),
+// d_rec [ceil(n_blocks / min(n_coh_search, n_coh_lock))][n_ch], every byte of it written.  d_bad_prn as launch_track_epl's.
+void launch_track_loop_weighted_sync(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
+                                     gpsx_wsync_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wsync_rec_t *d_rec,
+                                     uint32_t *d_bad_prn);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -1,0 +1,311 @@
+// k_track_loop_weighted_sync.hip -- EXTENSION, not in the reference: the closed loop on WEIGHTED two-bit samples with a 20 ms bit
+// synchroniser per channel and windows aligned with every channel's own bit edge (include/gpsx.h gpsx_track_loop_weighted_sync;
+// DESIGN.md 4.6.3).
+//
+// k_track_wloop's shape (k_track_loop_weighted.hip): lane 4 c + k of a wave holds channel c of the wave, the blocks run one after
+// the other, the workgroup stages block b's planes into LDS buffer b & 1 and meets at ONE barrier per block that every wave
+// reaches; the correlators are gpsx_track_weighted_wave.hpp's, the same integers.  What differs:
+//  * the open window (six sums, its length) and the synchroniser's words come from the state and go back to it, so a launch may
+//    be cut anywhere;
+//  * a window's end is a per-lane condition (the mode's n_coh reached, or a locked channel's bit edge).  The update code is skipped
+//    with one wave-uniform test when no channel of the wave ends a window at this block and runs under the lanes' mask otherwise;
+//    the search's decision (once per 20 (sync_bits + 1) blocks) likewise;
+//  * the search arrays (base[20][2], e[20]: 320 B per channel) stay in HBM / L2 and are updated in place by the quad's Prompt lane,
+//    whose correlator result IS the block's prompt: one candidate per block (the prefix form), 16 B in and 16 B out, for channels
+//    in SEARCH only;
+//  * a record is three 16-byte stores by the quad's lanes 0 .. 2, and a slot in which no window ended gets the empty pattern.
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "gpsx_device.hpp"
+#include "gpsx_kernels.hpp"
+#include "gpsx_libm.hpp"
+#include "gpsx_track_loop_weighted_plan.hpp"
+#include "gpsx_track_weighted_wave.hpp"
+
+namespace gpsx {
+
+namespace {
+
+template <int K>
+__device__ __forceinline__ int quad_get(int v)   // lane k of this lane's quad
+{
+  return __builtin_amdgcn_update_dpp(0, v, K | (K << 2) | (K << 4) | (K << 6), 0xF, 0xF, true);
+}
+
+constexpr float kCyclesPerRadian = 0.15915494f;
+constexpr float kSpan = 16368.0f;
+
+static_assert(sizeof(gpsx_wsync_cfg_t) == 68 && offsetof(gpsx_wsync_cfg_t, search) == 16 && offsetof(gpsx_wsync_cfg_t, lock) == 36 &&
+              offsetof(gpsx_wsync_cfg_t, sync_bits) == 56, "gpsx_wsync_cfg_t layout");
+static_assert(sizeof(gpsx_wsync_state_t) == 448 && offsetof(gpsx_wsync_state_t, win_iq) == 40 && offsetof(gpsx_wsync_state_t, win_n) == 64 &&
+              offsetof(gpsx_wsync_state_t, ms_count) == 68 && offsetof(gpsx_wsync_state_t, mode) == 72 && offsetof(gpsx_wsync_state_t, edge) == 76 &&
+              offsetof(gpsx_wsync_state_t, bit_ip) == 80 && offsetof(gpsx_wsync_state_t, search_n) == 84 &&
+              offsetof(gpsx_wsync_state_t, prev_best_p1) == 88 && offsetof(gpsx_wsync_state_t, sync_rounds) == 92 &&
+              offsetof(gpsx_wsync_state_t, p_i) == 96 && offsetof(gpsx_wsync_state_t, last_best_e) == 104 &&
+              offsetof(gpsx_wsync_state_t, last_opp_e) == 112 && offsetof(gpsx_wsync_state_t, zero) == 120 &&
+              offsetof(gpsx_wsync_state_t, base) == 128 && offsetof(gpsx_wsync_state_t, e) == 288, "gpsx_wsync_state_t layout");
+static_assert(sizeof(gpsx_wsync_rec_t) == 48 && offsetof(gpsx_wsync_rec_t, end_block) == 36 && offsetof(gpsx_wsync_rec_t, flags) == 40 &&
+              offsetof(gpsx_wsync_rec_t, bit_ip) == 44, "gpsx_wsync_rec_t layout");
+
+struct alignas(4) Rec16 { u32 w[4]; };   // a third of a record at a dword-aligned address: one global_store_dwordx4
+
+}  // namespace
+
+__global__ __launch_bounds__(256, 4) void k_track_wsync(const uint8_t *__restrict__ if_blocks, int n_blocks, int if_hz, gpsx_wsync_cfg_t cfg,
+                                                     gpsx_wsync_state_t *__restrict__ st, int n_ch, int cpw,
+                                                     const u32 *__restrict__ rep_all, gpsx_wsync_rec_t *__restrict__ rec,
+                                                     u32 *__restrict__ bad_prn)
+{
+  using namespace trkweighted;
+  __shared__ __attribute__((aligned(16))) u32 s_x[2][512], s_m[2][512];   // this and the next block's planes
+  __shared__ uint2 s_carrier[4];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int c_l = lane >> 2, k_l = lane & 3;
+  const int ch0 = ((int)blockIdx.x * 4 + wave) * cpw;
+  const int n_here = ch0 < n_ch ? min(cpw, n_ch - ch0) : 0;   // 0: an idle wave of the last workgroup still stages and waits
+  const bool in_wave = c_l < n_here;
+  const bool mine = in_wave && k_l < 3;
+  const int ch_l = in_wave ? ch0 + c_l : (n_here ? ch0 : 0);  // (always a channel below n_ch)
+  const int use_magnitude = cfg.weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;
+  const int span = min(cfg.n_coh_search, cfg.n_coh_lock);
+  const int decide_at = 20 * (cfg.sync_bits + 1);
+  gpsx_wsync_state_t *const my = st + ch_l;
+
+  if (threadIdx.x < 4)
+    s_carrier[threadIdx.x] = uint2{carrier_i(threadIdx.x), carrier_q(threadIdx.x)};   // (visible after the first block's barrier)
+
+  // the loop's state in registers, as in k_track_wloop; every lane of a quad carries all of it
+  struct Live { float code_phase_fine, if_freq_offset_hz; u32 if_freq_accum; float dll_err, pll_err; int prev_ip, prev_qp; u32 n_updates; };
+  static_assert(sizeof(Live) == 32 && offsetof(gpsx_wloop_state_t, code_phase_fine) == 4 && offsetof(gpsx_wloop_state_t, n_updates) == 32,
+                "gpsx_wloop_state_t layout");
+  Live s = {};
+  int sum_i = 0, sum_q = 0;   // lane 4 c + k: tap k's sums over the open window (win_iq[2 k], [2 k + 1])
+  int win_n = 0, ms = 0, mode = 0, edge = 0, bit_ip = 0, search_n = 0;
+  int p_i = 0, p_q = 0;       // the round's running prompt: the quad's Prompt lane (k = 1) alone keeps it
+  int prn_ok = 0;             // the validated PRN; 0: a bad channel (reported here); -1: a padding channel (never reported)
+  if (n_here) {
+    const int raw = my->loop.prn;
+    __builtin_memcpy(&s, &my->loop.code_phase_fine, sizeof s);
+    prn_ok = raw == kTrackPadPrn ? -1 : track_prn(raw, bad_prn, mine && k_l == 0);
+    if (k_l < 3) {
+      sum_i = my->win_iq[2 * k_l];
+      sum_q = my->win_iq[2 * k_l + 1];
+    }
+    win_n = my->win_n; ms = my->ms_count; mode = my->mode; edge = my->edge;
+    bit_ip = my->bit_ip; search_n = my->search_n;
+    p_i = my->p_i; p_q = my->p_q;
+    // the caller's words: out of range -> a bad channel, like a bad PRN
+    if ((unsigned)mode > 2u || (unsigned)ms >= 20u || (unsigned)edge >= 20u || (unsigned)win_n > 20u || (unsigned)search_n > 4020u) {
+      if (prn_ok > 0 && mine && k_l == 0 && bad_prn)
+        *bad_prn = 1u;
+      prn_ok = prn_ok < 0 ? -1 : 0;
+    }
+  }
+
+  // what a window's correlators use: the state's floats, which change at a window's end only
+  int tau = 0, prn = 0;   // prn == 0: a bad channel, or no channel -- nothing but the accumulator moves
+  u32 step = 0;
+  auto begin_window = [&]() {
+    const bool phase_ok = weighted_tau(s.code_phase_fine, tau);
+    prn = in_wave && phase_ok && prn_ok > 0 ? prn_ok : 0;   // (the lanes beyond the wave's channels mirror its first: they must not act)
+    if (!phase_ok && mine && k_l == 0 && bad_prn && prn_ok > 0)
+      *bad_prn = 1u;
+    step = nco_step_per_word((float)if_hz + s.if_freq_offset_hz);
+  };
+  begin_window();
+  int slot = 0, in_slot = 0;
+  bool wrote = false;   // a window of this channel ended in the current slot
+
+#pragma unroll 1
+  for (int b = 0; b < n_blocks; b++) {
+    stage_planes(if_blocks + (size_t)b * GPSX_BYTES_PER_MS_2BIT, use_magnitude, s_x[b & 1], s_m[b & 1]);
+    __syncthreads();
+    if (!n_here)   // (wave-uniform)
+      continue;
+    const bool ok = prn != 0;
+    if (ok && mode == GPSX_WSYNC_WAIT && ms == edge)
+      mode = GPSX_WSYNC_LOCKED;   // this block is a bit's first
+    const bool corr = ok && mode != GPSX_WSYNC_WAIT;
+    u32 pop_m;
+    const u32 counts = wave_counts(s_x[b & 1], s_m[b & 1], s_carrier, lane, n_here, prn, tau, cfg.spacing, step, s.if_freq_accum, rep_all, pop_m);
+    int res_i = 0, res_q = 0;
+    if (mine)
+      finish_tap(s_carrier, lane, prn, tau, cfg.spacing, step, s.if_freq_accum, rep_all, counts, pop_m, res_i, res_q);
+    if (corr) {
+      sum_i += res_i;
+      sum_q += res_q;
+      win_n++;
+    }
+    s.if_freq_accum += step * (u32)kWords32;
+    bool ends = false, decide = false;
+    if (ok) {
+      ms = ms == 19 ? 0 : ms + 1;
+      if (mode == GPSX_WSYNC_SEARCH) {
+        if (k_l == 1) {   // this lane's res_i, res_q ARE the block's prompt: the prefix form touches one candidate per block
+          p_i = (int)((u32)p_i + (u32)res_i);
+          p_q = (int)((u32)p_q + (u32)res_q);
+          int2 *bp = reinterpret_cast<int2 *>(&my->base[ms][0]);
+          if (search_n >= 20) {
+            const int2 old = *bp;
+            const long long di = (int)((u32)p_i - (u32)old.x), dq = (int)((u32)p_q - (u32)old.y);
+            unsigned long long *ep = reinterpret_cast<unsigned long long *>(&my->e[ms]);
+            *ep = *ep + (unsigned long long)(di * di) + (unsigned long long)(dq * dq);
+          }
+          *bp = int2{p_i, p_q};
+        }
+        search_n++;
+        decide = search_n >= decide_at;
+      }
+      const bool locked = mode == GPSX_WSYNC_LOCKED;
+      ends = corr && (win_n >= (locked ? cfg.n_coh_lock : cfg.n_coh_search) || (locked && ms == edge));
+    }
+
+    // ---- a window's end, for the lanes whose channel has one: the quad gathers its six sums, every lane of it runs the loop ------
+    if (__builtin_amdgcn_ballot_w64(ends) != 0) {   // (wave-uniform: every lane is active for the quad exchanges)
+      const int IE = quad_get<0>(sum_i), QE = quad_get<0>(sum_q), IP = quad_get<1>(sum_i), QP = quad_get<1>(sum_q);
+      const int IL = quad_get<2>(sum_i), QL = quad_get<2>(sum_q);
+      if (ends) {
+        const bool locked = mode == GPSX_WSYNC_LOCKED;
+        const float dll_c1 = locked ? cfg.lock.dll_c1 : cfg.search.dll_c1, dll_c2 = locked ? cfg.lock.dll_c2 : cfg.search.dll_c2;
+        const float pll_c1 = locked ? cfg.lock.pll_c1 : cfg.search.pll_c1, pll_c2 = locked ? cfg.lock.pll_c2 : cfg.search.pll_c2;
+        const float fll_c = locked ? cfg.lock.fll_c : cfg.search.fll_c;
+        const float T = (float)win_n * 0.001f;
+        // DLL
+        const long long e2 = (long long)IE * IE + (long long)QE * QE, l2 = (long long)IL * IL + (long long)QL * QL;
+        float d = 0.0f;
+        if (e2 + l2 != 0)
+          d = (float)(e2 - l2) / (float)(e2 + l2);
+        float phase = s.code_phase_fine - (dll_c1 * (d - s.dll_err) + (dll_c2 * T) * d);
+        if (phase < 0.0f)
+          phase = phase + kSpan;
+        else if (phase >= kSpan)
+          phase = phase - kSpan;
+        s.code_phase_fine = phase;
+        s.dll_err = d;
+        // Costas PLL, in cycles
+        float p;
+        if (IP == 0)
+          p = QP > 0 ? 0.25f : (QP < 0 ? -0.25f : 0.0f);
+        else
+          p = gpsx_libm::atanf_fdlibm((float)QP / (float)IP) * kCyclesPerRadian;
+        // FLL, in Hz
+        float fe = 0.0f;
+        if (fll_c != 0.0f && s.n_updates > 0) {
+          const long long cross = (long long)s.prev_ip * QP - (long long)s.prev_qp * IP;
+          const long long dot = (long long)s.prev_ip * IP + (long long)s.prev_qp * QP;
+          if (dot != 0)
+            fe = gpsx_libm::atanf_fdlibm((float)cross / (float)dot) * kCyclesPerRadian / T;
+        }
+        s.if_freq_offset_hz = s.if_freq_offset_hz - ((pll_c1 * (p - s.pll_err) + (pll_c2 * T) * p) + fll_c * fe);
+        s.pll_err = p;
+        s.prev_ip = IP;
+        s.prev_qp = QP;
+        s.n_updates++;
+        // the bit's prompt sum and the record
+        u32 flags = GPSX_WSYNC_WINDOW;
+        int bit_out = 0;
+        if (locked) {
+          flags |= GPSX_WSYNC_LOCKED_FLAG;
+          bit_ip = (int)((u32)bit_ip + (u32)IP);
+          if (ms == edge) {
+            flags |= GPSX_WSYNC_BIT;
+            bit_out = bit_ip;
+            bit_ip = 0;
+          }
+        }
+        if (k_l < 3) {
+          Rec16 v;
+          if (k_l == 0)
+            v = Rec16{{(u32)IE, (u32)QE, (u32)IP, (u32)QP}};
+          else if (k_l == 1)
+            v = Rec16{{(u32)IL, (u32)QL, __float_as_uint(s.code_phase_fine), __float_as_uint(s.if_freq_offset_hz)}};
+          else
+            v = Rec16{{s.if_freq_accum, (u32)b, flags, (u32)bit_out}};
+          reinterpret_cast<Rec16 *>(&rec[(size_t)slot * (size_t)n_ch + (size_t)ch_l])[k_l] = v;
+        }
+        wrote = true;
+        sum_i = sum_q = 0;
+        win_n = 0;
+        begin_window();   // tau, validity and step of the next window, in registers
+      }
+    }
+
+    // ---- the search's decision, for the lanes whose channel has seen 20 (sync_bits + 1) blocks ---------------------------------
+    if (__builtin_amdgcn_ballot_w64(decide) != 0) {   // (wave-uniform)
+      int best = 0, accept = 0;
+      if (decide && k_l == 1) {
+        long long e_best = my->e[0];
+#pragma unroll 1
+        for (int c = 1; c < 20; c++) {
+          const long long v = my->e[c];
+          if (v > e_best) {
+            e_best = v;
+            best = c;
+          }
+        }
+        const long long opp = my->e[best < 10 ? best + 10 : best - 10];
+        accept = best + 1 == my->prev_best_p1 && (long long)((unsigned long long)e_best * (unsigned long long)cfg.sync_den) >=
+                                                     (long long)((unsigned long long)opp * (unsigned long long)cfg.sync_num);
+        my->last_best_e = e_best;
+        my->last_opp_e = opp;
+        my->prev_best_p1 = best + 1;
+        my->sync_rounds = (int)((u32)my->sync_rounds + 1u);
+#pragma unroll 1
+        for (int c = 0; c < 20; c++)
+          my->e[c] = 0;
+        p_i = p_q = 0;
+      }
+      best = quad_get<1>(best);
+      accept = quad_get<1>(accept);
+      if (decide) {
+        search_n = 0;
+        if (accept) {   // wait for the edge; the open window is discarded
+          edge = best;
+          mode = GPSX_WSYNC_WAIT;
+          sum_i = sum_q = 0;
+          win_n = 0;
+          bit_ip = 0;
+          s.n_updates = 0;
+        }
+      }
+    }
+
+    // ---- the slot's end: a channel without a window in it gets the empty pattern -------------------------------------------------
+    if (++in_slot == span || b == n_blocks - 1) {   // (uniform over the launch)
+      if (mine && !wrote)
+        reinterpret_cast<Rec16 *>(&rec[(size_t)slot * (size_t)n_ch + (size_t)ch_l])[k_l] = Rec16{{0u, k_l == 2 ? ~0u : 0u, 0u, 0u}};
+      wrote = false;
+      in_slot = 0;
+      slot++;
+    }
+  }
+
+  if (mine) {
+    my->win_iq[2 * k_l] = sum_i;
+    my->win_iq[2 * k_l + 1] = sum_q;
+    if (k_l == 0) {
+      __builtin_memcpy(&my->loop.code_phase_fine, &s, sizeof s);
+      my->win_n = win_n; my->ms_count = ms; my->mode = mode; my->edge = edge;
+      my->bit_ip = bit_ip; my->search_n = search_n;
+    }
+    if (k_l == 1) {
+      my->p_i = p_i;
+      my->p_q = p_q;
+    }
+  }
+}
+
+void launch_track_loop_weighted_sync(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
+                                     gpsx_wsync_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wsync_rec_t *d_rec,
+                                     uint32_t *d_bad_prn)
+{
+  if (n_ch <= 0 || n_blocks <= 0)
+    return;
+  const TrackLoopWeightedPlan p = plan_track_loop_weighted(n_ch);   // the same shape as k_track_wloop's (gpsx_track_loop_weighted_plan.hpp)
+  hipLaunchKernelGGL(k_track_wsync, dim3(p.groups), dim3(256), 0, s, d_if_blocks_2bit, n_blocks, if_hz, cfg, d_st, n_ch, p.cpw, d_trk_rep,
+                     d_rec, d_bad_prn);
+}
+
+}  // namespace gpsx

@@ -15,7 +15,15 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       gpsx_track_epl_batch_dev -- time per channel-millisecond and the two
                                                       closed-over-open ratios; then the host-driven alternative: one K = 200,
                                                       n_coh = 10 launch against twenty gpsx_track_epl_weighted calls of K = 10 with the
-                                                      records copied back and the states rewritten by the host (wall clock)"""
+                                                      records copied back and the states rewritten by the host (wall clock)
+  bench_track_kernel.py --weighted-sync [channels ...]
+                                                      gpsx_track_loop_weighted_sync_dev (EXTENSION: the loop with a bit synchroniser per
+                                                      channel, K = 200) in three states -- (a) every channel LOCKED at n_coh_lock = 20
+                                                      with edges spread over 0 .. 19, (b) the same with all edges equal, (c) every channel
+                                                      in SEARCH at n_coh_search = 4 (ratio 1024 / 1: noise never leaves it) -- beside
+                                                      gpsx_track_loop_weighted_dev at n_coh = 1, 4, 20 in the same process, the calls
+                                                      taking turns; then the wall clock of 2000 ms in host launches of 200 with the
+                                                      records copied back"""
 import ctypes as C
 import json
 import os
@@ -188,9 +196,80 @@ def weighted_loop(n_coh_arg, counts, k_loop=200, k_open=20):
         eng.free(d_wst)
 
 
+def weighted_sync(counts, k_loop=200):
+    import time
+    from stm32f4_sdr_gps_amd import capi
+    eng = capi.Engine(0)
+    blocks2 = np.random.default_rng(7).integers(0, 256, (k_loop, 4092), dtype=np.uint8)
+    d_if2 = eng.malloc(blocks2.nbytes)
+    eng.h2d(d_if2, blocks2)
+    gains = dict(dll=(1.0, 300.0), pll=(4.0, 3000.0), fll=0.1)
+    for n in counts:
+        trk = _bench_states(n)
+        wst = np.zeros(n, capi.WLOOP_STATE_DTYPE)
+        for f in ("prn", "code_phase_fine", "if_freq_offset_hz"):
+            wst[f] = trk[f]
+        legs = {}
+        for leg in ("a_locked_spread", "b_locked_equal", "c_search"):
+            st = np.zeros(n, capi.WSYNC_STATE_DTYPE)
+            st["loop"] = wst
+            if leg != "c_search":
+                st["mode"] = capi.WSYNC_LOCKED
+                st["edge"] = np.arange(n) % 20 if leg == "a_locked_spread" else 0
+            legs[leg] = st
+        d_wst, d_rec = eng.malloc(wst.nbytes), eng.malloc(k_loop * n * 36)
+        eng.h2d(d_wst, wst)
+        d_sync = {leg: eng.malloc(st.nbytes) for leg, st in legs.items()}
+        for leg, st in legs.items():
+            eng.h2d(d_sync[leg], st)
+        d_srec = eng.malloc(capi.wsync_slots(k_loop, 4, 4) * n * 48)
+        calls, keep = {}, []
+        for n_coh in (1, 4, 20):
+            c = capi.wloop_cfg(n_coh, True, 8, gains["dll"], gains["pll"], gains["fll"])
+            keep.append(c)
+            calls[f"weighted_loop_k{k_loop}_ncoh{n_coh}"] = (k_loop, lambda c=c: eng.lib.gpsx_track_loop_weighted_dev(
+                eng.h, c.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d_wst), n, C.c_void_p(d_rec)))
+        for leg in legs:
+            pair = (4, 4) if leg == "c_search" else (20, 20)
+            c = capi.wsync_cfg(pair[0], pair[1], gains, gains, 20, (1024, 1))
+            keep.append(c)
+            calls[f"weighted_sync_k{k_loop}_{leg}"] = (k_loop, lambda c=c, d=d_sync[leg]: eng.lib.gpsx_track_loop_weighted_sync_dev(
+                eng.h, c.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d), n, C.c_void_p(d_srec)))
+        med = _timed_rows(eng, calls, {"channels": n})
+        for leg, against in (("a_locked_spread", 1), ("b_locked_equal", 20), ("c_search", 4)):
+            ratio = med[f"weighted_sync_k{k_loop}_{leg}"] / med[f"weighted_loop_k{k_loop}_ncoh{against}"]
+            print(json.dumps({"ratio": "k_track_wsync over k_track_wloop", "channels": n, "leg": leg, "against_n_coh": against,
+                              "value": round(ratio, 4), **({"bound": 1.10, "within_bound": bool(ratio <= 1.10)} if leg != "c_search" else {})}), flush=True)
+        after = legs["c_search"].copy()
+        eng.d2h(after, d_sync["c_search"])
+        print(json.dumps({"leg_c_check": "channels still in SEARCH", "channels": n, "in_search": int((after["mode"] == 0).sum()),
+                          "sync_rounds_max": int(after["sync_rounds"].max())}), flush=True)
+        for p in [d_wst, d_rec, d_srec] + [d_sync[leg] for leg in ("a_locked_spread", "b_locked_equal")]:
+            eng.free(p)
+        if n <= 65536:      # the scenario's shape: 2000 ms in ten host launches of 200, records copied back (wall clock)
+            eng.h2d(d_sync["c_search"], legs["c_search"])
+            c = capi.wsync_cfg(4, 20, gains, gains, 20, (5, 4))
+            eng.track_loop_weighted_sync(blocks2, d_sync["c_search"], n, c)      # (warm-up: the arena grows once)
+            eng.h2d(d_sync["c_search"], legs["c_search"])
+            t0 = time.perf_counter()
+            for _ in range(10):
+                eng.track_loop_weighted_sync(blocks2, d_sync["c_search"], n, c)
+            wall = time.perf_counter() - t0
+            print(json.dumps({"scenario_wall_clock": True, "channels": n, "blocks": 10 * k_loop, "launches": 10, "n_coh_search": 4, "n_coh_lock": 20,
+                              "seconds": round(wall, 4), "record_bytes_per_launch": capi.wsync_slots(k_loop, 4, 20) * n * 48}), flush=True)
+        eng.free(d_sync["c_search"])
+
+
 def main():
     global WINDOW_S
     from stm32f4_sdr_gps_amd import capi, synth
+    if "--weighted-sync" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-sync"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_sync([int(a) for a in args] or [65536, 212992])
     if "--weighted-loop" in sys.argv[1:]:
         args = sys.argv[1:]
         at = args.index("--weighted-loop")
