@@ -32,7 +32,7 @@ extern "C" {
                                             * so did gpsx_acq_grid_weighted_coh(_dev).
                                             * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change;
                                             * gpsx_track_loop_weighted(_dev) and gpsx_track_loop_weighted_sync(_dev) too (new
-                                            * structs of their own). */
+                                            * structs of their own); gpsx_wnav_words(_dev) and gpsx_wnav_subframe_image likewise. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -603,6 +603,117 @@ int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg
                                       gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec);
 int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
                                   gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec);
+
+/* ---- EXTENSION, not in the reference: LNAV frame sync and parity-checked words from the sync loop's bit records -----------------
+ * What lies between a BIT record of gpsx_track_loop_weighted_sync and a navigation word, done on the device: a kernel reads the
+ * loop's records where they are (d_rec, in HBM), keeps a 64-byte frame state per channel and returns parity-checked 30-bit words
+ * only, 16 bytes each and at most n_blocks / 600 + 2 per channel and launch.  Unlike the reference's word layer it does not accept
+ * a bare preamble: a channel synchronises on TLM + HOW as a whole (62 consecutive bits: two parity-checked words, the preamble,
+ * the HOW's two zero bits and a subframe ID of 1 .. 5), in either polarity, and the polarity is what that test found.
+ * gpsx_track_loop_weighted_sync, its structs and k_track_wsync are unchanged.
+ *
+ * Parity: the six equations of IS-GPS-200 table 20-XIV (kParityMask / kParityFromD30 of gpsx_steps.cpp).  For a received 30-bit
+ * word W (its first bit in bit 29) and the two bits P29, P30 received before it: d = (W >> 6) ^ (P30 ? 0xFFFFFF : 0) are the source
+ * bits d1 .. d24 (d1 in bit 23), and the word passes iff for k = 0 .. 5 bit 5 - k of W equals parity(d & mask_k) ^ (P29 for k = 0,
+ * 2, 5; P30 for k = 1, 3, 4).  The test is invariant under inversion of the whole stream, and so is d.
+ *
+ * Definition, per channel: the slots of d_rec are read in order.  A record is a BIT if its flags have GPSX_WSYNC_WINDOW and
+ * GPSX_WSYNC_BIT and 0 <= end_block < n_blocks; every other record is skipped.  For a bit, with E = blocks_seen + end_block:
+ *   1 continuity   if last_bit_end_p1 != 0 and E + 1 != last_bit_end_p1 + 20 the stream broke (a re-armed search, another edge, a
+ *                  gap): n_drop++ if mode == SYNCED; then mode = HUNT and fresh = word_idx = bit_idx = bad_run = ok_mask = 0.
+ *                  In every case last_bit_end_p1 = E + 1
+ *   2 shift        r = bit_ip < 0 (bit 0 is a positive prompt); hist = hist << 1 | r; fresh = min(fresh + 1, 62)
+ *   3 HUNT         (mode == HUNT) only when fresh == 62: for inv' = 0, then 1, with x = hist ^ (inv' ? ~0 : 0), bits 61 and 60 of x
+ *                  are D29*, D30*, bits 59 .. 30 word 1, bits 29 .. 0 word 2.  The first inv' is accepted for which word 1's first
+ *                  eight bits are 10001011, word 1 passes parity against D29*, D30*, word 2 passes against word 1's last two
+ *                  bits, word 2's last two bits are 0 and its source bits d20 .. d22 give an ID in 1 .. 5.  On accept: inv = inv',
+ *                  mode = SYNCED, word_idx = 2, bit_idx = 0, bad_run = 0, ok_mask = 3 | ID << 16, n_sync++, and two records go out:
+ *                  index 1 with end_block - 600 (which may be negative: the word ended before this launch; flags == 0 is what
+ *                  marks an empty slot), then index 2 with end_block; both GPSX_WNAV_WORD | _OK | _SYNC (| _INVERTED if inv), both
+ *                  with the ID, index 2 with the TOW count.  The bit is done
+ *   4 SYNCED       (mode == SYNCED when the bit came, after step 1) bit_idx++; at 30 the word word_idx + 1 is complete: W = the
+ *                  newest 30 bits of hist, P29 / P30 bits 31 / 30 of hist; passed = parity.  Word 1: with t = the first eight
+ *                  bits of W ^ (inv ? ~0 : 0): t == 01110100 and passed: inv ^= 1 and the record gets _FLIPPED; t neither that nor
+ *                  10001011: passed = 0 (an inverted preamble on a word that fails parity fails and flips nothing).  Word 2
+ *                  passes only if it also ends in two zero bits and has an ID in 1 .. 5 (both after inv); the ID kept for the
+ *                  subframe's records (ok_mask bits 16 .. 18) is that ID if word 2 passed, else 0.  The record: index, the word as
+ *                  below with the inv that holds now, _WORD (| _OK if passed) (| _INVERTED if inv), the kept ID (0 for word 1: its
+ *                  HOW is yet to come), aux = the TOW count (d1 .. d17 of word 2) for index 2 with _OK.  ok_mask |= passed << (index
+ *                  - 1); bad_run = passed ? 0 : min(bad_run + 1, 10); bit_idx = 0; word_idx = (word_idx + 1) % 10.  After word 10:
+ *                  _SUBFRAME and n_subframes++ if ok_mask's bits 0 .. 9 are all set, then ok_mask = 0.  Then, if bad_run >=
+ *                  max_bad_words: _DROPPED, n_drop++, mode = HUNT, fresh = 0, word_idx = 0.
+ * A record's word: x = W ^ (inv ? 0x3FFFFFFF : 0); bits 29 .. 6 = d1 .. d24 (the source bits: polarity and D30* removed -- the d of
+ * the parity test), bits 5 .. 0 = x's D25 .. D30.  That is the word as gps_nav_data_decode_subframe's image holds it.
+ * Output: a channel's records go to its slots 0, 1, .. of d_words[n_blocks / 600 + 2][n_ch] in order of completion; the remaining
+ * slots get the empty pattern (end_block = -1, the rest 0): every byte of d_words is written.  The bound holds for any input: bits
+ * count as consecutive only 20 blocks apart, a word needs 30 consecutive bits (600 blocks) and a sync, which yields two words,
+ * 62 fresh ones (1220 blocks); the "+ 2" is a launch that begins one bit before a sync or a word's end.  At the launch's end
+ * blocks_seen += n_blocks.
+ * What can be trusted: parity is blind to the inversion of a whole word, and so are the source bits: d = D ^ D30* comes out the
+ * same in either polarity.  After a half-cycle slip of the carrier loop the word the slip fell into fails (none, on a word boundary), the words up to the
+ * next TLM pass with the right d1 .. d24 but under the OLD polarity: their six parity bits in `word` and their _INVERTED flag are
+ * inverted until the TLM gets _FLIPPED.  Words 1 and 2 are the only ones whose test sees the polarity.  A consumer of whole
+ * subframes takes the ten words that end with a word 10 flagged _SUBFRAME; a _FLIPPED TLM says that a slip lies in the subframe
+ * before it.
+ * Errors: NULL pointers, max_bad_words outside 1 .. 10, reserved != 0, n_blocks outside 1 .. 4096, n_slots outside 1 .. n_blocks,
+ * n_ch < 1 and a size that overflows return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.  A channel whose state is
+ * out of range -- mode outside 0 .. 1, inv outside 0 .. 1, word_idx outside 0 .. 9, bit_idx outside 0 .. 29, fresh outside 0 .. 62,
+ * bad_run outside 0 .. 10, blocks_seen or last_bit_end_p1 outside 0 .. 2^62 (E + 1 is then never 0, the value that means "no bit
+ * yet", which the slot bound rests on) -- is BAD as gpsx_track_loop_weighted_sync's are: its state stays as it was, its slots are
+ * empty, and GPSX_EINVAL comes from gpsx_wnav_words after its wait / from the next gpsx_synchronize() after _dev.
+ * Vector ALU (k_wnav_words: one channel per lane, the records' three words loaded eight slots ahead of the recurrence).  On one
+ * stream: gpsx_track_loop_weighted_sync_dev, then gpsx_wnav_words_dev on its d_rec with the same n_blocks and n_slots =
+ * ceil(n_blocks / min(n_coh_search, n_coh_lock)). */
+#define GPSX_WNAV_HUNT      0
+#define GPSX_WNAV_SYNCED    1
+#define GPSX_WNAV_WORD      1u   /* flags: the slot holds a word */
+#define GPSX_WNAV_OK        2u   /* it passed parity (and, words 1 and 2, what is asked of a TLM / HOW) */
+#define GPSX_WNAV_INVERTED  4u   /* the received polarity was inverted (removed in `word`) */
+#define GPSX_WNAV_SYNC      8u   /* words 1 and 2 of the TLM + HOW test that took the channel from HUNT to SYNCED */
+#define GPSX_WNAV_FLIPPED   16u  /* word 1 showed the inverted preamble and passed: the polarity changed with this word */
+#define GPSX_WNAV_SUBFRAME  32u  /* word 10 of a subframe all of whose ten words passed */
+#define GPSX_WNAV_DROPPED   64u  /* max_bad_words consecutive words failed: the channel is back in HUNT */
+
+typedef struct {
+  int32_t max_bad_words;         /* 1 .. 10: consecutive failed words that drop a channel back to HUNT */
+  int32_t reserved;              /* 0 */
+} gpsx_wnav_cfg_t;
+
+typedef struct {                 /* 64 bytes, device resident; all zero = a fresh channel */
+  uint64_t hist;                 /*  0  received hard bits, newest in bit 0, polarity as received */
+  int64_t  blocks_seen;          /*  8  blocks of all earlier launches: the absolute time base */
+  int64_t  last_bit_end_p1;      /* 16  absolute last block of the newest bit, + 1; 0: none yet */
+  int32_t  fresh;                /* 24  consecutive bits in hist since the last reset, saturating at 62 */
+  int32_t  mode;                 /* 28  GPSX_WNAV_HUNT / GPSX_WNAV_SYNCED */
+  int32_t  inv;                  /* 32  0 / 1: received polarity is inverted */
+  int32_t  word_idx;             /* 36  words of the current subframe completed, 0 .. 9 */
+  int32_t  bit_idx;              /* 40  bits of the current word, 0 .. 29 */
+  int32_t  bad_run;              /* 44  consecutive failed words */
+  uint32_t ok_mask;              /* 48  bit w (0 .. 9): word w + 1 of the current subframe passed; bits 16 .. 18: its ID from the
+                                  *     HOW if that passed, else 0 (what later words' records report) */
+  uint32_t n_sync, n_drop, n_subframes;   /* 52  counters */
+} gpsx_wnav_state_t;
+
+typedef struct {                 /* 16 bytes, one per (word slot, channel) */
+  int32_t  end_block;            /*  0  last block of the word's last bit, from the launch's first block; empty slot: -1 */
+  uint32_t word;                 /*  4  bit 29 = d1 .. bit 6 = d24 (source bits), bits 5 .. 0 = D25 .. D30 (polarity removed) */
+  uint8_t  index;                /*  8  1 .. 10 */
+  uint8_t  flags;                /*  9  GPSX_WNAV_WORD | ...; empty slot: 0 */
+  uint8_t  subframe_id;          /* 10  from the current subframe's HOW if it passed, else 0 */
+  uint8_t  zero;                 /* 11 */
+  uint32_t aux;                  /* 12  index 2 with GPSX_WNAV_OK: the 17-bit TOW count; else 0 */
+} gpsx_wnav_word_t;
+
+/* d_rec: what gpsx_track_loop_weighted_sync(_dev) wrote for n_blocks blocks, [n_slots][n_ch], on the device in both variants;
+ * d_words / words: [n_blocks / 600 + 2][n_ch] */
+int gpsx_wnav_words_dev(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                        gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *d_words);
+int gpsx_wnav_words(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                    gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *words /* host */);
+/* host only, no GPU: ten records of one subframe (index 1 .. 10 in this order, all GPSX_WNAV_OK; GPSX_EINVAL otherwise, and for
+ * NULL) -> the 38-byte image gps_nav_data_decode_subframe reads (bit n of the subframe = bit n & 7 of byte n >> 3; the image's
+ * last four bits are 0). */
+int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38]);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

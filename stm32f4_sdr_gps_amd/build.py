@@ -92,7 +92,11 @@ def check_no_scratch() -> dict:
     wsync = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted_sync.o")).items() if "k_track_wsync" in k}
     if len(wsync) != 1:
         raise RuntimeError(f"expected k_track_wsync in build/k_track_loop_weighted_sync.o, found {sorted(wsync)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync}
+    # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
+    wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
+    if len(wnav) != 1:
+        raise RuntimeError(f"expected k_wnav_words in build/k_wnav_words.o, found {sorted(wnav)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **wnav}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

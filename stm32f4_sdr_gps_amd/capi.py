@@ -94,6 +94,36 @@ def wsync_slots(n_blocks, n_coh_search, n_coh_lock) -> int:
     return (n_blocks + span - 1) // span
 
 
+# gpsx_wnav_cfg_t / gpsx_wnav_state_t / gpsx_wnav_word_t (LNAV frame sync and parity-checked words from the sync loop's records)
+WNAV_HUNT, WNAV_SYNCED = 0, 1
+WNAV_FLAG_WORD, WNAV_FLAG_OK, WNAV_FLAG_INVERTED, WNAV_FLAG_SYNC, WNAV_FLAG_FLIPPED, WNAV_FLAG_SUBFRAME, WNAV_FLAG_DROPPED = 1, 2, 4, 8, 16, 32, 64
+WNAV_CFG_DTYPE = np.dtype([("max_bad_words", "<i4"), ("reserved", "<i4")])
+WNAV_STATE_DTYPE = np.dtype([("hist", "<u8"), ("blocks_seen", "<i8"), ("last_bit_end_p1", "<i8"), ("fresh", "<i4"), ("mode", "<i4"),
+                             ("inv", "<i4"), ("word_idx", "<i4"), ("bit_idx", "<i4"), ("bad_run", "<i4"), ("ok_mask", "<u4"),
+                             ("n_sync", "<u4"), ("n_drop", "<u4"), ("n_subframes", "<u4")])
+WNAV_WORD_DTYPE = np.dtype([("end_block", "<i4"), ("word", "<u4"), ("index", "u1"), ("flags", "u1"), ("subframe_id", "u1"), ("zero", "u1"),
+                            ("aux", "<u4")])
+assert WNAV_CFG_DTYPE.itemsize == 8 and WNAV_STATE_DTYPE.itemsize == 64 and WNAV_WORD_DTYPE.itemsize == 16
+
+
+def wnav_word_slots(n_blocks) -> int:
+    """word slots per channel of a launch: n_blocks / 600 + 2"""
+    return n_blocks // 600 + 2
+
+
+def subframe_image(ten: np.ndarray) -> np.ndarray:
+    """ten WNAV_WORD_DTYPE records of one subframe (index 1 .. 10 in order, all OK) -> the 38-byte image
+    gps_nav_data_decode_subframe reads; GpsxError otherwise.  Host only."""
+    ten = np.ascontiguousarray(ten, WNAV_WORD_DTYPE)
+    if ten.shape != (10,):
+        raise GpsxError("subframe_image takes ten word records")
+    image = np.zeros(38, np.uint8)
+    rc = load_library().gpsx_wnav_subframe_image(ten.ctypes.data, image.ctypes.data)
+    if rc != 0:
+        raise GpsxError(f"gpsx_wnav_subframe_image -> {rc}: the records are not words 1 .. 10 of one subframe, all of them OK")
+    return image
+
+
 TRK_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"),
                       ("if_freq_accum", "<u4")])
 JOB_DTYPE = np.dtype([("block", "<i4"), ("n_ms", "<i4"), ("prn", "<i4"), ("freq_hz", "<f4"), ("offset_bits", "<i4"),
@@ -191,6 +221,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_track_loop_weighted_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
     lib.gpsx_track_loop_weighted_sync.argtypes = lib.gpsx_track_loop_weighted.argtypes
     lib.gpsx_track_loop_weighted_sync_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
+    lib.gpsx_wnav_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_wnav_words_dev.argtypes = lib.gpsx_wnav_words.argtypes
+    lib.gpsx_wnav_subframe_image.argtypes = [C.c_void_p, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -577,6 +610,18 @@ class Engine:
         self._chk(self.lib.gpsx_track_loop_weighted_sync(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), C.c_void_p(d_state),
                                                          n_ch, rec.ctypes.data), "gpsx_track_loop_weighted_sync")
         return rec
+
+    def wnav_words(self, d_rec: int, n_slots: int, n_blocks: int, d_state: int, n_ch: int, max_bad_words: int = 3) -> np.ndarray:
+        """EXTENSION: LNAV frame sync and parity-checked words from the WSYNC_REC_DTYPE [n_slots, n_ch] records at device address
+        d_rec that gpsx_track_loop_weighted_sync_dev wrote for n_blocks blocks, on the n_ch WNAV_STATE_DTYPE frame states at device
+        address d_state (all zero: a fresh channel).  -> WNAV_WORD_DTYPE [n_blocks // 600 + 2, n_ch]; an empty slot has flags 0 and
+        end_block -1"""
+        cfg = np.zeros(1, WNAV_CFG_DTYPE)
+        cfg["max_bad_words"] = max_bad_words
+        words = np.zeros((wnav_word_slots(n_blocks), n_ch), WNAV_WORD_DTYPE)
+        self._chk(self.lib.gpsx_wnav_words(self.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_state), n_ch,
+                                           words.ctypes.data), "gpsx_wnav_words")
+        return words
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

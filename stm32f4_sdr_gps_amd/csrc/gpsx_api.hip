@@ -1205,6 +1205,84 @@ int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, co
   return track_prn_verdict(ctx);
 }
 
+/* ---- extension: LNAV frame sync and parity-checked words from the sync loop's bit records ----------------------------------- */
+
+namespace {
+// every refusal of gpsx_wnav_words(_dev), before anything is written; *words_bytes = the word records' size
+int wnav_words_check(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const void *d_rec, int n_slots, int n_blocks, const void *st, int n_ch,
+                     const void *words, size_t *words_bytes)
+{
+  if (!cfg || !d_rec || !st || !words)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->max_bad_words < 1 || cfg->max_bad_words > 10)
+    return fail(ctx, GPSX_EINVAL, "max_bad_words must be 1..10");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_blocks < 1 || n_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
+  if (n_slots < 1 || n_slots > n_blocks)
+    return fail(ctx, GPSX_EINVAL, "n_slots must be 1..n_blocks");
+  if (n_ch < 1)
+    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
+  size_t n = 0, rec_bytes = 0;
+  if (__builtin_mul_overflow((size_t)n_slots, (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wsync_rec_t), &rec_bytes) ||
+      __builtin_mul_overflow((size_t)(n_blocks / 600 + 2), (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wnav_word_t), words_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  return GPSX_OK;
+}
+}  // namespace
+
+int gpsx_wnav_words_dev(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                        gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *d_words)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t words_bytes = 0;
+  if (int rc = wnav_words_check(ctx, cfg, d_rec, n_slots, n_blocks, d_state, n_ch, d_words, &words_bytes)) return rc;
+  launch_wnav_words(ctx->stream, d_rec, n_slots, n_blocks, cfg->max_bad_words, d_state, n_ch, d_words,
+                    ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
+  LAUNCHCHK(ctx, "k_wnav_words");
+  ctx->last_kernel = "k_wnav_words";
+  return GPSX_OK;
+}
+
+int gpsx_wnav_words(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                    gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *words)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t words_bytes = 0;
+  if (int rc = wnav_words_check(ctx, cfg, d_rec, n_slots, n_blocks, d_state, n_ch, words, &words_bytes)) return rc;
+  if (int rc = arena_reset(ctx, arena_size(words_bytes)))
+    return rc;
+  gpsx_wnav_word_t *d_words = arena_take<gpsx_wnav_word_t>(ctx, words_bytes / sizeof(gpsx_wnav_word_t));
+  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel)
+  launch_wnav_words(ctx->stream, d_rec, n_slots, n_blocks, cfg->max_bad_words, d_state, n_ch, d_words, ctx->d_bad_prn);
+  LAUNCHCHK(ctx, "k_wnav_words");
+  ctx->last_kernel = "k_wnav_words";
+  HIPCHK(ctx, hipMemcpyAsync(words, d_words, words_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (*ctx->h_bad_prn) {
+    *ctx->h_bad_prn = 0;
+    return fail(ctx, GPSX_EINVAL, "a channel's frame state is out of range (its state is untouched, its slots are empty)");
+  }
+  return GPSX_OK;
+}
+
+int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38])
+{
+  if (!ten || !image)
+    return GPSX_EINVAL;
+  for (int w = 0; w < 10; w++)
+    if (ten[w].index != w + 1 || (ten[w].flags & (GPSX_WNAV_WORD | GPSX_WNAV_OK)) != (GPSX_WNAV_WORD | GPSX_WNAV_OK))
+      return GPSX_EINVAL;
+  std::memset(image, 0, 38);
+  for (int w = 0; w < 10; w++)
+    for (int i = 0; i < 30; i++) {
+      const int bit = 30 * w + i;
+      image[bit >> 3] |= (uint8_t)(((ten[w].word >> (29 - i)) & 1u) << (bit & 7));
+    }
+  return GPSX_OK;
+}
+
 /* ---- extension: weighted two-bit acquisition grid ------------------------------------------------------------------------ */
 
 namespace {

@@ -146,6 +146,12 @@ void launch_track_loop_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, 
 void launch_track_loop_weighted_sync(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
                                      gpsx_wsync_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wsync_rec_t *d_rec,
                                      uint32_t *d_bad_prn);
+// extension: gpsx_wnav_words (k_wnav_words.hip: k_wnav_words) -- LNAV frame sync and parity-checked words from the [n_slots][n_ch]
+// records launch_track_loop_weighted_sync wrote for n_blocks blocks: one channel per lane, 64-byte frame states in HBM,
+// d_words [n_blocks / 600 + 2][n_ch], every byte of it written.  d_bad_state (may be null): set to 1 by a channel whose state
+// words are out of range.
+void launch_wnav_words(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks, int max_bad_words, gpsx_wnav_state_t *d_st,
+                       int n_ch, gpsx_wnav_word_t *d_words, uint32_t *d_bad_state);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -1,0 +1,263 @@
+"""LNAV frame sync and parity-checked words on the device (EXTENSION, not in the reference: include/gpsx.h gpsx_wnav_words;
+k_wnav_words on the vector ALU, one channel per lane) against its exact CPU restatement (tests/weighted_nav_ref.py, pinned in
+tests/test_weighted_nav_reference.py).  Every comparison is for equality, byte for byte, on the word records and on the 64-byte
+states.  The sync loop's records are fabricated (tests/weighted_nav_cases.py: 32 distinct bit streams tiled over the channels, with
+bit errors, a slip, a gap, another edge and noise; initial states from the restatement's run over the stream's earlier blocks);
+only the last test starts from IF samples."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import weighted_loop_cases as S
+import weighted_nav_cases as W
+import weighted_nav_ref as N
+import weighted_sync_cases as K
+import weighted_sync_ref as Y
+
+pytestmark = pytest.mark.gpu
+
+EINVAL = -22
+GUARD = 4096
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from stm32f4_sdr_gps_amd import capi
+    e = capi.Engine(0)
+    yield e
+    e.close()
+
+
+def _cfg(max_bad_words, reserved=0):
+    from stm32f4_sdr_gps_amd import capi
+    cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
+    cfg["max_bad_words"], cfg["reserved"] = max_bad_words, reserved
+    return cfg
+
+
+def _gpu(eng, launches, st, max_bad_words, dev=True):
+    """the library on a copy of `st` in device memory, launch after launch.  launches: [(records [n_slots][n_ch], n_blocks)].
+    States and word records sit between canaries, the word records are prefilled with 0xA5.
+    -> ([word records per launch], states after, [return codes])"""
+    n_ch = len(st)
+    cfg = _cfg(max_bad_words)
+    h_st = np.full(GUARD + st.nbytes + GUARD, 0x5A, np.uint8)
+    h_st[GUARD:GUARD + st.nbytes] = np.ascontiguousarray(st).view(np.uint8)
+    d_st = eng.malloc(h_st.nbytes)
+    words_out, codes = [], []
+    try:
+        eng.h2d(d_st, h_st)
+        for rec, n_blocks in launches:
+            rec = np.ascontiguousarray(rec)
+            assert rec.dtype == Y.REC_DTYPE and rec.shape[1] == n_ch
+            n_words = N.max_words(n_blocks)
+            size = n_words * n_ch * 16
+            h_words = np.full(GUARD + size + GUARD, 0xA5, np.uint8)
+            d_rec, d_words = eng.malloc(rec.nbytes), eng.malloc(h_words.nbytes)
+            try:
+                eng.h2d(d_rec, rec)
+                if dev:
+                    eng.h2d(d_words, h_words)
+                    rc = eng.lib.gpsx_wnav_words_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_st + GUARD), n_ch,
+                                                     C.c_void_p(d_words + GUARD))
+                    assert rc == 0 and eng.lib.gpsx_last_kernel(eng.h) == b"k_wnav_words"
+                    codes.append(eng.lib.gpsx_synchronize(eng.h))
+                    eng.d2h(h_words, d_words)
+                else:
+                    codes.append(eng.lib.gpsx_wnav_words(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_st + GUARD),
+                                                         n_ch, h_words[GUARD:].ctypes.data))
+            finally:
+                eng.free(d_rec)
+                eng.free(d_words)
+            assert (h_words[:GUARD] == 0xA5).all() and (h_words[GUARD + size:] == 0xA5).all(), "canary around the word records"
+            words_out.append(h_words[GUARD:GUARD + size].view(N.WORD_DTYPE).reshape(n_words, n_ch).copy())
+        eng.d2h(h_st, d_st)
+    finally:
+        eng.free(d_st)
+    assert (h_st[:GUARD] == 0x5A).all() and (h_st[GUARD + st.nbytes:] == 0x5A).all(), "canary around the states"
+    return words_out, h_st[GUARD:GUARD + st.nbytes].view(N.STATE_DTYPE).copy(), codes
+
+
+def _same(words, after, want_words, want_st, what):
+    assert words.shape == want_words.shape, what
+    bad = [c for c in range(words.shape[1]) if words[:, c].tobytes() != want_words[:, c].tobytes()]
+    assert not bad, (what, "words", bad[:4], words[:, bad[0]], want_words[:, bad[0]])
+    bad = [c for c in range(len(after)) if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
+    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+
+
+@pytest.mark.parametrize("i", range(len(W.CASES)))
+def test_words_and_states_match_the_restatement(eng, i):
+    """the table: 1, 3, 64, 65, 257 and 1000 channels (one lane, part of a wave, the wave's edge, part of the last workgroup), spans
+    20 / 1 / 4 / 5, launches of 4096, 1237, 600, 2047, 1 and 19 blocks, fresh states and states in the middle of anything.  The word
+    records were prefilled: equality says that every byte was written"""
+    rec, n_blocks, st0, max_bad, want, want_st = W.case(i)
+    for dev in (True, False):
+        words, after, codes = _gpu(eng, [(rec, n_blocks)], st0, max_bad, dev)
+        assert codes == [0]
+        _same(words[0], after, want, want_st, (W.CASES[i], dev))
+    W.absolute_words([(0, words[0])])      # (filled slots first, then the empty pattern)
+
+
+SPLIT = dict(n_ch=64, span=20, n_blocks=4096, warm=500, max_bad=3)      # stream 0 synchronises at block 1240: 140 blocks after a cut at 600
+_split = {}
+
+
+def _split_whole():
+    """the one launch on the restatement, once per process -> (states before, words wanted, states wanted)"""
+    if not _split:
+        st0 = W.warm_states(SPLIT["warm"], SPLIT["max_bad"])[W.tiled(SPLIT["n_ch"])].copy()
+        after = st0.copy()
+        rec = W.launch_records(W.specs(), W.tiled(SPLIT["n_ch"]), SPLIT["warm"], SPLIT["n_blocks"], SPLIT["span"])
+        words, bad = N.run(rec, SPLIT["n_blocks"], after, SPLIT["max_bad"])
+        assert not bad
+        _split["whole"] = (st0, words, after)
+    return _split["whole"]
+
+
+@pytest.mark.parametrize("cut", [1, 599, 600, 2050, 4095])
+def test_split_launches_equal_one_launch(eng, cut):
+    """one 4096-block record array cut in two: states byte-identical, word records the same once end_block is absolute"""
+    st0, want, want_st = _split_whole()
+    warm, n_blocks = SPLIT["warm"], SPLIT["n_blocks"]
+    parts = [(warm, cut), (warm + cut, n_blocks - cut)]
+    launches = [(W.launch_records(W.specs(), W.tiled(SPLIT["n_ch"]), at, n, SPLIT["span"]), n) for at, n in parts]
+    words, after, codes = _gpu(eng, launches, st0, SPLIT["max_bad"])
+    assert codes == [0, 0] and after.tobytes() == want_st.tobytes()
+    got = W.absolute_words([(at, w) for (at, _), w in zip(parts, words)])
+    assert got == W.absolute_words([(warm, want)]) and sum(len(g) for g in got) > SPLIT["n_ch"]
+    if cut == 600:      # a sync early in the second launch: its word 1 ended in the first
+        early = (words[1]["flags"][0] & N.F_SYNC != 0) & (words[1]["end_block"][0] < 0)
+        assert early.any() and (words[1]["end_block"][1][early] == words[1]["end_block"][0][early] + 600).all()
+
+
+def test_every_byte_of_the_word_records_is_written(eng):
+    """257 channels, a launch in which most slots stay empty: no byte of the 0xA5 prefill is left, and an empty slot is the pattern"""
+    rec, n_blocks, st0, max_bad, want, _ = W.case(4)
+    words, _, _ = _gpu(eng, [(rec, n_blocks)], st0, max_bad)
+    empty = words[0]["flags"] == 0
+    assert empty.any() and (~empty).any()
+    assert (words[0]["end_block"][empty] == -1).all() and not words[0]["word"][empty].any() and not words[0]["aux"][empty].any()
+    assert not words[0]["zero"].any() and words[0].tobytes() == want.tobytes()
+
+
+BAD_FIELDS = [("mode", 2), ("mode", -1), ("inv", 2), ("inv", -1), ("word_idx", 10), ("bit_idx", 30), ("bit_idx", -1), ("fresh", 63), ("fresh", -1),
+              ("bad_run", 11), ("blocks_seen", -1), ("blocks_seen", (1 << 62) + 1), ("last_bit_end_p1", -5), ("last_bit_end_p1", (1 << 62) + 1)]
+
+
+def test_bad_channels(eng):
+    """one bad state per field among good neighbours of the same wave: untouched, their slots empty, GPSX_EINVAL from the host
+    variant and from the next synchronize after the device variant; the neighbours are the restatement's"""
+    rec, n_blocks, st0, max_bad, _, _ = W.case(2)
+    st0 = st0.copy()
+    bad = [3 + 4 * k for k in range(len(BAD_FIELDS))]
+    for ch, (field, value) in zip(bad, BAD_FIELDS):
+        st0[field][ch] = value
+    want_st = st0.copy()
+    want, found = N.run(rec, n_blocks, want_st, max_bad)
+    assert found == bad and (want["flags"][:, bad] == 0).all() and want_st[bad].tobytes() == st0[bad].tobytes()
+    for dev in (True, False):
+        words, after, codes = _gpu(eng, [(rec, n_blocks)], st0, max_bad, dev)
+        assert codes == [EINVAL] and eng.lib.gpsx_last_error(eng.h), dev
+        assert eng.lib.gpsx_synchronize(eng.h) == 0
+        _same(words[0], after, want, want_st, ("bad channels", dev))
+    good = [c for c in range(len(st0)) if c not in bad]
+    words, after, codes = _gpu(eng, [(np.ascontiguousarray(rec[:, good]), n_blocks)], st0[good].copy(), max_bad)
+    assert codes == [0]
+    _same(words[0], after, np.ascontiguousarray(want[:, good]), want_st[good], "the same channels without the bad ones")
+
+
+def test_argument_checks_write_nothing(eng):
+    n_ch, n_blocks, n_slots = 5, 40, 2
+    rec = W.launch_records(W.specs(), np.arange(n_ch), 0, n_blocks, 20)
+    st0 = W.warm_states(0)[:n_ch].copy()
+    good = dict(null_cfg=False, null_rec=False, null_st=False, null_out=False, max_bad=3, reserved=0, n_slots=n_slots, n_blocks=n_blocks, n_ch=n_ch)
+    refusals = [dict(null_cfg=True), dict(null_rec=True), dict(null_st=True), dict(null_out=True), dict(max_bad=0), dict(max_bad=11), dict(max_bad=-1),
+                dict(reserved=1), dict(reserved=-1), dict(n_blocks=0), dict(n_blocks=-40), dict(n_blocks=4097), dict(n_slots=0), dict(n_slots=-1),
+                dict(n_slots=41), dict(n_blocks=1, n_slots=2), dict(n_ch=0), dict(n_ch=-3)]
+    n_words = N.max_words(n_blocks) * n_ch * 16
+    d_rec, d_st, d_words = eng.malloc(rec.nbytes), eng.malloc(st0.nbytes), eng.malloc(n_words)
+    try:
+        eng.h2d(d_rec, rec)
+        for dev, fn in ((False, eng.lib.gpsx_wnav_words), (True, eng.lib.gpsx_wnav_words_dev)):
+            for change in refusals:
+                a = {**good, **change}
+                cfg = _cfg(a["max_bad"], a["reserved"])
+                host = np.full(n_words, 0xA5, np.uint8)
+                eng.h2d(d_st, st0)
+                eng.h2d(d_words, host)
+                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else C.c_void_p(d_rec), a["n_slots"], a["n_blocks"],
+                        None if a["null_st"] else C.c_void_p(d_st), a["n_ch"], None if a["null_out"] else (C.c_void_p(d_words) if dev else host.ctypes.data))
+                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h), (dev, change)
+                eng.synchronize()      # nothing was enqueued, nothing is pending
+                st, dw = st0.copy(), np.zeros_like(host)
+                eng.d2h(st, d_st)
+                eng.d2h(dw, d_words)
+                assert (host == 0xA5).all() and (dw == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
+    finally:
+        for p in (d_rec, d_st, d_words):
+            eng.free(p)
+
+
+def test_records_that_are_no_bits_are_ignored(eng):
+    """BIT records whose end_block lies outside the launch, and BIT without WINDOW, in the slots between the bits: nothing changes"""
+    rec, n_blocks, st0, max_bad, want, want_st = W.case(4)      # span 4: four slots in five hold no bit
+    rec = rec.copy()
+    free = (rec["flags"] & Y.F_BIT) == 0
+    slots, chans = np.nonzero(free)
+    values = np.array([n_blocks, n_blocks + 5, -1, -7, -2**31, 2**31 - 1, 4096, 3], np.int32)
+    rec["end_block"][free] = values[(slots + chans) % 8]
+    rec["flags"][free] = np.where((slots + chans) % 8 == 7, Y.F_BIT | Y.F_LOCKED, W.F_BITREC)      # (the in-range one lacks WINDOW)
+    rec["bit_ip"][free] = -12345
+    check_st = st0.copy()
+    check, _ = N.run(rec, n_blocks, check_st, max_bad)
+    assert check.tobytes() == want.tobytes() and check_st.tobytes() == want_st.tobytes()
+    words, after, codes = _gpu(eng, [(rec, n_blocks)], st0, max_bad)
+    assert codes == [0]
+    _same(words[0], after, want, want_st, "ignored records")
+
+
+def test_if_samples_to_words_on_the_device(eng):
+    """seed 1: IF samples -> gpsx_track_loop_weighted_sync_dev -> gpsx_wnav_words_dev on one stream, 3500 blocks in launches of
+    1000 / 1000 / 1500.  What comes back per launch is 16 B x (n_blocks / 600 + 2) per channel: the sync at the restatement's end
+    blocks, words 3 and 4 passed, the source bits those that were synthesised"""
+    from stm32f4_sdr_gps_amd import capi
+    blocks, truth = W.e2e_scenario(1)
+    sync = capi.wsync_cfg(K.N_COH_SEARCH, K.N_COH_LOCK, S.PULL_IN, S.STEADY, K.SYNC_BITS, K.RATIO)
+    cfg = _cfg(3)
+    st = K.handover_states(1)
+    nav = np.zeros(3, N.STATE_DTYPE)
+    max_slots = capi.wsync_slots(1500, K.N_COH_SEARCH, K.N_COH_LOCK)
+    d_if, d_st, d_nav = eng.malloc(blocks.nbytes), eng.malloc(st.nbytes), eng.malloc(nav.nbytes)
+    d_rec, d_words = eng.malloc(max_slots * 3 * 48), eng.malloc(N.max_words(1500) * 3 * 16)
+    word_list, copied, at = [], 0, 0
+    try:
+        eng.h2d(d_if, blocks)
+        eng.h2d(d_st, st)
+        eng.h2d(d_nav, nav)
+        for n in (1000, 1000, 1500):
+            n_slots = capi.wsync_slots(n, K.N_COH_SEARCH, K.N_COH_LOCK)
+            eng._chk(eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, sync.ctypes.data, C.c_void_p(d_if + at * 4092), n, C.c_void_p(d_st), 3,
+                                                               C.c_void_p(d_rec)), "gpsx_track_loop_weighted_sync_dev")
+            eng._chk(eng.lib.gpsx_wnav_words_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_nav), 3, C.c_void_p(d_words)),
+                     "gpsx_wnav_words_dev")
+            words = np.zeros((N.max_words(n), 3), N.WORD_DTYPE)
+            eng.synchronize()
+            eng.d2h(words, d_words)
+            copied += words.nbytes
+            word_list.append((at, words))
+            at += n
+        eng.d2h(nav, d_nav)
+    finally:
+        for p in (d_if, d_st, d_nav, d_rec, d_words):
+            eng.free(p)
+    assert copied == 16 * 3 * (3 + 3 + 4)
+    words_abs = W.absolute_words(word_list)
+    for ch in range(3):
+        assert int(nav["mode"][ch]) == N.SYNCED and int(nav["n_sync"][ch]) == 1 and int(nav["n_drop"][ch]) == 0 and int(nav["blocks_seen"][ch]) == 3500
+        W.e2e_check_words(ch, words_abs[ch], W.e2e_bit_seed(1, ch), int(nav["inv"][ch]))
+        # inv against the truth: the newest received bits (hist, polarity as received) are the satellite's, inverted iff inv
+        last = (int(nav["last_bit_end_p1"][ch]) - 1 - 19 - K.EDGES_FOUND[ch]) // 20
+        got = [(int(nav["hist"][ch]) >> k) & 1 for k in range(40)]
+        assert got == [int(truth[ch][last - k]) ^ int(nav["inv"][ch]) for k in range(40)], ch

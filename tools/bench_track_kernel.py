@@ -23,7 +23,15 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       in SEARCH at n_coh_search = 4 (ratio 1024 / 1: noise never leaves it) -- beside
                                                       gpsx_track_loop_weighted_dev at n_coh = 1, 4, 20 in the same process, the calls
                                                       taking turns; then the wall clock of 2000 ms in host launches of 200 with the
-                                                      records copied back"""
+                                                      records copied back
+  bench_track_kernel.py --weighted-nav [channels ...]
+                                                      gpsx_wnav_words_dev (EXTENSION: LNAV frame sync and parity-checked words from the
+                                                      sync loop's records) on the records of a 4000-block launch at span 20 (200 slots,
+                                                      one bit per slot, every channel SYNCED on a parity-correct stream) beside (1) a
+                                                      device-to-device hipMemcpyAsync of the same record array -- the bar: the kernel
+                                                      takes no longer -- and (2) the gpsx_track_loop_weighted_sync_dev launch that
+                                                      writes such records (n_coh_lock = 20, every channel LOCKED), the calls taking
+                                                      turns in one process"""
 import ctypes as C
 import json
 import os
@@ -260,9 +268,93 @@ def weighted_sync(counts, k_loop=200):
         eng.free(d_sync["c_search"])
 
 
+def weighted_nav(counts, n_blocks=4000, span=20):
+    from stm32f4_sdr_gps_amd import capi, synth
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    capi.load_library()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    eng = capi.Engine(0, stream=stream.value)      # (the copy below goes onto the stream the engine's events are recorded on)
+    n_slots = n_blocks // span
+    blocks2 = np.random.default_rng(7).integers(0, 256, (n_blocks, 4092), dtype=np.uint8)
+    d_if2 = eng.malloc(blocks2.nbytes)
+    eng.h2d(d_if2, blocks2)
+    gains = dict(dll=(1.0, 300.0), pll=(4.0, 3000.0), fll=0.1)
+    # 32 distinct channels on ONE parity-correct subframe repeated for ever (it ends in D29 = D30 = 0, as every subframe does), each
+    # at its own offset into it and half of them inverted: three consecutive launches of 200 bits are two subframes, so the record
+    # arrays A, B, C used in turn keep every channel SYNCED, with words completing in different slots from lane to lane
+    sub = np.array(synth.lnav_subframe(3, 4711, np.random.Generator(np.random.PCG64(5))), np.int64)
+    distinct = 32
+    bits = np.stack([np.tile(sub, 4)[(37 * j) % 300:(37 * j) % 300 + 600] ^ (j & 1) for j in range(distinct)], axis=1)      # [600][32]
+    cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
+    cfg["max_bad_words"] = 3
+    for n in counts:
+        idx = np.arange(n) % distinct
+        rec_bytes = n_slots * n * 48
+        d_recs = []
+        for leg in range(3):
+            small = np.zeros((n_slots, distinct), capi.WSYNC_REC_DTYPE)
+            small["end_block"] = (np.arange(n_slots) * span + span - 1)[:, None]
+            small["flags"] = capi.WSYNC_FLAG_WINDOW | capi.WSYNC_FLAG_LOCKED | capi.WSYNC_FLAG_BIT
+            small["bit_ip"] = (1 - 2 * bits[leg * n_slots:(leg + 1) * n_slots]) * 20000
+            d = eng.malloc(rec_bytes)
+            eng.h2d(d, np.ascontiguousarray(small[:, idx]))
+            d_recs.append(d)
+        d_copy, d_srec = eng.malloc(rec_bytes), eng.malloc(rec_bytes)
+        nav = np.zeros(n, capi.WNAV_STATE_DTYPE)
+        d_nav, d_words = eng.malloc(nav.nbytes), eng.malloc(capi.wnav_word_slots(n_blocks) * n * 16)
+        eng.h2d(d_nav, nav)
+        trk = _bench_states(n)
+        st = np.zeros(n, capi.WSYNC_STATE_DTYPE)
+        for f in ("prn", "code_phase_fine", "if_freq_offset_hz"):
+            st["loop"][f] = trk[f]
+        st["mode"] = capi.WSYNC_LOCKED
+        d_sync = eng.malloc(st.nbytes)
+        eng.h2d(d_sync, st)
+        c_sync = capi.wsync_cfg(20, 20, gains, gains, 20, (1024, 1))
+        turn = [0]
+
+        def words():
+            d = d_recs[turn[0] % 3]
+            turn[0] += 1
+            return eng.lib.gpsx_wnav_words_dev(eng.h, cfg.ctypes.data, C.c_void_p(d), n_slots, n_blocks, C.c_void_p(d_nav), n, C.c_void_p(d_words))
+
+        for _ in range(6):      # 1200 bits: every channel has met TLM + HOW with 62 fresh bits by now
+            eng._chk(words(), "gpsx_wnav_words_dev")
+        eng.synchronize()
+        eng.d2h(nav, d_nav)
+        synced_before = int((nav["mode"] == capi.WNAV_SYNCED).sum())
+        calls = {"d2d_copy_of_d_rec": (n_blocks, lambda: hip.hipMemcpyAsync(d_copy, d_recs[0], rec_bytes, 3, stream)),
+                 "wnav_words": (n_blocks, words),
+                 "weighted_sync_locked_ncoh20": (n_blocks, lambda: eng.lib.gpsx_track_loop_weighted_sync_dev(
+                     eng.h, c_sync.ctypes.data, C.c_void_p(d_if2), n_blocks, C.c_void_p(d_sync), n, C.c_void_p(d_srec)))}
+        med = _timed_rows(eng, calls, {"channels": n, "slots": n_slots, "rec_bytes": rec_bytes})
+        eng.d2h(nav, d_nav)
+        print(json.dumps({"wnav_check": "channels SYNCED before / after the timed launches", "channels": n, "before": synced_before,
+                          "after": int((nav["mode"] == capi.WNAV_SYNCED).sum()), "drops": int(nav["n_drop"].sum()),
+                          "launches": turn[0], "subframes_min": int(nav["n_subframes"].min())}), flush=True)
+        r = med["wnav_words"] / med["d2d_copy_of_d_rec"]
+        print(json.dumps({"ratio": "k_wnav_words over a device-to-device copy of d_rec", "channels": n, "value": round(r, 4), "bound": 1.0,
+                          "within_bound": bool(r <= 1.0), "read_GBps": round(rec_bytes / med["wnav_words"] / 1e3, 1),
+                          "copy_GBps_read_plus_write": round(2 * rec_bytes / med["d2d_copy_of_d_rec"] / 1e3, 1)}), flush=True)
+        print(json.dumps({"ratio": "k_wnav_words over the k_track_wsync launch that writes its records", "channels": n,
+                          "value": round(med["wnav_words"] / med["weighted_sync_locked_ncoh20"], 5)}), flush=True)
+        for p in d_recs + [d_copy, d_srec, d_nav, d_words, d_sync]:
+            eng.free(p)
+
+
 def main():
     global WINDOW_S
     from stm32f4_sdr_gps_amd import capi, synth
+    if "--weighted-nav" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-nav"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_nav([int(a) for a in args] or [65536, 212992])
     if "--weighted-sync" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-sync"]
         if "--window-s" in args:
