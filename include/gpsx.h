@@ -32,7 +32,8 @@ extern "C" {
                                             * so did gpsx_acq_grid_weighted_coh(_dev).
                                             * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change;
                                             * gpsx_track_loop_weighted(_dev) and gpsx_track_loop_weighted_sync(_dev) too (new
-                                            * structs of their own); gpsx_wnav_words(_dev) and gpsx_wnav_subframe_image likewise. */
+                                            * structs of their own); gpsx_wnav_words(_dev) and gpsx_wnav_subframe_image likewise;
+                                            * gpsx_wobs(_dev) and gpsx_wobs_pseudoranges too. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -714,6 +715,120 @@ int gpsx_wnav_words(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_
  * NULL) -> the 38-byte image gps_nav_data_decode_subframe reads (bit n of the subframe = bit n & 7 of byte n >> 3; the image's
  * last four bits are 0). */
 int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38]);
+
+/* ---- EXTENSION, not in the reference: weighted observables -- every channel's transmit time at the launch's end, on the device ----
+ * What a receiver needs next on the weighted path: for every channel, the transmit time of the signal that arrives at one common
+ * receiver instant -- here the first sample of the block that follows the launch.  Pseudoranges are differences of such times.
+ * gpsx_wobs(_dev) is a fourth stage behind gpsx_track_loop_weighted_sync_dev and gpsx_wnav_words_dev: a kernel reads the two
+ * arrays those left in HBM -- the window records d_rec[n_slots][n_ch] and the word records d_words[n_blocks / 600 + 2][n_ch] --
+ * keeps an 80-byte state per channel and returns one 32-byte observable per channel and launch: a whole millisecond of the GPS
+ * week, the code phase that goes with it, and flags that say what the number rests on.  Nothing existing changes.
+ *
+ * The time base: a channel's bit edges lie at absolute sample code_phase + 16368 (Z + 20 j) of the stream, Z = edge_block.  The
+ * sync loop places a bit's end on a block; the true edge lies code_phase samples into the block after it (code phase below half
+ * a block) or into that very block (at or above): "nearest block start".  A parity-checked HOW then says which millisecond of
+ * the week the edge of block Z is: Tz.  Two things move afterwards and are followed from the window records alone:
+ *   the seam       a channel whose code phase crosses the ends of the 16 368-sample circle moves its code-period boundary across a
+ *                  block boundary: the phase jumps by nearly a block, and Z moves by one the other way.  k_track_wsync keeps its
+ *                  ms_count through such a wrap, so the loop state's `edge` does not say which millisecond an edge is in; Z does.
+ *   breaks         a SEARCH window or a bit that does not end 20 blocks after its predecessor ends the chain: EDGE and TOW go,
+ *                  and the next bit starts another.
+ *
+ * Definition, per channel; every float operation is one IEEE single operation.
+ * Pass 1: the slots of d_rec are read in order.  A record counts if its flags have GPSX_WSYNC_WINDOW, 0 <= end_block < n_blocks
+ * and its p = w.code_phase_fine satisfies p >= 0.0f && p < 16368.0f (a NaN does not); every other record is skipped.  For a
+ * record that counts, with W = blocks_seen + end_block, in this order:
+ *   1 SEARCH       (no GPSX_WSYNC_LOCKED_FLAG) n_break++ if EDGE is set; EDGE, TOW, CONFIRMED and AMBIGUOUS are cleared;
+ *                  last_bit_end_p1 = 0
+ *   2 wrap         if EDGE and PHASE are set, with d = p - last_phase: d > 8184.0f: Z -= 1, n_wraps++; d < -8184.0f: Z += 1,
+ *                  n_wraps++
+ *   3 newest       last_phase = p, last_freq = w.if_freq_offset_hz, last_win_end_p1 = W + 1, PHASE is set
+ *   4 bit          (GPSX_WSYNC_BIT and GPSX_WSYNC_LOCKED_FLAG) if last_bit_end_p1 != 0 and W + 1 != last_bit_end_p1 + 20 the chain
+ *                  broke: n_break++ if EDGE is set, and EDGE, TOW, CONFIRMED, AMBIGUOUS are cleared.  If EDGE is not set (now):
+ *                  Z = W + 1 - (p >= 8184.0f ? 1 : 0), chain_first_p1 = W + 1, EDGE is set, and AMBIGUOUS iff
+ *                  fabsf(p - 8184.0f) < edge_guard.  Then last_bit_end_p1 = W + 1
+ * Pass 2: the slots of d_words are read in order, on the state pass 1 left.  A record is used only if its flags have
+ * GPSX_WNAV_WORD and GPSX_WNAV_OK, index == 2, aux < 100800, 0 <= end_block < n_blocks, EDGE is set, and with E = blocks_seen +
+ * end_block: E + 1 >= chain_first_p1 + 1220, E + 1 <= last_bit_end_p1 and (last_bit_end_p1 - E - 1) % 20 == 0 (gpsx_wnav_words
+ * needs 62 fresh bits for a HOW: one from before a break in the same launch cannot anchor the chain that came after it).  For a
+ * used record: T = 6000 * ((aux + 100799) % 100800) + 1200 (the HOW's count is the next subframe's; word 2 ends 1.2 s into its
+ * own), j = floor((E + 1 - Z + 10) / 20), r = E + 1 - Z - 20 j.  |r| > 5: n_mismatch++, the word is not used (the edge the words
+ * stand on is not the chain's).  Otherwise Tc = (T - 20 j) mod 604 800 000, non-negative, and: no TOW yet: Tz = Tc, TOW is set,
+ * n_anchor++; Tc == Tz: CONFIRMED is set; otherwise Tz = Tc, CONFIRMED is cleared, n_mismatch++.
+ * Output: blocks_seen += n_blocks = B, and the observable as its struct says; every byte of d_obs is written.  The four
+ * counters n_* wrap at 2^32.
+ *
+ * What the number is and is not.  tx_ms - code_phase_fine / 16368 ms is the transmit time of what arrives at sample 0 of block B,
+ * but the code phase is that of the newest window's END, up to n_coh_lock blocks before B, and it is not extrapolated:
+ * age_blocks says how old it is (the loop's drift over 20 ms is a few hundredths of a sample at 5 kHz of Doppler; a caller who
+ * needs it extrapolates with if_freq_offset_hz / 1540 chips per second).  GPSX_WOBS_AMBIGUOUS says that the chain's edge was fixed with the
+ * code phase within edge_guard samples of mid-block, where "nearest block start" is decided by the loop's noise: tx_ms may be
+ * exactly 1 ms off, in either direction.  That is 300 km in a pseudorange -- try +-1 ms and let the solver's residuals decide.
+ * It is reported, not resolved: resolving needs 1 ms prompts around the edge, which records of 20-block windows do not hold.
+ * The call must be made on every launch of a stream, as gpsx_wnav_words must: blocks_seen is the time base, and a wrap between
+ * two launches that were not both seen is a millisecond lost.
+ * Where a stream is cut into launches does not matter to the observables, nor to the states but for this: pass 2 sees the state
+ * as the launch left it.  A HOW that a break follows in its own launch anchors nothing, while with a cut between the two it
+ * anchors the chain that then ends (n_anchor counts it, tx_ms_at_edge keeps it, no flag does); and r is taken against the Z of the
+ * launch's end, which matters only to a channel that crosses the seam more than five times one way within one launch.
+ * Errors: NULL pointers, an edge_guard that is not finite or outside 0 .. 8184, reserved != 0, n_blocks outside 1 .. 4096,
+ * n_slots outside 1 .. n_blocks, n_ch < 1 and a size that overflows return GPSX_EINVAL (with a gpsx_last_error text) and write
+ * nothing.  A channel is BAD if its state has flag bits other than GPSX_WOBS_PHASE .. _AMBIGUOUS or reserved != 0, if blocks_seen,
+ * last_bit_end_p1, chain_first_p1 or last_win_end_p1 lies outside 0 .. 2^62, if |edge_block| > 2^62, if tx_ms_at_edge lies outside
+ * 0 .. 604 799 999, or if last_phase is not in [0, 16368) while PHASE is set: its state stays as it was, its observable is all
+ * zero with age_blocks = -1, and GPSX_EINVAL comes from gpsx_wobs after its wait / from the next gpsx_synchronize() after _dev.
+ * Vector ALU (k_wobs: one channel per lane, a record's four words loaded eight slots ahead of the recurrence).  On one stream:
+ * gpsx_track_loop_weighted_sync_dev, gpsx_wnav_words_dev, then gpsx_wobs_dev on their d_rec and d_words with the same n_blocks
+ * and n_slots. */
+#define GPSX_WOBS_PHASE      1u   /* a window record has been seen: code_phase_fine / if_freq_offset_hz are a record's */
+#define GPSX_WOBS_EDGE       2u   /* an unbroken chain of bits is running and its edge block is known */
+#define GPSX_WOBS_TOW        4u   /* a parity-checked HOW of this chain has anchored the time of week */
+#define GPSX_WOBS_CONFIRMED  8u   /* a second HOW agreed with the anchor */
+#define GPSX_WOBS_AMBIGUOUS 16u   /* the chain's edge was fixed with the code phase within edge_guard of mid-block: tx_ms may be 1 ms off */
+#define GPSX_WOBS_VALID     32u   /* output only: PHASE, EDGE and TOW all hold */
+
+typedef struct {
+  float    edge_guard;           /* samples, 0 .. 8184, finite: |code phase - 8184| below it marks a new chain AMBIGUOUS (0: never) */
+  int32_t  reserved;             /* 0 */
+} gpsx_wobs_cfg_t;
+
+typedef struct {                 /* 80 bytes, device resident; all zero = a fresh channel */
+  int64_t  blocks_seen;          /*  0  blocks of all earlier launches */
+  int64_t  last_bit_end_p1;      /*  8  absolute last block of the newest bit, + 1; 0: none */
+  int64_t  chain_first_p1;       /* 16  the same for the first bit of the running chain */
+  int64_t  edge_block;           /* 24  Z: the chain's bit edges are at absolute sample code_phase + 16368 (Z + 20 j) */
+  int64_t  tx_ms_at_edge;        /* 32  Tz: transmit time, ms of week 0 .. 604 799 999, at the edge of block Z */
+  int64_t  last_win_end_p1;      /* 40  absolute last block of the newest window record, + 1; 0: none */
+  float    last_phase, last_freq;/* 48  that record's code_phase_fine, if_freq_offset_hz */
+  uint32_t flags;                /* 56  GPSX_WOBS_PHASE .. _AMBIGUOUS */
+  uint32_t n_wraps;              /* 60  seam crossings followed while a chain ran */
+  uint32_t n_anchor, n_mismatch, n_break, reserved;   /* 64  HOWs that set Tz first; HOWs refused or contradicting; chains ended; 0 */
+} gpsx_wobs_state_t;
+
+typedef struct {                 /* 32 bytes, one per channel and launch */
+  int64_t  tx_ms;                /*  0  with VALID: (Tz + B - Z) mod 604 800 000, B = blocks_seen + n_blocks after this launch; else 0 */
+  float    code_phase_fine;      /*  8  transmit time at sample 0 of block B = tx_ms - code_phase_fine / 16368 ms (0 without PHASE) */
+  float    if_freq_offset_hz;    /* 12  the newest window record's (0 without PHASE) */
+  uint32_t flags;                /* 16  the state's flags | VALID */
+  int32_t  age_blocks;           /* 20  B - last_win_end_p1, kept within 0 .. 2^31 - 1; -1 without PHASE */
+  uint32_t n_wraps, reserved;    /* 24  the state's n_wraps; 0 */
+} gpsx_wobs_t;
+
+/* d_rec [n_slots][n_ch] and d_words [n_blocks / 600 + 2][n_ch]: what the two earlier stages wrote for these n_blocks blocks, on the
+ * device in both variants, as d_state [n_ch] is; d_obs / obs: [n_ch] */
+int gpsx_wobs_dev(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                  const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *d_obs);
+int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+              const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *obs /* host */);
+/* host only, no GPU: pseudoranges from the VALID observables of one launch.  The reference channel is the one with the latest
+ * transmit time (the nearest satellite), found through differences of tx_ms folded into -302 400 000 .. 302 399 999 ms minus
+ * the difference of the code phases / 16368, the first of equals; then for every VALID i
+ *   pr_m[i] = 299792458e-3 * ((double)(folded tx_ms_ref - tx_ms_i) + ((double)phase_i - (double)phase_ref) / 16368.0 + offset_ms)
+ * and pr_m[i] = 0 for the others.  *rx_tow_s = (tx_ms_ref - phase_ref / 16368 + offset_ms) / 1000, folded into 0 .. 604 800 s: the
+ * receiver time that offset_ms stands for (0 without a VALID observable).  offset_ms is the reference channel's travel time as the
+ * caller assumes it (the reference's own pseudorange step uses 68.802 ms: include/gpsx_compat.h); the solver's clock term takes
+ * the rest.  Returns the number of VALID observables, or GPSX_EINVAL for NULL, n < 1 or an offset_ms that is not finite. */
+int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, double *pr_m, double *rx_tow_s);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

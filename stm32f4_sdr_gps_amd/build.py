@@ -96,7 +96,11 @@ def check_no_scratch() -> dict:
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
         raise RuntimeError(f"expected k_wnav_words in build/k_wnav_words.o, found {sorted(wnav)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **wnav}
+    # ... and the observables behind both (k_wobs: two register sets of eight slots' four words, eight word records, the state)
+    wobs = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wobs.o")).items() if "k_wobs" in k}
+    if len(wobs) != 1:
+        raise RuntimeError(f"expected k_wobs in build/k_wobs.o, found {sorted(wobs)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **wnav, **wobs}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

@@ -124,6 +124,29 @@ def subframe_image(ten: np.ndarray) -> np.ndarray:
     return image
 
 
+# gpsx_wobs_cfg_t / gpsx_wobs_state_t / gpsx_wobs_t (every channel's transmit time at the launch's end, from the records and the words)
+WOBS_FLAG_PHASE, WOBS_FLAG_EDGE, WOBS_FLAG_TOW, WOBS_FLAG_CONFIRMED, WOBS_FLAG_AMBIGUOUS, WOBS_FLAG_VALID = 1, 2, 4, 8, 16, 32
+WOBS_CFG_DTYPE = np.dtype([("edge_guard", "<f4"), ("reserved", "<i4")])
+WOBS_STATE_DTYPE = np.dtype([("blocks_seen", "<i8"), ("last_bit_end_p1", "<i8"), ("chain_first_p1", "<i8"), ("edge_block", "<i8"),
+                             ("tx_ms_at_edge", "<i8"), ("last_win_end_p1", "<i8"), ("last_phase", "<f4"), ("last_freq", "<f4"), ("flags", "<u4"),
+                             ("n_wraps", "<u4"), ("n_anchor", "<u4"), ("n_mismatch", "<u4"), ("n_break", "<u4"), ("reserved", "<u4")])
+WOBS_DTYPE = np.dtype([("tx_ms", "<i8"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"), ("flags", "<u4"), ("age_blocks", "<i4"),
+                       ("n_wraps", "<u4"), ("reserved", "<u4")])
+assert WOBS_CFG_DTYPE.itemsize == 8 and WOBS_STATE_DTYPE.itemsize == 80 and WOBS_DTYPE.itemsize == 32
+
+
+def wobs_pseudoranges(obs: np.ndarray, offset_ms: float = 68.802):
+    """WOBS_DTYPE observables of one launch -> (pr_m float64 [n], 0 where an observable is not VALID; rx_tow_s; the number of VALID
+    ones), against the channel with the latest transmit time at offset_ms of travel time.  Host only."""
+    obs = np.ascontiguousarray(obs, WOBS_DTYPE).reshape(-1)
+    pr = np.zeros(len(obs), np.float64)
+    rx = C.c_double(0.0)
+    n = load_library().gpsx_wobs_pseudoranges(obs.ctypes.data, len(obs), float(offset_ms), pr.ctypes.data, C.byref(rx))
+    if n < 0:
+        raise GpsxError(f"gpsx_wobs_pseudoranges -> {n}: no observables, or an offset that is not finite")
+    return pr, rx.value, n
+
+
 TRK_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"),
                       ("if_freq_accum", "<u4")])
 JOB_DTYPE = np.dtype([("block", "<i4"), ("n_ms", "<i4"), ("prn", "<i4"), ("freq_hz", "<f4"), ("offset_bits", "<i4"),
@@ -224,6 +247,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wnav_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wnav_words_dev.argtypes = lib.gpsx_wnav_words.argtypes
     lib.gpsx_wnav_subframe_image.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gpsx_wobs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_wobs_dev.argtypes = lib.gpsx_wobs.argtypes
+    lib.gpsx_wobs_pseudoranges.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double)]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -622,6 +648,18 @@ class Engine:
         self._chk(self.lib.gpsx_wnav_words(self.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_state), n_ch,
                                            words.ctypes.data), "gpsx_wnav_words")
         return words
+
+    def wobs(self, d_rec: int, n_slots: int, n_blocks: int, d_words: int, d_state: int, n_ch: int, edge_guard: float = 512.0) -> np.ndarray:
+        """EXTENSION: every channel's transmit time at the first sample of the block that follows the launch, from the WSYNC_REC_DTYPE
+        [n_slots, n_ch] records at device address d_rec and the WNAV_WORD_DTYPE [n_blocks // 600 + 2, n_ch] words at d_words that the
+        two earlier stages wrote for n_blocks blocks, on the n_ch WOBS_STATE_DTYPE states at device address d_state (all zero: a fresh
+        channel).  -> WOBS_DTYPE [n_ch]"""
+        cfg = np.zeros(1, WOBS_CFG_DTYPE)
+        cfg["edge_guard"] = edge_guard
+        obs = np.zeros(n_ch, WOBS_DTYPE)
+        self._chk(self.lib.gpsx_wobs(self.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_words), C.c_void_p(d_state), n_ch,
+                                     obs.ctypes.data), "gpsx_wobs")
+        return obs
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1283,6 +1283,97 @@ int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38])
   return GPSX_OK;
 }
 
+/* ---- extension: weighted observables -- every channel's transmit time at the launch's end ---------------------------------------- */
+
+namespace {
+// every refusal of gpsx_wobs(_dev), before anything is written; *obs_bytes = the observables' size
+int wobs_check(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const void *d_rec, int n_slots, int n_blocks, const void *d_words, const void *st,
+               int n_ch, const void *obs, size_t *obs_bytes)
+{
+  if (!cfg || !d_rec || !d_words || !st || !obs)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (!(cfg->edge_guard >= 0.0f && cfg->edge_guard <= 8184.0f))   // (a NaN fails both)
+    return fail(ctx, GPSX_EINVAL, "edge_guard must be finite and 0..8184");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_blocks < 1 || n_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
+  if (n_slots < 1 || n_slots > n_blocks)
+    return fail(ctx, GPSX_EINVAL, "n_slots must be 1..n_blocks");
+  if (n_ch < 1)
+    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
+  size_t n = 0, bytes = 0;
+  if (__builtin_mul_overflow((size_t)n_slots, (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wsync_rec_t), &bytes) ||
+      __builtin_mul_overflow((size_t)(n_blocks / 600 + 2), (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wnav_word_t), &bytes) ||
+      __builtin_mul_overflow((size_t)n_ch, sizeof(gpsx_wobs_state_t), &bytes) || __builtin_mul_overflow((size_t)n_ch, sizeof(gpsx_wobs_t), obs_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  return GPSX_OK;
+}
+}  // namespace
+
+int gpsx_wobs_dev(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                  const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *d_obs)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t obs_bytes = 0;
+  if (int rc = wobs_check(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, d_obs, &obs_bytes)) return rc;
+  launch_wobs(ctx->stream, d_rec, n_slots, n_blocks, cfg->edge_guard, d_words, d_state, n_ch, d_obs,
+              ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
+  LAUNCHCHK(ctx, "k_wobs");
+  ctx->last_kernel = "k_wobs";
+  return GPSX_OK;
+}
+
+int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+              const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *obs)
+{
+  if (int rc = use_device(ctx)) return rc;
+  size_t obs_bytes = 0;
+  if (int rc = wobs_check(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, obs, &obs_bytes)) return rc;
+  if (int rc = arena_reset(ctx, arena_size(obs_bytes)))
+    return rc;
+  gpsx_wobs_t *d_obs = arena_take<gpsx_wobs_t>(ctx, (size_t)n_ch);
+  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel)
+  launch_wobs(ctx->stream, d_rec, n_slots, n_blocks, cfg->edge_guard, d_words, d_state, n_ch, d_obs, ctx->d_bad_prn);
+  LAUNCHCHK(ctx, "k_wobs");
+  ctx->last_kernel = "k_wobs";
+  HIPCHK(ctx, hipMemcpyAsync(obs, d_obs, obs_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (*ctx->h_bad_prn) {
+    *ctx->h_bad_prn = 0;
+    return fail(ctx, GPSX_EINVAL, "a channel's observable state is out of range (its state is untouched, its observable is zero)");
+  }
+  return GPSX_OK;
+}
+
+int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, double *pr_m, double *rx_tow_s)
+{
+  if (!obs || !pr_m || !rx_tow_s || n < 1 || !(offset_ms - offset_ms == 0.0))   // (not finite: the difference is a NaN)
+    return GPSX_EINVAL;
+  constexpr int64_t kWeek = 604800000, kHalf = kWeek / 2;
+  auto fold = [](int64_t d) { return ((d + kHalf) % kWeek + kWeek) % kWeek - kHalf; };   // into -302 400 000 .. 302 399 999
+  int ref = -1, count = 0;
+  for (int i = 0; i < n; i++) {
+    pr_m[i] = 0.0;
+    if (!(obs[i].flags & GPSX_WOBS_VALID))
+      continue;
+    count++;
+    // later than the reference so far: more whole milliseconds, or a smaller code phase
+    if (ref < 0 || (double)fold(obs[i].tx_ms - obs[ref].tx_ms) - ((double)obs[i].code_phase_fine - (double)obs[ref].code_phase_fine) / 16368.0 > 0.0)
+      ref = i;
+  }
+  *rx_tow_s = 0.0;
+  if (ref < 0)
+    return 0;
+  for (int i = 0; i < n; i++)
+    if (obs[i].flags & GPSX_WOBS_VALID)
+      pr_m[i] = 299792458e-3 * ((double)fold(obs[ref].tx_ms - obs[i].tx_ms) +
+                                ((double)obs[i].code_phase_fine - (double)obs[ref].code_phase_fine) / 16368.0 + offset_ms);
+  const double rx = ((double)obs[ref].tx_ms - (double)obs[ref].code_phase_fine / 16368.0 + offset_ms) / 1000.0;
+  *rx_tow_s = rx >= 604800.0 ? rx - 604800.0 : (rx < 0.0 ? rx + 604800.0 : rx);
+  return count;
+}
+
 /* ---- extension: weighted two-bit acquisition grid ------------------------------------------------------------------------ */
 
 namespace {

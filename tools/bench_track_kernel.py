@@ -31,7 +31,15 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       device-to-device hipMemcpyAsync of the same record array -- the bar: the kernel
                                                       takes no longer -- and (2) the gpsx_track_loop_weighted_sync_dev launch that
                                                       writes such records (n_coh_lock = 20, every channel LOCKED), the calls taking
-                                                      turns in one process"""
+                                                      turns in one process
+  bench_track_kernel.py --weighted-obs [channels ...]
+                                                      gpsx_wobs_dev (EXTENSION: every channel's transmit time at the launch's end, from
+                                                      the records and the words) on the same fabricated record arrays, with code
+                                                      phases in them (one channel in four drifts through the seam) and with the word
+                                                      records gpsx_wnav_words_dev made of each, beside (1) a device-to-device
+                                                      hipMemcpyAsync of the record array -- the bar: the kernel takes no longer -- and
+                                                      (2) gpsx_wnav_words_dev, which reads the same lines, the calls taking turns in one
+                                                      process"""
 import ctypes as C
 import json
 import os
@@ -345,8 +353,100 @@ def weighted_nav(counts, n_blocks=4000, span=20):
             eng.free(p)
 
 
+def weighted_obs(counts, n_blocks=4000, span=20):
+    from stm32f4_sdr_gps_amd import capi, synth
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    capi.load_library()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    eng = capi.Engine(0, stream=stream.value)      # (the copy below goes onto the stream the engine's events are recorded on)
+    n_slots = n_blocks // span
+    # weighted_nav's streams: 32 distinct channels on one parity-correct subframe repeated for ever, three record arrays used in turn
+    sub = np.array(synth.lnav_subframe(3, 4711, np.random.Generator(np.random.PCG64(5))), np.int64)
+    distinct = 32
+    bits = np.stack([np.tile(sub, 4)[(37 * j) % 300:(37 * j) % 300 + 600] ^ (j & 1) for j in range(distinct)], axis=1)      # [600][32]
+    # code phases: three channels in four stand still somewhere on the circle, the fourth drifts through the seam (0.004 samples per
+    # block: 5 kHz of Doppler) -- up, and back down where the three arrays start over, so that its edge block moves both ways
+    j = np.arange(distinct)
+    still = (511.0 * j + 100.0) % 16368.0
+    nav_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
+    nav_cfg["max_bad_words"] = 3
+    cfg = np.zeros(1, capi.WOBS_CFG_DTYPE)
+    cfg["edge_guard"] = 512.0
+    for n in counts:
+        idx = np.arange(n) % distinct
+        rec_bytes = n_slots * n * 48
+        word_slots = capi.wnav_word_slots(n_blocks)
+        d_recs, d_words = [], []
+        for leg in range(3):
+            small = np.zeros((n_slots, distinct), capi.WSYNC_REC_DTYPE)
+            ends = np.arange(n_slots) * span + span - 1
+            small["end_block"] = ends[:, None]
+            small["flags"] = capi.WSYNC_FLAG_WINDOW | capi.WSYNC_FLAG_LOCKED | capi.WSYNC_FLAG_BIT
+            small["bit_ip"] = (1 - 2 * bits[leg * n_slots:(leg + 1) * n_slots]) * 20000
+            drift = (16368.0 - 24.0 + 0.004 * (leg * n_blocks + ends)) % 16368.0
+            small["w"]["code_phase_fine"] = np.where(j[None, :] % 4 == 3, drift[:, None], still[None, :]).astype(np.float32)
+            small["w"]["if_freq_offset_hz"] = (-5000.0 + 300.0 * j)[None, :].astype(np.float32)
+            d = eng.malloc(rec_bytes)
+            eng.h2d(d, np.ascontiguousarray(small[:, idx]))
+            d_recs.append(d)
+            d_words.append(eng.malloc(word_slots * n * 16))
+        d_copy, d_words_timed = eng.malloc(rec_bytes), eng.malloc(word_slots * n * 16)
+        nav, obs_st = np.zeros(n, capi.WNAV_STATE_DTYPE), np.zeros(n, capi.WOBS_STATE_DTYPE)
+        d_nav, d_obs_st, d_obs = eng.malloc(nav.nbytes), eng.malloc(obs_st.nbytes), eng.malloc(n * 32)
+        eng.h2d(d_nav, nav)
+        eng.h2d(d_obs_st, obs_st)
+        turn = {"words": 0, "obs": 0}
+
+        def words(out=None):
+            leg = turn["words"] % 3
+            turn["words"] += 1
+            return eng.lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, C.c_void_p(d_recs[leg]), n_slots, n_blocks, C.c_void_p(d_nav), n,
+                                               C.c_void_p(d_words_timed if out is None else out[leg]))
+
+        def observables():
+            leg = turn["obs"] % 3
+            turn["obs"] += 1
+            return eng.lib.gpsx_wobs_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_recs[leg]), n_slots, n_blocks, C.c_void_p(d_words[leg]),
+                                         C.c_void_p(d_obs_st), n, C.c_void_p(d_obs))
+
+        for _ in range(6):      # 1200 bits: every channel has met TLM + HOW with 62 fresh bits by now ...
+            eng._chk(words(), "gpsx_wnav_words_dev")
+        for _ in range(3):      # ... and these are the words of each array from then on (the stream repeats after the three)
+            eng._chk(words(d_words), "gpsx_wnav_words_dev")
+        eng.synchronize()
+        calls = {"d2d_copy_of_d_rec": (n_blocks, lambda: hip.hipMemcpyAsync(d_copy, d_recs[0], rec_bytes, 3, stream)),
+                 "wobs": (n_blocks, observables),
+                 "wnav_words": (n_blocks, words)}
+        med = _timed_rows(eng, calls, {"channels": n, "slots": n_slots, "rec_bytes": rec_bytes})
+        obs = np.zeros(n, capi.WOBS_DTYPE)
+        eng.d2h(obs, d_obs)
+        eng.d2h(obs_st, d_obs_st)
+        print(json.dumps({"wobs_check": "observables after the timed launches", "channels": n, "launches": turn["obs"],
+                          "valid": int((obs["flags"] & capi.WOBS_FLAG_VALID != 0).sum()), "breaks": int(obs_st["n_break"].sum()),
+                          "wraps_min_of_the_drifting": int(obs_st["n_wraps"][idx % 4 == 3].min()), "wraps_of_the_others": int(obs_st["n_wraps"][idx % 4 != 3].sum()),
+                          "blocks_seen": int(obs_st["blocks_seen"].min())}), flush=True)
+        r = med["wobs"] / med["d2d_copy_of_d_rec"]
+        print(json.dumps({"ratio": "k_wobs over a device-to-device copy of d_rec", "channels": n, "value": round(r, 4), "bound": 1.0,
+                          "within_bound": bool(r <= 1.0), "read_GBps": round(rec_bytes / med["wobs"] / 1e3, 1),
+                          "copy_GBps_read_plus_write": round(2 * rec_bytes / med["d2d_copy_of_d_rec"] / 1e3, 1)}), flush=True)
+        print(json.dumps({"ratio": "k_wobs over k_wnav_words on the same records (no bar)", "channels": n,
+                          "value": round(med["wobs"] / med["wnav_words"], 4)}), flush=True)
+        for p in d_recs + d_words + [d_copy, d_words_timed, d_nav, d_obs_st, d_obs]:
+            eng.free(p)
+
+
 def main():
     global WINDOW_S
+    if "--weighted-obs" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-obs"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_obs([int(a) for a in args] or [65536, 212992])
     from stm32f4_sdr_gps_amd import capi, synth
     if "--weighted-nav" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-nav"]
