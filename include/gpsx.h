@@ -452,14 +452,18 @@ int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const
  *                  n_coh * 511 * step32 (the step of the window just processed)
  *   DLL            e2 = IE^2 + QE^2, l2 = IL^2 + QL^2 in int64; d = (e2 + l2 == 0) ? 0 : (float)(e2 - l2) / (float)(e2 + l2)
  *                  (int64 -> float rounds to nearest even); d > 0: tau is too large.  T = (float)n_coh * 0.001f;
- *                  code_phase_fine = code_phase_fine - (dll_c1 * (d - dll_err) + (dll_c2 * T) * d); one wrap into [0, 16368):
- *                  + 16368.0f if negative, - 16368.0f if >= 16368.0f; dll_err = d
+ *                  code_phase_fine = code_phase_fine - (dll_c1 * (d - dll_err) + (dll_c2 * T) * d); one wrap towards [0, 16368):
+ *                  + 16368.0f if negative, - 16368.0f if >= 16368.0f; dll_err = d.  The wrap's own sum can round to 16368.0f (a
+ *                  difference in about (-2^-11, 0)): that phase is used as tau = 0 by the next window, and gpsx_wobs treats a
+ *                  record that carries it as one without a phase
  *   Costas PLL     IP == 0: p = QP > 0 ? 0.25f : QP < 0 ? -0.25f : 0; else p = atanf((float)QP / (float)IP) * 0.15915494f
  *                  (cycles; atanf is glibc <= 2.40's fdlibm one, operation by operation); insensitive to data bits
  *   FLL            only if fll_c != 0 and n_updates > 0: cross = prev_ip * QP - prev_qp * IP, dot = prev_ip * IP + prev_qp * QP in
  *                  int64; fe = (dot == 0) ? 0 : atanf((float)cross / (float)dot) * 0.15915494f / T (Hz); otherwise fe = 0
  *   carrier        if_freq_offset_hz = if_freq_offset_hz - ((pll_c1 * (p - pll_err) + (pll_c2 * T) * p) + fll_c * fe)
  *   end of window  pll_err = p; prev_ip = IP; prev_qp = QP; n_updates++; then the record is written
+ * The int64 expressions above (e2, l2, cross, dot) are exact while the window sums, prev_ip and prev_qp have magnitudes <= 2^30;
+ * sums the call forms itself stay below 2^20, so only a caller's state (gpsx_wsync_state_t's win_iq, prev_ip, prev_qp) can exceed that.
  * The loop rests at if_freq_offset_hz ~ fd (1 + 1/1022): the NCO mixes 16 352 of a block's 16 368 samples, so the accumulator loses
  * 16 samples of phase per block (as in the grids) and the loop makes that up in frequency.
  * Errors: NULL pointers, weights / spacing / n_coh out of range, n_blocks outside 1 .. 4096 or not a multiple of n_coh, n_ch < 1 and

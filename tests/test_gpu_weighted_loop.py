@@ -5,13 +5,15 @@ counts that fill waves partly and fully and leave waves of a workgroup idle, eve
 (tests/weighted_loop_cases.py, asserted without a GPU in tests/test_track_loop_weighted_plan.py), n_coh 1 / 4 / 10 / 20, both
 weights, spacings 1 / 8 / 15, a non-default IF, a few hundred blocks; with gains 0 the window sums against
 gpsx_track_epl_weighted_dev on every channel (GPU against GPU); split launches against one; the device against the host variant;
-the exact handover from a coherent grid's record; bad channels and refusals, with canaries; and the pull-in scenario, truncated."""
+the exact handover from a coherent grid's record; bad channels and refusals, with canaries; the pull-in scenario, truncated; and
+the branches of the update that the state alone can force (tests/weighted_forced_cases.py wloop_table)."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+import weighted_forced_cases as W
 import weighted_loop_cases as S
 import weighted_loop_ref as L
 
@@ -356,3 +358,21 @@ def test_the_pull_in_scenario_truncated(eng, oracle):
         errors, n_bits = S.bit_errors(recs, bits, S.PULL_IN_MS // 20, n_ms)
         print("channel", ch, "bit errors", errors, "of", n_bits, "code phase", after["code_phase_fine"][ch], "carrier", after["if_freq_offset_hz"][ch])
         assert errors == 0 and n_bits == 20
+
+
+@pytest.mark.parametrize("n_ch", [257, 8195])
+def test_the_branches_the_state_alone_can_force(eng, oracle, n_ch):
+    """k_track_wloop's own copy of the update, two windows of one block (tests/weighted_forced_cases.py wloop_table; what the rows
+    meet is asserted in tests/test_weighted_forced_reference.py): prev is the restatement's first-window prompt rotated, so that
+    the FLL sees dot == 0 (a quarter turn either way, and prev = (0, 0) with n_updates > 0), cross == 0 with dot < 0, and cross / dot
+    well on either side of 7/16, 11/16, 19/16 and 39/16 in both signs; n_updates = 0xFFFFFFFF, whose second window skips the FLL;
+    and phases with a dll_err that carry the code phase across either end.  The rows are tiled over cpw 1 and cpw 2 with a period
+    coprime to the cpw; every channel's records and state are the restatement's.
+    IP == 0, e2 + l2 == 0 and the outer arctangent intervals (below 2^-29, from 2^25 on) cannot be forced here: this kernel's
+    state holds no open window, so its sums are whatever the samples give.  They are forced in k_track_wsync only, which carries
+    the same update (tests/test_gpu_weighted_forced.py)."""
+    cpw = S.tabled(n_ch)
+    names, st0, want, want_st, _ = W.wloop_table(oracle)
+    idx = W.tiled(n_ch, len(names), cpw)
+    rec, after = _gpu(eng, W.blocks(W.WLOOP_BLOCKS), st0[idx].copy(), W.wloop_cfg(), dev=True)
+    _same(rec, after, np.ascontiguousarray(want[:, idx]), want_st[idx].copy(), range(n_ch), (n_ch, [names[i] for i in idx[:len(names)]]))
