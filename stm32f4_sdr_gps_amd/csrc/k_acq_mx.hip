@@ -131,7 +131,11 @@ __device__ __forceinline__ void mx_load_block(MxShared &sh, const uint8_t *blk, 
   if (tid < 2)
     sh.ones[tid] = 0;
 }
-__device__ void mx_wipe_block(MxShared &sh, u32 step_word, int tid, int lane)
+// the wipe-off and the wrap word: all that the vectors of sample offset 0 (and a direct start's) read of a block
+// WRAP_IN_PLACE: the thread of word 511 makes the wrap word itself, from the stream's word 0 as it recomputes it (the NCO's
+// phase at word 0 is 0) -- no barrier and no second step for it; the caller's next barrier publishes everything
+template <bool WRAP_IN_PLACE = false>
+__device__ __forceinline__ void mx_wipe_stream(MxShared &sh, u32 step_word, int tid, int lane)
 {
   {
     const u32 *x32 = reinterpret_cast<const u32 *>(sh.x);
@@ -143,10 +147,14 @@ __device__ void mx_wipe_block(MxShared &sh, u32 step_word, int tid, int lane)
         vi = carrier_i(quad) ^ x32[w];
         vq = carrier_q(quad) ^ x32[w];
       }
-      sh.d[0][w] = vi;
-      sh.d[1][w] = vq;
       ones_i += __popc(vi);
       ones_q += __popc(vq);
+      if (WRAP_IN_PLACE && w == 511) {   // samples 16352..16367 are zero, then the stream wraps to sample 0
+        vi = (carrier_i(0u) ^ x32[0]) << 16;
+        vq = (carrier_q(0u) ^ x32[0]) << 16;
+      }
+      sh.d[0][w] = vi;
+      sh.d[1][w] = vq;
     }
     ones_i = wave_sum_to_lane63(ones_i);   // (DPP: no lane-address constants to keep in -- or spill from -- registers)
     ones_q = wave_sum_to_lane63(ones_q);
@@ -155,9 +163,28 @@ __device__ void mx_wipe_block(MxShared &sh, u32 step_word, int tid, int lane)
       atomicAdd(&sh.ones[1], ones_q);
     }
   }
-  __syncthreads();
-  if (tid < 2)
-    sh.d[tid][511] = sh.d[tid][0] << 16;   // samples 16352..16367 are zero, then the stream wraps to sample 0
+  if constexpr (!WRAP_IN_PLACE) {
+    __syncthreads();
+    if (tid < 2)
+      sh.d[tid][511] = sh.d[tid][0] << 16;   // samples 16352..16367 are zero, then the stream wraps to sample 0
+    // (the caller's next barrier publishes the wrap word)
+  }
+}
+// word w >= 32 of a circularly extended plane: the 32 bits from position 32 w mod 1023 of the 1023-bit period in words 0..31
+__device__ __forceinline__ u32 mx_plane_ext_word(const u32 *pl, int w)
+{
+  const int pos = 32 * w - (w >= 64 ? 2 * kChips : kChips);
+  const int lo = pos >> 5;
+  u32 v = __builtin_amdgcn_alignbit(lo < 31 ? pl[lo + 1] : 0u, pl[lo], (u32)(pos & 31));
+  if (pos + 32 > kChips) {   // the period ends inside the word: its first bits follow
+    const int k = kChips - pos;
+    v = (v & ((1u << k) - 1u)) | (pl[0] << k);
+  }
+  return v;
+}
+__device__ void mx_wipe_block(MxShared &sh, u32 step_word, int tid, int lane)
+{
+  mx_wipe_stream(sh, step_word, tid, lane);
   __syncthreads();
   // plane[iq][t0] bit i = D(16 (i mod 1023) + t0), i < 2112.  First period: word w of offset t0 takes bit t0 and bit 16 + t0
   // of the stream words 16 w .. 16 w + 15 (bit 1023 = D(16368 + t0) is the wrap-around copy in word 511: D(t0), as it has
@@ -179,17 +206,44 @@ __device__ void mx_wipe_block(MxShared &sh, u32 step_word, int tid, int lane)
   for (int m = tid; m < 2 * 16 * (kPlaneWordsMx - 32); m += kMxThreads) {
     const int w = 32 + m % (kPlaneWordsMx - 32);
     const int r = m / (kPlaneWordsMx - 32);
-    const u32 *pl = sh.plane[r >> 4][r & 15];
-    const int pos = 32 * w - (w >= 64 ? 2 * kChips : kChips);
-    const int lo = pos >> 5;
-    u32 v = __builtin_amdgcn_alignbit(lo < 31 ? pl[lo + 1] : 0u, pl[lo], (u32)(pos & 31));
-    if (pos + 32 > kChips) {   // the period ends inside the word: its first bits follow
-      const int k = kChips - pos;
-      v = (v & ((1u << k) - 1u)) | (pl[0] << k);
-    }
-    sh.plane[r >> 4][r & 15][w] = v;
+    sh.plane[r >> 4][r & 15][w] = mx_plane_ext_word(sh.plane[r >> 4][r & 15], w);
   }
   // (the caller's next barrier publishes the planes)
+}
+
+// Eight of the sixteen planes (sample offsets t0_lo .. t0_lo + 7, both streams) with their circular extension, by the four waves
+// of ONE role while the other role is inside an MFMA pass (the single-block form's start-up, mx_unit): wave v owns the four rows
+// (stream v >> 1, t0 = t0_lo + 4 (v & 1) + 0..3) WHOLE, so that an extension word depends only on words its own wave wrote -- a
+// wavefront-scope fence and a wait for the LDS order them, where mx_wipe_block needs a workgroup barrier that the other role,
+// inside its pass, would not arrive at.  Lane (t0 = lane & 3, w = lane >> 2 (+ 16)): the four lanes of a word read the same
+// sixteen stream words (LDS broadcast), the sixteen words of a wave in rotated order -- 16 w + (k + w) mod 16: sixteen banks per
+// parity of w -- where the plain order would put all sixteen on two banks.
+__device__ __forceinline__ void mx_planes_half(MxShared &sh, int t0_lo, int v, int lane)
+{
+  const int iq = v >> 1, t0_first = t0_lo + 4 * (v & 1);
+  const int t0 = t0_first + (lane & 3), rot = lane >> 2;
+#pragma unroll 1
+  for (int it = 0; it < 2; it++) {
+    const int w = rot + 16 * it;
+    const u32 *src = &sh.d[iq][16 * w];
+    u32 bits = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const int kk = (k + rot) & 15;
+      const u32 sk = src[kk];
+      bits |= ((sk >> t0) & 1u) << (2 * kk);
+      bits |= ((sk >> (16 + t0)) & 1u) << (2 * kk + 1);
+    }
+    sh.plane[iq][t0][w] = bits;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's words 0..31 of its four rows are in LDS
+#pragma unroll 1
+  for (int m = lane; m < 4 * (kPlaneWordsMx - 32); m += 64) {
+    const int r = m / (kPlaneWordsMx - 32), w = 32 + m % (kPlaneWordsMx - 32);
+    u32 *pl = sh.plane[iq][t0_first + r];
+    pl[w] = mx_plane_ext_word(pl, w);
+  }
 }
 
 // FP4 (E2M1) code of a small integer: 0, +-1, +-2, +-3, +-4 (and 6)
@@ -202,14 +256,14 @@ __device__ __forceinline__ u32 fp4_code(int v)
 // The vector builders' lookup tables (once per workgroup): what they replace is the bit -> nibble spreading, a dozen
 // vector instructions per dword of the vectors -- and the vectors are built once per sample offset next to the MFMA passes,
 // by waves that have better things to do.
-__device__ void mx_fill_tables(MxShared &sh, int tid)
+__device__ void mx_fill_tables(MxShared &sh, int tid, int nthreads = kMxThreads)
 {
-  for (int w = tid; w < 512; w += kMxThreads) {
+  for (int w = tid; w < 512; w += nthreads) {
     const u32 cur = (u32)w & 0xFFu, nxt = ((u32)w >> 1) & 0xFFu;
     const u32 plus = spread8(nxt & ~cur), minus = spread8(cur & ~nxt);   // e = +1 -> -2 (code C), e = -1 -> +2 (code 4)
     sh.t_lut[w] = (plus << 2) | (plus << 3) | (minus << 2);
   }
-  for (int x = tid; x < 256; x += kMxThreads)
+  for (int x = tid; x < 256; x += nthreads)
     sh.t_lut[512 + x] = (spread8((u32)x) << 1) | (spread8(~(u32)x & 0xFFu) * 0xAu);   // +1 -> code 2, -1 -> code A
 }
 
@@ -379,6 +433,35 @@ __device__ __forceinline__ void mx_vector_build_direct(MxShared &sh, int which, 
 #pragma unroll
   for (int c = 0; c < 8; c++)
     dst[c * kCopyDwords] = c ? __builtin_amdgcn_alignbit(w2[1], w2[0], 4u * (u32)c) : w2[0];
+}
+
+// The same vector with the wave's lanes sharing their work (the single-block form's start-up, where vector 0 is all that stands
+// between the wiped block and the first MFMA): thread (stream, j) builds dword j of copy 0 only (eight block sums) and takes
+// dword j + 1 from the lane above (DPP wave shift); the dword above the wave's last one -- 64, 128, 192 or 256 -- is built by the
+// wave together, lane l its entry l & 7, the eight nibbles ORed within every group of eight lanes.  Nine block sums per thread
+// instead of sixteen.  Waves must be whole: tid & 63 is the lane.
+__device__ __forceinline__ void mx_vector_build_direct_wave(MxShared &sh, int which, int t0s, u32 *e8_dst, int tid)
+{
+  const int iq = tid >> 8, j = tid & 255, l8 = tid & 7;
+  const u32 *dd = sh.d[iq];
+  auto code = [&](int entry) {
+    const int pos = 16 * wrap1023(entry) + t0s;
+    const u32 sum = pop16(__builtin_amdgcn_alignbit(dd[(pos >> 5) + 1], dd[pos >> 5], (u32)(pos & 31)));
+    return which == 0 ? (0xFEC0u >> (4u * (sum & 3u))) & 0xFu : (0xEDCA0u >> (4u * (sum >> 2))) & 0xFu;
+  };
+  u32 lo = 0;
+#pragma unroll
+  for (int e = 0; e < 8; e++)
+    lo |= code(8 * j + e) << (4 * e);
+  u32 above = code(8 * ((j | 63) + 1) + l8) << (4 * l8);
+  above |= dpp<0xB1>(above, above);    // quad_perm [1,0,3,2]
+  above |= dpp<0x4E>(above, above);    // quad_perm [2,3,0,1]
+  above |= dpp<0x141>(above, above);   // row_half_mirror: every lane holds the dword
+  const u32 hi = dpp<0x130>(above, lo);   // wave_shl:1 -- lane i reads lane i + 1's dword, lane 63 keeps `above`
+  u32 *dst = e8_dst + (iq * 8) * kCopyDwords + j;   // [stream][copy][dword]
+#pragma unroll
+  for (int c = 0; c < 8; c++)
+    dst[c * kCopyDwords] = c ? __builtin_amdgcn_alignbit(hi, lo, 4u * (u32)c) : lo;
 }
 
 // One anti-diagonal of a pass (fragment Q0 + 2 S): request the fragments of the next one, then the MFMAs of this one.
@@ -1278,6 +1361,9 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
   // 0..7 and 8..15, the second one started directly at offset 8 (as the byte-phase form does); their search results meet in
   // two global u32 planes (`energy` = packed keys, behind them the sums: atomicMax / atomicAdd) that k_acq_finalize converts
   constexpr bool SPLIT = MODE == kMxSplit;
+  // SINGLE: the headline form's start-up schedule -- the preamble builds only what pass 0 reads, the rest of it (planes, lookup
+  // tables, vector 1, the result slots' zeroes) is made by the role that has no pass of its own in half steps 0..2 (see the loop)
+  constexpr bool SINGLE = MODE == kMxSingle;
   typedef SumRecT<S16> SumRec;
   if constexpr (MODE == kMxWalk) {
     if (flags && flags[wg] == 0)   // (uniform: the 16-bit run of this cluster was exact)
@@ -1321,11 +1407,14 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
     const u32 *src_t = mx_t + (size_t)set * 1032;
     for (int i = tid; i < 1032; i += kMxThreads)
       sh.chip_t[i] = src_t[i];
-    mx_fill_tables(sh, tid);
+    if constexpr (!SINGLE)   // (SINGLE: role 1 fills them in half step 0)
+      mx_fill_tables(sh, tid);
     tables_set = set;
   }
-  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
-    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
+  if constexpr (!SINGLE) {   // (SINGLE: role 0 zeroes them in half step 1)
+    for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
+      reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
+  }
   const size_t block_bytes = prm.if_format == GPSX_IF_2BIT_SM ? GPSX_BYTES_PER_MS_2BIT : kBytes;
   const uint8_t *block0 = if_blocks + (size_t)(search * prm.search_stride_blocks + (STORE ? wg % prm.n_ms : 0)) * block_bytes;
   mx_load_block(sh, block0, prm.if_format, tid);
@@ -1361,14 +1450,21 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
       mx_load_block(sh, block0 + (size_t)ms * block_bytes, prm.if_format, tid_p);
       __syncthreads();
     }
-    mx_wipe_block(sh, step_word, tid_p, lane_p);
-    if (SPLIT && seg) {
+    if constexpr (SINGLE) {
+      // all that pass 0 reads: the chips (above), vector 0 -- in one phase, from the block sums themselves: the values of
+      // mx_vector_phase1 + phase2 (0) without the round trip through sh.base -- and pop(D) for the start values
+      mx_wipe_stream<true>(sh, step_word, tid_p, lane_p);
+      __syncthreads();
+      mx_vector_build_direct_wave(sh, 0, 0, &sh.e8[0][0][0][0], tid);
+    } else if (SPLIT && seg) {
+      mx_wipe_block(sh, step_word, tid_p, lane_p);
       // not the first run: the first two vectors from the block sums of sample offset t0s (the planes' barrier is the loop's first)
       mx_vector_build_direct(sh, 0, t0s, &sh.e8[0][0][0][0], tid);
       mx_vector_build_direct(sh, 1, t0s, &sh.e8[1][0][0][0], tid);
       for (int i = tid; i < 2 * 2 * 2 * 128; i += kMxThreads)
         (&sh.corr[0][0][0][0])[i] = 0;
     } else {
+      mx_wipe_block(sh, step_word, tid_p, lane_p);
       __syncthreads();
       // the first two vectors (from the popcounts of sample offset 0), by the two-phase builders
       mx_vector_phase1(sh, 0, 0, tid_p, kMxThreads);
@@ -1381,15 +1477,55 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
     }
 
     v16f acc[2][kMxTiles];
-    mx_init_acc(sh.ones, lane_p, q0_tile, acc, prm.win_start, prm.win_stop);
+    if (!SINGLE || role == 0)   // (SINGLE: role 1's start values wait until role 0 is inside pass 0)
+      mx_init_acc(sh.ones, lane_p, q0_tile, acc, prm.win_start, prm.win_stop);
     SumRec pre[MULTI ? 16 : 1];
 
     // Steps of two halves: role 0 runs pass p, then the epilogue of sample offset p - 1; role 1 the epilogue of sample
     // offset p - 2, then pass p -- one wave of a SIMD on the matrix pipe while the other has the vector ALU, with nothing
     // but their own pace between the halves: ONE barrier per step, where all eight waves build the vector of pass p + 1
     // into the buffer that both roles read during step p - 1.
+    //
+    // Passes 0 and 1 produce no sample offset, so in half steps 0..3 the roles take strict turns and each has slots with no work
+    // in the loop's schedule: role 1 in half steps 0 and 2, role 0 in 1.  SINGLE runs those four half steps as straight-line
+    // code and fills the slots with the part of the preamble that pass 0 does not read, next to a partner that issues MFMAs and
+    // LDS reads only (the other forms enter the loop at half step 0 with everything made before it):
+    //   piece, maker                                    first reader                                  published by the barrier of
+    //   role 1's start values:             role 1, 0    its pass 0                                    (its own)
+    //   vector 1 (e8[1]), t_lut:           role 1, 0    pass 1 (both roles); mx_vector_build(2)       half step 2
+    //   planes t0 0..7 + extension:        role 0, 1    mx_vector_build(2), behind that barrier       half step 2
+    //   zeroes of sh.part:                 role 0, 1    role 0's epilogue in half step 3, role 1's in 4   half step 2
+    //   planes t0 8..15 + extension:       role 1, 2    mx_vector_build(10), half step 18             half step 4
+    if constexpr (SINGLE) {
+      // (thread indices made opaque per piece, as tid_p above: a piece's per-thread addresses are computed where it runs, not
+      //  hoisted over the passes into registers that the passes do not have)
+      auto opaque = [](int v) {
+        asm volatile("" : "+v"(v));
+        return v;
+      };
+      __syncthreads();               // half step 0: vector 0, the chips and the block are in LDS
+      if (role) {                    // (threads 256..511; all of it is done before role 0, alone on the matrix pipe, ends its pass)
+        mx_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop);
+        mx_vector_build_direct_wave(sh, 1, 0, &sh.e8[1][0][0][0], opaque(tid) - 256);   // stream I
+        mx_vector_build_direct_wave(sh, 1, 0, &sh.e8[1][0][0][0], opaque(tid));         // stream Q
+        mx_fill_tables(sh, opaque(tid) & 255, 256);
+      }
+      mx_pass<true>(sh, 0, lane, q0_tile, acc, kScaleOne, a_corr, false);
+      if (!role) {                   // half step 1 of role 0 (threads 0..255), under role 1's pass
+        mx_planes_half(sh, 0, wave, opaque(lane));
+        for (int i = opaque(tid); i < 8 * 32 * 2 * 32 / 4; i += 256)
+          reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
+      }
+      __syncthreads();               // half step 2: everybody is done with vector 0; planes 0..7, t_lut, vector 1, sh.part are published
+      mx_vector_build(sh, 2, opaque(tid));
+      if (role)
+        mx_planes_half(sh, 8, wave & 3, opaque(lane));
+      mx_pass<true>(sh, 1, lane, q0_tile, acc, kScaleEight, a_corr, false);
+      if (!role)                     // half step 3 of role 0
+        mx_epilogue_single(sh, lane, kq, 0, acc);
+    }
 #pragma unroll 1
-    for (int hs = 0; hs <= 2 * n_pass; hs++) {
+    for (int hs = SINGLE ? 4 : 0; hs <= 2 * n_pass; hs++) {
       if ((hs & 1) == 0)
         __syncthreads();
       // The vector of the next step: built behind the barrier by everybody (single-block forms), or behind this step's epilogue
