@@ -11,7 +11,9 @@
 // offset to the next, IS M_t0.  Operands are MX-FP4 (E2M1: 0, +-1, 2, 3, 4 exact; block scale E8M0 2^0 or 2^2),
 // v_mfma_scale_f32_32x32x64_f8f6f4 accumulates in f32: every partial sum is an integer below 2^24, so the result is
 // exact whatever the order (tools/microbench/mfma_fp4_corr.hip checks layouts and exactness on the device).
-// M for the first offset takes two passes: S = (S & 3) + 4 (S >> 2), both parts FP4-exact, the second at a block scale.
+// M for the first offset takes two passes: S = (S & 3) + 4 (S >> 2), both parts FP4-exact, the second at a block scale -- or,
+// in the single-block form, ONE pass with the vector as E3M2 (six-bit codes, the same MFMA rate): 8 - S, every integer in -8..8
+// exact (gpsx_anchor_codes.hpp; tools/microbench/mfma_fp6_anchor.hip checks that operand's layout on the device).
 //
 // Data movement: B never exists.  The nibble vector (2048 entries: one period + its wrap-around) sits in LDS in eight
 // copies, copy c starting at nibble c, so that lane (n, h) of tile (Q, kappa) -- column q = 32 Q + n, chips
@@ -50,6 +52,7 @@
 #endif
 #include <cstdlib>
 
+#include "gpsx_anchor_codes.hpp"
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
 
@@ -75,7 +78,10 @@ constexpr u32 kScaleA = 0x72727272u;
 constexpr float kAccScale = 1.0f / 8192.0f;
 constexpr float kUnscaleSq = 67108864.0f;   // 2^26: scaled squares -> integers
 constexpr u32 kScaleEight = 0x82828282u; // E8M0 130 = 2^3
+constexpr u32 kScaleTwo = 0x80808080u;   // E8M0 128 = 2^1
 constexpr int kPasses = 17;            // 2 for the first offset + 15 recurrence steps
+constexpr int kPassesAnchor = 16;      // the single-block form: 1 (E3M2 anchor) + 15
+constexpr int kAnchorDwords = 392;     // one stream's anchor vector: 2048 six-bit codes = 384 dwords, + slack
 
 struct MxShared {
   uint16_t x[1024];                      // raw IF block (sign plane)
@@ -435,35 +441,6 @@ __device__ __forceinline__ void mx_vector_build_direct(MxShared &sh, int which, 
     dst[c * kCopyDwords] = c ? __builtin_amdgcn_alignbit(w2[1], w2[0], 4u * (u32)c) : w2[0];
 }
 
-// The same vector with the wave's lanes sharing their work (the single-block form's start-up, where vector 0 is all that stands
-// between the wiped block and the first MFMA): thread (stream, j) builds dword j of copy 0 only (eight block sums) and takes
-// dword j + 1 from the lane above (DPP wave shift); the dword above the wave's last one -- 64, 128, 192 or 256 -- is built by the
-// wave together, lane l its entry l & 7, the eight nibbles ORed within every group of eight lanes.  Nine block sums per thread
-// instead of sixteen.  Waves must be whole: tid & 63 is the lane.
-__device__ __forceinline__ void mx_vector_build_direct_wave(MxShared &sh, int which, int t0s, u32 *e8_dst, int tid)
-{
-  const int iq = tid >> 8, j = tid & 255, l8 = tid & 7;
-  const u32 *dd = sh.d[iq];
-  auto code = [&](int entry) {
-    const int pos = 16 * wrap1023(entry) + t0s;
-    const u32 sum = pop16(__builtin_amdgcn_alignbit(dd[(pos >> 5) + 1], dd[pos >> 5], (u32)(pos & 31)));
-    return which == 0 ? (0xFEC0u >> (4u * (sum & 3u))) & 0xFu : (0xEDCA0u >> (4u * (sum >> 2))) & 0xFu;
-  };
-  u32 lo = 0;
-#pragma unroll
-  for (int e = 0; e < 8; e++)
-    lo |= code(8 * j + e) << (4 * e);
-  u32 above = code(8 * ((j | 63) + 1) + l8) << (4 * l8);
-  above |= dpp<0xB1>(above, above);    // quad_perm [1,0,3,2]
-  above |= dpp<0x4E>(above, above);    // quad_perm [2,3,0,1]
-  above |= dpp<0x141>(above, above);   // row_half_mirror: every lane holds the dword
-  const u32 hi = dpp<0x130>(above, lo);   // wave_shl:1 -- lane i reads lane i + 1's dword, lane 63 keeps `above`
-  u32 *dst = e8_dst + (iq * 8) * kCopyDwords + j;   // [stream][copy][dword]
-#pragma unroll
-  for (int c = 0; c < 8; c++)
-    dst[c * kCopyDwords] = c ? __builtin_amdgcn_alignbit(hi, lo, 4u * (u32)c) : lo;
-}
-
 // One anti-diagonal of a pass (fragment Q0 + 2 S): request the fragments of the next one, then the MFMAs of this one.
 // The sched_group_barriers pin that order -- the DS reads first, (8 MFMAs = 260 cycles ahead of their use) -- which the
 // scheduler, short of registers, would otherwise turn into "requested one MFMA before the wait": the LDS is kept busy by
@@ -624,6 +601,101 @@ __device__ __forceinline__ void mx_pass(const MxShared &sh, int buf, int lane, i
   }
 }
 
+// ---- the single-block form's anchor: sample offset 0 in ONE pass ---------------------------------------------------------------
+// The vector holds 8 - S_0[k] as E3M2 codes (gpsx_anchor_codes.hpp) at block scale 2^1: against chips in {0, 1} the pass adds
+// 2 sum_c chip[c] (8 - S_0[q + c]) = 8192 - 2 M_0(q) (512 ones per code), so the start values are the two-pass form's less 8192.
+// ONE copy per stream, 2048 codes in 384 dwords: a lane's window starts at bit 6 (32 f + n), dword aligned only every 16 lanes,
+// and is cut out in registers (mx_anchor_pass).  Thread (stream, j): the codes of entries 8 j .. 8 j + 7, 48 bits; the two lanes
+// of a pair write the three dwords they fill.
+__device__ __forceinline__ void mx_anchor_build(MxShared &sh, u32 *dst, int tid)
+{
+  const int iq = tid >> 8, j = tid & 255;
+  const u32 *dd = sh.d[iq];
+  u64 bits = 0;
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const int pos = 16 * wrap1023(8 * j + e);
+    const u32 sum = pop16(__builtin_amdgcn_alignbit(dd[(pos >> 5) + 1], dd[pos >> 5], (u32)(pos & 31)));
+    bits |= (u64)gpsx_anchor_code((int)sum) << (6 * e);
+  }
+  const u32 lo = (u32)bits, hi = (u32)(bits >> 32);   // (hi: 16 bits)
+  const u32 lo_pair = dpp<0xB1>(lo, lo);              // quad_perm [1,0,3,2]: the other lane of the pair
+  u32 *d3 = dst + iq * kAnchorDwords + 3 * (j >> 1);
+  if (j & 1) {
+    d3[2] = (lo >> 16) | (hi << 16);
+  } else {
+    d3[0] = lo;
+    d3[1] = hi | (lo_pair << 16);
+  }
+}
+
+// Seven dwords from the window's dword, shifted down by 6 n mod 32: the lane's 32 codes in six dwords (v_alignbit_b32)
+struct AnchorRaw {
+  u32 d[7];
+};
+__device__ __forceinline__ AnchorRaw mx_anchor_raw(lds_cu32 *w, int dw)
+{
+  AnchorRaw r;
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+    r.d[i] = w[dw + i];
+  return r;
+}
+__device__ __forceinline__ v8i mx_anchor_frag(const AnchorRaw &r, u32 shift)
+{
+  v8i f = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+    f[i] = (int)__builtin_amdgcn_alignbit(r.d[i + 1], r.d[i], shift);
+  return f;
+}
+// One anti-diagonal, as mx_pass_step: the raw dwords of the next one are requested first, then this one's MFMAs go out, and the
+// shifts that make the next fragments run under them.
+template <int S, int NT>
+__device__ __forceinline__ void mx_anchor_step(lds_cu32 *wi, lds_cu32 *wq, const v4i *ca, v4i (&a)[16], v8i &fi, v8i &fq,
+                                               v16f (&acc)[2][NT], u32 shift)
+{
+  constexpr int kSteps = 16 + NT - 1;
+  constexpr bool more = S + 1 < kSteps;
+  AnchorRaw ri, rq;
+  if constexpr (more) {
+    ri = mx_anchor_raw(wi, 12 * (S + 1));                  // fragment Q0 + 2 (S + 1): six dwords per fragment
+    rq = mx_anchor_raw(wq, 12 * (S + 1));
+    if constexpr (S + 1 < 16)
+      a[S + 1] = ca[(S + 1) * 64];                         // chips_a[S + 1][h][n]
+  }
+  constexpr int j_lo = S - 15 > 0 ? S - 15 : 0, j_hi = S < NT - 1 ? S : NT - 1;
+#pragma unroll
+  for (int j = j_lo; j <= j_hi; j++) {
+    acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), fi, acc[0][j], 4, 3, 0, kScaleA, 0, kScaleTwo);
+    acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), fq, acc[1][j], 4, 3, 0, kScaleA, 0, kScaleTwo);
+  }
+  if constexpr (more) {
+    __builtin_amdgcn_sched_group_barrier(0x100, S + 1 < 16 ? 9 : 8, 0);      // DS reads
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * (j_hi - j_lo + 1), 0);   // MFMAs
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (more) {
+    fi = mx_anchor_frag(ri, shift);
+    fq = mx_anchor_frag(rq, shift);
+    __builtin_amdgcn_sched_barrier(0);
+    mx_anchor_step<S + 1, NT>(wi, wq, ca, a, fi, fq, acc, shift);
+  }
+}
+template <int NT>
+__device__ __forceinline__ void mx_anchor_pass(const MxShared &sh, const u32 *anchor, int lane, int q0_tile, v16f (&acc)[2][NT])
+{
+  const int n = lane & 31, h = lane >> 5;
+  const u32 shift = (u32)(6 * n) & 31u;
+  lds_cu32 *wi = lds_opaque(anchor + 6 * (q0_tile + h) + ((6 * n) >> 5));
+  lds_cu32 *wq = lds_opaque(anchor + kAnchorDwords + 6 * (q0_tile + h) + ((6 * n) >> 5));
+  const v4i *ca = &sh.chips_a[0][h][n];
+  v4i a[16];
+  v8i fi = mx_anchor_frag(mx_anchor_raw(wi, 0), shift), fq = mx_anchor_frag(mx_anchor_raw(wq, 0), shift);
+  a[0] = ca[0];
+  mx_anchor_step<0, NT>(wi, wq, ca, a, fi, fq, acc, shift);
+}
+
 // gps_correlation8's magnitude (PM/GPS/gps_misc.c:106-118) on the centred counts as the accumulators hold them (exact
 // integers / 8192 in f32): one-sided clip and square in one instruction, the f32 sum of the two, the correctly rounded root
 // (v_sqrt_f32 + the neighbour test, as mag8_fast), truncation.
@@ -711,12 +783,14 @@ constexpr float kOutside = -1048576.0f * kAccScale;   // start value (scaled) of
 
 // Start of a block: every accumulator = the part of  cnt - 8184  that does not depend on the code (even byte offsets)
 // (ones: pop(D) of the two streams -- sh.ones, or the other block's pair in the pipelined byte-phase form)
+// (pass_bias: what the first offset's passes add beyond -2 M -- 0, or kGpsxAnchorPassBias for the one-pass anchor)
 template <int NT>
 __device__ __forceinline__ void mx_init_acc(const u32 *ones, int lane, int q0_tile, v16f (&acc)[2][NT], int win_start,
-                                            int win_stop)
+                                            int win_stop, int pass_bias = 0)
 {
   const int n = lane & 31;
-  const float base_i = (float)((int)ones[0] + 8192 - kHalf) * kAccScale, base_q = (float)((int)ones[1] + 8192 - kHalf) * kAccScale;
+  const float base_i = (float)((int)ones[0] + 8192 - kHalf - pass_bias) * kAccScale,
+              base_q = (float)((int)ones[1] + 8192 - kHalf - pass_bias) * kAccScale;
 #pragma unroll
   for (int j = 0; j < NT; j++) {
     const int q = 32 * (q0_tile + 2 * j) + n;
@@ -1361,9 +1435,11 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
   // 0..7 and 8..15, the second one started directly at offset 8 (as the byte-phase form does); their search results meet in
   // two global u32 planes (`energy` = packed keys, behind them the sums: atomicMax / atomicAdd) that k_acq_finalize converts
   constexpr bool SPLIT = MODE == kMxSplit;
-  // SINGLE: the headline form's start-up schedule -- the preamble builds only what pass 0 reads, the rest of it (planes, lookup
-  // tables, vector 1, the result slots' zeroes) is made by the role that has no pass of its own in half steps 0..2 (see the loop)
+  // SINGLE: the headline form's start-up schedule -- sample offset 0 in ONE pass (the E3M2 anchor, mx_anchor_pass: kPassesAnchor
+  // passes, pass p >= 1 is the other forms' pass p + 1), and the preamble builds only what that pass reads and the first epilogue
+  // writes; the rest of it (planes, lookup tables) is made by the role that has no pass of its own in half step 0 (see the loop)
   constexpr bool SINGLE = MODE == kMxSingle;
+  constexpr int kShift = SINGLE ? 1 : 0;   // this form's pass p is pass p + kShift of the two-pass numbering (vectors, buffers, quirks)
   typedef SumRecT<S16> SumRec;
   if constexpr (MODE == kMxWalk) {
     if (flags && flags[wg] == 0)   // (uniform: the 16-bit run of this cluster was exact)
@@ -1411,10 +1487,9 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
       mx_fill_tables(sh, tid);
     tables_set = set;
   }
-  if constexpr (!SINGLE) {   // (SINGLE: role 0 zeroes them in half step 1)
-    for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
-      reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
-  }
+  // (SINGLE: role 0's first epilogue runs in half step 1 -- the zeroes are published by the barrier of half step 0, like the block)
+  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
+    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
   const size_t block_bytes = prm.if_format == GPSX_IF_2BIT_SM ? GPSX_BYTES_PER_MS_2BIT : kBytes;
   const uint8_t *block0 = if_blocks + (size_t)(search * prm.search_stride_blocks + (STORE ? wg % prm.n_ms : 0)) * block_bytes;
   mx_load_block(sh, block0, prm.if_format, tid);
@@ -1435,7 +1510,7 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
   const int n_ms = MULTI ? prm.n_ms : 1;
   // SPLIT: two direct passes at sample offset t0s, then 16 / n_seg - 1 steps of the walk (local pass lp >= 2 is pass t0s + lp)
   const int t0s = SPLIT ? seg * (16 / n_seg) : 0;
-  const int n_pass = SPLIT ? 16 / n_seg + 1 : kPasses;
+  const int n_pass = SPLIT ? 16 / n_seg + 1 : SINGLE ? kPassesAnchor : kPasses;
   const int pbase = t0s;
 #pragma unroll 1
   for (int ms = 0; ms < n_ms; ms++) {
@@ -1451,11 +1526,11 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
       __syncthreads();
     }
     if constexpr (SINGLE) {
-      // all that pass 0 reads: the chips (above), vector 0 -- in one phase, from the block sums themselves: the values of
-      // mx_vector_phase1 + phase2 (0) without the round trip through sh.base -- and pop(D) for the start values
+      // all that pass 0 reads: the chips (above), the anchor vector -- from the block sums themselves, in sh.e8[0], which the
+      // recurrence's vectors take over behind the barrier that ends the anchor passes -- and pop(D) for the start values
       mx_wipe_stream<true>(sh, step_word, tid_p, lane_p);
       __syncthreads();
-      mx_vector_build_direct_wave(sh, 0, 0, &sh.e8[0][0][0][0], tid);
+      mx_anchor_build(sh, &sh.e8[0][0][0][0], tid);
     } else if (SPLIT && seg) {
       mx_wipe_block(sh, step_word, tid_p, lane_p);
       // not the first run: the first two vectors from the block sums of sample offset t0s (the planes' barrier is the loop's first)
@@ -1478,7 +1553,7 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
 
     v16f acc[2][kMxTiles];
     if (!SINGLE || role == 0)   // (SINGLE: role 1's start values wait until role 0 is inside pass 0)
-      mx_init_acc(sh.ones, lane_p, q0_tile, acc, prm.win_start, prm.win_stop);
+      mx_init_acc(sh.ones, lane_p, q0_tile, acc, prm.win_start, prm.win_stop, SINGLE ? kGpsxAnchorPassBias : 0);
     SumRec pre[MULTI ? 16 : 1];
 
     // Steps of two halves: role 0 runs pass p, then the epilogue of sample offset p - 1; role 1 the epilogue of sample
@@ -1487,15 +1562,18 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
     // into the buffer that both roles read during step p - 1.
     //
     // Passes 0 and 1 produce no sample offset, so in half steps 0..3 the roles take strict turns and each has slots with no work
-    // in the loop's schedule: role 1 in half steps 0 and 2, role 0 in 1.  SINGLE runs those four half steps as straight-line
-    // code and fills the slots with the part of the preamble that pass 0 does not read, next to a partner that issues MFMAs and
-    // LDS reads only (the other forms enter the loop at half step 0 with everything made before it):
+    // in the loop's schedule.  SINGLE has ONE such pass, the anchor, and enters the loop at half step 2; half steps 0 and 1 are
+    // straight-line code, and role 1 fills its empty half step 0 with the part of the preamble that the anchor pass does not read,
+    // next to a partner that issues MFMAs, LDS reads and the fragments' shifts only:
     //   piece, maker                                    first reader                                  published by the barrier of
-    //   role 1's start values:             role 1, 0    its pass 0                                    (its own)
-    //   vector 1 (e8[1]), t_lut:           role 1, 0    pass 1 (both roles); mx_vector_build(2)       half step 2
-    //   planes t0 0..7 + extension:        role 0, 1    mx_vector_build(2), behind that barrier       half step 2
-    //   zeroes of sh.part:                 role 0, 1    role 0's epilogue in half step 3, role 1's in 4   half step 2
-    //   planes t0 8..15 + extension:       role 1, 2    mx_vector_build(10), half step 18             half step 4
+    //   anchor vector (in e8[0]), zeroes of sh.part,    the anchor passes; role 0's epilogue of       half step 0
+    //   block, pop(D), chips:              all, preamble   offset 0 in half step 1
+    //   role 1's start values:             role 1, 0    its anchor pass                               (its own)
+    //   planes t0 0..7 + extension, t_lut: role 1, 0    mx_vector_build(1), behind that barrier       half step 2
+    //   planes t0 8..15 + extension:       role 1, 0    mx_vector_build(9), half step 16              half step 2
+    //   vector 1 (e8[0], over the anchor): all, 2       pass 1, half steps 2 / 3                      the loop's first (half step 2)
+    // The barrier of half step 2 is taken twice: once to end the anchor passes and publish the planes, once -- the loop's own --
+    // behind the build of vector 1, where the loop goes on to build vector 2 next to pass 1 as in every later step.
     if constexpr (SINGLE) {
       // (thread indices made opaque per piece, as tid_p above: a piece's per-thread addresses are computed where it runs, not
       //  hoisted over the passes into registers that the passes do not have)
@@ -1503,29 +1581,21 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
         asm volatile("" : "+v"(v));
         return v;
       };
-      __syncthreads();               // half step 0: vector 0, the chips and the block are in LDS
+      __syncthreads();               // half step 0: the anchor vector, the chips, the block and the result slots' zeroes are in LDS
       if (role) {                    // (threads 256..511; all of it is done before role 0, alone on the matrix pipe, ends its pass)
-        mx_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop);
-        mx_vector_build_direct_wave(sh, 1, 0, &sh.e8[1][0][0][0], opaque(tid) - 256);   // stream I
-        mx_vector_build_direct_wave(sh, 1, 0, &sh.e8[1][0][0][0], opaque(tid));         // stream Q
+        mx_planes_half(sh, 0, wave & 3, opaque(lane));
         mx_fill_tables(sh, opaque(tid) & 255, 256);
-      }
-      mx_pass<true>(sh, 0, lane, q0_tile, acc, kScaleOne, a_corr, false);
-      if (!role) {                   // half step 1 of role 0 (threads 0..255), under role 1's pass
-        mx_planes_half(sh, 0, wave, opaque(lane));
-        for (int i = opaque(tid); i < 8 * 32 * 2 * 32 / 4; i += 256)
-          reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
-      }
-      __syncthreads();               // half step 2: everybody is done with vector 0; planes 0..7, t_lut, vector 1, sh.part are published
-      mx_vector_build(sh, 2, opaque(tid));
-      if (role)
         mx_planes_half(sh, 8, wave & 3, opaque(lane));
-      mx_pass<true>(sh, 1, lane, q0_tile, acc, kScaleEight, a_corr, false);
-      if (!role)                     // half step 3 of role 0
+        mx_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
+      }
+      mx_anchor_pass(sh, &sh.e8[0][0][0][0], lane, q0_tile, acc);
+      if (!role)                     // half step 1 of role 0, under role 1's pass
         mx_epilogue_single(sh, lane, kq, 0, acc);
+      __syncthreads();               // half step 2: everybody is done with the anchor vector; the planes and t_lut are published
+      mx_vector_build(sh, 1 + kShift, opaque(tid));
     }
 #pragma unroll 1
-    for (int hs = SINGLE ? 4 : 0; hs <= 2 * n_pass; hs++) {
+    for (int hs = SINGLE ? 2 : 0; hs <= 2 * n_pass; hs++) {
       if ((hs & 1) == 0)
         __syncthreads();
       // The vector of the next step: built behind the barrier by everybody (single-block forms), or behind this step's epilogue
@@ -1541,7 +1611,7 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
           int tid_v = tid;
           if constexpr (MULTI)
             asm volatile("" : "+v"(tid_v));   // (as above: the builder's addresses are not worth registers across the passes)
-          mx_vector_build(sh, pbase + p_vec, tid_v);
+          mx_vector_build(sh, pbase + p_vec + kShift, tid_v);
         }
       }
       int lane_s = lane;         // (walk forms: opaque per half step, see tid_p -- record addresses are recomputed, not spilled)
@@ -1549,7 +1619,7 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
         asm volatile("" : "+v"(lane_s));
       const int x = hs - role;   // role-local half step: even = MFMA pass x / 2, odd = epilogue after pass (x - 1) / 2
       const bool active = x >= 0 && x < 2 * n_pass;
-      const int p = x >> 1;
+      const int p = (x >> 1) + kShift;   // (in the two-pass numbering from here on)
       if (active && (x & 1) == 0) {
         if constexpr (MULTI) {
           if (p >= 1)
@@ -2130,7 +2200,6 @@ struct MxwShared {
   int wsum[2];                      // sum over the mixed samples of (2 d - 1) m, per stream
 };
 constexpr int kWPasses = 18;                 // 3 for the first offset + 15 recurrence steps
-constexpr u32 kScaleTwo = 0x80808080u;       // E8M0 128 = 2^1
 constexpr u32 kScaleFour = 0x81818181u;      // 2^2
 constexpr u32 kScaleSixteen = 0x83838383u;   // 2^4
 
