@@ -8,6 +8,9 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(PKG, "lib", "libgpsx.so")
 LAB_LIB = os.path.join(PKG, "lib", "libgpsx_lab.so")
+LLVM_BIN = "/opt/rocm/lib/llvm/bin"
+# the matrix-core grid's objects: the single-block / walk / store / split forms, the byte-phase form, the weighted kernels
+MX_OBJECTS = ("k_acq_mx.o", "k_acq_mx_byte.o", "k_acq_mxw.o")
 
 
 def build(verbose: bool = False, jobs: int = 4) -> str:
@@ -24,24 +27,31 @@ def build(verbose: bool = False, jobs: int = 4) -> str:
     return LIB
 
 
+def unbundle_gfx950(obj: str, img: str) -> None:
+    """Write the gfx950 code object inside the host object `obj` (its .hip_fatbin offload bundle) to `img`."""
+    raw = open(obj, "rb").read()
+    at = raw.find(b"__CLANG_OFFLOAD_BUNDLE__")
+    if at < 0:
+        raise RuntimeError(f"{obj}: no offload bundle inside")
+    fat = img + ".fatbin"
+    with open(fat, "wb") as f:
+        f.write(raw[at:])
+    subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                           f"--input={fat}", f"--output={img}"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    os.remove(fat)
+
+
 def kernel_resources(obj: str | None = None) -> dict:
-    """{kernel symbol: {"vgprs", "sgprs", "scratch_bytes", "lds_bytes"}} of the device code in build/k_acq_mx.o (or `obj`), read
-    from the code object's metadata notes (llvm-readelf --notes on the unbundled gfx950 image)."""
+    """{kernel symbol: {"vgprs", "sgprs", "scratch_bytes", "lds_bytes"}} of the device code in the object file `obj` (default:
+    build/k_acq_mx.o, the first of MX_OBJECTS), read from the code object's metadata notes (llvm-readelf --notes on the unbundled
+    gfx950 image)."""
     import re
     import tempfile
-    obj = obj or os.path.join(PKG, "build", "k_acq_mx.o")
-    llvm = "/opt/rocm/lib/llvm/bin"
+    obj = obj or os.path.join(PKG, "build", MX_OBJECTS[0])
     with tempfile.TemporaryDirectory() as tmp:
-        raw = open(obj, "rb").read()
-        at = raw.find(b"__CLANG_OFFLOAD_BUNDLE__")     # the .hip_fatbin section of the host object
-        if at < 0:
-            raise RuntimeError(f"{obj}: no offload bundle inside")
-        fat, img = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")
-        with open(fat, "wb") as f:
-            f.write(raw[at:])
-        subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={fat}", f"--output={img}"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        notes = subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", img], text=True)
+        img = os.path.join(tmp, "dev.co")
+        unbundle_gfx950(obj, img)
+        notes = subprocess.check_output([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", img], text=True)
     out = {}
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk)
@@ -56,14 +66,16 @@ def kernel_resources(obj: str | None = None) -> dict:
 def check_no_scratch() -> dict:
     """The matrix-core grid kernels live one register from the spill cliff (k_acq_mx<3>: 255 VGPRs): a build whose k_acq_mx
     instance spills to scratch memory is refused here, not discovered as a slow kernel on the GPU box."""
-    res = kernel_resources()
+    res = {}
+    for name in MX_OBJECTS:   # (no kernel is in two of them)
+        res.update(kernel_resources(os.path.join(PKG, "build", name)))
     mx = {k: v for k, v in res.items() if "k_acq_mx" in k}
     # ... the weighted grid's multi-block matrix-core kernel beside them (its own name: the counts above are k_acq_mx's)
     wmx = {k: v for k, v in res.items() if "k_acq_wmx" in k}
     if len(wmx) != 1:
-        raise RuntimeError(f"expected k_acq_wmx_ms in build/k_acq_mx.o, found {sorted(wmx)}")
+        raise RuntimeError(f"expected k_acq_wmx_ms in build/k_acq_mxw.o, found {sorted(wmx)}")
     if not mx:
-        raise RuntimeError("no k_acq_mx kernels found in build/k_acq_mx.o's code object metadata")
+        raise RuntimeError(f"no k_acq_mx kernels found in the code object metadata of {MX_OBJECTS}")
     # ... and the device tracking loops, whose occupancy (three waves per SIMD: 168 VGPRs) is asked for by __launch_bounds__
     loops = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop.o")).items() if "k_track_loop" in k}
     if len(loops) != 4:

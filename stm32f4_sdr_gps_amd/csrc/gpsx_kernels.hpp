@@ -65,7 +65,7 @@ void launch_acq(hipStream_t s, int group, long local_units, const AcqParams &prm
 // Polyphase variant (k_acq_poly.hip): AND + popcount recurrence across the 16 sample offsets.
 void launch_acq_poly(hipStream_t s, const AcqPlan &plan, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_cw8,
                      const uint32_t *d_chipbits, uint32_t *d_planes, uint32_t *d_energy);
-// Matrix-core variant (k_acq_mx.hip): one 512-thread workgroup per (search, Doppler, 32 PRN slots).  Tables: mx_a [sets][4096]
+// Matrix-core variant (k_acq_mx.hip, k_acq_mx_byte.hip): one 512-thread workgroup per (search, Doppler, 32 PRN slots).  Tables: mx_a [sets][4096]
 // A fragments, mx_t [sets][1032] transposed chip words (launch_build_mx_tables).
 void launch_build_mx_tables(hipStream_t s, const uint32_t *d_chipbits, int n_slots, uint32_t *d_mx_a, uint32_t *d_mx_t);
 void launch_acq_mx(hipStream_t s, const AcqPlan &plan, const AcqParams &prm, const uint8_t *d_if, const uint32_t *d_mx_a,
@@ -104,7 +104,7 @@ void launch_build_track_rep(hipStream_t s, const uint32_t *d_chipbits_all, int n
 int launch_acq_weighted(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_prn,
                         const uint8_t *d_chips_all, const uint8_t *d_prns, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp,
                         int use_magnitude, gpsx_peak_t *d_peaks);
-// the same grid on the matrix cores (k_acq_mx.hip: k_acq_mxw): d_mx_a = the chip tables of the sign-only grid (launch_build_mx_tables)
+// the same grid on the matrix cores (k_acq_mxw.hip: k_acq_mxw): d_mx_a = the chip tables of the sign-only grid (launch_build_mx_tables)
 void launch_acq_mxw(hipStream_t s, const uint8_t *d_if_blocks, int n_search, int stride_blocks, int n_prn, const uint32_t *d_mx_a,
                     int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp, int use_magnitude, gpsx_peak_t *d_peaks);
 // gpsx_acq_grid_weighted_ms (plan_acq_weighted): clusters [cluster_lo, + n_clusters) walk n_ms blocks each, d_scratch = n_clusters x

@@ -251,8 +251,9 @@ def test_loop_state_conversion_round_trips_and_touches_only_the_loops_fields(lib
 
 def test_product_and_lab_builds_and_no_register_spills(lib_path):
     """lib/libgpsx.so is the product: built without GPSX_LAB, it reads none of the $GPSX_ACQ_* / $GPSX_TRACK_WAVE_FROM knobs that
-    force a kernel form (the getenv block is not compiled into it) and cannot carry an A/B variant of the matrix-core kernel
-    (k_acq_mx.hip refuses MX_VARIANT_B without GPSX_LAB).  lib/libgpsx_lab.so is the same sources with the knobs.
+    force a kernel form (the getenv block is not compiled into it) and cannot carry an A/B variant of the matrix-core kernels
+    (gpsx_mx_parts.hpp, hence k_acq_mx.hip, k_acq_mx_byte.hip and k_acq_mxw.hip each, refuses MX_VARIANT_B without GPSX_LAB).
+    lib/libgpsx_lab.so is the same sources with the knobs.
     And no instance of the matrix-core grid kernel spills registers (k_acq_mx<3> sits at 255 VGPRs)."""
     import ctypes as C
     import os
@@ -276,11 +277,12 @@ def test_product_and_lab_builds_and_no_register_spills(lib_path):
     # the device tracking loops: no spills, and the two xorshift instantiations (the ones that run at scale) at three waves per SIMD
     assert len(loops) == 4 and all(v["scratch_bytes"] == 0 for v in loops.values())
     assert sorted(v["vgprs"] for v in loops.values())[:2] <= [168, 168]
-    # the A/B variant macro does not compile into a product object
-    src = os.path.join(os.path.dirname(os.path.dirname(lib_path)), "csrc", "k_acq_mx.hip")
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-DMX_VARIANT_B", src],
-                       capture_output=True, text=True)
-    assert r.returncode != 0 and "GPSX_LAB" in r.stderr
+    # the A/B variant macro does not compile into a product object: none of the matrix-core grid's three
+    for name in ("k_acq_mx.hip", "k_acq_mx_byte.hip", "k_acq_mxw.hip"):
+        src = os.path.join(os.path.dirname(os.path.dirname(lib_path)), "csrc", name)
+        r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-DMX_VARIANT_B", src],
+                           capture_output=True, text=True)
+        assert r.returncode != 0 and "GPSX_LAB" in r.stderr, name
 
 
 def test_abi_handshake_accepts_this_header_and_refuses_another_layout(lib_path):

@@ -88,7 +88,7 @@ def test_sad_formulation_codes_with_both_end_chips(oracle):
 
 
 def mx_byte_phase_counts(d_words, chips):
-    """The byte-phase grid (replica bit shift 0) as k_acq_mx<4> forms it on the matrix cores (csrc/k_acq_mx.hip, mx_byte_pipe):
+    """The byte-phase grid (replica bit shift 0) as k_acq_mx<4> forms it on the matrix cores (csrc/k_acq_mx_byte.hip, mx_byte_pipe):
     both sample offsets started directly from their block sums S_t0[k] = pop(D[16 k + t0, +16)), as ONE Toeplitz product each,
         even o = 2 q:      cnt - 8184 = pop(D) + 8 + sum_c chip[c] (-2 S_0[(q + c) mod 1023])
         odd  o = 2 q + 1:  cnt - 8184 = pop(D) + 8 - pop(W) + sum_c chip[c] (-2 E[q + c]) + [q > 0] (sgn S_8[q - 1] - 16 chip[1022])

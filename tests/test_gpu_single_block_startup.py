@@ -2,7 +2,7 @@
 planes, the lookup tables, vector 1 and the zeroes of the result slots are made in the first three half steps by the role that
 has no pass of its own there, each published by a barrier in front of its first reader.  A piece that its reader overtakes is a
 wrong triplet somewhere -- or a different one from run to run: everything here is compared bit for bit, against the CPU oracle
-computed live, and one launch is repeated into fresh buffers.  The split form (k_acq_mx<5>) shares mx_unit and keeps the old
+computed live, and one launch is repeated into fresh buffers.  The split form (k_acq_mx<5>, mx_unit) keeps the old
 start-up: one case checks that it still gives what it gave.
 """
 import ctypes as C
@@ -183,7 +183,7 @@ def test_two_prn_sets_and_a_window_inside_the_block_vs_live_oracle(eng_no_split)
 
 def test_split_tail_next_to_the_single_form_is_unchanged(eng, oracle):
     """16 captures = 336 clusters: 256 on k_acq_mx<0>, the 80 of the last round as 160 workgroups of the split form (k_acq_mx<5>,
-    which shares mx_unit and keeps the all-hands start-up) behind k_acq_finalize_from.  Captures 0 (single form), 12 (the seam
+    mx_unit, which keeps the all-hands start-up) behind k_acq_finalize_from.  Captures 0 (single form), 12 (the seam
     runs through its Doppler bins) and 15 (split form) against the oracle."""
     from stm32f4_sdr_gps_amd import synth
     blocks = synth.cold_start_block(16, seed=23, amp_scale=0.5)
