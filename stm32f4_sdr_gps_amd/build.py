@@ -100,7 +100,8 @@ def check_no_scratch() -> dict:
     wloop = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted.o")).items() if "k_track_wloop" in k}
     if len(wloop) != 1:
         raise RuntimeError(f"expected k_track_wloop in build/k_track_loop_weighted.o, found {sorted(wloop)}")
-    # ... and the loop with the bit synchroniser (k_track_wsync: the open window and the synchroniser's words on top of that)
+    # ... and the loop with the bit synchroniser (k_track_wsync: the open window and the synchroniser's words on top of that; the
+    #     update, state image and lane places of both loops are one header, gpsx_track_wloop_parts.hpp)
     wsync = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted_sync.o")).items() if "k_track_wsync" in k}
     if len(wsync) != 1:
         raise RuntimeError(f"expected k_track_wsync in build/k_track_loop_weighted_sync.o, found {sorted(wsync)}")

@@ -818,15 +818,6 @@ gpsx_ctx::TrackGraph *track_graph_prepare(gpsx_ctx *ctx, int n_ch_asked, size_t 
 
 }  // namespace
 
-// what the kernels of the step just waited for said about its PRNs
-static int track_prn_verdict(gpsx_ctx *ctx)
-{
-  if (*ctx->h_bad_prn == 0)
-    return GPSX_OK;
-  *ctx->h_bad_prn = 0;
-  return fail(ctx, GPSX_EINVAL, "prn must be 1..210 (the channel was correlated against the empty code)");
-}
-
 // The side streams and events of the chunked tracking step, created on first use.  Failure-atomic: everything is made into
 // locals and committed to the context only when all of it exists, so a half-built set is never seen by a later call.
 static int track_pipeline_init(gpsx_ctx *ctx)
@@ -1003,376 +994,7 @@ int gpsx_track_epl_batch(gpsx_ctx *ctx, const uint8_t *if_block, gpsx_trk_state_
   return track_prn_verdict(ctx);
 }
 
-/* ---- extension: E/P/L on weighted two-bit samples, K blocks per launch ----------------------------------------------------- */
-
-namespace {
-// every refusal of gpsx_track_epl_weighted(_dev), before anything is written; *iq_bytes = the records' size
-int track_weighted_check(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *blocks, int n_blocks, const void *st, int n_ch,
-                         const void *iq_out, size_t *iq_bytes)
-{
-  if (!cfg || !blocks || !st || !iq_out)
-    return fail(ctx, GPSX_EINVAL, "null argument");
-  if (cfg->weights != GPSX_WEIGHTS_SIGN_ONLY && cfg->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
-    return fail(ctx, GPSX_EINVAL, "unknown weights");
-  if (cfg->spacing < 1 || cfg->spacing > 15)
-    return fail(ctx, GPSX_EINVAL, "spacing must be 1..15 samples");
-  if (n_blocks < 1 || n_blocks > 4096)
-    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
-  if (n_ch < 1)
-    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
-  size_t recs = 0;
-  if (__builtin_mul_overflow((size_t)n_blocks, (size_t)n_ch, &recs) || __builtin_mul_overflow(recs, 6 * sizeof(int32_t), iq_bytes))
-    return fail(ctx, GPSX_EINVAL, "n_blocks x n_ch records overflow a size");
-  return GPSX_OK;
-}
-}  // namespace
-
-int gpsx_track_epl_weighted_dev(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
-                                gpsx_trk_state_t *d_st, int n_ch, int32_t *d_iq_out)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t iq_bytes = 0;
-  if (int rc = track_weighted_check(ctx, cfg, d_if_blocks_2bit, n_blocks, d_st, n_ch, d_iq_out, &iq_bytes)) return rc;
-  launch_track_epl_weighted(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), n_blocks, ctx->if_hz,
-                            cfg->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, cfg->spacing, d_st, n_ch, ctx->d_trk_rep, d_iq_out,
-                            ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize, as gpsx_track_epl_batch_dev)
-  LAUNCHCHK(ctx, "k_track_epl_weighted");
-  ctx->last_kernel = "k_track_epl_weighted";
-  return GPSX_OK;
-}
-
-int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
-                            gpsx_trk_state_t *st, int n_ch, int32_t *iq_out)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t iq_bytes = 0;
-  if (int rc = track_weighted_check(ctx, cfg, if_blocks_2bit, n_blocks, st, n_ch, iq_out, &iq_bytes)) return rc;
-  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, st_bytes = (size_t)n_ch * sizeof(gpsx_trk_state_t);
-  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(st_bytes) + arena_size(iq_bytes)))
-    return rc;
-  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
-  gpsx_trk_state_t *d_st = arena_take<gpsx_trk_state_t>(ctx, n_ch);
-  int32_t *d_iq = arena_take<int32_t>(ctx, iq_bytes / sizeof(int32_t));
-  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernels, as gpsx_track_epl_batch does)
-  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d_st, st, st_bytes, hipMemcpyHostToDevice, ctx->stream));
-  launch_track_epl_weighted(ctx->stream, d_if, n_blocks, ctx->if_hz, cfg->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, cfg->spacing, d_st,
-                            n_ch, ctx->d_trk_rep, d_iq, ctx->d_bad_prn);
-  LAUNCHCHK(ctx, "k_track_epl_weighted");
-  ctx->last_kernel = "k_track_epl_weighted";
-  HIPCHK(ctx, hipMemcpyAsync(st, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(iq_out, d_iq, iq_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return track_prn_verdict(ctx);
-}
-
-/* ---- extension: the closed DLL / PLL / FLL on weighted two-bit samples, K blocks per launch ---------------------------------- */
-
-namespace {
-// every refusal of gpsx_track_loop_weighted(_dev), before anything is written; *rec_bytes = the records' size
-int track_loop_weighted_check(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *blocks, int n_blocks, const void *st, int n_ch,
-                              const void *rec, size_t *rec_bytes)
-{
-  if (!cfg || !blocks || !st || !rec)
-    return fail(ctx, GPSX_EINVAL, "null argument");
-  if (cfg->weights != GPSX_WEIGHTS_SIGN_ONLY && cfg->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
-    return fail(ctx, GPSX_EINVAL, "unknown weights");
-  if (cfg->spacing < 1 || cfg->spacing > 15)
-    return fail(ctx, GPSX_EINVAL, "spacing must be 1..15 samples");
-  if (cfg->n_coh < 1 || cfg->n_coh > 20)
-    return fail(ctx, GPSX_EINVAL, "n_coh must be 1..20 blocks");
-  if (n_blocks < 1 || n_blocks > 4096)
-    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
-  if (n_blocks % cfg->n_coh != 0)
-    return fail(ctx, GPSX_EINVAL, "n_blocks must be a multiple of n_coh");
-  if (n_ch < 1)
-    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
-  for (float g : {cfg->dll_c1, cfg->dll_c2, cfg->pll_c1, cfg->pll_c2, cfg->fll_c})
-    if (!(__builtin_fabsf(g) <= 3.402823466e+38f))
-      return fail(ctx, GPSX_EINVAL, "a loop gain is not finite");
-  size_t recs = 0;
-  if (__builtin_mul_overflow((size_t)(n_blocks / cfg->n_coh), (size_t)n_ch, &recs) ||
-      __builtin_mul_overflow(recs, sizeof(gpsx_wloop_rec_t), rec_bytes))
-    return fail(ctx, GPSX_EINVAL, "windows x n_ch records overflow a size");
-  return GPSX_OK;
-}
-}  // namespace
-
-int gpsx_track_loop_weighted_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
-                                 gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t rec_bytes = 0;
-  if (int rc = track_loop_weighted_check(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, &rec_bytes)) return rc;
-  launch_track_loop_weighted(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), n_blocks, ctx->if_hz, *cfg, d_state, n_ch,
-                             ctx->d_trk_rep, d_rec, ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
-  LAUNCHCHK(ctx, "k_track_wloop");
-  ctx->last_kernel = "k_track_wloop";
-  return GPSX_OK;
-}
-
-int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
-                             gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t rec_bytes = 0;
-  if (int rc = track_loop_weighted_check(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, &rec_bytes)) return rc;
-  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT;
-  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(rec_bytes)))
-    return rc;
-  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
-  gpsx_wloop_rec_t *d_rec = arena_take<gpsx_wloop_rec_t>(ctx, rec_bytes / sizeof(gpsx_wloop_rec_t));
-  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel, as gpsx_track_loop does)
-  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
-  launch_track_loop_weighted(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, ctx->d_bad_prn);
-  LAUNCHCHK(ctx, "k_track_wloop");
-  ctx->last_kernel = "k_track_wloop";
-  HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return track_prn_verdict(ctx);
-}
-
-/* ---- extension: the weighted loop with a per-channel bit synchroniser and bit-aligned windows ------------------------------- */
-
-namespace {
-// every refusal of gpsx_track_loop_weighted_sync(_dev), before anything is written; *rec_bytes = the records' size
-int track_loop_weighted_sync_check(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *blocks, int n_blocks, const void *st, int n_ch,
-                                   const void *rec, size_t *rec_bytes)
-{
-  if (!cfg || !blocks || !st || !rec)
-    return fail(ctx, GPSX_EINVAL, "null argument");
-  if (cfg->weights != GPSX_WEIGHTS_SIGN_ONLY && cfg->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
-    return fail(ctx, GPSX_EINVAL, "unknown weights");
-  if (cfg->spacing < 1 || cfg->spacing > 15)
-    return fail(ctx, GPSX_EINVAL, "spacing must be 1..15 samples");
-  for (int n : {cfg->n_coh_search, cfg->n_coh_lock})
-    if (n < 1 || n > 20 || 20 % n != 0)
-      return fail(ctx, GPSX_EINVAL, "n_coh_search and n_coh_lock must be 1, 2, 4, 5, 10 or 20 blocks");
-  if (cfg->sync_bits < 1 || cfg->sync_bits > 200)
-    return fail(ctx, GPSX_EINVAL, "sync_bits must be 1..200");
-  if (cfg->sync_num < 1 || cfg->sync_num > 1024 || cfg->sync_den < 1 || cfg->sync_den > 1024)
-    return fail(ctx, GPSX_EINVAL, "sync_num and sync_den must be 1..1024");
-  if (cfg->sync_num < cfg->sync_den)
-    return fail(ctx, GPSX_EINVAL, "sync_num must not be below sync_den");
-  if (n_blocks < 1 || n_blocks > 4096)
-    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
-  if (n_ch < 1)
-    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
-  for (const gpsx_wsync_gains_t *g : {&cfg->search, &cfg->lock})
-    for (float v : {g->dll_c1, g->dll_c2, g->pll_c1, g->pll_c2, g->fll_c})
-      if (!(__builtin_fabsf(v) <= 3.402823466e+38f))
-        return fail(ctx, GPSX_EINVAL, "a loop gain is not finite");
-  const int span = cfg->n_coh_search < cfg->n_coh_lock ? cfg->n_coh_search : cfg->n_coh_lock;
-  size_t recs = 0;
-  if (__builtin_mul_overflow((size_t)((n_blocks + span - 1) / span), (size_t)n_ch, &recs) ||
-      __builtin_mul_overflow(recs, sizeof(gpsx_wsync_rec_t), rec_bytes))
-    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
-  return GPSX_OK;
-}
-}  // namespace
-
-int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
-                                      gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t rec_bytes = 0;
-  if (int rc = track_loop_weighted_sync_check(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, &rec_bytes)) return rc;
-  launch_track_loop_weighted_sync(ctx->stream, static_cast<const uint8_t *>(d_if_blocks_2bit), n_blocks, ctx->if_hz, *cfg, d_state, n_ch,
-                                  ctx->d_trk_rep, d_rec, ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
-  LAUNCHCHK(ctx, "k_track_wsync");
-  ctx->last_kernel = "k_track_wsync";
-  return GPSX_OK;
-}
-
-int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
-                                  gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t rec_bytes = 0;
-  if (int rc = track_loop_weighted_sync_check(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, &rec_bytes)) return rc;
-  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT;
-  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(rec_bytes)))
-    return rc;
-  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
-  gpsx_wsync_rec_t *d_rec = arena_take<gpsx_wsync_rec_t>(ctx, rec_bytes / sizeof(gpsx_wsync_rec_t));
-  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel, as gpsx_track_loop_weighted does)
-  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
-  launch_track_loop_weighted_sync(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, ctx->d_bad_prn);
-  LAUNCHCHK(ctx, "k_track_wsync");
-  ctx->last_kernel = "k_track_wsync";
-  HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return track_prn_verdict(ctx);
-}
-
-/* ---- extension: LNAV frame sync and parity-checked words from the sync loop's bit records ----------------------------------- */
-
-namespace {
-// every refusal of gpsx_wnav_words(_dev), before anything is written; *words_bytes = the word records' size
-int wnav_words_check(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const void *d_rec, int n_slots, int n_blocks, const void *st, int n_ch,
-                     const void *words, size_t *words_bytes)
-{
-  if (!cfg || !d_rec || !st || !words)
-    return fail(ctx, GPSX_EINVAL, "null argument");
-  if (cfg->max_bad_words < 1 || cfg->max_bad_words > 10)
-    return fail(ctx, GPSX_EINVAL, "max_bad_words must be 1..10");
-  if (cfg->reserved != 0)
-    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
-  if (n_blocks < 1 || n_blocks > 4096)
-    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
-  if (n_slots < 1 || n_slots > n_blocks)
-    return fail(ctx, GPSX_EINVAL, "n_slots must be 1..n_blocks");
-  if (n_ch < 1)
-    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
-  size_t n = 0, rec_bytes = 0;
-  if (__builtin_mul_overflow((size_t)n_slots, (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wsync_rec_t), &rec_bytes) ||
-      __builtin_mul_overflow((size_t)(n_blocks / 600 + 2), (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wnav_word_t), words_bytes))
-    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
-  return GPSX_OK;
-}
-}  // namespace
-
-int gpsx_wnav_words_dev(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
-                        gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *d_words)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t words_bytes = 0;
-  if (int rc = wnav_words_check(ctx, cfg, d_rec, n_slots, n_blocks, d_state, n_ch, d_words, &words_bytes)) return rc;
-  launch_wnav_words(ctx->stream, d_rec, n_slots, n_blocks, cfg->max_bad_words, d_state, n_ch, d_words,
-                    ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
-  LAUNCHCHK(ctx, "k_wnav_words");
-  ctx->last_kernel = "k_wnav_words";
-  return GPSX_OK;
-}
-
-int gpsx_wnav_words(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
-                    gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *words)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t words_bytes = 0;
-  if (int rc = wnav_words_check(ctx, cfg, d_rec, n_slots, n_blocks, d_state, n_ch, words, &words_bytes)) return rc;
-  if (int rc = arena_reset(ctx, arena_size(words_bytes)))
-    return rc;
-  gpsx_wnav_word_t *d_words = arena_take<gpsx_wnav_word_t>(ctx, words_bytes / sizeof(gpsx_wnav_word_t));
-  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel)
-  launch_wnav_words(ctx->stream, d_rec, n_slots, n_blocks, cfg->max_bad_words, d_state, n_ch, d_words, ctx->d_bad_prn);
-  LAUNCHCHK(ctx, "k_wnav_words");
-  ctx->last_kernel = "k_wnav_words";
-  HIPCHK(ctx, hipMemcpyAsync(words, d_words, words_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (*ctx->h_bad_prn) {
-    *ctx->h_bad_prn = 0;
-    return fail(ctx, GPSX_EINVAL, "a channel's frame state is out of range (its state is untouched, its slots are empty)");
-  }
-  return GPSX_OK;
-}
-
-int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38])
-{
-  if (!ten || !image)
-    return GPSX_EINVAL;
-  for (int w = 0; w < 10; w++)
-    if (ten[w].index != w + 1 || (ten[w].flags & (GPSX_WNAV_WORD | GPSX_WNAV_OK)) != (GPSX_WNAV_WORD | GPSX_WNAV_OK))
-      return GPSX_EINVAL;
-  std::memset(image, 0, 38);
-  for (int w = 0; w < 10; w++)
-    for (int i = 0; i < 30; i++) {
-      const int bit = 30 * w + i;
-      image[bit >> 3] |= (uint8_t)(((ten[w].word >> (29 - i)) & 1u) << (bit & 7));
-    }
-  return GPSX_OK;
-}
-
-/* ---- extension: weighted observables -- every channel's transmit time at the launch's end ---------------------------------------- */
-
-namespace {
-// every refusal of gpsx_wobs(_dev), before anything is written; *obs_bytes = the observables' size
-int wobs_check(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const void *d_rec, int n_slots, int n_blocks, const void *d_words, const void *st,
-               int n_ch, const void *obs, size_t *obs_bytes)
-{
-  if (!cfg || !d_rec || !d_words || !st || !obs)
-    return fail(ctx, GPSX_EINVAL, "null argument");
-  if (!(cfg->edge_guard >= 0.0f && cfg->edge_guard <= 8184.0f))   // (a NaN fails both)
-    return fail(ctx, GPSX_EINVAL, "edge_guard must be finite and 0..8184");
-  if (cfg->reserved != 0)
-    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
-  if (n_blocks < 1 || n_blocks > 4096)
-    return fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096");
-  if (n_slots < 1 || n_slots > n_blocks)
-    return fail(ctx, GPSX_EINVAL, "n_slots must be 1..n_blocks");
-  if (n_ch < 1)
-    return fail(ctx, GPSX_EINVAL, "n_ch must be at least 1");
-  size_t n = 0, bytes = 0;
-  if (__builtin_mul_overflow((size_t)n_slots, (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wsync_rec_t), &bytes) ||
-      __builtin_mul_overflow((size_t)(n_blocks / 600 + 2), (size_t)n_ch, &n) || __builtin_mul_overflow(n, sizeof(gpsx_wnav_word_t), &bytes) ||
-      __builtin_mul_overflow((size_t)n_ch, sizeof(gpsx_wobs_state_t), &bytes) || __builtin_mul_overflow((size_t)n_ch, sizeof(gpsx_wobs_t), obs_bytes))
-    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
-  return GPSX_OK;
-}
-}  // namespace
-
-int gpsx_wobs_dev(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
-                  const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *d_obs)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t obs_bytes = 0;
-  if (int rc = wobs_check(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, d_obs, &obs_bytes)) return rc;
-  launch_wobs(ctx->stream, d_rec, n_slots, n_blocks, cfg->edge_guard, d_words, d_state, n_ch, d_obs,
-              ctx->d_bad_prn + 1);   // (flag 1: reported by the next gpsx_synchronize)
-  LAUNCHCHK(ctx, "k_wobs");
-  ctx->last_kernel = "k_wobs";
-  return GPSX_OK;
-}
-
-int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
-              const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *obs)
-{
-  if (int rc = use_device(ctx)) return rc;
-  size_t obs_bytes = 0;
-  if (int rc = wobs_check(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, obs, &obs_bytes)) return rc;
-  if (int rc = arena_reset(ctx, arena_size(obs_bytes)))
-    return rc;
-  gpsx_wobs_t *d_obs = arena_take<gpsx_wobs_t>(ctx, (size_t)n_ch);
-  ctx->h_bad_prn[0] = 0;   // (flag 0: this entry point waits for its kernel)
-  launch_wobs(ctx->stream, d_rec, n_slots, n_blocks, cfg->edge_guard, d_words, d_state, n_ch, d_obs, ctx->d_bad_prn);
-  LAUNCHCHK(ctx, "k_wobs");
-  ctx->last_kernel = "k_wobs";
-  HIPCHK(ctx, hipMemcpyAsync(obs, d_obs, obs_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (*ctx->h_bad_prn) {
-    *ctx->h_bad_prn = 0;
-    return fail(ctx, GPSX_EINVAL, "a channel's observable state is out of range (its state is untouched, its observable is zero)");
-  }
-  return GPSX_OK;
-}
-
-int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, double *pr_m, double *rx_tow_s)
-{
-  if (!obs || !pr_m || !rx_tow_s || n < 1 || !(offset_ms - offset_ms == 0.0))   // (not finite: the difference is a NaN)
-    return GPSX_EINVAL;
-  constexpr int64_t kWeek = 604800000, kHalf = kWeek / 2;
-  auto fold = [](int64_t d) { return ((d + kHalf) % kWeek + kWeek) % kWeek - kHalf; };   // into -302 400 000 .. 302 399 999
-  int ref = -1, count = 0;
-  for (int i = 0; i < n; i++) {
-    pr_m[i] = 0.0;
-    if (!(obs[i].flags & GPSX_WOBS_VALID))
-      continue;
-    count++;
-    // later than the reference so far: more whole milliseconds, or a smaller code phase
-    if (ref < 0 || (double)fold(obs[i].tx_ms - obs[ref].tx_ms) - ((double)obs[i].code_phase_fine - (double)obs[ref].code_phase_fine) / 16368.0 > 0.0)
-      ref = i;
-  }
-  *rx_tow_s = 0.0;
-  if (ref < 0)
-    return 0;
-  for (int i = 0; i < n; i++)
-    if (obs[i].flags & GPSX_WOBS_VALID)
-      pr_m[i] = 299792458e-3 * ((double)fold(obs[ref].tx_ms - obs[i].tx_ms) +
-                                ((double)obs[i].code_phase_fine - (double)obs[ref].code_phase_fine) / 16368.0 + offset_ms);
-  const double rx = ((double)obs[ref].tx_ms - (double)obs[ref].code_phase_fine / 16368.0 + offset_ms) / 1000.0;
-  *rx_tow_s = rx >= 604800.0 ? rx - 604800.0 : (rx < 0.0 ? rx + 604800.0 : rx);
-  return count;
-}
+/* (the weighted two-bit tracking chain -- gpsx_track_epl_weighted .. gpsx_wobs -- is gpsx_api_wtrack.hip) */
 
 /* ---- extension: weighted two-bit acquisition grid ------------------------------------------------------------------------ */
 

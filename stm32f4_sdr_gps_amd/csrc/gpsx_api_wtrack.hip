@@ -1,0 +1,345 @@
+// gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync, gpsx_wnav_words, gpsx_wobs, each with its _dev twin, and the two host
+// helpers behind them.  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
+//
+// A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
+// waits for its kernel and reports a bad channel itself (flag 0).  Otherwise (_dev) they are device memory, the call returns after
+// the launch and the next gpsx_synchronize reports (flag 1).  The refusals come first; the first clause that fails decides the text.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <initializer_list>
+
+#include "gpsx_ctx.hpp"
+
+using namespace gpsx;
+using namespace gpsx_host;
+
+namespace {
+
+// ---- the clauses the refusals share, the overflow-checked count x n_ch x sizeof -------------------------------------------------------
+int check_weights_spacing(gpsx_ctx *ctx, int weights, int spacing)
+{
+  if (weights != GPSX_WEIGHTS_SIGN_ONLY && weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
+    return fail(ctx, GPSX_EINVAL, "unknown weights");
+  return spacing < 1 || spacing > 15 ? fail(ctx, GPSX_EINVAL, "spacing must be 1..15 samples") : GPSX_OK;
+}
+int check_n_blocks(gpsx_ctx *ctx, int n) { return n < 1 || n > 4096 ? fail(ctx, GPSX_EINVAL, "n_blocks must be 1..4096") : GPSX_OK; }
+int check_n_slots(gpsx_ctx *ctx, int n, int n_blocks) { return n < 1 || n > n_blocks ? fail(ctx, GPSX_EINVAL, "n_slots must be 1..n_blocks") : GPSX_OK; }
+int check_n_ch(gpsx_ctx *ctx, int n) { return n < 1 ? fail(ctx, GPSX_EINVAL, "n_ch must be at least 1") : GPSX_OK; }
+int check_gains(gpsx_ctx *ctx, std::initializer_list<float> gains)
+{
+  for (float g : gains)
+    if (!(__builtin_fabsf(g) <= 3.402823466e+38f))
+      return fail(ctx, GPSX_EINVAL, "a loop gain is not finite");
+  return GPSX_OK;
+}
+bool records_overflow(size_t count, int n_ch, size_t each, size_t *bytes)
+{
+  size_t recs = 0;   // (true: the product overflows a size)
+  return __builtin_mul_overflow(count, (size_t)n_ch, &recs) || __builtin_mul_overflow(recs, each, bytes);
+}
+
+// ---- the launch and what follows it -----------------------------------------------------------------------------------------------
+// `launch(flag)` starts the kernel with the flag it raises for a bad channel; `copy_back()` (host calls only) enqueues the copies of
+// the results.  `bad_state`: what a host call says when the flag was raised; nullptr: the tracking calls' PRN verdict.
+template <typename Launch, typename CopyBack>
+int launch_and_report(gpsx_ctx *ctx, bool host, const char *kernel, const char *bad_state, Launch launch, CopyBack copy_back)
+{
+  if (host)
+    ctx->h_bad_prn[0] = 0;   // (flag 0 is the waiting calls' own: each reads it before it returns, so nothing can be pending in it)
+  launch(ctx->d_bad_prn + (host ? 0 : 1));
+  LAUNCHCHK(ctx, kernel);
+  ctx->last_kernel = kernel;
+  if (!host)
+    return GPSX_OK;
+  if (int rc = copy_back()) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (!bad_state)
+    return track_prn_verdict(ctx);
+  if (*ctx->h_bad_prn == 0)
+    return GPSX_OK;
+  *ctx->h_bad_prn = 0;
+  return fail(ctx, GPSX_EINVAL, bad_state);
+}
+
+// ---- E/P/L on weighted two-bit samples, K blocks per launch -------------------------------------------------------------------------
+int track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *if_blocks_2bit, int n_blocks, gpsx_trk_state_t *st,
+                       int n_ch, int32_t *iq_out, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !if_blocks_2bit || !st || !iq_out)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (int rc = check_weights_spacing(ctx, cfg->weights, cfg->spacing)) return rc;
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  size_t iq_bytes = 0;
+  if (records_overflow((size_t)n_blocks, n_ch, 6 * sizeof(int32_t), &iq_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_blocks x n_ch records overflow a size");
+  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, st_bytes = (size_t)n_ch * sizeof(gpsx_trk_state_t);
+  const uint8_t *d_blocks = static_cast<const uint8_t *>(if_blocks_2bit);
+  gpsx_trk_state_t *d_st = st;
+  int32_t *d_iq = iq_out;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(st_bytes) + arena_size(iq_bytes))) return rc;
+    uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
+    d_st = arena_take<gpsx_trk_state_t>(ctx, n_ch);
+    d_iq = arena_take<int32_t>(ctx, iq_bytes / sizeof(int32_t));
+    HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_st, st, st_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_blocks = d_if;
+  }
+  return launch_and_report(
+      ctx, host, "k_track_epl_weighted", nullptr,
+      [&](uint32_t *flag) { launch_track_epl_weighted(ctx->stream, d_blocks, n_blocks, ctx->if_hz, cfg->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE,
+                                                      cfg->spacing, d_st, n_ch, ctx->d_trk_rep, d_iq, flag); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(st, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(iq_out, d_iq, iq_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
+// ---- the closed loops: DLL / PLL / FLL, K blocks per launch; the second with a bit synchroniser and bit-aligned windows -------------
+// what a host call of either stages: the capture into the arena, room for the records.  The state is device memory in both variants.
+template <typename Rec>
+int stage_loop_call(gpsx_ctx *ctx, const uint8_t *if_blocks_2bit, int n_blocks, size_t rec_bytes, const uint8_t **d_blocks, Rec **d_rec)
+{
+  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT;
+  if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(rec_bytes))) return rc;
+  uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
+  *d_rec = arena_take<Rec>(ctx, rec_bytes / sizeof(Rec));
+  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+  *d_blocks = d_if;
+  return GPSX_OK;
+}
+
+int track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *if_blocks_2bit, int n_blocks, gpsx_wloop_state_t *d_state,
+                        int n_ch, gpsx_wloop_rec_t *rec, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !if_blocks_2bit || !d_state || !rec)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (int rc = check_weights_spacing(ctx, cfg->weights, cfg->spacing)) return rc;
+  if (cfg->n_coh < 1 || cfg->n_coh > 20)
+    return fail(ctx, GPSX_EINVAL, "n_coh must be 1..20 blocks");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (n_blocks % cfg->n_coh != 0)
+    return fail(ctx, GPSX_EINVAL, "n_blocks must be a multiple of n_coh");
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  if (int rc = check_gains(ctx, {cfg->dll_c1, cfg->dll_c2, cfg->pll_c1, cfg->pll_c2, cfg->fll_c})) return rc;
+  size_t rec_bytes = 0;
+  if (records_overflow((size_t)(n_blocks / cfg->n_coh), n_ch, sizeof(gpsx_wloop_rec_t), &rec_bytes))
+    return fail(ctx, GPSX_EINVAL, "windows x n_ch records overflow a size");
+  const uint8_t *d_if = static_cast<const uint8_t *>(if_blocks_2bit);
+  gpsx_wloop_rec_t *d_rec = rec;
+  if (host)
+    if (int rc = stage_loop_call(ctx, d_if, n_blocks, rec_bytes, &d_if, &d_rec)) return rc;
+  return launch_and_report(
+      ctx, host, "k_track_wloop", nullptr,
+      [&](uint32_t *flag) { launch_track_loop_weighted(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag); },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
+int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *if_blocks_2bit, int n_blocks,
+                             gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !if_blocks_2bit || !d_state || !rec)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (int rc = check_weights_spacing(ctx, cfg->weights, cfg->spacing)) return rc;
+  for (int n : {cfg->n_coh_search, cfg->n_coh_lock})
+    if (n < 1 || n > 20 || 20 % n != 0)
+      return fail(ctx, GPSX_EINVAL, "n_coh_search and n_coh_lock must be 1, 2, 4, 5, 10 or 20 blocks");
+  if (cfg->sync_bits < 1 || cfg->sync_bits > 200)
+    return fail(ctx, GPSX_EINVAL, "sync_bits must be 1..200");
+  if (cfg->sync_num < 1 || cfg->sync_num > 1024 || cfg->sync_den < 1 || cfg->sync_den > 1024)
+    return fail(ctx, GPSX_EINVAL, "sync_num and sync_den must be 1..1024");
+  if (cfg->sync_num < cfg->sync_den)
+    return fail(ctx, GPSX_EINVAL, "sync_num must not be below sync_den");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  for (const gpsx_wsync_gains_t *g : {&cfg->search, &cfg->lock})
+    if (int rc = check_gains(ctx, {g->dll_c1, g->dll_c2, g->pll_c1, g->pll_c2, g->fll_c})) return rc;
+  const int span = cfg->n_coh_search < cfg->n_coh_lock ? cfg->n_coh_search : cfg->n_coh_lock;
+  size_t rec_bytes = 0;
+  if (records_overflow((size_t)((n_blocks + span - 1) / span), n_ch, sizeof(gpsx_wsync_rec_t), &rec_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  const uint8_t *d_if = static_cast<const uint8_t *>(if_blocks_2bit);
+  gpsx_wsync_rec_t *d_rec = rec;
+  if (host)
+    if (int rc = stage_loop_call(ctx, d_if, n_blocks, rec_bytes, &d_if, &d_rec)) return rc;
+  return launch_and_report(
+      ctx, host, "k_track_wsync", nullptr,
+      [&](uint32_t *flag) { launch_track_loop_weighted_sync(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag); },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
+// ---- LNAV frame sync and parity-checked words from the sync loop's bit records; the observables behind both -------------------------
+// (d_rec, d_words as input and the states are device memory in both variants; only the results are staged)
+int wnav_words(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+               gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *words, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !d_rec || !d_state || !words)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->max_bad_words < 1 || cfg->max_bad_words > 10)
+    return fail(ctx, GPSX_EINVAL, "max_bad_words must be 1..10");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (int rc = check_n_slots(ctx, n_slots, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  size_t rec_bytes = 0, words_bytes = 0;
+  if (records_overflow((size_t)n_slots, n_ch, sizeof(gpsx_wsync_rec_t), &rec_bytes) ||
+      records_overflow((size_t)(n_blocks / 600 + 2), n_ch, sizeof(gpsx_wnav_word_t), &words_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  gpsx_wnav_word_t *d_words = words;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(words_bytes))) return rc;
+    d_words = arena_take<gpsx_wnav_word_t>(ctx, words_bytes / sizeof(gpsx_wnav_word_t));
+  }
+  return launch_and_report(
+      ctx, host, "k_wnav_words", "a channel's frame state is out of range (its state is untouched, its slots are empty)",
+      [&](uint32_t *flag) { launch_wnav_words(ctx->stream, d_rec, n_slots, n_blocks, cfg->max_bad_words, d_state, n_ch, d_words, flag); },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(words, d_words, words_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
+int wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks, const gpsx_wnav_word_t *d_words,
+         gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *obs, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !d_rec || !d_words || !d_state || !obs)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (!(cfg->edge_guard >= 0.0f && cfg->edge_guard <= 8184.0f))   // (a NaN fails both)
+    return fail(ctx, GPSX_EINVAL, "edge_guard must be finite and 0..8184");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (int rc = check_n_slots(ctx, n_slots, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  size_t bytes = 0, obs_bytes = 0;
+  if (records_overflow((size_t)n_slots, n_ch, sizeof(gpsx_wsync_rec_t), &bytes) ||
+      records_overflow((size_t)(n_blocks / 600 + 2), n_ch, sizeof(gpsx_wnav_word_t), &bytes) ||
+      records_overflow(1, n_ch, sizeof(gpsx_wobs_state_t), &bytes) || records_overflow(1, n_ch, sizeof(gpsx_wobs_t), &obs_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  gpsx_wobs_t *d_obs = obs;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(obs_bytes))) return rc;
+    d_obs = arena_take<gpsx_wobs_t>(ctx, (size_t)n_ch);
+  }
+  return launch_and_report(
+      ctx, host, "k_wobs", "a channel's observable state is out of range (its state is untouched, its observable is zero)",
+      [&](uint32_t *flag) { launch_wobs(ctx->stream, d_rec, n_slots, n_blocks, cfg->edge_guard, d_words, d_state, n_ch, d_obs, flag); },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(obs, d_obs, obs_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpsx_track_epl_weighted_dev(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                gpsx_trk_state_t *d_st, int n_ch, int32_t *d_iq_out)
+{
+  return track_epl_weighted(ctx, cfg, d_if_blocks_2bit, n_blocks, d_st, n_ch, d_iq_out, false);
+}
+
+int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                            gpsx_trk_state_t *st, int n_ch, int32_t *iq_out)
+{
+  return track_epl_weighted(ctx, cfg, if_blocks_2bit, n_blocks, st, n_ch, iq_out, true);
+}
+
+int gpsx_track_loop_weighted_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                 gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec)
+{
+  return track_loop_weighted(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
+}
+
+int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                             gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec)
+{
+  return track_loop_weighted(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
+}
+
+int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
+                                      gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec)
+{
+  return track_loop_weighted_sync(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
+}
+
+int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
+                                  gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec)
+{
+  return track_loop_weighted_sync(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
+}
+
+int gpsx_wnav_words_dev(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                        gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *d_words)
+{
+  return wnav_words(ctx, cfg, d_rec, n_slots, n_blocks, d_state, n_ch, d_words, false);
+}
+
+int gpsx_wnav_words(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                    gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *words)
+{
+  return wnav_words(ctx, cfg, d_rec, n_slots, n_blocks, d_state, n_ch, words, true);
+}
+
+int gpsx_wobs_dev(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                  const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *d_obs)
+{
+  return wobs(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, d_obs, false);
+}
+
+int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+              const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *obs)
+{
+  return wobs(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, obs, true);
+}
+
+int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38])
+{
+  if (!ten || !image)
+    return GPSX_EINVAL;
+  for (int w = 0; w < 10; w++)
+    if (ten[w].index != w + 1 || (ten[w].flags & (GPSX_WNAV_WORD | GPSX_WNAV_OK)) != (GPSX_WNAV_WORD | GPSX_WNAV_OK))
+      return GPSX_EINVAL;
+  std::memset(image, 0, 38);
+  for (int w = 0; w < 10; w++)
+    for (int i = 0; i < 30; i++) {
+      const int bit = 30 * w + i;
+      image[bit >> 3] |= (uint8_t)(((ten[w].word >> (29 - i)) & 1u) << (bit & 7));
+    }
+  return GPSX_OK;
+}
+
+int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, double *pr_m, double *rx_tow_s)
+{
+  if (!obs || !pr_m || !rx_tow_s || n < 1 || !(offset_ms - offset_ms == 0.0))   // (not finite: the difference is a NaN)
+    return GPSX_EINVAL;
+  constexpr int64_t kWeek = 604800000, kHalf = kWeek / 2;
+  auto fold = [](int64_t d) { return ((d + kHalf) % kWeek + kWeek) % kWeek - kHalf; };   // into -302 400 000 .. 302 399 999
+  int ref = -1, count = 0;
+  for (int i = 0; i < n; i++) {
+    pr_m[i] = 0.0;
+    if (!(obs[i].flags & GPSX_WOBS_VALID))
+      continue;
+    count++;
+    // later than the reference so far: more whole milliseconds, or a smaller code phase
+    if (ref < 0 || (double)fold(obs[i].tx_ms - obs[ref].tx_ms) - ((double)obs[i].code_phase_fine - (double)obs[ref].code_phase_fine) / 16368.0 > 0.0)
+      ref = i;
+  }
+  *rx_tow_s = 0.0;
+  if (ref < 0)
+    return 0;
+  for (int i = 0; i < n; i++)
+    if (obs[i].flags & GPSX_WOBS_VALID)
+      pr_m[i] = 299792458e-3 * ((double)fold(obs[ref].tx_ms - obs[i].tx_ms) +
+                                ((double)obs[i].code_phase_fine - (double)obs[ref].code_phase_fine) / 16368.0 + offset_ms);
+  const double rx = ((double)obs[ref].tx_ms - (double)obs[ref].code_phase_fine / 16368.0 + offset_ms) / 1000.0;
+  *rx_tow_s = rx >= 604800.0 ? rx - 604800.0 : (rx < 0.0 ? rx + 604800.0 : rx);
+  return count;
+}
+
+}  // extern "C"

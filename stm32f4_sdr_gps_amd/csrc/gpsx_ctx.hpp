@@ -1,5 +1,5 @@
-// gpsx_ctx.hpp -- internals shared by the host-side translation units of libgpsx.so (gpsx_api.hip, gpsx_capture.hip,
-// gpsx_group.hip): the context record, the capture ring record, error plumbing, the scratch arena.
+// gpsx_ctx.hpp -- internals shared by the host-side translation units of libgpsx.so (gpsx_api.hip, gpsx_api_wtrack.hip,
+// gpsx_capture.hip, gpsx_group.hip): the context record, the capture ring record, error plumbing, the scratch arena.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -161,6 +161,15 @@ inline int use_device(gpsx_ctx *ctx)
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return GPSX_OK;
+}
+
+// what the kernels of the tracking step just waited for said about its PRNs (flag 0)
+inline int track_prn_verdict(gpsx_ctx *ctx)
+{
+  if (*ctx->h_bad_prn == 0)
+    return GPSX_OK;
+  *ctx->h_bad_prn = 0;
+  return fail(ctx, GPSX_EINVAL, "prn must be 1..210 (the channel was correlated against the empty code)");
 }
 
 // A host pointer that lies in a committed, unmodified part of one of the context's capture rings has an HBM mirror:

@@ -1,12 +1,13 @@
-// gpsx_track_loop_weighted_plan.hpp -- the launch shape of k_track_wloop (k_track_loop_weighted.hip): how many channels a wave
-// serves one after the other and how many workgroups that takes.  The blocks run one after the other inside the kernel (the loop
+// gpsx_track_loop_weighted_plan.hpp -- the launch shape of k_track_wloop (k_track_loop_weighted.hip) and of k_track_wsync
+// (k_track_loop_weighted_sync.hip), which takes the same plan: how many channels a wave serves one after the other and how many
+// workgroups that takes.  The blocks run one after the other inside the kernel (the loop
 // is a recurrence in time), so there is no block dimension to spread over: the shape depends on n_ch alone.  Pure host C++ (no
 // HIP): tests/test_track_loop_weighted_plan.py compiles it with g++ and checks the shapes the GPU tests run.
 #pragma once
 
 namespace gpsx {
 
-constexpr int kTrackLoopWeightedMaxCpw = 16;   // lanes 4 c + k carry channel c's values: sixteen channels fill a wave
+constexpr int kTrackLoopWeightedMaxCpw = 16;   // both kernels: lanes 4 c + k carry channel c's values, sixteen channels fill a wave
 
 struct TrackLoopWeightedPlan {
   int cpw;           // channels per wave, 1 .. 16; wave w of workgroup g serves channels (4 g + w) cpw .. + cpw - 1 below n_ch

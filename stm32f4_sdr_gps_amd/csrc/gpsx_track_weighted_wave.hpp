@@ -1,6 +1,7 @@
 // gpsx_track_weighted_wave.hpp -- the weighted two-bit E/P/L correlators of one block for the channels of a wave, as device
-// functions shared by k_track_epl_weighted (open loop: a (block, channel group) grid, k_track_weighted.hip) and k_track_wloop (the
-// closed loop: the blocks one after the other inside the kernel, k_track_loop_weighted.hip).  The formulation -- two planes,
+// functions shared by k_track_epl_weighted (open loop: a (block, channel group) grid, k_track_weighted.hip) and the closed loops
+// k_track_wloop and k_track_wsync (the blocks one after the other inside the kernel, k_track_loop_weighted.hip and
+// k_track_loop_weighted_sync.hip; what those two share beyond the correlators is gpsx_track_wloop_parts.hpp).  The formulation -- two planes,
 // pop(y) + 2 pop(y & m), the circular table with Late at the window's first bit, stream word 511 staged as zero and taken back,
 // pop(m) per block -- is described in front of k_track_epl_weighted.
 #pragma once

@@ -4,7 +4,8 @@
 //
 // k_track_wloop's shape (k_track_loop_weighted.hip): lane 4 c + k of a wave holds channel c of the wave, the blocks run one after
 // the other, the workgroup stages block b's planes into LDS buffer b & 1 and meets at ONE barrier per block that every wave
-// reaches; the correlators are gpsx_track_weighted_wave.hpp's, the same integers.  What differs:
+// reaches; the correlators are gpsx_track_weighted_wave.hpp's, the same integers; the loop update, the lanes' places, the state load
+// and a window's start are gpsx_track_wloop_parts.hpp's, the same code.  What differs:
 //  * the open window (six sums, its length) and the synchroniser's words come from the state and go back to it, so a launch may
 //    be cut anywhere;
 //  * a window's end is a per-lane condition (the mode's n_coh reached, or a locked channel's bit edge).  The update code is skipped
@@ -20,22 +21,13 @@
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
-#include "gpsx_libm.hpp"
 #include "gpsx_track_loop_weighted_plan.hpp"
 #include "gpsx_track_weighted_wave.hpp"
+#include "gpsx_track_wloop_parts.hpp"
 
 namespace gpsx {
 
 namespace {
-
-template <int K>
-__device__ __forceinline__ int quad_get(int v)   // lane k of this lane's quad
-{
-  return __builtin_amdgcn_update_dpp(0, v, K | (K << 2) | (K << 4) | (K << 6), 0xF, 0xF, true);
-}
-
-constexpr float kCyclesPerRadian = 0.15915494f;
-constexpr float kSpan = 16368.0f;
 
 static_assert(sizeof(gpsx_wsync_cfg_t) == 68 && offsetof(gpsx_wsync_cfg_t, search) == 16 && offsetof(gpsx_wsync_cfg_t, lock) == 36 &&
               offsetof(gpsx_wsync_cfg_t, sync_bits) == 56, "gpsx_wsync_cfg_t layout");
@@ -59,36 +51,26 @@ __global__ __launch_bounds__(256, 4) void k_track_wsync(const uint8_t *__restric
                                                      u32 *__restrict__ bad_prn)
 {
   using namespace trkweighted;
+  using namespace trkwloop;
   __shared__ __attribute__((aligned(16))) u32 s_x[2][512], s_m[2][512];   // this and the next block's planes
   __shared__ uint2 s_carrier[4];
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const int c_l = lane >> 2, k_l = lane & 3;
-  const int ch0 = ((int)blockIdx.x * 4 + wave) * cpw;
-  const int n_here = ch0 < n_ch ? min(cpw, n_ch - ch0) : 0;   // 0: an idle wave of the last workgroup still stages and waits
-  const bool in_wave = c_l < n_here;
-  const bool mine = in_wave && k_l < 3;
-  const int ch_l = in_wave ? ch0 + c_l : (n_here ? ch0 : 0);  // (always a channel below n_ch)
+  const Lanes l = lanes_of(n_ch, cpw);   // gpsx_track_wloop_parts.hpp, like everything the two loops share
+  const int lane = l.lane, k_l = l.k_l, n_here = l.n_here, ch_l = l.ch_l;
+  const bool in_wave = l.in_wave(), mine = l.mine();
   const int use_magnitude = cfg.weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;
   const int span = min(cfg.n_coh_search, cfg.n_coh_lock);
   const int decide_at = 20 * (cfg.sync_bits + 1);
   gpsx_wsync_state_t *const my = st + ch_l;
 
-  if (threadIdx.x < 4)
-    s_carrier[threadIdx.x] = uint2{carrier_i(threadIdx.x), carrier_q(threadIdx.x)};   // (visible after the first block's barrier)
+  fill_carrier(s_carrier);
 
-  // the loop's state in registers, as in k_track_wloop; every lane of a quad carries all of it
-  struct Live { float code_phase_fine, if_freq_offset_hz; u32 if_freq_accum; float dll_err, pll_err; int prev_ip, prev_qp; u32 n_updates; };
-  static_assert(sizeof(Live) == 32 && offsetof(gpsx_wloop_state_t, code_phase_fine) == 4 && offsetof(gpsx_wloop_state_t, n_updates) == 32,
-                "gpsx_wloop_state_t layout");
   Live s = {};
   int sum_i = 0, sum_q = 0;   // lane 4 c + k: tap k's sums over the open window (win_iq[2 k], [2 k + 1])
   int win_n = 0, ms = 0, mode = 0, edge = 0, bit_ip = 0, search_n = 0;
   int p_i = 0, p_q = 0;       // the round's running prompt: the quad's Prompt lane (k = 1) alone keeps it
   int prn_ok = 0;             // the validated PRN; 0: a bad channel (reported here); -1: a padding channel (never reported)
   if (n_here) {
-    const int raw = my->loop.prn;
-    __builtin_memcpy(&s, &my->loop.code_phase_fine, sizeof s);
-    prn_ok = raw == kTrackPadPrn ? -1 : track_prn(raw, bad_prn, mine && k_l == 0);
+    prn_ok = load_state(&my->loop, l, bad_prn, s);
     if (k_l < 3) {
       sum_i = my->win_iq[2 * k_l];
       sum_q = my->win_iq[2 * k_l + 1];
@@ -104,17 +86,16 @@ __global__ __launch_bounds__(256, 4) void k_track_wsync(const uint8_t *__restric
     }
   }
 
-  // what a window's correlators use: the state's floats, which change at a window's end only
-  int tau = 0, prn = 0;   // prn == 0: a bad channel, or no channel -- nothing but the accumulator moves
-  u32 step = 0;
-  auto begin_window = [&]() {
-    const bool phase_ok = weighted_tau(s.code_phase_fine, tau);
-    prn = in_wave && phase_ok && prn_ok > 0 ? prn_ok : 0;   // (the lanes beyond the wave's channels mirror its first: they must not act)
+  // tau, PRN and step of a window, in registers: from the state's floats, which change at a window's end only.  This kernel's rule,
+  // unlike k_track_wloop's: the lanes beyond the wave's channels (they mirror its first) get PRN 0 -- they must not act -- and a bad
+  // phase is reported for a good channel only (prn_ok > 0).
+  Window w;
+  auto rule = [&](bool phase_ok) {
+    w.prn = in_wave && phase_ok && prn_ok > 0 ? prn_ok : 0;
     if (!phase_ok && mine && k_l == 0 && bad_prn && prn_ok > 0)
       *bad_prn = 1u;
-    step = nco_step_per_word((float)if_hz + s.if_freq_offset_hz);
   };
-  begin_window();
+  begin_window(w, s, if_hz, rule);
   int slot = 0, in_slot = 0;
   bool wrote = false;   // a window of this channel ended in the current slot
 
@@ -124,21 +105,21 @@ __global__ __launch_bounds__(256, 4) void k_track_wsync(const uint8_t *__restric
     __syncthreads();
     if (!n_here)   // (wave-uniform)
       continue;
-    const bool ok = prn != 0;
+    const bool ok = w.prn != 0;
     if (ok && mode == GPSX_WSYNC_WAIT && ms == edge)
       mode = GPSX_WSYNC_LOCKED;   // this block is a bit's first
     const bool corr = ok && mode != GPSX_WSYNC_WAIT;
     u32 pop_m;
-    const u32 counts = wave_counts(s_x[b & 1], s_m[b & 1], s_carrier, lane, n_here, prn, tau, cfg.spacing, step, s.if_freq_accum, rep_all, pop_m);
+    const u32 counts = wave_counts(s_x[b & 1], s_m[b & 1], s_carrier, lane, n_here, w.prn, w.tau, cfg.spacing, w.step, s.if_freq_accum, rep_all, pop_m);
     int res_i = 0, res_q = 0;
     if (mine)
-      finish_tap(s_carrier, lane, prn, tau, cfg.spacing, step, s.if_freq_accum, rep_all, counts, pop_m, res_i, res_q);
+      finish_tap(s_carrier, lane, w.prn, w.tau, cfg.spacing, w.step, s.if_freq_accum, rep_all, counts, pop_m, res_i, res_q);
     if (corr) {
       sum_i += res_i;
       sum_q += res_q;
       win_n++;
     }
-    s.if_freq_accum += step * (u32)kWords32;
+    s.if_freq_accum += w.step * (u32)kWords32;
     bool ends = false, decide = false;
     if (ok) {
       ms = ms == 19 ? 0 : ms + 1;
@@ -168,41 +149,9 @@ __global__ __launch_bounds__(256, 4) void k_track_wsync(const uint8_t *__restric
       const int IL = quad_get<2>(sum_i), QL = quad_get<2>(sum_q);
       if (ends) {
         const bool locked = mode == GPSX_WSYNC_LOCKED;
-        const float dll_c1 = locked ? cfg.lock.dll_c1 : cfg.search.dll_c1, dll_c2 = locked ? cfg.lock.dll_c2 : cfg.search.dll_c2;
-        const float pll_c1 = locked ? cfg.lock.pll_c1 : cfg.search.pll_c1, pll_c2 = locked ? cfg.lock.pll_c2 : cfg.search.pll_c2;
-        const float fll_c = locked ? cfg.lock.fll_c : cfg.search.fll_c;
+        const gpsx_wsync_gains_t g = locked ? cfg.lock : cfg.search;
         const float T = (float)win_n * 0.001f;
-        // DLL
-        const long long e2 = (long long)IE * IE + (long long)QE * QE, l2 = (long long)IL * IL + (long long)QL * QL;
-        float d = 0.0f;
-        if (e2 + l2 != 0)
-          d = (float)(e2 - l2) / (float)(e2 + l2);
-        float phase = s.code_phase_fine - (dll_c1 * (d - s.dll_err) + (dll_c2 * T) * d);
-        if (phase < 0.0f)
-          phase = phase + kSpan;
-        else if (phase >= kSpan)
-          phase = phase - kSpan;
-        s.code_phase_fine = phase;
-        s.dll_err = d;
-        // Costas PLL, in cycles
-        float p;
-        if (IP == 0)
-          p = QP > 0 ? 0.25f : (QP < 0 ? -0.25f : 0.0f);
-        else
-          p = gpsx_libm::atanf_fdlibm((float)QP / (float)IP) * kCyclesPerRadian;
-        // FLL, in Hz
-        float fe = 0.0f;
-        if (fll_c != 0.0f && s.n_updates > 0) {
-          const long long cross = (long long)s.prev_ip * QP - (long long)s.prev_qp * IP;
-          const long long dot = (long long)s.prev_ip * IP + (long long)s.prev_qp * QP;
-          if (dot != 0)
-            fe = gpsx_libm::atanf_fdlibm((float)cross / (float)dot) * kCyclesPerRadian / T;
-        }
-        s.if_freq_offset_hz = s.if_freq_offset_hz - ((pll_c1 * (p - s.pll_err) + (pll_c2 * T) * p) + fll_c * fe);
-        s.pll_err = p;
-        s.prev_ip = IP;
-        s.prev_qp = QP;
-        s.n_updates++;
+        window_update(s, Gains{g.dll_c1, g.dll_c2, g.pll_c1, g.pll_c2, g.fll_c, T}, IE, QE, IP, QP, IL, QL);
         // the bit's prompt sum and the record
         u32 flags = GPSX_WSYNC_WINDOW;
         int bit_out = 0;
@@ -228,7 +177,7 @@ __global__ __launch_bounds__(256, 4) void k_track_wsync(const uint8_t *__restric
         wrote = true;
         sum_i = sum_q = 0;
         win_n = 0;
-        begin_window();   // tau, validity and step of the next window, in registers
+        begin_window(w, s, if_hz, rule);   // the next window
       }
     }
 

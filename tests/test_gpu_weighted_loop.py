@@ -246,17 +246,25 @@ def test_argument_checks_write_nothing(eng):
     st0 = _states(4, 9)
     good = dict(cfg=dict(n_coh=4), null_cfg=False, null_if=False, null_st=False, null_out=False, n_blocks=8, n_ch=4)
     nan, inf = float("nan"), float("inf")
-    refusals = [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(cfg=dict(n_coh=4, weights=2)),
-                dict(cfg=dict(n_coh=4, weights=-1)), dict(cfg=dict(n_coh=4, spacing=0)), dict(cfg=dict(n_coh=4, spacing=16)),
-                dict(cfg=dict(n_coh=0)), dict(cfg=dict(n_coh=-4)), dict(cfg=dict(n_coh=21)), dict(cfg=dict(n_coh=3)), dict(cfg=dict(n_coh=16)),
-                dict(n_blocks=0), dict(n_blocks=-4), dict(n_blocks=4100), dict(n_blocks=6), dict(n_ch=0), dict(n_ch=-3),
-                dict(cfg=dict(n_coh=4, dll=(nan, 1.0))), dict(cfg=dict(n_coh=4, dll=(1.0, inf))), dict(cfg=dict(n_coh=4, pll=(-inf, 1.0))),
-                dict(cfg=dict(n_coh=4, pll=(1.0, nan))), dict(cfg=dict(n_coh=4, fll=inf))]
+    # every refusal with its exact text; the last row of a group fails a later clause as well: the first failing clause decides
+    by_message = {
+        b"null argument": [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(null_out=True, n_ch=0)],
+        b"unknown weights": [dict(cfg=dict(n_coh=4, weights=2)), dict(cfg=dict(n_coh=4, weights=-1)), dict(cfg=dict(n_coh=4, weights=2), n_blocks=0),
+                             dict(cfg=dict(n_coh=4, weights=2, spacing=0))],
+        b"spacing must be 1..15 samples": [dict(cfg=dict(n_coh=4, spacing=0)), dict(cfg=dict(n_coh=4, spacing=16)), dict(cfg=dict(n_coh=0, spacing=16))],
+        b"n_coh must be 1..20 blocks": [dict(cfg=dict(n_coh=0)), dict(cfg=dict(n_coh=-4)), dict(cfg=dict(n_coh=21)), dict(cfg=dict(n_coh=21), n_blocks=0)],
+        b"n_blocks must be 1..4096": [dict(n_blocks=0), dict(n_blocks=-4), dict(n_blocks=4100), dict(n_blocks=4098, n_ch=0)],
+        b"n_blocks must be a multiple of n_coh": [dict(cfg=dict(n_coh=3)), dict(cfg=dict(n_coh=16)), dict(n_blocks=6), dict(n_blocks=6, n_ch=0)],
+        b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3), dict(n_ch=0, cfg=dict(n_coh=4, fll=inf))],
+        b"a loop gain is not finite": [dict(cfg=dict(n_coh=4, dll=(nan, 1.0))), dict(cfg=dict(n_coh=4, dll=(1.0, inf))), dict(cfg=dict(n_coh=4, pll=(-inf, 1.0))),
+                                       dict(cfg=dict(n_coh=4, pll=(1.0, nan))), dict(cfg=dict(n_coh=4, fll=inf))],
+    }
+    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
     d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(2 * 4 * 36)
     try:
         eng.h2d(d_if, blocks)
         for dev, fn in ((False, eng.lib.gpsx_track_loop_weighted), (True, eng.lib.gpsx_track_loop_weighted_dev)):
-            for change in refusals:
+            for message, change in refusals:
                 a = {**good, **change}
                 c = a["cfg"]
                 cfg = capi.wloop_cfg(c["n_coh"], True, c.get("spacing", 8), c.get("dll", (1.0, 100.0)), c.get("pll", (56.0, 1600.0)), c.get("fll", 0.1))
@@ -268,7 +276,7 @@ def test_argument_checks_write_nothing(eng):
                 rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (C.c_void_p(d_if) if dev else blocks.ctypes.data),
                         a["n_blocks"], None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
                         None if a["null_out"] else (C.c_void_p(d_rec) if dev else rec.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h), (dev, change)
+                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
                 eng.synchronize()   # nothing was enqueued, nothing is pending
                 st, dr = st0.copy(), np.zeros_like(rec)
                 eng.d2h(st, d_st)

@@ -205,16 +205,24 @@ def test_argument_checks_write_nothing(eng):
     rec, words, st0 = np.ascontiguousarray(rec[:, :n_ch]), np.ascontiguousarray(words[:, :n_ch]), st0[:n_ch].copy()
     good = dict(null_cfg=False, null_rec=False, null_words=False, null_st=False, null_out=False, guard=512.0, reserved=0, n_slots=n_slots,
                 n_blocks=n_blocks, n_ch=n_ch)
-    refusals = [dict(null_cfg=True), dict(null_rec=True), dict(null_words=True), dict(null_st=True), dict(null_out=True), dict(guard=-0.001),
-                dict(guard=8184.001), dict(guard=np.nan), dict(guard=np.inf), dict(guard=-np.inf), dict(reserved=1), dict(reserved=-1), dict(n_blocks=0),
-                dict(n_blocks=-40), dict(n_blocks=4097), dict(n_slots=0), dict(n_slots=-1), dict(n_slots=41), dict(n_blocks=1, n_slots=2), dict(n_ch=0),
-                dict(n_ch=-3)]
+    # every refusal with its exact text; the last row of a group fails a later clause as well: the first failing clause decides
+    by_message = {
+        b"null argument": [dict(null_cfg=True), dict(null_rec=True), dict(null_words=True), dict(null_st=True), dict(null_out=True),
+                           dict(null_words=True, n_ch=0)],
+        b"edge_guard must be finite and 0..8184": [dict(guard=-0.001), dict(guard=8184.001), dict(guard=np.nan), dict(guard=np.inf), dict(guard=-np.inf),
+                                                   dict(guard=np.nan, reserved=1), dict(guard=-1.0, n_blocks=0)],
+        b"reserved must be 0": [dict(reserved=1), dict(reserved=-1), dict(reserved=1, n_blocks=4097)],
+        b"n_blocks must be 1..4096": [dict(n_blocks=0), dict(n_blocks=-40), dict(n_blocks=4097), dict(n_blocks=0, n_slots=0)],
+        b"n_slots must be 1..n_blocks": [dict(n_slots=0), dict(n_slots=-1), dict(n_slots=41), dict(n_blocks=1, n_slots=2), dict(n_slots=0, n_ch=0)],
+        b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3)],
+    }
+    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
     d_rec, d_words, d_st, d_obs = eng.malloc(rec.nbytes), eng.malloc(words.nbytes), eng.malloc(st0.nbytes), eng.malloc(n_ch * 32)
     try:
         eng.h2d(d_rec, rec)
         eng.h2d(d_words, words)
         for dev, fn in ((False, eng.lib.gpsx_wobs), (True, eng.lib.gpsx_wobs_dev)):
-            for change in refusals:
+            for message, change in refusals:
                 a = {**good, **change}
                 cfg = _cfg(a["guard"], a["reserved"])
                 host = np.full(n_ch * 32, 0xA5, np.uint8)
@@ -223,7 +231,7 @@ def test_argument_checks_write_nothing(eng):
                 rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else C.c_void_p(d_rec), a["n_slots"], a["n_blocks"],
                         None if a["null_words"] else C.c_void_p(d_words), None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
                         None if a["null_out"] else (C.c_void_p(d_obs) if dev else host.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h), (dev, change)
+                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
                 eng.synchronize()      # nothing was enqueued, nothing is pending
                 st, dw = st0.copy(), np.zeros_like(host)
                 eng.d2h(st, d_st)

@@ -272,21 +272,30 @@ def test_argument_checks_write_nothing(eng):
     st0 = K.mixed_states(4, 9)
     good = dict(cfg={}, null_cfg=False, null_if=False, null_st=False, null_out=False, n_blocks=8, n_ch=4)
     nan, inf = float("nan"), float("inf")
-    refusals = [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(cfg=dict(weights=2)), dict(cfg=dict(weights=-1)),
-                dict(cfg=dict(spacing=0)), dict(cfg=dict(spacing=16)), dict(cfg=dict(n_coh_search=0)), dict(cfg=dict(n_coh_search=3)),
-                dict(cfg=dict(n_coh_search=40)), dict(cfg=dict(n_coh_lock=-20)), dict(cfg=dict(n_coh_lock=8)), dict(cfg=dict(n_coh_lock=21)),
-                dict(cfg=dict(sync_bits=0)), dict(cfg=dict(sync_bits=201)), dict(cfg=dict(sync_num=0, sync_den=0)), dict(cfg=dict(sync_num=1025)),
-                dict(cfg=dict(sync_den=0)), dict(cfg=dict(sync_num=4, sync_den=5)), dict(cfg=dict(sync_num=2000, sync_den=1025)),
-                dict(n_blocks=0), dict(n_blocks=-4), dict(n_blocks=4097), dict(n_ch=0), dict(n_ch=-3)]
-    for which in ("search", "lock"):
-        for field, value in (("dll_c1", nan), ("dll_c2", inf), ("pll_c1", -inf), ("pll_c2", nan), ("fll_c", inf)):
-            refusals.append(dict(cfg={(which, field): value}))
+    # every refusal with its exact text; the last row of a group fails a later clause as well: the first failing clause decides
+    by_message = {
+        b"null argument": [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(null_st=True, n_blocks=0)],
+        b"unknown weights": [dict(cfg=dict(weights=2)), dict(cfg=dict(weights=-1)), dict(cfg=dict(weights=2), n_blocks=0), dict(cfg=dict(weights=2, spacing=0))],
+        b"spacing must be 1..15 samples": [dict(cfg=dict(spacing=0)), dict(cfg=dict(spacing=16)), dict(cfg=dict(spacing=16, n_coh_lock=8))],
+        b"n_coh_search and n_coh_lock must be 1, 2, 4, 5, 10 or 20 blocks": [
+            dict(cfg=dict(n_coh_search=0)), dict(cfg=dict(n_coh_search=3)), dict(cfg=dict(n_coh_search=40)), dict(cfg=dict(n_coh_lock=-20)),
+            dict(cfg=dict(n_coh_lock=8)), dict(cfg=dict(n_coh_lock=21)), dict(cfg=dict(n_coh_lock=8, sync_bits=0))],
+        b"sync_bits must be 1..200": [dict(cfg=dict(sync_bits=0)), dict(cfg=dict(sync_bits=201)), dict(cfg=dict(sync_bits=0, sync_den=0))],
+        b"sync_num and sync_den must be 1..1024": [dict(cfg=dict(sync_num=0, sync_den=0)), dict(cfg=dict(sync_num=1025)), dict(cfg=dict(sync_den=0)),
+                                                   dict(cfg=dict(sync_num=2000, sync_den=1025)), dict(cfg=dict(sync_num=4, sync_den=1025))],
+        b"sync_num must not be below sync_den": [dict(cfg=dict(sync_num=4, sync_den=5)), dict(cfg=dict(sync_num=4, sync_den=5), n_blocks=0)],
+        b"n_blocks must be 1..4096": [dict(n_blocks=0), dict(n_blocks=-4), dict(n_blocks=4097), dict(n_blocks=0, n_ch=0)],
+        b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3), dict(n_ch=0, cfg={("lock", "fll_c"): inf})],
+        b"a loop gain is not finite": [dict(cfg={(which, field): value}) for which in ("search", "lock")
+                                       for field, value in (("dll_c1", nan), ("dll_c2", inf), ("pll_c1", -inf), ("pll_c2", nan), ("fll_c", inf))],
+    }
+    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
     n_slots = 2
     d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(n_slots * 4 * 48)
     try:
         eng.h2d(d_if, blocks)
         for dev, fn in ((False, eng.lib.gpsx_track_loop_weighted_sync), (True, eng.lib.gpsx_track_loop_weighted_sync_dev)):
-            for change in refusals:
+            for message, change in refusals:
                 a = {**good, **change}
                 cfg = _cfg(Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 20, (5, 4)))
                 for key, value in a["cfg"].items():
@@ -300,7 +309,7 @@ def test_argument_checks_write_nothing(eng):
                 rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (C.c_void_p(d_if) if dev else blocks.ctypes.data),
                         a["n_blocks"], None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
                         None if a["null_out"] else (C.c_void_p(d_rec) if dev else rec.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h), (dev, change)
+                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
                 eng.synchronize()   # nothing was enqueued, nothing is pending
                 st, dr = st0.copy(), np.zeros_like(rec)
                 eng.d2h(st, d_st)

@@ -208,18 +208,24 @@ def test_argument_checks_write_nothing(eng):
     blocks = _blocks(2)
     st0 = _states(4, 9)
     good = dict(cfg=(1, 8), null_cfg=False, null_if=False, null_st=False, null_out=False, n_blocks=2, n_ch=4)
-    refusals = [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(cfg=(2, 8)), dict(cfg=(-1, 8)),
-                dict(cfg=(1, 0)), dict(cfg=(1, 16)), dict(cfg=(1, -8)), dict(n_blocks=0), dict(n_blocks=-1), dict(n_blocks=4097),
-                dict(n_ch=0), dict(n_ch=-3)]
+    # every refusal with its exact text; the last row of a group fails a later clause as well: the first failing clause decides
+    by_message = {
+        b"null argument": [dict(null_cfg=True), dict(null_if=True), dict(null_st=True), dict(null_out=True), dict(null_if=True, n_ch=0)],
+        b"unknown weights": [dict(cfg=(2, 8)), dict(cfg=(-1, 8)), dict(cfg=(2, 8), n_blocks=0), dict(cfg=(2, 0))],
+        b"spacing must be 1..15 samples": [dict(cfg=(1, 0)), dict(cfg=(1, 16)), dict(cfg=(1, -8)), dict(cfg=(1, 16), n_blocks=4097)],
+        b"n_blocks must be 1..4096": [dict(n_blocks=0), dict(n_blocks=-1), dict(n_blocks=4097), dict(n_blocks=0, n_ch=0)],
+        b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3)],
+    }
+    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
     for fn in (eng.lib.gpsx_track_epl_weighted, eng.lib.gpsx_track_epl_weighted_dev):
-        for change in refusals:
+        for message, change in refusals:
             a = {**good, **change}
             cfg = np.array(a["cfg"], np.int32)
             st = st0.copy()
             iq = np.full((2, 4, 6), 0xA5A5A5A5, np.uint32)
             rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else blocks.ctypes.data, a["n_blocks"],
                     None if a["null_st"] else st.ctypes.data, a["n_ch"], None if a["null_out"] else iq.ctypes.data)
-            assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h), change
+            assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (change, eng.lib.gpsx_last_error(eng.h))
             assert (iq == 0xA5A5A5A5).all() and st.tobytes() == st0.tobytes(), change
     eng.synchronize()   # nothing was enqueued, nothing is pending
 
