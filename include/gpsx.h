@@ -33,7 +33,8 @@ extern "C" {
                                             * gpsx_track_epl_weighted(_dev) likewise: new entry points, no layout change;
                                             * gpsx_track_loop_weighted(_dev) and gpsx_track_loop_weighted_sync(_dev) too (new
                                             * structs of their own); gpsx_wnav_words(_dev) and gpsx_wnav_subframe_image likewise;
-                                            * gpsx_wobs(_dev) and gpsx_wobs_pseudoranges too. */
+                                            * gpsx_wobs(_dev) and gpsx_wobs_pseudoranges too; gpsx_weph(_dev) and
+                                            * gpsx_weph_to_eph (include/gpsx_compat.h) likewise. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -833,6 +834,83 @@ int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t 
  * caller assumes it (the reference's own pseudorange step uses 68.802 ms: include/gpsx_compat.h); the solver's clock term takes
  * the rest.  Returns the number of VALID observables, or GPSX_EINVAL for NULL, n < 1 or an offset_ms that is not finite. */
 int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, double *pr_m, double *rx_tow_s);
+
+/* ---- EXTENSION, not in the reference: weighted ephemerides -- every channel's broadcast ephemeris from the words, on the device ----
+ * What a position needs beside the transmit times: the satellite's broadcast ephemeris.  gpsx_weph(_dev) is a fifth stage behind
+ * gpsx_wnav_words_dev: a kernel reads the word records d_words[n_blocks / 600 + 2][n_ch] where the word layer left them, keeps a
+ * 192-byte state per channel, assembles subframes across launches, keeps the newest complete subframes 1, 2 and 3 and returns one
+ * 256-byte record per channel and launch.  When the three are of one issue of data the record holds the decoded ephemeris: what
+ * gps_nav_data_decode_subframe (include/gpsx_compat.h) produces, field for field and bit for bit.  Nothing existing changes.
+ *
+ * Definition, per channel.  The slots of d_words are read in order.  A record counts only if its flags have GPSX_WNAV_WORD,
+ * 1 <= index <= 10, -600 <= end_block < n_blocks (word 1 of a GPSX_WNAV_SYNC pair ends before its launch may) and, with
+ * E1 = blocks_seen + end_block + 1, E1 >= 1; every other record is skipped.  `passed`: the record has GPSX_WNAV_OK -- and, for
+ * index 2, subframe_id in 1 .. 5 and aux < 100800.  For a record that counts:
+ *   1 word 1       cur_mask = passed, cur_next = 2, cur_id = cur_tow = 0, last_word_end_p1 = E1
+ *   2 the expected word  (index == cur_next and E1 == last_word_end_p1 + 600)  if passed: cur_mask |= 1 << (index - 1); if passed
+ *                  and index is 2: cur_id = subframe_id, cur_tow = aux; if passed and index >= 3: cur[index - 3] = (word >> 6) &
+ *                  0xFFFFFF.  Then last_word_end_p1 = E1 and cur_next = index == 10 ? 0 : index + 1.  At index 10 with cur_mask ==
+ *                  0x3FF: n_subframes++, and the subframe is committed if cur_id is 1 .. 3
+ *   3 anything else  (a gap, a word out of order, a word while waiting for a word 1)  cur_next = 0, cur_mask = 0,
+ *                  last_word_end_p1 = E1
+ * Commit, with k = cur_id - 1: changed = !(have >> k & 1) || sf[k] != cur in any of the eight words; sf[k] = cur, sf_tow[k] =
+ * cur_tow, have |= 1 << k; consistent = have == 7 && (sf[1][0] >> 16) == (sf[2][7] >> 16) && (sf[1][0] >> 16) == (sf[0][5] >> 16)
+ * -- IODE of subframe 2 word 3, IODE of subframe 3 word 10, the low byte of IODC in subframe 1 word 8.  Consistent: VALID is set;
+ * if it was not set before the commit, or `changed`, n_sets++ and the launch's record gets NEW.  Not consistent: VALID is cleared
+ * (a data-set cutover is in progress: the caller keeps the set it has).  A break in the words never clears VALID, and a
+ * reacquired satellite that sends the same set again is VALID without NEW.  (Word 10s lie 6000 blocks apart: at most one commit
+ * per launch.)
+ * Output: blocks_seen += n_blocks.  With VALID the record holds what gps_nav_data_decode_subframe leaves in eph_data.eph of a zeroed
+ * channel after it has been given subframes 1, 2 and 3 in this order, with sf[0 .. 2] as the source bits and sf_tow[0] as the HOW
+ * count of subframe 1: the same fields at the same bit positions (subframe bit n lies in word n / 30, and bits 0 .. 23 of a word are
+ * d1 .. d24), the same decimal scale literals (three of which are not powers of two), the same order of double operations (one
+ * IEEE multiply each: the scale, then 3.1415926535898 for semicircles; A = sqrtA * sqrtA), the week resolved around build week 2290,
+ * and gps_time with its (int)sec split.  Without VALID every field but flags, n_sets and have is zero.  Every byte of d_eph is
+ * written.  n_sets and n_subframes wrap at 2^32.  The call must be made on every launch of a stream, as gpsx_wnav_words must:
+ * blocks_seen is the time base.  Where a stream is cut into launches matters to nothing but which launch's record gets NEW.
+ * Errors: NULL pointers, a reserved field != 0, n_blocks outside 1 .. 4096, n_ch < 1 and a size that overflows return GPSX_EINVAL
+ * (with a gpsx_last_error text) and write nothing.  A channel is BAD if blocks_seen or last_word_end_p1 lies outside 0 .. 2^62,
+ * cur_next is not 0 or 2 .. 10, cur_mask > 0x3FF, cur_id > 5, cur_tow or a sf_tow >= 100800, a cur / sf word >= 2^24, have > 7, its
+ * flags have bits other than VALID or VALID without have == 7, or reserved != 0: its state stays as it was, its record is all zero,
+ * and GPSX_EINVAL comes from gpsx_weph after its wait / from the next gpsx_synchronize() after _dev.
+ * Vector ALU (k_weph: one channel per lane, the word records' 16-byte loads all in flight before the first is looked at, the
+ * records stored through LDS so that a wave writes consecutive lines).  On one
+ * stream: gpsx_track_loop_weighted_sync_dev, gpsx_wnav_words_dev, then gpsx_wobs_dev and gpsx_weph_dev on their arrays with the
+ * same n_blocks.  gpsx_weph_to_eph (include/gpsx_compat.h) turns a VALID record into the reference's eph_t. */
+#define GPSX_WEPH_VALID 1u   /* subframes 1, 2, 3 are held and IODE(2) == IODE(3) == IODC(1) & 0xFF */
+#define GPSX_WEPH_NEW   2u   /* output only: a commit in this launch made the set VALID with contents it did not have before */
+
+typedef struct { int32_t reserved0, reserved1; } gpsx_weph_cfg_t;          /* both 0 */
+
+typedef struct {                 /* 192 bytes, device resident; all zero = a fresh channel */
+  int64_t  blocks_seen;          /*   0  blocks of all earlier launches */
+  int64_t  last_word_end_p1;     /*   8  absolute last block of the newest word that counted, + 1; 0: none */
+  uint32_t cur[8];               /*  16  d1 .. d24 (d1 in bit 23) of words 3 .. 10 of the subframe being assembled */
+  uint32_t cur_mask;             /*  48  bit w (0 .. 9): word w + 1 of it counted and passed */
+  uint32_t cur_next;             /*  52  index of the word expected next, 2 .. 10; 0: waiting for a word 1 */
+  uint32_t cur_id, cur_tow;      /*  56  from its HOW if that passed: 1 .. 5 and the 17-bit count; else 0 */
+  uint32_t sf[3][8];             /*  64  words 3 .. 10 of the newest complete subframes 1, 2, 3 */
+  uint32_t sf_tow[3];            /* 160  their HOW counts */
+  uint32_t have;                 /* 172  bit k: sf[k] holds a subframe */
+  uint32_t flags;                /* 176  GPSX_WEPH_VALID */
+  uint32_t n_sets, n_subframes, reserved;   /* 180  sets that became NEW; complete subframes of any ID; 0 */
+} gpsx_weph_state_t;
+
+typedef struct {                 /* 256 bytes, one per channel and launch */
+  uint32_t flags;                /*   0  the state's flags | NEW */
+  int32_t  iode, iodc, sva, svh, week, code, flag;            /*   4 */
+  int64_t  toe_time, toc_time, ttr_time;                      /*  32  gtime_t.time of eph_t's toe / toc / ttr */
+  double   toe_sec, toc_sec, ttr_sec;                         /*  56  gtime_t.sec */
+  double   A, e, i0, OMG0, omg, M0, deln, OMGd, idot, crc, crs, cuc, cus, cic, cis, toes, fit, f0, f1, f2, tgd;   /* 80 */
+  uint32_t n_sets, have;         /* 248  the state's */
+} gpsx_weph_t;
+
+/* d_words [n_blocks / 600 + 2][n_ch]: what gpsx_wnav_words(_dev) wrote for these n_blocks blocks, on the device in both variants, as
+ * d_state [n_ch] is; d_eph / eph: [n_ch]; d_eph 16-byte aligned, as every gpsx_malloc pointer is (GPSX_EINVAL otherwise) */
+int gpsx_weph_dev(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks,
+                  gpsx_weph_state_t *d_state, int n_ch, gpsx_weph_t *d_eph);
+int gpsx_weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks,
+              gpsx_weph_state_t *d_state, int n_ch, gpsx_weph_t *eph /* host */);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

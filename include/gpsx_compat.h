@@ -341,6 +341,12 @@ const double *gpsx_pvt_azel(void);
 void gpsx_loop_state_from_channel(const gps_ch_t *ch, uint32_t rng_seed, gpsx_loop_state_t *out);
 void gpsx_loop_state_to_channel(const gpsx_loop_state_t *in, gps_ch_t *ch);
 
+/* not in the reference: a VALID record of the weighted chain's ephemeris stage (gpsx_weph, include/gpsx.h) as the reference's
+ * eph_t: *out is zeroed with memset, every field is filled -- what gps_nav_data_decode_subframe leaves in eph_data.eph of a zeroed
+ * channel with that prn after subframes 1, 2, 3 of the record's bits, byte for byte -- and sat = prn.  Host only, no GPU.
+ * GPSX_EINVAL for NULL and for a record without GPSX_WEPH_VALID (*out is then untouched). */
+int gpsx_weph_to_eph(const gpsx_weph_t *in, int prn, eph_t *out);
+
 /* The word layer behind the device tracking loops: feeds the completed navigation bits of one gpsx_track_loop launch
  * (flags [n_blocks][n_ch], first block at tick first_tick) to gps_nav_data_words_detection with each bit's own tick and
  * keeps the records' bit-edge time current (and period_sync_ok_flag as of the channel's last completed bit or located edge:

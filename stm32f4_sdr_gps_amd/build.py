@@ -113,7 +113,12 @@ def check_no_scratch() -> dict:
     wobs = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wobs.o")).items() if "k_wobs" in k}
     if len(wobs) != 1:
         raise RuntimeError(f"expected k_wobs in build/k_wobs.o, found {sorted(wobs)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **wnav, **wobs}
+    # ... and the ephemerides behind the words (k_weph: eight word records, the state's 48 words and the record's 64 in registers,
+    #     cur[] / sf[][] reached through select chains, never through an index; 17 KiB of LDS stage the records' stores)
+    weph = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_weph.o")).items() if "k_weph" in k}
+    if len(weph) != 1:
+        raise RuntimeError(f"expected k_weph in build/k_weph.o, found {sorted(weph)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **wnav, **wobs, **weph}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

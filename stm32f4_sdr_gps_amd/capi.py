@@ -147,6 +147,35 @@ def wobs_pseudoranges(obs: np.ndarray, offset_ms: float = 68.802):
     return pr, rx.value, n
 
 
+# gpsx_weph_cfg_t / gpsx_weph_state_t / gpsx_weph_t (every channel's broadcast ephemeris from the words) and eph_t (include/gpsx_compat.h)
+WEPH_FLAG_VALID, WEPH_FLAG_NEW = 1, 2
+WEPH_CFG_DTYPE = np.dtype([("reserved0", "<i4"), ("reserved1", "<i4")])
+WEPH_STATE_DTYPE = np.dtype([("blocks_seen", "<i8"), ("last_word_end_p1", "<i8"), ("cur", "<u4", (8,)), ("cur_mask", "<u4"), ("cur_next", "<u4"),
+                             ("cur_id", "<u4"), ("cur_tow", "<u4"), ("sf", "<u4", (3, 8)), ("sf_tow", "<u4", (3,)), ("have", "<u4"), ("flags", "<u4"),
+                             ("n_sets", "<u4"), ("n_subframes", "<u4"), ("reserved", "<u4")])
+WEPH_DOUBLES = ("A", "e", "i0", "OMG0", "omg", "M0", "deln", "OMGd", "idot", "crc", "crs", "cuc", "cus", "cic", "cis", "toes", "fit", "f0", "f1", "f2", "tgd")
+WEPH_DTYPE = np.dtype([("flags", "<u4")] + [(k, "<i4") for k in ("iode", "iodc", "sva", "svh", "week", "code", "flag")] +
+                      [(k, "<i8") for k in ("toe_time", "toc_time", "ttr_time")] + [(k, "<f8") for k in ("toe_sec", "toc_sec", "ttr_sec")] +
+                      [(k, "<f8") for k in WEPH_DOUBLES] + [("n_sets", "<u4"), ("have", "<u4")])
+EPH_DTYPE = np.dtype([(k, "<i4") for k in ("sat", "iode", "iodc", "sva", "svh", "week", "code", "flag")] +
+                     [(k, t) for g in ("toe", "toc", "ttr") for k, t in ((g + "_time", "<i8"), (g + "_sec", "<f8"))] +
+                     [(k, "<f8") for k in WEPH_DOUBLES[:-1]] + [("tgd", "<f8", (4,))])
+assert WEPH_CFG_DTYPE.itemsize == 8 and WEPH_STATE_DTYPE.itemsize == 192 and WEPH_DTYPE.itemsize == 256 and EPH_DTYPE.itemsize == 272
+
+
+def weph_to_eph(rec, prn: int) -> np.ndarray:
+    """one VALID WEPH_DTYPE record -> the reference's eph_t as EPH_DTYPE [1] (what gps_nav_data_decode_subframe leaves in a zeroed
+    channel's eph_data.eph after subframes 1, 2, 3 of the record's bits, with sat = prn); GpsxError without VALID.  Host only."""
+    rec = np.ascontiguousarray(rec, WEPH_DTYPE).reshape(-1)
+    if len(rec) != 1:
+        raise GpsxError("weph_to_eph takes one record")
+    out = np.zeros(1, EPH_DTYPE)
+    rc = load_library().gpsx_weph_to_eph(rec.ctypes.data, int(prn), out.ctypes.data)
+    if rc != 0:
+        raise GpsxError(f"gpsx_weph_to_eph -> {rc}: the record is not VALID")
+    return out
+
+
 TRK_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"),
                       ("if_freq_accum", "<u4")])
 JOB_DTYPE = np.dtype([("block", "<i4"), ("n_ms", "<i4"), ("prn", "<i4"), ("freq_hz", "<f4"), ("offset_bits", "<i4"),
@@ -250,6 +279,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wobs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wobs_dev.argtypes = lib.gpsx_wobs.argtypes
     lib.gpsx_wobs_pseudoranges.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double)]
+    lib.gpsx_weph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_weph_dev.argtypes = lib.gpsx_weph.argtypes
+    lib.gpsx_weph_to_eph.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -660,6 +692,15 @@ class Engine:
         self._chk(self.lib.gpsx_wobs(self.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_words), C.c_void_p(d_state), n_ch,
                                      obs.ctypes.data), "gpsx_wobs")
         return obs
+
+    def weph(self, d_words: int, n_blocks: int, d_state: int, n_ch: int) -> np.ndarray:
+        """EXTENSION: every channel's broadcast ephemeris from the WNAV_WORD_DTYPE [n_blocks // 600 + 2, n_ch] words at device address
+        d_words that gpsx_wnav_words_dev wrote for n_blocks blocks, on the n_ch WEPH_STATE_DTYPE states at device address d_state (all
+        zero: a fresh channel).  -> WEPH_DTYPE [n_ch]; a record with WEPH_FLAG_VALID holds the decoded ephemeris (weph_to_eph)"""
+        cfg = np.zeros(1, WEPH_CFG_DTYPE)
+        eph = np.zeros(n_ch, WEPH_DTYPE)
+        self._chk(self.lib.gpsx_weph(self.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, C.c_void_p(d_state), n_ch, eph.ctypes.data), "gpsx_weph")
+        return eph
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

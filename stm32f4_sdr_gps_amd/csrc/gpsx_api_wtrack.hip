@@ -1,6 +1,6 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync, gpsx_wnav_words, gpsx_wobs, each with its _dev twin, and the two host
-// helpers behind them.  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync, gpsx_wnav_words, gpsx_wobs, gpsx_weph, each with its _dev twin, and the two
+// host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
 // waits for its kernel and reports a bad channel itself (flag 0).  Otherwise (_dev) they are device memory, the call returns after
@@ -234,6 +234,34 @@ int wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t *d_re
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(obs, d_obs, obs_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
+// ---- the broadcast ephemerides from the words (d_words and the states are device memory in both variants) -----------------------------
+int weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, gpsx_weph_state_t *d_state, int n_ch,
+         gpsx_weph_t *eph, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !d_words || !d_state || !eph)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->reserved0 != 0 || cfg->reserved1 != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  if (!host && (reinterpret_cast<uintptr_t>(eph) & 15u) != 0)   // (k_weph stores the records 16 bytes at a time)
+    return fail(ctx, GPSX_EINVAL, "d_eph must be 16-byte aligned");
+  size_t bytes = 0, eph_bytes = 0;
+  if (records_overflow((size_t)(n_blocks / 600 + 2), n_ch, sizeof(gpsx_wnav_word_t), &bytes) ||
+      records_overflow(1, n_ch, sizeof(gpsx_weph_state_t), &bytes) || records_overflow(1, n_ch, sizeof(gpsx_weph_t), &eph_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  gpsx_weph_t *d_eph = eph;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(eph_bytes))) return rc;
+    d_eph = arena_take<gpsx_weph_t>(ctx, (size_t)n_ch);
+  }
+  return launch_and_report(
+      ctx, host, "k_weph", "a channel's ephemeris state is out of range (its state is untouched, its record is zero)",
+      [&](uint32_t *flag) { launch_weph(ctx->stream, d_words, n_blocks, d_state, n_ch, d_eph, flag); },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(eph, d_eph, eph_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
 }  // namespace
 
 extern "C" {
@@ -296,6 +324,18 @@ int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t 
               const gpsx_wnav_word_t *d_words, gpsx_wobs_state_t *d_state, int n_ch, gpsx_wobs_t *obs)
 {
   return wobs(ctx, cfg, d_rec, n_slots, n_blocks, d_words, d_state, n_ch, obs, true);
+}
+
+int gpsx_weph_dev(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, gpsx_weph_state_t *d_state,
+                  int n_ch, gpsx_weph_t *d_eph)
+{
+  return weph(ctx, cfg, d_words, n_blocks, d_state, n_ch, d_eph, false);
+}
+
+int gpsx_weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, gpsx_weph_state_t *d_state,
+              int n_ch, gpsx_weph_t *eph)
+{
+  return weph(ctx, cfg, d_words, n_blocks, d_state, n_ch, eph, true);
 }
 
 int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38])

@@ -7,6 +7,7 @@
 // n >> 3, parity bits included, data bits already un-inverted.
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/gpsx_compat.h"
 
@@ -173,4 +174,25 @@ extern "C" __attribute__((weak)) uint8_t gps_nav_data_decode_subframe(gps_ch_t *
   }
   s.sub_cnt++;
   return (uint8_t)id;
+}
+
+// A VALID record of gpsx_weph (k_weph.hip decodes on the device what the tables above decode here) as an eph_t.
+extern "C" int gpsx_weph_to_eph(const gpsx_weph_t *in, int prn, eph_t *out)
+{
+  if (!in || !out || !(in->flags & GPSX_WEPH_VALID))
+    return GPSX_EINVAL;
+  std::memset(out, 0, sizeof *out);
+  eph_t &e = *out;
+  e.sat = prn;
+  e.iode = in->iode; e.iodc = in->iodc; e.sva = in->sva; e.svh = in->svh;
+  e.week = in->week; e.code = in->code; e.flag = in->flag;
+  e.toe.time = (time_t)in->toe_time; e.toe.sec = in->toe_sec;
+  e.toc.time = (time_t)in->toc_time; e.toc.sec = in->toc_sec;
+  e.ttr.time = (time_t)in->ttr_time; e.ttr.sec = in->ttr_sec;
+  e.A = in->A; e.e = in->e; e.i0 = in->i0; e.OMG0 = in->OMG0; e.omg = in->omg; e.M0 = in->M0;
+  e.deln = in->deln; e.OMGd = in->OMGd; e.idot = in->idot;
+  e.crc = in->crc; e.crs = in->crs; e.cuc = in->cuc; e.cus = in->cus; e.cic = in->cic; e.cis = in->cis;
+  e.toes = in->toes; e.fit = in->fit;
+  e.f0 = in->f0; e.f1 = in->f1; e.f2 = in->f2; e.tgd[0] = in->tgd;
+  return GPSX_OK;
 }

@@ -157,6 +157,11 @@ void launch_wnav_words(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots
 // HBM, d_obs [n_ch], every byte of it written.  d_bad_state (may be null): set to 1 by a channel whose state is out of range.
 void launch_wobs(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks, float edge_guard, const gpsx_wnav_word_t *d_words,
                  gpsx_wobs_state_t *d_st, int n_ch, gpsx_wobs_t *d_obs, uint32_t *d_bad_state);
+// extension: gpsx_weph (k_weph.hip: k_weph) -- every channel's broadcast ephemeris from the [n_blocks / 600 + 2][n_ch] word records
+// launch_wnav_words wrote: one channel per lane, 192-byte states in HBM, d_eph [n_ch] 256-byte records, every byte of them written.
+// d_bad_state (may be null): set to 1 by a channel whose state is out of range.
+void launch_weph(hipStream_t s, const gpsx_wnav_word_t *d_words, int n_blocks, gpsx_weph_state_t *d_st, int n_ch, gpsx_weph_t *d_eph,
+                 uint32_t *d_bad_state);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -39,7 +39,17 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       records gpsx_wnav_words_dev made of each, beside (1) a device-to-device
                                                       hipMemcpyAsync of the record array -- the bar: the kernel takes no longer -- and
                                                       (2) gpsx_wnav_words_dev, which reads the same lines, the calls taking turns in one
-                                                      process"""
+                                                      process
+  bench_track_kernel.py --weighted-eph [channels ...]
+                                                      gpsx_weph_dev (EXTENSION: every channel's broadcast ephemeris from the words) on
+                                                      the word records of 4000-block launches -- every channel mid-stream on a repeating
+                                                      parity-correct 1-2-3-4-5 frame, 32 distinct offsets, fifteen word arrays (two
+                                                      frames) used in turn -- beside (a) a device-to-device hipMemcpyAsync of half the
+                                                      768 bytes per channel it touches (a copy reads and writes what it is given) and
+                                                      (b) gpsx_wnav_words_dev on the records of a 4000-block launch -- the bar: the stage
+                                                      at the chain's end takes no longer than the one before it -- the calls taking
+                                                      turns in one process; then what a host does without the stage: d_words copied
+                                                      back, gpsx_wnav_subframe_image and gps_nav_data_decode_subframe per channel"""
 import ctypes as C
 import json
 import os
@@ -438,8 +448,148 @@ def weighted_obs(counts, n_blocks=4000, span=20):
             eng.free(p)
 
 
+def weighted_eph(counts, n_blocks=4000, span=20):
+    import time
+    from stm32f4_sdr_gps_amd import capi, synth
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    lib = capi.load_library()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    eng = capi.Engine(0, stream=stream.value)      # (the copy below goes onto the stream the engine's events are recorded on)
+    distinct, legs, frame = 32, 15, 30000
+    n_slots, word_slots = n_blocks // span, capi.wnav_word_slots(n_blocks)
+    # one frame of five parity-correct subframes; subframes 1, 2, 3 of one issue of data (IODC's low byte, IODE twice)
+    rng = np.random.Generator(np.random.PCG64(5))
+    frame_words = []      # 50 x (word as the word layer writes it, index, subframe ID, TOW count)
+    for sub_id in range(1, 6):
+        payload = [[int(b) for b in rng.integers(0, 2, 24)] for _ in range(8)]
+        for word, first in ((5, sub_id == 1), (0, sub_id == 2), (7, sub_id == 3)):
+            if first:
+                payload[word][:8] = [0, 1, 0, 0, 1, 1, 0, 1]
+        bits = synth.lnav_subframe(sub_id, 1000 + sub_id, rng, payload)
+        d30 = 0
+        for w in range(10):
+            t = bits[30 * w:30 * w + 30]
+            data = int("".join(str(b ^ d30) for b in t[:24]), 2)
+            frame_words.append((data << 6 | int("".join(str(b) for b in t[24:]), 2), w + 1, sub_id, 1000 + sub_id if w == 1 else 0))
+            d30 = t[29]
+    offsets = [(937 * j + 11) % frame for j in range(distinct)]      # word 1 of subframe 1 of channel j ends at block offsets[j] + 599 (mod the frame)
+    small = np.zeros((legs, word_slots, distinct), capi.WNAV_WORD_DTYPE)
+    small["end_block"] = -1
+    for j, off in enumerate(offsets):
+        fill = [0] * legs
+        for k in range(-50, 2 * 50 + 50):      # words of the frame before, of the two frames of the fifteen launches, of the one after
+            end = off + 600 * (k + 1) - 1
+            leg = end // n_blocks
+            if 0 <= end and leg < legs:
+                word, index, sub_id, aux = frame_words[k % 50]
+                small[leg, fill[leg], j] = (end - leg * n_blocks, word, index, capi.WNAV_FLAG_WORD | capi.WNAV_FLAG_OK, sub_id if index >= 2 else 0, 0, aux)
+                fill[leg] += 1
+    # gpsx_wnav_words_dev's input as in --weighted-nav: one parity-correct subframe repeated for ever, three record arrays used in turn
+    sub = np.array(synth.lnav_subframe(3, 4711, np.random.Generator(np.random.PCG64(5))), np.int64)
+    nav_bits = np.stack([np.tile(sub, 4)[(37 * j) % 300:(37 * j) % 300 + 600] ^ (j & 1) for j in range(distinct)], axis=1)
+    nav_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
+    nav_cfg["max_bad_words"] = 3
+    cfg = np.zeros(1, capi.WEPH_CFG_DTYPE)
+    for n in counts:
+        idx = np.arange(n) % distinct
+        words_bytes, rec_bytes, touched = word_slots * n * 16, n_slots * n * 48, n * (word_slots * 16 + 2 * 192 + 256)
+        d_words = []
+        for leg in range(legs):
+            d = eng.malloc(words_bytes)
+            eng.h2d(d, np.ascontiguousarray(small[leg][:, idx]))
+            d_words.append(d)
+        d_recs = []
+        for leg in range(3):
+            rec = np.zeros((n_slots, distinct), capi.WSYNC_REC_DTYPE)
+            rec["end_block"] = (np.arange(n_slots) * span + span - 1)[:, None]
+            rec["flags"] = capi.WSYNC_FLAG_WINDOW | capi.WSYNC_FLAG_LOCKED | capi.WSYNC_FLAG_BIT
+            rec["bit_ip"] = (1 - 2 * nav_bits[leg * n_slots:(leg + 1) * n_slots]) * 20000
+            d = eng.malloc(rec_bytes)
+            eng.h2d(d, np.ascontiguousarray(rec[:, idx]))
+            d_recs.append(d)
+        nav, st = np.zeros(n, capi.WNAV_STATE_DTYPE), np.zeros(n, capi.WEPH_STATE_DTYPE)
+        d_nav, d_st, d_eph, d_nav_words = eng.malloc(nav.nbytes), eng.malloc(st.nbytes), eng.malloc(n * 256), eng.malloc(words_bytes)
+        d_src, d_dst = eng.malloc(touched // 2), eng.malloc(touched // 2)
+        eng.h2d(d_nav, nav)
+        eng.h2d(d_st, st)
+        turn = {"words": 0, "eph": 0}
+
+        def words():
+            leg = turn["words"] % 3
+            turn["words"] += 1
+            return eng.lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, C.c_void_p(d_recs[leg]), n_slots, n_blocks, C.c_void_p(d_nav), n,
+                                               C.c_void_p(d_nav_words))
+
+        def ephemerides():
+            leg = turn["eph"] % legs
+            turn["eph"] += 1
+            return eng.lib.gpsx_weph_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_words[leg]), n_blocks, C.c_void_p(d_st), n, C.c_void_p(d_eph))
+
+        for _ in range(6):          # every channel of the word layer SYNCED ...
+            eng._chk(words(), "gpsx_wnav_words_dev")
+        for _ in range(legs):       # ... and every channel here holding its set, mid-stream
+            eng._chk(ephemerides(), "gpsx_weph_dev")
+        eng.synchronize()
+        calls = {"d2d_copy_of_half_the_bytes_touched": (n_blocks, lambda: hip.hipMemcpyAsync(d_dst, d_src, touched // 2, 3, stream)),
+                 "weph": (n_blocks, ephemerides),
+                 "wnav_words": (n_blocks, words)}
+        med = _timed_rows(eng, calls, {"channels": n, "word_slots": word_slots, "bytes_touched": touched})
+        eph = np.zeros(n, capi.WEPH_DTYPE)
+        eng.d2h(eph, d_eph)
+        eng.d2h(st, d_st)
+        print(json.dumps({"weph_check": "records after the timed launches", "channels": n, "launches": turn["eph"],
+                          "valid": int((eph["flags"] & capi.WEPH_FLAG_VALID != 0).sum()), "n_sets_max": int(st["n_sets"].max()),
+                          "subframes_min": int(st["n_subframes"].min()), "subframes_max": int(st["n_subframes"].max()),
+                          "blocks_seen": int(st["blocks_seen"].min())}), flush=True)
+        print(json.dumps({"ratio": "k_weph over k_wnav_words on the 4000-block launch that feeds it", "channels": n,
+                          "value": round(med["weph"] / med["wnav_words"], 4), "bound": 1.0, "within_bound": bool(med["weph"] <= med["wnav_words"])}), flush=True)
+        print(json.dumps({"ratio": "k_weph over a device-to-device copy of the bytes it touches (no bar)", "channels": n,
+                          "value": round(med["weph"] / med["d2d_copy_of_half_the_bytes_touched"], 4),
+                          "touched_GBps": round(touched / med["weph"] / 1e3, 1),
+                          "copy_GBps_read_plus_write": round(touched / med["d2d_copy_of_half_the_bytes_touched"] / 1e3, 1)}), flush=True)
+        # the alternative without the stage: d_words back to the host (wall clock, three copies), then per channel and complete subframe
+        # gpsx_wnav_subframe_image + gps_nav_data_decode_subframe -- timed through ctypes on up to 4096 subframes (the figure includes
+        # the two foreign calls' overhead) and scaled to the n_blocks / 6000 subframes a channel completes per launch
+        host_words = np.zeros((word_slots, n), capi.WNAV_WORD_DTYPE)
+        copies = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            eng.d2h(host_words, d_words[0])
+            copies.append(time.perf_counter() - t0)
+        lib.gps_nav_data_decode_subframe.argtypes = [C.c_void_p]
+        ten = np.zeros(10, capi.WNAV_WORD_DTYPE)
+        for w in range(10):
+            ten[w] = (600 * w + 599, frame_words[w][0], w + 1, capi.WNAV_FLAG_WORD | capi.WNAV_FLAG_OK, 1, 0, frame_words[w][3])
+        ch = np.zeros(1688, np.uint8)      # a gps_ch_t
+        image = ch[212 + 71:212 + 71 + 38]
+        m = min(n, 4096)
+        t0 = time.perf_counter()
+        for _ in range(m):
+            lib.gpsx_wnav_subframe_image(ten.ctypes.data, image.ctypes.data)
+            lib.gps_nav_data_decode_subframe(ch.ctypes.data)
+        per_subframe = (time.perf_counter() - t0) / m
+        decode_s = per_subframe * n * n_blocks / 6000
+        print(json.dumps({"alternative": "d_words copied back + host decode per channel and subframe", "channels": n,
+                          "d_words_MB": round(words_bytes / 1e6, 1), "copy_back_ms_median": round(float(np.median(copies)) * 1e3, 3),
+                          "host_decode_us_per_subframe_through_ctypes": round(per_subframe * 1e6, 3), "host_decode_ms_per_launch": round(decode_s * 1e3, 3),
+                          "total_ms_per_launch": round((float(np.median(copies)) + decode_s) * 1e3, 3), "weph_ms_per_launch": round(med["weph"] / 1e3, 4)}),
+              flush=True)
+        for p in d_words + d_recs + [d_nav, d_st, d_eph, d_nav_words, d_src, d_dst]:
+            eng.free(p)
+
+
 def main():
     global WINDOW_S
+    if "--weighted-eph" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-eph"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_eph([int(a) for a in args] or [65536, 212992])
     if "--weighted-obs" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-obs"]
         if "--window-s" in args:
