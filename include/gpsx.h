@@ -443,7 +443,12 @@ int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const
  * window, one 36-byte record per (window, channel) and nothing else back to the host.  cfg is per launch: a pull-in launch with
  * fll_c set and a small n_coh, then steady-state launches, on the same state array.  A grid record hands over by filling the
  * first four fields of a zeroed state (they ARE a gpsx_trk_state_t); the alignment of a 20 ms window with the data bit edge stays
- * the caller's business (the _hyb grid's guidance above).  No carrier aiding of the code loop.
+ * the caller's business (the _hyb grid's guidance above).  No carrier aiding of the code loop: a satellite's code slides by
+ * fd x 0.01039 samples per second (fd / 1540 chips), the PI DLL follows that ramp with its integrator alone, and its discriminator
+ * rests at d = fd x 0.01039 / dll_c2 -- with d(tau) = 16 tau / (64 + tau^2) at spacing 8, dll_c2 = 40 leaves the code 3.3 samples
+ * behind at 2.7 kHz, d reaches 1 at |fd| = 3.85 kHz = dll_c2 x 96.25 Hz, and beyond that the code is lost.  On satellites on
+ * orbits (tests/test_weighted_pvt_reference.py, |fd| up to 2.9 kHz) the steady gains dll = (0.5, 200) at n_coh = 20 hold the lag
+ * to 0.6 samples and the fix of four channels to 35 m, where (0.5, 40) gives 125 m.
  *
  * Definition, for window u of a channel.  Every float operation is one IEEE single operation in the order written: no
  * contraction, correctly rounded division.

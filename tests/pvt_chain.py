@@ -217,11 +217,13 @@ def pick_satellites(rx, tow, n, seed, min_el_deg=25.0):
     return [(raw, q) for raw, q, _ in out]
 
 
-def make_if_from_orbits(n_ms, sats, rx, tow0, amp=0.6, noise_amp=1.0, seed=7, nav_seed=100, cycle=5):
+def make_if_from_orbits(n_ms, sats, rx, tow0, amp=0.6, noise_amp=1.0, seed=7, nav_seed=100, cycle=5, two_bit=False, mag_threshold=0.6):
     """1-bit IF blocks [n_ms, 2046] a receiver at ECEF rx records from GPS time-of-week tow0 on (its clock IS GPS time):
     per satellite (raw, row) code, LNAV data and carrier, all delayed by the travel time of that millisecond (linear inside
     it) and shifted by the satellite's own clock offset.  tow0 must be a multiple of 6 s (a subframe boundary at the
-    satellites).  Also returns per satellite the Doppler (Hz) and code delay (samples into a block) at the first block."""
+    satellites).  Also returns per satellite the Doppler (Hz) and code delay (samples into a block) at the first block.
+    two_bit: [n_ms, 4092] sign / magnitude pairs in synth.pack_2bit's layout instead, of the same float samples (magnitude bit =
+    |x| > mag_threshold, as synth.make_if has it): the sign plane is the one-bit stream."""
     from stm32f4_sdr_gps_amd import synth
     assert tow0 % 6 == 0
     t_edges = tow0 + np.arange(n_ms + 1) * 1e-3
@@ -236,7 +238,7 @@ def make_if_from_orbits(n_ms, sats, rx, tow0, amp=0.6, noise_amp=1.0, seed=7, na
     frac = np.arange(synth.SAMPLES_PER_MS, dtype=np.float64) / synth.SAMPLES_PER_MS
     t_in_ms = frac * 1e-3
     quarter = (np.arange(synth.SAMPLES_PER_MS) % 4) * 0.25     # IF / fs = 1/4 cycle per sample, exactly
-    out = np.zeros((n_ms, synth.BYTES_PER_MS), np.uint8)
+    out = np.zeros((n_ms, 2 * synth.BYTES_PER_MS if two_bit else synth.BYTES_PER_MS), np.uint8)
 
     def chunk(m0m1):      # a run of milliseconds as [ms, sample] arrays: the same float64 arithmetic per sample whatever the
         m0, m1 = m0m1     # chunking (noise by position), large enough operations for the threads to run side by side
@@ -249,7 +251,12 @@ def make_if_from_orbits(n_ms, sats, rx, tow0, amp=0.6, noise_amp=1.0, seed=7, na
             bit = np.floor(t_sv / 0.02).astype(np.int64) + 300        # the stream began one subframe before tow0
             cyc = quarter[None, :] - F_L1 * lag
             x = x + amp * bits[bit] * code[chip] * np.cos(2.0 * math.pi * (cyc - np.floor(cyc)))
-        out[m0:m1] = np.packbits(x >= 0, axis=1, bitorder="little")
+        if two_bit:       # a whole chunk at once: sample n in bits 2 (n & 3) (sign) and 2 (n & 3) + 1 (magnitude) of byte n >> 2
+            pairs = np.empty((m1 - m0, 2 * synth.SAMPLES_PER_MS), bool)
+            pairs[:, 0::2], pairs[:, 1::2] = x >= 0, np.abs(x) > mag_threshold
+            out[m0:m1] = np.packbits(pairs, axis=1, bitorder="little")
+        else:
+            out[m0:m1] = np.packbits(x >= 0, axis=1, bitorder="little")
 
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(synth._n_threads()) as ex:
