@@ -34,7 +34,8 @@ extern "C" {
                                             * gpsx_track_loop_weighted(_dev) and gpsx_track_loop_weighted_sync(_dev) too (new
                                             * structs of their own); gpsx_wnav_words(_dev) and gpsx_wnav_subframe_image likewise;
                                             * gpsx_wobs(_dev) and gpsx_wobs_pseudoranges too; gpsx_weph(_dev) and
-                                            * gpsx_weph_to_eph (include/gpsx_compat.h) likewise. */
+                                            * gpsx_weph_to_eph (include/gpsx_compat.h) likewise; so are the four carrier-aided loop
+                                            * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -443,7 +444,9 @@ int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const
  * window, one 36-byte record per (window, channel) and nothing else back to the host.  cfg is per launch: a pull-in launch with
  * fll_c set and a small n_coh, then steady-state launches, on the same state array.  A grid record hands over by filling the
  * first four fields of a zeroed state (they ARE a gpsx_trk_state_t); the alignment of a 20 ms window with the data bit edge stays
- * the caller's business (the _hyb grid's guidance above).  No carrier aiding of the code loop: a satellite's code slides by
+ * the caller's business (the _hyb grid's guidance above).  No carrier aiding of the code loop in THIS call -- on real satellites
+ * use gpsx_track_loop_weighted_aided / gpsx_track_loop_weighted_sync_aided below, which feed the slide forward; this definition
+ * stays as it is for parity.  Unaided, a satellite's code slides by
  * fd x 0.01039 samples per second (fd / 1540 chips), the PI DLL follows that ramp with its integrator alone, and its discriminator
  * rests at d = fd x 0.01039 / dll_c2 -- with d(tau) = 16 tau / (64 + tau^2) at spacing 8, dll_c2 = 40 leaves the code 3.3 samples
  * behind at 2.7 kHz, d reaches 1 at |fd| = 3.85 kHz = dll_c2 x 96.25 Hz, and beyond that the code is lost.  On satellites on
@@ -614,6 +617,53 @@ int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg
                                       gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec);
 int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
                                   gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec);
+
+/* ---- EXTENSION, not in the reference: carrier aiding of the weighted code loop ----------------------------------------------------
+ * gpsx_track_loop_weighted and gpsx_track_loop_weighted_sync with ONE clause added to the DLL step of the window update: the code's
+ * slide, which the carrier loop knows from its own offset, is fed forward, so that the PI DLL no longer has to follow the ramp with
+ * its integrator.  An opt-in: the four unaided calls, their structs, their definitions and their kernels are unchanged, and cfg,
+ * state, record, slot and launch-cut rules, channel validation and the errors of the aided calls are the unaided calls' to the letter.
+ *
+ * Definition.  In the DLL step (float operations as above: one IEEE single operation each in the order written, no contraction)
+ *   phase = code_phase_fine - (dll_c1 * (d - dll_err) + (dll_c2 * T) * d)                     (as in the unaided call)
+ *   if code_per_hz != 0.0f:  phase = phase - (code_per_hz * if_freq_offset_hz) * T
+ *   one wrap towards [0, 16368) as in the unaided call, on that phase; code_phase_fine = phase; dll_err = d
+ * if_freq_offset_hz is the value the window's correlators ran with: the state's BEFORE this window's carrier step.  T is the
+ * window's own ((float)n_coh * 0.001f; in _sync (float)win_n * 0.001f), and in _sync the same factor serves SEARCH and LOCKED
+ * windows.  With code_per_hz == 0.0f the term is not formed and the call returns the unaided call's bytes.  A bad channel takes no
+ * step (its floats stay as they were).  For GPS L1 C/A at this sampling rate the factor is GPSX_WAID_L1CA: a Doppler of fd Hz
+ * moves the code by fd x 16 / 1540 samples per second towards smaller code_phase_fine.
+ * Rounding: the step is rounded into the phase, whose ulp is at most 2^-10 sample (phases of 8192 and above), so what a window's
+ * step loses is at most 2^-11 sample; nothing accumulates the remainders, the DLL sees them as part of its error.
+ * No step is taken while a _sync channel sits in WAIT (no window ends there): in up to 19 blocks the code slides by up to one
+ * sample at 5 kHz, and the DLL takes that back in the first locked windows.
+ * Which instant the recorded phase belongs to: the DLL zeroes the code error averaged over a window, and the step for window u is
+ * taken at its end, so the recorded code_phase_fine is the phase for the MIDDLE of the window that follows, seen from the record's
+ * instant (the window's end): against the true delay at that instant it is offset by about half a window's slide,
+ * 0.5 x fd x 0.01039 x T samples (0.28 at 2.7 kHz and T = 20 ms, 0.47 at 4.5 kHz), towards smaller phases for positive fd.
+ * Measured on the restatement, one satellite at +4500 / -4500 Hz, steady gains (0.5, 40), T = 20 ms: the recorded phase minus the true
+ * delay at the record's instant is +0.40 / +1.50 samples in the mean, and +0.87 / +1.03 against the delay half a window later -- the
+ * half-window term on either side of an offset of about 0.95 samples that all Dopplers share and a fix's clock term takes; the
+ * largest error at the record's instant is 0.77 / 1.90 samples (tests/weighted_aided_cases.py MEASURED; EXPERIMENTS.md "Carrier
+ * aiding of the weighted code loop").  gpsx_wobs is unchanged and does not take this term out.
+ * Errors: the unaided call's, and with them: aid NULL ("null argument"), code_per_hz not finite or of magnitude above 1,
+ * reserved != 0: GPSX_EINVAL with a gpsx_last_error text, nothing written.
+ * Vector ALU (k_track_waid_loop, k_track_waid_sync: the bodies of k_track_wloop and k_track_wsync instantiated with the clause; the
+ * same launch plan and resources). */
+#define GPSX_WAID_L1CA 0.010389610f          /* 16 samples per chip / 1540 carrier cycles per chip */
+typedef struct {
+  float   code_per_hz;           /* samples of code phase per second and Hz of carrier offset; |.| <= 1; 0: no aiding */
+  int32_t reserved;              /* 0 */
+} gpsx_waid_t;
+
+int gpsx_track_loop_weighted_aided_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const gpsx_waid_t *aid, const void *d_if_blocks_2bit,
+                                       int n_blocks, gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec);
+int gpsx_track_loop_weighted_aided(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const gpsx_waid_t *aid, const uint8_t *if_blocks_2bit,
+                                   int n_blocks, gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec);
+int gpsx_track_loop_weighted_sync_aided_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const void *d_if_blocks_2bit,
+                                            int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec);
+int gpsx_track_loop_weighted_sync_aided(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const uint8_t *if_blocks_2bit,
+                                        int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec);
 
 /* ---- EXTENSION, not in the reference: LNAV frame sync and parity-checked words from the sync loop's bit records -----------------
  * What lies between a BIT record of gpsx_track_loop_weighted_sync and a navigation word, done on the device: a kernel reads the

@@ -105,6 +105,18 @@ def check_no_scratch() -> dict:
     wsync = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted_sync.o")).items() if "k_track_wsync" in k}
     if len(wsync) != 1:
         raise RuntimeError(f"expected k_track_wsync in build/k_track_loop_weighted_sync.o, found {sorted(wsync)}")
+    # ... and the carrier-aided instance of each loop (k_track_waid_loop, k_track_waid_sync: the same kernel texts with window_update's
+    #     aiding clause, in the same objects; names of their own, so that the two counts above stay counts of the unaided kernels).
+    #     The same occupancy is asked of them: four waves per SIMD, 128 VGPRs
+    waid = {}
+    for obj, name in (("k_track_loop_weighted.o", "k_track_waid_loop"), ("k_track_loop_weighted_sync.o", "k_track_waid_sync")):
+        hits = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", obj)).items() if name in k}
+        if len(hits) != 1:
+            raise RuntimeError(f"expected {name} in build/{obj}, found {sorted(hits)}")
+        waid.update(hits)
+    wide = {k: v for k, v in waid.items() if v["vgprs"] > 128}
+    if wide:
+        raise RuntimeError(f"carrier-aided loop kernels above 128 VGPRs (four waves per SIMD): {wide}")
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -118,7 +130,7 @@ def check_no_scratch() -> dict:
     weph = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_weph.o")).items() if "k_weph" in k}
     if len(weph) != 1:
         raise RuntimeError(f"expected k_weph in build/k_weph.o, found {sorted(weph)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **wnav, **wobs, **weph}
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **waid, **wnav, **wobs, **weph}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

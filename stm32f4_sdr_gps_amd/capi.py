@@ -94,6 +94,19 @@ def wsync_slots(n_blocks, n_coh_search, n_coh_lock) -> int:
     return (n_blocks + span - 1) // span
 
 
+# gpsx_waid_t (carrier aiding of the weighted code loop: gpsx_track_loop_weighted_aided, gpsx_track_loop_weighted_sync_aided)
+WAID_L1CA = np.float32(0.010389610)      # GPSX_WAID_L1CA: 16 samples per chip / 1540 carrier cycles per chip
+WAID_DTYPE = np.dtype([("code_per_hz", "<f4"), ("reserved", "<i4")])
+assert WAID_DTYPE.itemsize == 8
+
+
+def waid(code_per_hz=WAID_L1CA) -> np.ndarray:
+    """a gpsx_waid_t as a one-element WAID_DTYPE array"""
+    aid = np.zeros(1, WAID_DTYPE)
+    aid["code_per_hz"] = code_per_hz
+    return aid
+
+
 # gpsx_wnav_cfg_t / gpsx_wnav_state_t / gpsx_wnav_word_t (LNAV frame sync and parity-checked words from the sync loop's records)
 WNAV_HUNT, WNAV_SYNCED = 0, 1
 WNAV_FLAG_WORD, WNAV_FLAG_OK, WNAV_FLAG_INVERTED, WNAV_FLAG_SYNC, WNAV_FLAG_FLIPPED, WNAV_FLAG_SUBFRAME, WNAV_FLAG_DROPPED = 1, 2, 4, 8, 16, 32, 64
@@ -273,6 +286,10 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_track_loop_weighted_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
     lib.gpsx_track_loop_weighted_sync.argtypes = lib.gpsx_track_loop_weighted.argtypes
     lib.gpsx_track_loop_weighted_sync_dev.argtypes = lib.gpsx_track_loop_weighted.argtypes
+    lib.gpsx_track_loop_weighted_aided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_track_loop_weighted_aided_dev.argtypes = lib.gpsx_track_loop_weighted_aided.argtypes
+    lib.gpsx_track_loop_weighted_sync_aided.argtypes = lib.gpsx_track_loop_weighted_aided.argtypes
+    lib.gpsx_track_loop_weighted_sync_aided_dev.argtypes = lib.gpsx_track_loop_weighted_aided.argtypes
     lib.gpsx_wnav_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wnav_words_dev.argtypes = lib.gpsx_wnav_words.argtypes
     lib.gpsx_wnav_subframe_image.argtypes = [C.c_void_p, C.c_void_p]
@@ -667,6 +684,31 @@ class Engine:
         rec = np.zeros((wsync_slots(len(blocks), int(cfg["n_coh_search"][0]), int(cfg["n_coh_lock"][0])), n_ch), WSYNC_REC_DTYPE)
         self._chk(self.lib.gpsx_track_loop_weighted_sync(self.h, cfg.ctypes.data, blocks.ctypes.data, len(blocks), C.c_void_p(d_state),
                                                          n_ch, rec.ctypes.data), "gpsx_track_loop_weighted_sync")
+        return rec
+
+    def track_loop_weighted_aided(self, blocks_2bit: np.ndarray, d_state: int, n_ch: int, n_coh: int, code_per_hz: float = WAID_L1CA,
+                                  use_magnitude: bool = True, spacing: int = 8, dll=(1.0, 300.0), pll=(4.0, 3000.0),
+                                  fll: float = 0.0) -> np.ndarray:
+        """EXTENSION: track_loop_weighted with carrier aiding of the code loop: per window the code phase also steps by
+        -(code_per_hz * if_freq_offset_hz) * T, the offset the window ran with (code_per_hz 0: track_loop_weighted's bytes).
+        -> WLOOP_REC_DTYPE [n_blocks / n_coh, n_ch]"""
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        cfg, aid = wloop_cfg(n_coh, use_magnitude, spacing, dll, pll, fll), waid(code_per_hz)
+        rec = np.zeros((len(blocks) // max(n_coh, 1), n_ch), WLOOP_REC_DTYPE)
+        self._chk(self.lib.gpsx_track_loop_weighted_aided(self.h, cfg.ctypes.data, aid.ctypes.data, blocks.ctypes.data, len(blocks),
+                                                          C.c_void_p(d_state), n_ch, rec.ctypes.data), "gpsx_track_loop_weighted_aided")
+        return rec
+
+    def track_loop_weighted_sync_aided(self, blocks_2bit: np.ndarray, d_state: int, n_ch: int, cfg: np.ndarray,
+                                       code_per_hz: float = WAID_L1CA) -> np.ndarray:
+        """EXTENSION: track_loop_weighted_sync with carrier aiding of the code loop (as track_loop_weighted_aided; the same factor in
+        SEARCH and LOCKED windows, no step in WAIT).  -> WSYNC_REC_DTYPE [slots, n_ch]"""
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        assert cfg.dtype == WSYNC_CFG_DTYPE and cfg.size == 1
+        aid = waid(code_per_hz)
+        rec = np.zeros((wsync_slots(len(blocks), int(cfg["n_coh_search"][0]), int(cfg["n_coh_lock"][0])), n_ch), WSYNC_REC_DTYPE)
+        self._chk(self.lib.gpsx_track_loop_weighted_sync_aided(self.h, cfg.ctypes.data, aid.ctypes.data, blocks.ctypes.data, len(blocks),
+                                                               C.c_void_p(d_state), n_ch, rec.ctypes.data), "gpsx_track_loop_weighted_sync_aided")
         return rec
 
     def wnav_words(self, d_rec: int, n_slots: int, n_blocks: int, d_state: int, n_ch: int, max_bad_words: int = 3) -> np.ndarray:

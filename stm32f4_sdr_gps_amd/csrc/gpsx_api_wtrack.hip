@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync, gpsx_wnav_words, gpsx_wobs, gpsx_weph, each with its _dev twin, and the two
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_wnav_words, gpsx_wobs, gpsx_weph, each with its _dev twin, and the two
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -33,6 +33,13 @@ int check_gains(gpsx_ctx *ctx, std::initializer_list<float> gains)
     if (!(__builtin_fabsf(g) <= 3.402823466e+38f))
       return fail(ctx, GPSX_EINVAL, "a loop gain is not finite");
   return GPSX_OK;
+}
+// the aided calls' own clauses (aided: the call has an `aid` argument at all)
+int check_aid(gpsx_ctx *ctx, const gpsx_waid_t *aid)
+{
+  if (!(__builtin_fabsf(aid->code_per_hz) <= 1.0f))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "code_per_hz must be finite and -1..1");
+  return aid->reserved != 0 ? fail(ctx, GPSX_EINVAL, "reserved must be 0") : GPSX_OK;
 }
 bool records_overflow(size_t count, int n_ch, size_t each, size_t *bytes)
 {
@@ -114,11 +121,12 @@ int stage_loop_call(gpsx_ctx *ctx, const uint8_t *if_blocks_2bit, int n_blocks, 
   return GPSX_OK;
 }
 
-int track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *if_blocks_2bit, int n_blocks, gpsx_wloop_state_t *d_state,
-                        int n_ch, gpsx_wloop_rec_t *rec, bool host)
+// `aided`: the _aided pair (k_track_waid_loop with aid's factor); otherwise aid is not looked at
+int track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, bool aided, const gpsx_waid_t *aid, const void *if_blocks_2bit, int n_blocks,
+                        gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec, bool host)
 {
   if (int rc = use_device(ctx)) return rc;
-  if (!cfg || !if_blocks_2bit || !d_state || !rec)
+  if (!cfg || (aided && !aid) || !if_blocks_2bit || !d_state || !rec)
     return fail(ctx, GPSX_EINVAL, "null argument");
   if (int rc = check_weights_spacing(ctx, cfg->weights, cfg->spacing)) return rc;
   if (cfg->n_coh < 1 || cfg->n_coh > 20)
@@ -128,6 +136,8 @@ int track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *
     return fail(ctx, GPSX_EINVAL, "n_blocks must be a multiple of n_coh");
   if (int rc = check_n_ch(ctx, n_ch)) return rc;
   if (int rc = check_gains(ctx, {cfg->dll_c1, cfg->dll_c2, cfg->pll_c1, cfg->pll_c2, cfg->fll_c})) return rc;
+  if (aided)
+    if (int rc = check_aid(ctx, aid)) return rc;
   size_t rec_bytes = 0;
   if (records_overflow((size_t)(n_blocks / cfg->n_coh), n_ch, sizeof(gpsx_wloop_rec_t), &rec_bytes))
     return fail(ctx, GPSX_EINVAL, "windows x n_ch records overflow a size");
@@ -136,16 +146,21 @@ int track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *
   if (host)
     if (int rc = stage_loop_call(ctx, d_if, n_blocks, rec_bytes, &d_if, &d_rec)) return rc;
   return launch_and_report(
-      ctx, host, "k_track_wloop", nullptr,
-      [&](uint32_t *flag) { launch_track_loop_weighted(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag); },
+      ctx, host, aided ? "k_track_waid_loop" : "k_track_wloop", nullptr,
+      [&](uint32_t *flag) {
+        if (aided)
+          launch_track_loop_weighted_aided(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, aid->code_per_hz, d_state, n_ch, ctx->d_trk_rep, d_rec, flag);
+        else
+          launch_track_loop_weighted(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag);
+      },
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
-int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *if_blocks_2bit, int n_blocks,
-                             gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec, bool host)
+int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, bool aided, const gpsx_waid_t *aid, const void *if_blocks_2bit,
+                             int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec, bool host)
 {
   if (int rc = use_device(ctx)) return rc;
-  if (!cfg || !if_blocks_2bit || !d_state || !rec)
+  if (!cfg || (aided && !aid) || !if_blocks_2bit || !d_state || !rec)
     return fail(ctx, GPSX_EINVAL, "null argument");
   if (int rc = check_weights_spacing(ctx, cfg->weights, cfg->spacing)) return rc;
   for (int n : {cfg->n_coh_search, cfg->n_coh_lock})
@@ -161,6 +176,8 @@ int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const v
   if (int rc = check_n_ch(ctx, n_ch)) return rc;
   for (const gpsx_wsync_gains_t *g : {&cfg->search, &cfg->lock})
     if (int rc = check_gains(ctx, {g->dll_c1, g->dll_c2, g->pll_c1, g->pll_c2, g->fll_c})) return rc;
+  if (aided)
+    if (int rc = check_aid(ctx, aid)) return rc;
   const int span = cfg->n_coh_search < cfg->n_coh_lock ? cfg->n_coh_search : cfg->n_coh_lock;
   size_t rec_bytes = 0;
   if (records_overflow((size_t)((n_blocks + span - 1) / span), n_ch, sizeof(gpsx_wsync_rec_t), &rec_bytes))
@@ -170,8 +187,13 @@ int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const v
   if (host)
     if (int rc = stage_loop_call(ctx, d_if, n_blocks, rec_bytes, &d_if, &d_rec)) return rc;
   return launch_and_report(
-      ctx, host, "k_track_wsync", nullptr,
-      [&](uint32_t *flag) { launch_track_loop_weighted_sync(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag); },
+      ctx, host, aided ? "k_track_waid_sync" : "k_track_wsync", nullptr,
+      [&](uint32_t *flag) {
+        if (aided)
+          launch_track_loop_weighted_sync_aided(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, aid->code_per_hz, d_state, n_ch, ctx->d_trk_rep, d_rec, flag);
+        else
+          launch_track_loop_weighted_sync(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag);
+      },
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
@@ -281,25 +303,49 @@ int gpsx_track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const
 int gpsx_track_loop_weighted_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
                                  gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec)
 {
-  return track_loop_weighted(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
+  return track_loop_weighted(ctx, cfg, false, nullptr, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
 }
 
 int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
                              gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec)
 {
-  return track_loop_weighted(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
+  return track_loop_weighted(ctx, cfg, false, nullptr, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
+}
+
+int gpsx_track_loop_weighted_aided_dev(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const gpsx_waid_t *aid, const void *d_if_blocks_2bit,
+                                       int n_blocks, gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *d_rec)
+{
+  return track_loop_weighted(ctx, cfg, true, aid, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
+}
+
+int gpsx_track_loop_weighted_aided(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const gpsx_waid_t *aid, const uint8_t *if_blocks_2bit,
+                                   int n_blocks, gpsx_wloop_state_t *d_state, int n_ch, gpsx_wloop_rec_t *rec)
+{
+  return track_loop_weighted(ctx, cfg, true, aid, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
 }
 
 int gpsx_track_loop_weighted_sync_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
                                       gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec)
 {
-  return track_loop_weighted_sync(ctx, cfg, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
+  return track_loop_weighted_sync(ctx, cfg, false, nullptr, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
 }
 
 int gpsx_track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const uint8_t *if_blocks_2bit, int n_blocks,
                                   gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec)
 {
-  return track_loop_weighted_sync(ctx, cfg, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
+  return track_loop_weighted_sync(ctx, cfg, false, nullptr, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
+}
+
+int gpsx_track_loop_weighted_sync_aided_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const void *d_if_blocks_2bit,
+                                            int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec)
+{
+  return track_loop_weighted_sync(ctx, cfg, true, aid, d_if_blocks_2bit, n_blocks, d_state, n_ch, d_rec, false);
+}
+
+int gpsx_track_loop_weighted_sync_aided(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const uint8_t *if_blocks_2bit,
+                                        int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec)
+{
+  return track_loop_weighted_sync(ctx, cfg, true, aid, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
 }
 
 int gpsx_wnav_words_dev(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,

@@ -146,6 +146,15 @@ void launch_track_loop_weighted(hipStream_t s, const uint8_t *d_if_blocks_2bit, 
 void launch_track_loop_weighted_sync(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
                                      gpsx_wsync_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wsync_rec_t *d_rec,
                                      uint32_t *d_bad_prn);
+// extension: gpsx_track_loop_weighted_aided / _sync_aided (k_track_waid_loop, k_track_waid_sync: the two kernels' bodies instantiated
+// with the carrier aiding clause of gpsx_track_wloop_parts.hpp's window_update, in the same files) -- everything as the two launches
+// above; code_per_hz: samples of code phase per second and Hz of carrier offset (0: the unaided bytes).
+void launch_track_loop_weighted_aided(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wloop_cfg_t &cfg,
+                                      float code_per_hz, gpsx_wloop_state_t *d_st, int n_ch, const uint32_t *d_trk_rep, gpsx_wloop_rec_t *d_rec,
+                                      uint32_t *d_bad_prn);
+void launch_track_loop_weighted_sync_aided(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
+                                           float code_per_hz, gpsx_wsync_state_t *d_st, int n_ch, const uint32_t *d_trk_rep,
+                                           gpsx_wsync_rec_t *d_rec, uint32_t *d_bad_prn);
 // extension: gpsx_wnav_words (k_wnav_words.hip: k_wnav_words) -- LNAV frame sync and parity-checked words from the [n_slots][n_ch]
 // records launch_track_loop_weighted_sync wrote for n_blocks blocks: one channel per lane, 64-byte frame states in HBM,
 // d_words [n_blocks / 600 + 2][n_ch], every byte of it written.  d_bad_state (may be null): set to 1 by a channel whose state

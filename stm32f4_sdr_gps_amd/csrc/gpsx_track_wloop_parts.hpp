@@ -1,5 +1,6 @@
 // gpsx_track_wloop_parts.hpp -- what the two closed loops on weighted two-bit samples share beyond the correlators of
-// gpsx_track_weighted_wave.hpp: k_track_wloop (k_track_loop_weighted.hip) and k_track_wsync (k_track_loop_weighted_sync.hip).  The
+// gpsx_track_weighted_wave.hpp: k_track_wloop (k_track_loop_weighted.hip) and k_track_wsync (k_track_loop_weighted_sync.hip), and the
+// carrier-aided instances of the same two bodies beside them (k_track_waid_loop, k_track_waid_sync).  The
 // lanes' places, the loop state in registers, a window's start and -- the ONE copy of it -- the DLL / Costas PLL / FLL update.
 // That update is exact arithmetic: every float operation one IEEE single operation in the order written (both files are built with
 // -ffp-contract=off and correctly rounded division), the arctangent gpsx_libm.hpp's; tests/weighted_loop_ref.py restates it and is
@@ -36,8 +37,12 @@ static_assert(sizeof(Live) == 32 && sizeof(gpsx_wloop_state_t) == 40 && offsetof
 // constants: the compiler hoists them out of its block loop)
 struct Gains { float dll_c1, dll_c2, pll_c1, pll_c2, fll_c, T; };
 
-// the window's end for a good channel: its six sums -> code phase, carrier offset and loop memory
-__device__ __forceinline__ void window_update(Live &s, const Gains &g, int IE, int QE, int IP, int QP, int IL, int QL)
+// the window's end for a good channel: its six sums -> code phase, carrier offset and loop memory.  Aided (the k_track_waid_*
+// kernels; include/gpsx.h gpsx_track_loop_weighted_aided): the carrier offset the window's correlators ran with -- read before the
+// carrier step below -- feeds the code's slide forward, one product per window, ahead of the wrap.  code_per_hz == 0: no term, the
+// unaided bytes.  Without Aided the parameter is not read and the function is what it was.
+template <bool Aided = false>
+__device__ __forceinline__ void window_update(Live &s, const Gains &g, int IE, int QE, int IP, int QP, int IL, int QL, float code_per_hz = 0.0f)
 {
   // DLL
   const long long e2 = (long long)IE * IE + (long long)QE * QE, l2 = (long long)IL * IL + (long long)QL * QL;
@@ -45,6 +50,9 @@ __device__ __forceinline__ void window_update(Live &s, const Gains &g, int IE, i
   if (e2 + l2 != 0)
     d = (float)(e2 - l2) / (float)(e2 + l2);
   float phase = s.code_phase_fine - (g.dll_c1 * (d - s.dll_err) + (g.dll_c2 * g.T) * d);
+  if constexpr (Aided)
+    if (code_per_hz != 0.0f)
+      phase = phase - (code_per_hz * s.if_freq_offset_hz) * g.T;
   if (phase < 0.0f)
     phase = phase + kSpan;
   else if (phase >= kSpan)

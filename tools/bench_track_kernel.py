@@ -13,7 +13,9 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       and measured against: gpsx_track_epl_weighted_dev at K = 20 (the same correlators,
                                                       open loop), and the sign plane's pair gpsx_track_loop_dev (K = 200) /
                                                       gpsx_track_epl_batch_dev -- time per channel-millisecond and the two
-                                                      closed-over-open ratios; then the host-driven alternative: one K = 200,
+                                                      closed-over-open ratios, and gpsx_track_loop_weighted_aided_dev (carrier
+                                                      aiding, GPSX_WAID_L1CA) beside every unaided row with that row timed a
+                                                      second time for the spread; then the host-driven alternative: one K = 200,
                                                       n_coh = 10 launch against twenty gpsx_track_epl_weighted calls of K = 10 with the
                                                       records copied back and the states rewritten by the host (wall clock)
   bench_track_kernel.py --weighted-sync [channels ...]
@@ -22,7 +24,8 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       with edges spread over 0 .. 19, (b) the same with all edges equal, (c) every channel
                                                       in SEARCH at n_coh_search = 4 (ratio 1024 / 1: noise never leaves it) -- beside
                                                       gpsx_track_loop_weighted_dev at n_coh = 1, 4, 20 in the same process, the calls
-                                                      taking turns; then the wall clock of 2000 ms in host launches of 200 with the
+                                                      taking turns, and gpsx_track_loop_weighted_sync_aided_dev (carrier aiding) beside
+                                                      every leg with the leg timed a second time; then the wall clock of 2000 ms in host launches of 200 with the
                                                       records copied back
   bench_track_kernel.py --weighted-nav [channels ...]
                                                       gpsx_wnav_words_dev (EXTENSION: LNAV frame sync and parity-checked words from the
@@ -192,7 +195,22 @@ def weighted_loop(n_coh_arg, counts, k_loop=200, k_open=20):
             cfgs[n_coh] = capi.wloop_cfg(n_coh, True, 8, (1.0, 300.0), (4.0, 3000.0), 0.1)
             calls[f"weighted_loop_k{k_loop}_ncoh{n_coh}"] = (k_loop, lambda c=cfgs[n_coh]: eng.lib.gpsx_track_loop_weighted_dev(
                 eng.h, c.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d_wst), n, C.c_void_p(d_rec)))
+        # the carrier-aided call beside each unaided row (k_track_waid_loop, GPSX_WAID_L1CA, states of its own), and the unaided row
+        # a second time: what two rows of ONE kernel differ by is the spread the aided row is read against
+        d_wst_aid = eng.malloc(wst.nbytes)
+        eng.h2d(d_wst_aid, wst)
+        aid = capi.waid()
+        for n_coh in cfgs:
+            calls[f"weighted_loop_aided_k{k_loop}_ncoh{n_coh}"] = (k_loop, lambda c=cfgs[n_coh]: eng.lib.gpsx_track_loop_weighted_aided_dev(
+                eng.h, c.ctypes.data, aid.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d_wst_aid), n, C.c_void_p(d_rec)))
+            calls[f"weighted_loop_k{k_loop}_ncoh{n_coh}_again"] = calls[f"weighted_loop_k{k_loop}_ncoh{n_coh}"]
         med = _timed_rows(eng, calls, {"channels": n})
+        for n_coh in cfgs:
+            base = med[f"weighted_loop_k{k_loop}_ncoh{n_coh}"]
+            print(json.dumps({"ratio": "k_track_waid_loop over k_track_wloop", "channels": n, "n_coh": n_coh,
+                              "aided": round(med[f"weighted_loop_aided_k{k_loop}_ncoh{n_coh}"] / base, 4),
+                              "unaided_again": round(med[f"weighted_loop_k{k_loop}_ncoh{n_coh}_again"] / base, 4)}), flush=True)
+        eng.free(d_wst_aid)
         per = {name: med[name] / calls[name][0] for name in calls}
         sign_ratio = per[f"sign_loop_k{k_loop}"] / per["sign_epl_k1"]
         for n_coh in cfgs:
@@ -261,7 +279,23 @@ def weighted_sync(counts, k_loop=200):
             keep.append(c)
             calls[f"weighted_sync_k{k_loop}_{leg}"] = (k_loop, lambda c=c, d=d_sync[leg]: eng.lib.gpsx_track_loop_weighted_sync_dev(
                 eng.h, c.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d), n, C.c_void_p(d_srec)))
+        # the carrier-aided call beside each leg (k_track_waid_sync, GPSX_WAID_L1CA, states of its own), and the unaided leg a second
+        # time: the spread the aided row is read against
+        d_aid = {leg: eng.malloc(st.nbytes) for leg, st in legs.items()}
+        aid = capi.waid()
+        for i, leg in enumerate(legs):
+            eng.h2d(d_aid[leg], legs[leg])
+            calls[f"weighted_sync_aided_k{k_loop}_{leg}"] = (k_loop, lambda c=keep[3 + i], d=d_aid[leg]: eng.lib.gpsx_track_loop_weighted_sync_aided_dev(
+                eng.h, c.ctypes.data, aid.ctypes.data, C.c_void_p(d_if2), k_loop, C.c_void_p(d), n, C.c_void_p(d_srec)))
+            calls[f"weighted_sync_k{k_loop}_{leg}_again"] = calls[f"weighted_sync_k{k_loop}_{leg}"]
         med = _timed_rows(eng, calls, {"channels": n})
+        for leg in legs:
+            base = med[f"weighted_sync_k{k_loop}_{leg}"]
+            print(json.dumps({"ratio": "k_track_waid_sync over k_track_wsync", "channels": n, "leg": leg,
+                              "aided": round(med[f"weighted_sync_aided_k{k_loop}_{leg}"] / base, 4),
+                              "unaided_again": round(med[f"weighted_sync_k{k_loop}_{leg}_again"] / base, 4)}), flush=True)
+        for p in d_aid.values():
+            eng.free(p)
         for leg, against in (("a_locked_spread", 1), ("b_locked_equal", 20), ("c_search", 4)):
             ratio = med[f"weighted_sync_k{k_loop}_{leg}"] / med[f"weighted_loop_k{k_loop}_ncoh{against}"]
             print(json.dumps({"ratio": "k_track_wsync over k_track_wloop", "channels": n, "leg": leg, "against_n_coh": against,

@@ -1,9 +1,11 @@
 """The weighted chain from orbiting satellites' IF samples to a position, on the CPU restatements, for three steady DLL gain pairs and
 the three hand-over errors of tests/weighted_loop_cases.HANDOVER: the measurement behind tests/weighted_pvt_cases.py's MOVING gains
 and BOUNDS (EXPERIMENTS.md has the table).  No GPU; needs the built library for the solver.  Nine chain runs side by side: about
-4 minutes on 8 CPUs.
+4 minutes on 8 CPUs.  Then the same three hand-overs with the quiet pair (0.5, 40) and carrier aiding of the code loop
+(gpsx_track_loop_weighted_sync_aided's restatement, GPSX_WAID_L1CA), the rows behind tests/weighted_aided_cases.py's MEASURED: with a
+lag model of zero their residual column is the transmit-time error minus the four channels' mean.
 
-    python tools/experiments/weighted_pvt_gains.py
+    python tools/experiments/weighted_pvt_gains.py [--aided-only]
 """
 import os
 import sys
@@ -13,13 +15,34 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import weighted_aided_cases as W  # noqa: E402
 import weighted_loop_cases as S  # noqa: E402
+import weighted_obs_ref as O  # noqa: E402
 import weighted_pvt_cases as P  # noqa: E402
+
+
+def aided_rows(lib):
+    handovers = [S.HANDOVER[h] for h in (1, 2, 3)]
+    for errors, (out, st) in zip(handovers, W.chains_on_restatements(handovers)):
+        try:
+            P.check_conditions(out, st)
+            ok = "hold"
+        except AssertionError as e:
+            ok = "FAIL " + str(e)[:60]
+        worst = max(float(np.abs(W.tx_residuals(o[4], o[0] + o[1])[1]).max()) for o in out if (o[4]["flags"] & O.F_VALID).all())
+        obs, eph = out[-1][4], out[-1][5]
+        err = P.tx_errors(obs, P.N_BLOCKS)
+        fixes = [P.position(lib, obs, eph, P.PRNS, off) for off in P.OFFSETS_MS]
+        clock = [(f["dtr"] - (off * 1e-3 - P.lag_s(P.sats()[f["ref"]][1], P.N_BLOCKS))) * 1e6 for f, off in zip(fixes, P.OFFSETS_MS)]
+        print(f"| {P.STILL['dll']} aided | {errors} | {ok} | {worst:.2f} | {' / '.join(f'{e:+.2f}' for e in err)} | "
+              f"{' / '.join(f'{P.position_error(f):.2f}' for f in fixes)} | {' / '.join(f'{c:+.3f}' for c in clock)} |")
 
 
 def main():
     from stm32f4_sdr_gps_amd import capi
     lib = capi.load_library()
+    if "--aided-only" in sys.argv[1:]:
+        return aided_rows(lib)
     combos = [(g, S.HANDOVER[h]) for g in ("still", "moving", "moving_ref") for h in (1, 2, 3)]
     chains = P.chains_on_restatements(combos)
     print("| steady DLL (c1, c2) | hand-over | conditions | largest lag residual (samples) | error at block 25 000 (samples) | position error (m) at 68.802 / 70 ms | clock term - (offset - travel), us |")
@@ -37,6 +60,7 @@ def main():
         clock = [(f["dtr"] - (off * 1e-3 - P.lag_s(P.sats()[f["ref"]][1], P.N_BLOCKS))) * 1e6 for f, off in zip(fixes, P.OFFSETS_MS)]
         print(f"| {P.GAINS[gains]['dll']} | {errors} | {ok} | {worst:.2f} | {' / '.join(f'{e:+.2f}' for e in err)} | "
               f"{' / '.join(f'{P.position_error(f):.2f}' for f in fixes)} | {' / '.join(f'{c:+.3f}' for c in clock)} |")
+    aided_rows(lib)
     print()
     for gains in ("still", "moving"):
         out, _ = chains[combos.index((gains, S.HANDOVER[1]))]
