@@ -35,7 +35,8 @@ extern "C" {
                                             * structs of their own); gpsx_wnav_words(_dev) and gpsx_wnav_subframe_image likewise;
                                             * gpsx_wobs(_dev) and gpsx_wobs_pseudoranges too; gpsx_weph(_dev) and
                                             * gpsx_weph_to_eph (include/gpsx_compat.h) likewise; so are the four carrier-aided loop
-                                            * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t. */
+                                            * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t; gpsx_wlock(_dev) and
+                                            * gpsx_wlock_cn0_dbhz likewise. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -523,7 +524,8 @@ int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const u
  *
  * Bit sync is NOT a presence detector: on noise alone two rounds agree with probability 1 / 20 and the energy ratio reaches what
  * weak signals give.  The caller decides whether a satellite is there (acquisition, the records' prompt energy) and re-arms a
- * search by writing mode = 0 into the state (search_n = 0 and prev_best_p1 = 0 with it for a fresh one).
+ * search by writing mode = 0 into the state (search_n = 0 and prev_best_p1 = 0 with it for a fresh one).  gpsx_wlock below makes
+ * that decision on the device from the records, and with its `rearm` does the writes.
  *
  * Definition, per channel and block b = 0 .. n_blocks - 1 of the launch, in this order.  Float operations as above: one IEEE
  * single operation each in the order written.  "The mode's" n_coh and gains: n_coh_search / `search` in SEARCH, n_coh_lock /
@@ -966,6 +968,125 @@ int gpsx_weph_dev(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_wor
                   gpsx_weph_state_t *d_state, int n_ch, gpsx_weph_t *d_eph);
 int gpsx_weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks,
               gpsx_weph_state_t *d_state, int n_ch, gpsx_weph_t *eph /* host */);
+
+/* ---- EXTENSION, not in the reference: weighted lock monitor -- is a channel tracking a satellite, and how strong, on the device ----
+ * What no stage above says: whether a channel's records are a satellite's at all.  gpsx_wlock(_dev) is a fifth reader of the sync
+ * loop's window records d_rec[n_slots][n_ch] (beside gpsx_wnav_words, gpsx_wobs and, through the words, gpsx_weph): a kernel reads
+ * the six correlator sums and the flags of every record, keeps a 128-byte state per channel and returns one 64-byte record per
+ * channel and launch: a code-lock (presence) and a carrier-lock indicator with hysteresis, the three ratios they rest on (one of
+ * them the C/N0 estimator's), loss events, and -- an opt-in -- the re-arm of the bit search that gpsx_track_loop_weighted_sync
+ * leaves to its caller.  Nothing existing changes.
+ *
+ * Definition, per channel.  Every float operation is one IEEE single operation in the order written: no contraction, int64 ->
+ * float rounds to nearest even, correctly rounded division.  The slots of d_rec are read in order.  A record counts if its flags
+ * have GPSX_WSYNC_WINDOW and 0 <= end_block < n_blocks (gpsx_wobs's rule, without the phase); every other record is skipped.
+ * With IE, QE, IP, QP, IL, QL = w.iq[0 .. 5] and locked = the record has GPSX_WSYNC_LOCKED_FLAG, for a record that counts:
+ *   1 range        if any |iq[k]| >= 2^20: n_range++, the launch's record gets GPSX_WLOCK_RANGE, and nothing else happens for this
+ *                  record.  (The sync loop's own sums stay below 20 x 49 056 < 2^20; only a caller's state can exceed that.)
+ *   2 SEARCH       if !locked: if CARRIER is set it is cleared, n_lost_carrier++ and the launch's record gets LOST_CARRIER;
+ *                  car_good = car_bad = 0, false_run = 0
+ *   3 kind         if epoch_n > 0 and the open epoch's kind (OPEN_LOCKED) differs from `locked`: the open epoch is discarded
+ *                  (the five sums = 0, epoch_n = 0).  OPEN_LOCKED = locked
+ *   4 sums         in int64, exactly: A += |IP|, P += IP^2 + QP^2, D += IP^2 - QP^2, E += IE^2 + QE^2, L += IL^2 + QL^2; epoch_n++
+ *   5 epoch end    if epoch_n >= (locked ? epoch_lock : epoch_search), with K = epoch_n:
+ *                    code_ratio = (E + L == 0) ? 0 : (float)(2 P) / (float)(E + L)
+ *                    car_ratio  = (P == 0) ? 0 : (float)D / (float)P
+ *                    snr        = (K P - A A == 0) ? 0 : (float)(A A) / (float)(K P - A A)
+ *                  They, P, K and the kind become the newest epoch's (last_*; EPOCH_LOCKED = locked), last_epoch_end_p1 =
+ *                  blocks_seen + end_block + 1, the launch's n_epochs++, then
+ *                  5a code     good = code_ratio >= code_min.  good: code_bad = 0, code_good = min(code_good + 1, 255), and
+ *                              code_good >= n_good sets CODE.  Not good: code_good = 0, code_bad = min(code_bad + 1, 255), and if
+ *                              CODE is set and code_bad >= n_bad: CODE is cleared, n_lost_code++, the launch's record gets
+ *                              LOST_CODE, and if rearm & 1 PENDING is set
+ *                  5b carrier  only if locked: good = car_ratio >= car_min && snr >= snr_min; was = CARRIER before this step.  The
+ *                              same rule on car_good, car_bad, CARRIER, n_lost_carrier and LOST_CARRIER (no PENDING from a loss).
+ *                              Then false_run = good || was ? 0 : false_run + 1, and if !good && !was && (rearm & 2) && false_run >=
+ *                              patience: PENDING is set and false_run = 0 -- a bit synchroniser that locked on noise or on a false
+ *                              frequency (the 1-in-20 remark of gpsx_track_loop_weighted_sync) never gets a carrier verdict
+ *                  then the five sums = 0 and epoch_n = 0.
+ * The bound of step 1 is what keeps every integer exact: a square is below 2^40, a window's term below 2^41, an epoch has at most
+ * 1024 windows (cfg's bound; a state's epoch_n is at most 1023 before step 4), so P, E, L, |D| <= 2^51 + 2^41, 2 P and E + L stay
+ * below 2^53, A <= 2^30 + 2^20, A A < 2^61 and K P < 2^62.  K P - A A >= 0 from sums this call formed (Cauchy-Schwarz on |IP|).
+ * What they are: code_ratio is the prompt's energy against the two half-chip taps' (about 1 on noise, 3 to 4 on a tracked
+ * code at a spacing of half a chip); it needs no phase lock and no bit alignment, so it works in SEARCH.  car_ratio is the narrow-band
+ * estimate of cos 2 phi, insensitive to data bits.  snr is the signal-to-noise-variance estimator on a window's prompt.
+ * At the launch's end: blocks_seen += n_blocks.  Then, if PENDING is set: if rearm != 0 and d_sync_state[ch].mode ==
+ * GPSX_WSYNC_LOCKED the channel's sync state gets what gpsx_track_loop_weighted_sync prescribes for a caller -- mode = 0,
+ * search_n = 0, prev_best_p1 = 0, and the open window discarded as an accept discards it: win_iq = 0, win_n = 0, bit_ip = 0,
+ * loop.n_updates = 0 -- the launch's record gets REARMED, n_rearm++, CODE and CARRIER, the four run counters, false_run and the
+ * open epoch (its sums, epoch_n and OPEN_LOCKED) are cleared.  PENDING is cleared in every case: a channel that has left LOCKED by itself needs no write, and with
+ * rearm == 0 nothing can act on it.  gpsx_wlock_dev is enqueued behind the sync launch on the context's stream; it reads the sync
+ * state only here, the mode word of PENDING channels alone, and writes only the fields above, so no launch of the sync loop runs
+ * beside it.  With rearm == 0 d_sync_state may be NULL and is never touched.
+ * Where a stream is cut into launches matters to the states only through the re-arm (which acts at a launch's end) and to the
+ * records only in their per-launch fields: n_epochs, the event flags and age_blocks.  The counters n_* wrap at 2^32, as false_run.
+ * Errors: NULL pointers (d_sync_state only with rearm != 0), epoch_search or epoch_lock outside 1 .. 1024, n_good or n_bad outside
+ * 1 .. 255, a threshold that is not finite, rearm outside 0 .. 3, patience < 0, reserved != 0, n_blocks outside 1 .. 4096, n_slots
+ * outside 1 .. n_blocks, n_ch < 1 and a size that overflows return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.
+ * A channel is BAD if its state has flag bits other than CODE .. EPOCH_LOCKED or a reserved word != 0, if blocks_seen or
+ * last_epoch_end_p1 lies outside 0 .. 2^62, if epoch_n > 1023 or last_k > 1024, if a run counter exceeds 255, if sum_a lies outside
+ * 0 .. 2^30, sum_p, sum_e or sum_l outside 0 .. 2^51 or |sum_d| > 2^51: its state (and its sync state) stays as it was, its record
+ * is all zero with age_blocks = -1, and GPSX_EINVAL comes from gpsx_wlock after its wait / from the next gpsx_synchronize() after
+ * _dev.  Vector ALU (k_wlock: one channel per lane, 32 of a record's 48 bytes loaded four slots ahead of the recurrence). */
+#define GPSX_WLOCK_CODE          1u    /* the code is there: n_good consecutive epochs with code_ratio >= code_min */
+#define GPSX_WLOCK_CARRIER       2u    /* the carrier is locked: n_good consecutive LOCKED epochs with car_ratio and snr above theirs */
+#define GPSX_WLOCK_PENDING       4u    /* state only: a re-arm is due at the launch's end */
+#define GPSX_WLOCK_OPEN_LOCKED   8u    /* state only: the open epoch's windows are LOCKED ones */
+#define GPSX_WLOCK_EPOCH_LOCKED  16u   /* the newest completed epoch was a LOCKED one */
+#define GPSX_WLOCK_LOST_CODE     32u   /* output only, this launch: CODE was cleared */
+#define GPSX_WLOCK_LOST_CARRIER  64u   /* output only, this launch: CARRIER was cleared */
+#define GPSX_WLOCK_REARMED       128u  /* output only, this launch: the channel's bit search was re-armed */
+#define GPSX_WLOCK_RANGE         256u  /* output only, this launch: a record with a sum of magnitude >= 2^20 was not accumulated */
+
+typedef struct {                 /* 40 bytes */
+  int32_t  epoch_search;         /* windows per epoch of SEARCH windows, 1 .. 1024 */
+  int32_t  epoch_lock;           /* windows per epoch of LOCKED windows, 1 .. 1024 */
+  float    code_min;             /* code verdict: code_ratio >= code_min (finite) */
+  float    car_min, snr_min;     /* carrier verdict: car_ratio >= car_min && snr >= snr_min (finite) */
+  int32_t  n_good, n_bad;        /* consecutive epochs that set / clear an indicator, 1 .. 255 */
+  int32_t  rearm;                /* mask; 0: never.  1: on a code loss.  2: after `patience` bad carrier verdicts without CARRIER */
+  int32_t  patience;             /* >= 0 */
+  int32_t  reserved;             /* 0 */
+} gpsx_wlock_cfg_t;
+
+typedef struct {                 /* 128 bytes, device resident; all zero = a fresh channel */
+  int64_t  blocks_seen;          /*   0  blocks of all earlier launches */
+  int64_t  last_epoch_end_p1;    /*   8  absolute last block of the newest completed epoch, + 1; 0: none */
+  int64_t  sum_a, sum_p, sum_d, sum_e, sum_l;   /*  16  the open epoch's A, P, D, E, L */
+  int64_t  last_p;               /*  56  the newest completed epoch's P */
+  float    last_code_ratio, last_car_ratio, last_snr;   /*  64  its three ratios */
+  uint32_t epoch_n;              /*  76  windows in the open epoch, 0 .. 1023 */
+  uint32_t flags;                /*  80  GPSX_WLOCK_CODE .. _EPOCH_LOCKED */
+  uint32_t last_k;               /*  84  the newest completed epoch's K; 0: none yet */
+  uint32_t code_good, code_bad, car_good, car_bad;   /*  88  runs of verdicts, 0 .. 255 */
+  uint32_t false_run;            /* 104  consecutive bad carrier verdicts met without CARRIER */
+  uint32_t n_lost_code, n_lost_carrier, n_rearm, n_range;   /* 108  losses of either indicator, re-arms, records refused by step 1 */
+  uint32_t reserved;             /* 124  0 */
+} gpsx_wlock_state_t;
+
+typedef struct {                 /* 64 bytes, one per channel and launch */
+  uint32_t flags;                /*  0  the state's CODE, CARRIER and EPOCH_LOCKED | this launch's LOST_CODE .. RANGE */
+  uint32_t n_epochs;             /*  4  epochs completed in this launch */
+  uint32_t last_k;               /*  8  the newest completed epoch's K (a launch without one repeats the state's); 0: none yet */
+  int32_t  age_blocks;           /* 12  B - last_epoch_end_p1, B = blocks_seen after this launch, within 0 .. 2^31 - 1; -1: none yet */
+  float    code_ratio, car_ratio, snr;   /* 16  that epoch's */
+  uint32_t n_range;              /* 28  the state's */
+  int64_t  p;                    /* 32  that epoch's P */
+  uint32_t n_lost_code, n_lost_carrier, n_rearm;   /* 40  the state's */
+  uint32_t reserved[3];          /* 52  0 */
+} gpsx_wlock_t;
+
+/* d_rec [n_slots][n_ch]: what gpsx_track_loop_weighted_sync(_dev) wrote for these n_blocks blocks, on the device in both variants,
+ * as d_state [n_ch] and d_sync_state [n_ch] (that loop's own states; NULL unless cfg->rearm) are; d_lock / lock: [n_ch] */
+int gpsx_wlock_dev(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                   gpsx_wlock_state_t *d_state, gpsx_wsync_state_t *d_sync_state, int n_ch, gpsx_wlock_t *d_lock);
+int gpsx_wlock(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+               gpsx_wlock_state_t *d_state, gpsx_wsync_state_t *d_sync_state, int n_ch, gpsx_wlock_t *lock /* host */);
+/* host only, no GPU: C/N0 in dB-Hz from the records of one launch.  For a record whose newest epoch was a LOCKED one (EPOCH_LOCKED,
+ * last_k > 0) with snr > 0: cn0_dbhz[i] = (float)(10 log10((double)snr / (n_coh_lock * 0.001))), n_coh_lock the sync loop's, the
+ * logarithm in double; 0 for every other record.  (The logarithm stays on the host: what a device logarithm costs in parity is
+ * told at snr_value below.)  Returns GPSX_OK, or GPSX_EINVAL for NULL, n < 1 or n_coh_lock outside 1 .. 20. */
+int gpsx_wlock_cn0_dbhz(const gpsx_wlock_t *lock, int n, int n_coh_lock, float *cn0_dbhz);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

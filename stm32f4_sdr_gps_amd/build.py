@@ -130,7 +130,11 @@ def check_no_scratch() -> dict:
     weph = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_weph.o")).items() if "k_weph" in k}
     if len(weph) != 1:
         raise RuntimeError(f"expected k_weph in build/k_weph.o, found {sorted(weph)}")
-    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **waid, **wnav, **wobs, **weph}
+    # ... and the lock monitor on the records (k_wlock: two register sets of four slots' eight words, five int64 sums, the state)
+    wlock = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wlock.o")).items() if "k_wlock" in k}
+    if len(wlock) != 1:
+        raise RuntimeError(f"expected k_wlock in build/k_wlock.o, found {sorted(wlock)}")
+    every = {**mx, **wmx, **loops, **wv, **coh, **hyb, **trw, **wloop, **wsync, **waid, **wnav, **wobs, **weph, **wlock}
     bad = {k: v for k, v in every.items() if v["scratch_bytes"] != 0}
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")

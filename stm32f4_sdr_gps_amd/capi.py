@@ -189,6 +189,43 @@ def weph_to_eph(rec, prn: int) -> np.ndarray:
     return out
 
 
+# gpsx_wlock_cfg_t / gpsx_wlock_state_t / gpsx_wlock_t (every channel's code-lock, carrier-lock and C/N0 indicators from the records)
+WLOCK_FLAG_CODE, WLOCK_FLAG_CARRIER, WLOCK_FLAG_PENDING, WLOCK_FLAG_OPEN_LOCKED, WLOCK_FLAG_EPOCH_LOCKED = 1, 2, 4, 8, 16
+WLOCK_FLAG_LOST_CODE, WLOCK_FLAG_LOST_CARRIER, WLOCK_FLAG_REARMED, WLOCK_FLAG_RANGE = 32, 64, 128, 256
+WLOCK_REARM_CODE_LOSS, WLOCK_REARM_NO_CARRIER = 1, 2
+WLOCK_CFG_DTYPE = np.dtype([("epoch_search", "<i4"), ("epoch_lock", "<i4"), ("code_min", "<f4"), ("car_min", "<f4"), ("snr_min", "<f4"),
+                            ("n_good", "<i4"), ("n_bad", "<i4"), ("rearm", "<i4"), ("patience", "<i4"), ("reserved", "<i4")])
+WLOCK_STATE_DTYPE = np.dtype([("blocks_seen", "<i8"), ("last_epoch_end_p1", "<i8"), ("sum_a", "<i8"), ("sum_p", "<i8"), ("sum_d", "<i8"),
+                              ("sum_e", "<i8"), ("sum_l", "<i8"), ("last_p", "<i8"), ("last_code_ratio", "<f4"), ("last_car_ratio", "<f4"),
+                              ("last_snr", "<f4"), ("epoch_n", "<u4"), ("flags", "<u4"), ("last_k", "<u4"), ("code_good", "<u4"),
+                              ("code_bad", "<u4"), ("car_good", "<u4"), ("car_bad", "<u4"), ("false_run", "<u4"), ("n_lost_code", "<u4"),
+                              ("n_lost_carrier", "<u4"), ("n_rearm", "<u4"), ("n_range", "<u4"), ("reserved", "<u4")])
+WLOCK_DTYPE = np.dtype([("flags", "<u4"), ("n_epochs", "<u4"), ("last_k", "<u4"), ("age_blocks", "<i4"), ("code_ratio", "<f4"),
+                        ("car_ratio", "<f4"), ("snr", "<f4"), ("n_range", "<u4"), ("p", "<i8"), ("n_lost_code", "<u4"),
+                        ("n_lost_carrier", "<u4"), ("n_rearm", "<u4"), ("reserved", "<u4", (3,))])
+assert WLOCK_CFG_DTYPE.itemsize == 40 and WLOCK_STATE_DTYPE.itemsize == 128 and WLOCK_DTYPE.itemsize == 64
+
+
+def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
+    """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
+    cfg = np.zeros(1, WLOCK_CFG_DTYPE)
+    for name, v in (("epoch_search", epoch_search), ("epoch_lock", epoch_lock), ("code_min", code_min), ("car_min", car_min), ("snr_min", snr_min),
+                    ("n_good", n_good), ("n_bad", n_bad), ("rearm", rearm), ("patience", patience)):
+        cfg[name] = v
+    return cfg
+
+
+def wlock_cn0_dbhz(lock: np.ndarray, n_coh_lock: int) -> np.ndarray:
+    """WLOCK_DTYPE records of one launch -> C/N0 in dB-Hz, float32 [n]: 10 log10(snr / (n_coh_lock ms)) where the newest epoch was a
+    LOCKED one with snr > 0, else 0.  Host only."""
+    lock = np.ascontiguousarray(lock, WLOCK_DTYPE).reshape(-1)
+    out = np.zeros(len(lock), np.float32)
+    rc = load_library().gpsx_wlock_cn0_dbhz(lock.ctypes.data, len(lock), int(n_coh_lock), out.ctypes.data)
+    if rc != 0:
+        raise GpsxError(f"gpsx_wlock_cn0_dbhz -> {rc}: no records, or n_coh_lock outside 1 .. 20")
+    return out
+
+
 TRK_DTYPE = np.dtype([("prn", "<i4"), ("code_phase_fine", "<f4"), ("if_freq_offset_hz", "<f4"),
                       ("if_freq_accum", "<u4")])
 JOB_DTYPE = np.dtype([("block", "<i4"), ("n_ms", "<i4"), ("prn", "<i4"), ("freq_hz", "<f4"), ("offset_bits", "<i4"),
@@ -299,6 +336,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_weph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_weph_dev.argtypes = lib.gpsx_weph.argtypes
     lib.gpsx_weph_to_eph.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_wlock.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_wlock_dev.argtypes = lib.gpsx_wlock.argtypes
+    lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.gpsx_loop_state_from_channel.restype = None
@@ -743,6 +783,17 @@ class Engine:
         eph = np.zeros(n_ch, WEPH_DTYPE)
         self._chk(self.lib.gpsx_weph(self.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, C.c_void_p(d_state), n_ch, eph.ctypes.data), "gpsx_weph")
         return eph
+
+    def wlock(self, cfg: np.ndarray, d_rec: int, n_slots: int, n_blocks: int, d_state: int, n_ch: int, d_sync_state: int | None = None) -> np.ndarray:
+        """EXTENSION: every channel's code-lock, carrier-lock and C/N0 indicators from the WSYNC_REC_DTYPE [n_slots, n_ch] records at
+        device address d_rec that gpsx_track_loop_weighted_sync_dev wrote for n_blocks blocks, on the n_ch WLOCK_STATE_DTYPE states at
+        device address d_state (all zero: a fresh channel); cfg from wlock_cfg.  d_sync_state: the sync loop's own states, needed when
+        cfg's rearm is not 0 -- a channel whose re-arm falls due has its bit search restarted there.  -> WLOCK_DTYPE [n_ch]"""
+        assert cfg.dtype == WLOCK_CFG_DTYPE and cfg.size == 1
+        lock = np.zeros(n_ch, WLOCK_DTYPE)
+        self._chk(self.lib.gpsx_wlock(self.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_state),
+                                      C.c_void_p(d_sync_state) if d_sync_state else None, n_ch, lock.ctypes.data), "gpsx_wlock")
+        return lock
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

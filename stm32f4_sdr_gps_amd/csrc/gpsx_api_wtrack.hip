@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_wnav_words, gpsx_wobs, gpsx_weph, each with its _dev twin, and the two
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -7,6 +7,7 @@
 // the launch and the next gpsx_synchronize reports (flag 1).  The refusals come first; the first clause that fails decides the text.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <initializer_list>
 
@@ -284,6 +285,46 @@ int weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_wo
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(eph, d_eph, eph_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
+// ---- the lock monitor on the sync loop's records (d_rec and all states are device memory in both variants) ----------------------------
+int wlock(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks, gpsx_wlock_state_t *d_state,
+          gpsx_wsync_state_t *d_sync_state, int n_ch, gpsx_wlock_t *lock, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !d_rec || !d_state || !lock)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->epoch_search < 1 || cfg->epoch_search > 1024 || cfg->epoch_lock < 1 || cfg->epoch_lock > 1024)
+    return fail(ctx, GPSX_EINVAL, "epoch_search and epoch_lock must be 1..1024 windows");
+  if (cfg->n_good < 1 || cfg->n_good > 255 || cfg->n_bad < 1 || cfg->n_bad > 255)
+    return fail(ctx, GPSX_EINVAL, "n_good and n_bad must be 1..255");
+  for (float t : {cfg->code_min, cfg->car_min, cfg->snr_min})
+    if (!(__builtin_fabsf(t) <= 3.402823466e+38f))
+      return fail(ctx, GPSX_EINVAL, "a threshold is not finite");
+  if (cfg->rearm < 0 || cfg->rearm > 3)
+    return fail(ctx, GPSX_EINVAL, "rearm must be 0..3");
+  if (cfg->patience < 0)
+    return fail(ctx, GPSX_EINVAL, "patience must not be negative");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (cfg->rearm != 0 && !d_sync_state)
+    return fail(ctx, GPSX_EINVAL, "rearm needs d_sync_state");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (int rc = check_n_slots(ctx, n_slots, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  size_t bytes = 0, lock_bytes = 0;
+  if (records_overflow((size_t)n_slots, n_ch, sizeof(gpsx_wsync_rec_t), &bytes) || records_overflow(1, n_ch, sizeof(gpsx_wsync_state_t), &bytes) ||
+      records_overflow(1, n_ch, sizeof(gpsx_wlock_state_t), &bytes) || records_overflow(1, n_ch, sizeof(gpsx_wlock_t), &lock_bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records overflow a size");
+  gpsx_wlock_t *d_lock = lock;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(lock_bytes))) return rc;
+    d_lock = arena_take<gpsx_wlock_t>(ctx, (size_t)n_ch);
+  }
+  return launch_and_report(
+      ctx, host, "k_wlock", "a channel's lock state is out of range (its state is untouched, its record is zero)",
+      [&](uint32_t *flag) { launch_wlock(ctx->stream, d_rec, n_slots, n_blocks, *cfg, d_state, cfg->rearm != 0 ? d_sync_state : nullptr, n_ch, d_lock, flag); },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(lock, d_lock, lock_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
 }  // namespace
 
 extern "C" {
@@ -382,6 +423,30 @@ int gpsx_weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t 
               int n_ch, gpsx_weph_t *eph)
 {
   return weph(ctx, cfg, d_words, n_blocks, d_state, n_ch, eph, true);
+}
+
+int gpsx_wlock_dev(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+                   gpsx_wlock_state_t *d_state, gpsx_wsync_state_t *d_sync_state, int n_ch, gpsx_wlock_t *d_lock)
+{
+  return wlock(ctx, cfg, d_rec, n_slots, n_blocks, d_state, d_sync_state, n_ch, d_lock, false);
+}
+
+int gpsx_wlock(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
+               gpsx_wlock_state_t *d_state, gpsx_wsync_state_t *d_sync_state, int n_ch, gpsx_wlock_t *lock)
+{
+  return wlock(ctx, cfg, d_rec, n_slots, n_blocks, d_state, d_sync_state, n_ch, lock, true);
+}
+
+int gpsx_wlock_cn0_dbhz(const gpsx_wlock_t *lock, int n, int n_coh_lock, float *cn0_dbhz)
+{
+  if (!lock || !cn0_dbhz || n < 1 || n_coh_lock < 1 || n_coh_lock > 20)
+    return GPSX_EINVAL;
+  const double t = n_coh_lock * 0.001;
+  for (int i = 0; i < n; i++) {
+    const bool have = (lock[i].flags & GPSX_WLOCK_EPOCH_LOCKED) && lock[i].last_k > 0 && lock[i].snr > 0.0f;
+    cn0_dbhz[i] = have ? (float)(10.0 * std::log10((double)lock[i].snr / t)) : 0.0f;
+  }
+  return GPSX_OK;
 }
 
 int gpsx_wnav_subframe_image(const gpsx_wnav_word_t *ten, uint8_t image[38])

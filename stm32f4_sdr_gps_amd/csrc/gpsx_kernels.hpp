@@ -171,6 +171,12 @@ void launch_wobs(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots, int 
 // d_bad_state (may be null): set to 1 by a channel whose state is out of range.
 void launch_weph(hipStream_t s, const gpsx_wnav_word_t *d_words, int n_blocks, gpsx_weph_state_t *d_st, int n_ch, gpsx_weph_t *d_eph,
                  uint32_t *d_bad_state);
+// extension: gpsx_wlock (k_wlock.hip: k_wlock) -- every channel's code-lock, carrier-lock and C/N0 indicators from the same
+// [n_slots][n_ch] records: one channel per lane, 128-byte states in HBM, d_lock [n_ch] 64-byte records, every byte of them written.
+// d_sync_st (null unless cfg.rearm): the sync loop's states, written where a re-arm is due.  d_bad_state (may be null): set to 1 by
+// a channel whose state is out of range.
+void launch_wlock(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks, const gpsx_wlock_cfg_t &cfg, gpsx_wlock_state_t *d_st,
+                  gpsx_wsync_state_t *d_sync_st, int n_ch, gpsx_wlock_t *d_lock, uint32_t *d_bad_state);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

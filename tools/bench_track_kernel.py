@@ -52,7 +52,16 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       (b) gpsx_wnav_words_dev on the records of a 4000-block launch -- the bar: the stage
                                                       at the chain's end takes no longer than the one before it -- the calls taking
                                                       turns in one process; then what a host does without the stage: d_words copied
-                                                      back, gpsx_wnav_subframe_image and gps_nav_data_decode_subframe per channel"""
+                                                      back, gpsx_wnav_subframe_image and gps_nav_data_decode_subframe per channel
+  bench_track_kernel.py --weighted-lock [channels ...]
+                                                      gpsx_wlock_dev (EXTENSION: every channel's code-lock, carrier-lock and C/N0
+                                                      indicators from the records) on the records of 4000-block launches at span 20 (200
+                                                      slots, every channel LOCKED; three channels in four carry a satellite's sums, the
+                                                      fourth noise), three record arrays used in turn, LOCKED epochs of 10 windows,
+                                                      beside (1) a device-to-device hipMemcpyAsync of the record array -- the bar: the
+                                                      kernel takes no longer -- and (2) gpsx_wobs_dev on the same lines (no bar: it
+                                                      reads 16 bytes of a record where this reads 32), the calls taking turns in one
+                                                      process"""
 import ctypes as C
 import json
 import os
@@ -615,8 +624,100 @@ def weighted_eph(counts, n_blocks=4000, span=20):
             eng.free(p)
 
 
+def weighted_lock(counts, n_blocks=4000, span=20):
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    capi.load_library()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    eng = capi.Engine(0, stream=stream.value)      # (the copy below goes onto the stream the engine's events are recorded on)
+    n_slots, distinct = n_blocks // span, 32
+    rng = np.random.default_rng(17)
+    j = np.arange(distinct)
+    there = (j % 4 != 3)[None, :]      # three channels in four: a prompt of 17 000 with data bits on noise of 1000, half of it on the taps
+    cfg = capi.wlock_cfg(25, 10, 2.3, 0.75, 6.0, 2, 2)
+    obs_cfg = np.zeros(1, capi.WOBS_CFG_DTYPE)
+    obs_cfg["edge_guard"] = 512.0
+    for n in counts:
+        idx = np.arange(n) % distinct
+        rec_bytes = n_slots * n * 48
+        word_slots = capi.wnav_word_slots(n_blocks)
+        d_recs = []
+        for leg in range(3):
+            small = np.zeros((n_slots, distinct), capi.WSYNC_REC_DTYPE)
+            small["end_block"] = (np.arange(n_slots) * span + span - 1)[:, None]
+            small["flags"] = capi.WSYNC_FLAG_WINDOW | capi.WSYNC_FLAG_LOCKED | capi.WSYNC_FLAG_BIT
+            noise = rng.normal(0.0, 1000.0, (n_slots, distinct, 6))
+            bit = rng.integers(0, 2, (n_slots, distinct)) * 2 - 1
+            noise[:, :, 2] += np.where(there, 17000.0 * bit, 0.0)
+            noise[:, :, 0] += np.where(there, 8500.0 * bit, 0.0)
+            noise[:, :, 4] += np.where(there, 8500.0 * bit, 0.0)
+            small["w"]["iq"] = np.rint(noise).astype(np.int32)
+            small["w"]["code_phase_fine"] = ((511.0 * j + 100.0) % 16368.0)[None, :].astype(np.float32)
+            small["bit_ip"] = small["w"]["iq"][:, :, 2]
+            d = eng.malloc(rec_bytes)
+            eng.h2d(d, np.ascontiguousarray(small[:, idx]))
+            d_recs.append(d)
+        words = np.zeros((word_slots, n), capi.WNAV_WORD_DTYPE)      # no words: k_wobs' time is its pass over d_rec
+        words["end_block"] = -1
+        st, obs_st = np.zeros(n, capi.WLOCK_STATE_DTYPE), np.zeros(n, capi.WOBS_STATE_DTYPE)
+        d_copy, d_words, d_st, d_obs_st = eng.malloc(rec_bytes), eng.malloc(words.nbytes), eng.malloc(st.nbytes), eng.malloc(obs_st.nbytes)
+        d_lock, d_obs = eng.malloc(n * 64), eng.malloc(n * 32)
+        eng.h2d(d_words, words)
+        eng.h2d(d_st, st)
+        eng.h2d(d_obs_st, obs_st)
+        turn = {"lock": 0, "obs": 0}
+
+        def lock():
+            leg = turn["lock"] % 3
+            turn["lock"] += 1
+            return eng.lib.gpsx_wlock_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_recs[leg]), n_slots, n_blocks, C.c_void_p(d_st), None, n, C.c_void_p(d_lock))
+
+        def observables():
+            leg = turn["obs"] % 3
+            turn["obs"] += 1
+            return eng.lib.gpsx_wobs_dev(eng.h, obs_cfg.ctypes.data, C.c_void_p(d_recs[leg]), n_slots, n_blocks, C.c_void_p(d_words), C.c_void_p(d_obs_st), n,
+                                         C.c_void_p(d_obs))
+
+        for _ in range(3):
+            eng._chk(lock(), "gpsx_wlock_dev")
+            eng._chk(observables(), "gpsx_wobs_dev")
+        eng.synchronize()
+        calls = {"d2d_copy_of_d_rec": (n_blocks, lambda: hip.hipMemcpyAsync(d_copy, d_recs[0], rec_bytes, 3, stream)),
+                 "wlock": (n_blocks, lock),
+                 "wobs": (n_blocks, observables)}
+        med = _timed_rows(eng, calls, {"channels": n, "slots": n_slots, "rec_bytes": rec_bytes})
+        rec = np.zeros(n, capi.WLOCK_DTYPE)
+        eng.d2h(rec, d_lock)
+        eng.d2h(st, d_st)
+        both = capi.WLOCK_FLAG_CODE | capi.WLOCK_FLAG_CARRIER
+        print(json.dumps({"wlock_check": "records after the timed launches", "channels": n, "launches": turn["lock"],
+                          "code_and_carrier": int((rec["flags"] & both == both).sum()), "neither": int((rec["flags"] & both == 0).sum()),
+                          "epochs_per_launch": int(rec["n_epochs"].min()), "losses": int(st["n_lost_code"].sum() + st["n_lost_carrier"].sum()),
+                          "cn0_dbhz_median_of_the_locked": round(float(np.median(capi.wlock_cn0_dbhz(rec, 20)[rec["flags"] & both == both])), 2),
+                          "blocks_seen": int(st["blocks_seen"].min())}), flush=True)
+        r = med["wlock"] / med["d2d_copy_of_d_rec"]
+        print(json.dumps({"ratio": "k_wlock over a device-to-device copy of d_rec", "channels": n, "value": round(r, 4), "bound": 1.0,
+                          "within_bound": bool(r <= 1.0), "read_GBps_of_the_32_bytes_per_record": round(rec_bytes * 2 / 3 / med["wlock"] / 1e3, 1),
+                          "read_GBps_of_whole_lines": round(rec_bytes / med["wlock"] / 1e3, 1),
+                          "copy_GBps_read_plus_write": round(2 * rec_bytes / med["d2d_copy_of_d_rec"] / 1e3, 1)}), flush=True)
+        print(json.dumps({"ratio": "k_wlock over k_wobs on the same records (no bar)", "channels": n,
+                          "value": round(med["wlock"] / med["wobs"], 4)}), flush=True)
+        for p in d_recs + [d_copy, d_words, d_st, d_obs_st, d_lock, d_obs]:
+            eng.free(p)
+
+
 def main():
     global WINDOW_S
+    if "--weighted-lock" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-lock"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_lock([int(a) for a in args] or [65536, 212992])
     if "--weighted-eph" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-eph"]
         if "--window-s" in args:
