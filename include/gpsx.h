@@ -36,7 +36,8 @@ extern "C" {
                                             * gpsx_wobs(_dev) and gpsx_wobs_pseudoranges too; gpsx_weph(_dev) and
                                             * gpsx_weph_to_eph (include/gpsx_compat.h) likewise; so are the four carrier-aided loop
                                             * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t; gpsx_wlock(_dev) and
-                                            * gpsx_wlock_cn0_dbhz likewise. */
+                                            * gpsx_wlock_cn0_dbhz likewise; gpsx_track_loop_weighted_sync_multi(_dev) with
+                                            * gpsx_wmulti_t and gpsx_wobs_pseudoranges_rx too. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -536,7 +537,9 @@ int gpsx_track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, const u
  *                  A channel that fails is BAD for the rest of the launch: per block only if_freq_accum += 511 * step32 happens;
  *                  it gets no window record (its slots are the empty pattern: zero sums), its floats, loop memory, window and
  *                  sync words stay as they were, and GPSX_EINVAL comes from gpsx_track_loop_weighted_sync after its wait / from
- *                  the next gpsx_synchronize() after _dev.  Steps 2 .. 7 are those of a good channel.
+ *                  the next gpsx_synchronize() after _dev.  Steps 2 .. 7 are those of a good channel.  A prn of GPSX_PRN_NONE
+ *                  (defined with gpsx_track_loop_weighted_sync_multi below) is a slot without a channel: treated like a BAD
+ *                  channel in every byte, but never reported -- no GPSX_EINVAL.
  *   2 leaving WAIT if mode == WAIT and ms_count == edge: mode = LOCKED (this block is the first of a data bit)
  *   3 correlators  if mode != WAIT: the six int32 values of gpsx_track_epl_weighted for this block, with tau, f = (float)if_hz +
  *                  if_freq_offset_hz and step32 those of the state's floats -- which change at a window's end only, so a window
@@ -666,6 +669,50 @@ int gpsx_track_loop_weighted_sync_aided_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_
                                             int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *d_rec);
 int gpsx_track_loop_weighted_sync_aided(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const uint8_t *if_blocks_2bit,
                                         int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec);
+
+/* ---- EXTENSION, not in the reference: the sync loop for many receivers per launch, one IF stream each -------------------------------
+ * gpsx_track_loop_weighted_sync(_aided) takes ONE stream, shared by all channels.  This call takes n_rx streams with ch_per_rx
+ * channel slots on each, in one launch.  No arithmetic is new: receiver r's bytes ARE, by definition, the single-stream call's on
+ * its stream.  The four single-stream calls, their structs, their kernels and GPSX_VERSION are unchanged.
+ *
+ * Definition.  Channel r * ch_per_rx + j is slot j of receiver r; n_ch = n_rx * ch_per_rx; d_state[n_ch] and d_rec[n_slots][n_ch]
+ * (n_slots as above) are the single-stream call's arrays, so gpsx_wnav_words, gpsx_wobs, gpsx_weph and gpsx_wlock read them
+ * unchanged with that n_ch.  Receiver r reads blocks b = 0 .. n_blocks - 1 at byte offset ((size_t)r * rx_stride_blocks + b) * 4092
+ * of d_if_blocks_2bit and no byte outside them (of a block, bytes 0 .. 4087: the sixteen unmixed samples are not read).  After the
+ * call the states [r * ch_per_rx, (r + 1) * ch_per_rx) and the matching record columns equal, byte for byte, what
+ * gpsx_track_loop_weighted_sync_aided writes for that receiver's blocks, those ch_per_rx states and the same cfg and aid; with
+ * aid == NULL, or a factor of 0, what gpsx_track_loop_weighted_sync writes.  The launch-cut rule carries over (launches of any
+ * lengths give the bytes of one launch; a later launch starts from the pointer advanced by its predecessor's blocks, the stride
+ * unchanged), and so do the empty-slot pattern and the BAD-channel policy: a bad channel of any receiver makes the call, or the
+ * next gpsx_synchronize after _dev, return GPSX_EINVAL and changes nothing in any other channel or receiver.
+ * A receiver with fewer than ch_per_rx satellites fills its spare slots with prn = GPSX_PRN_NONE (below).
+ * Errors: the single-stream call's, in its order, with these in the place of its n_ch clause: rx NULL ("null argument", with the
+ * other pointers), n_rx outside 1 .. 1 048 576, ch_per_rx outside 1 .. 64, rx_stride_blocks < n_blocks, reserved != 0,
+ * n_rx * ch_per_rx above INT32_MAX; and behind the others a byte count (records, states, streams) that overflows size_t.  Each
+ * returns GPSX_EINVAL with a gpsx_last_error text and writes nothing.
+ * Vector ALU (k_track_wsync_multi: k_track_waid_sync's text with a workgroup of four waves per receiver, which stages only that
+ * receiver's block; wave w serves slots w * cpw .. + cpw - 1, cpw = ceil(ch_per_rx / 4) -- hence 64 slots at most).  The host
+ * variant takes the streams (the same stride) and the records in host memory and the state on the device; what the arena cannot
+ * hold is refused with the arena's error.
+ *
+ * GPSX_PRN_NONE: a channel slot that holds no channel.  It names what every weighted tracking kernel already does with this prn
+ * value (the padding channel of the validation rules above): the slot gets no correlators and no window record, its record slots
+ * are the empty pattern, it is NOT reported as bad, and per block only its if_freq_accum moves (+= 511 * step32, as a bad
+ * channel's). */
+#define GPSX_PRN_NONE (-2147483647 - 1)   /* a channel slot that holds no channel */
+
+typedef struct {                 /* 16 bytes */
+  int32_t n_rx;                  /* receivers (IF streams): 1 .. 1 048 576 */
+  int32_t ch_per_rx;             /* channel slots per receiver: 1 .. 64 */
+  int32_t rx_stride_blocks;      /* 4092-byte blocks between two receivers' first blocks: >= n_blocks */
+  int32_t reserved;              /* 0 */
+} gpsx_wmulti_t;
+
+/* aid NULL: unaided.  d_state [n_rx * ch_per_rx]; d_rec / rec: [ceil(n_blocks / min(n_coh_search, n_coh_lock))][n_rx * ch_per_rx] */
+int gpsx_track_loop_weighted_sync_multi_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const gpsx_wmulti_t *rx,
+                                            const void *d_if_blocks_2bit, int n_blocks, gpsx_wsync_state_t *d_state, gpsx_wsync_rec_t *d_rec);
+int gpsx_track_loop_weighted_sync_multi(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const gpsx_wmulti_t *rx,
+                                        const uint8_t *if_blocks_2bit, int n_blocks, gpsx_wsync_state_t *d_state, gpsx_wsync_rec_t *rec);
 
 /* ---- EXTENSION, not in the reference: LNAV frame sync and parity-checked words from the sync loop's bit records -----------------
  * What lies between a BIT record of gpsx_track_loop_weighted_sync and a navigation word, done on the device: a kernel reads the
@@ -891,6 +938,12 @@ int gpsx_wobs(gpsx_ctx *ctx, const gpsx_wobs_cfg_t *cfg, const gpsx_wsync_rec_t 
  * caller assumes it (the reference's own pseudorange step uses 68.802 ms: include/gpsx_compat.h); the solver's clock term takes
  * the rest.  Returns the number of VALID observables, or GPSX_EINVAL for NULL, n < 1 or an offset_ms that is not finite. */
 int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, double *pr_m, double *rx_tow_s);
+/* host only, no GPU: gpsx_wobs_pseudoranges applied to each receiver's slice of the observables of a
+ * gpsx_track_loop_weighted_sync_multi chain: obs [n_rx * ch_per_rx], receiver r's are [r * ch_per_rx, (r + 1) * ch_per_rx).  The
+ * reference channel is chosen per receiver; pr_m [n_rx * ch_per_rx], rx_tow_s [n_rx] and n_valid [n_rx] (the per-slice return
+ * values; 0 for a receiver without a VALID observable) are bitwise those of n_rx separate calls.  Returns the sum of n_valid, or
+ * GPSX_EINVAL for NULL, n_rx < 1, ch_per_rx < 1, n_rx * ch_per_rx above INT32_MAX or an offset_ms that is not finite. */
+int gpsx_wobs_pseudoranges_rx(const gpsx_wobs_t *obs, int n_rx, int ch_per_rx, double offset_ms, double *pr_m, double *rx_tow_s, int *n_valid);
 
 /* ---- EXTENSION, not in the reference: weighted ephemerides -- every channel's broadcast ephemeris from the words, on the device ----
  * What a position needs beside the transmit times: the satellite's broadcast ephemeris.  gpsx_weph(_dev) is a fifth stage behind

@@ -117,6 +117,9 @@ def check_no_scratch() -> dict:
     wide = {k: v for k, v in waid.items() if v["vgprs"] > 128}
     if wide:
         raise RuntimeError(f"carrier-aided loop kernels above 128 VGPRs (four waves per SIMD): {wide}")
+    # ... and the sync loop for many receivers per launch (check_wmulti below: refused here like the others; not in the table this
+    #     returns, whose keys callers search for the single-stream kernels' names, which k_track_wsync_multi's contains)
+    check_wmulti()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -139,6 +142,18 @@ def check_no_scratch() -> dict:
     if bad:
         raise RuntimeError(f"kernels with scratch memory (register spills): {bad}")
     return every
+
+
+def check_wmulti() -> dict:
+    """k_track_wsync_multi (the aided sync kernel's text a third time, a workgroup per receiver; an object of its own): exactly one
+    instance, no scratch, and k_track_waid_sync's occupancy -- four waves per SIMD, 128 VGPRs at most.  -> {symbol: resources}"""
+    wmulti = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_track_loop_weighted_sync_multi.o")).items() if "k_track_wsync_multi" in k}
+    if len(wmulti) != 1:
+        raise RuntimeError(f"expected k_track_wsync_multi in build/k_track_loop_weighted_sync_multi.o, found {sorted(wmulti)}")
+    bad = {k: v for k, v in wmulti.items() if v["vgprs"] > 128 or v["scratch_bytes"] != 0}
+    if bad:
+        raise RuntimeError(f"multi-receiver sync loop kernel above 128 VGPRs (four waves per SIMD) or with scratch memory: {bad}")
+    return wmulti
 
 
 if __name__ == "__main__":

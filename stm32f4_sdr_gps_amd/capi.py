@@ -107,6 +107,19 @@ def waid(code_per_hz=WAID_L1CA) -> np.ndarray:
     return aid
 
 
+# gpsx_wmulti_t (gpsx_track_loop_weighted_sync_multi: many receivers per launch, one IF stream each)
+PRN_NONE = -2147483648                   # GPSX_PRN_NONE: a channel slot that holds no channel
+WMULTI_DTYPE = np.dtype([("n_rx", "<i4"), ("ch_per_rx", "<i4"), ("rx_stride_blocks", "<i4"), ("reserved", "<i4")])
+assert WMULTI_DTYPE.itemsize == 16
+
+
+def wmulti(n_rx, ch_per_rx, rx_stride_blocks) -> np.ndarray:
+    """a gpsx_wmulti_t as a one-element WMULTI_DTYPE array"""
+    rx = np.zeros(1, WMULTI_DTYPE)
+    rx["n_rx"], rx["ch_per_rx"], rx["rx_stride_blocks"] = n_rx, ch_per_rx, rx_stride_blocks
+    return rx
+
+
 # gpsx_wnav_cfg_t / gpsx_wnav_state_t / gpsx_wnav_word_t (LNAV frame sync and parity-checked words from the sync loop's records)
 WNAV_HUNT, WNAV_SYNCED = 0, 1
 WNAV_FLAG_WORD, WNAV_FLAG_OK, WNAV_FLAG_INVERTED, WNAV_FLAG_SYNC, WNAV_FLAG_FLIPPED, WNAV_FLAG_SUBFRAME, WNAV_FLAG_DROPPED = 1, 2, 4, 8, 16, 32, 64
@@ -158,6 +171,21 @@ def wobs_pseudoranges(obs: np.ndarray, offset_ms: float = 68.802):
     if n < 0:
         raise GpsxError(f"gpsx_wobs_pseudoranges -> {n}: no observables, or an offset that is not finite")
     return pr, rx.value, n
+
+
+def wobs_pseudoranges_rx(obs: np.ndarray, n_rx: int, ch_per_rx: int, offset_ms: float = 68.802):
+    """wobs_pseudoranges on each receiver's slice of the WOBS_DTYPE [n_rx * ch_per_rx] observables of a multi-receiver chain, the
+    reference channel chosen per receiver -> (pr_m float64 [n_rx * ch_per_rx], rx_tow_s float64 [n_rx], n_valid int32 [n_rx]).
+    Host only."""
+    obs = np.ascontiguousarray(obs, WOBS_DTYPE).reshape(-1)
+    if n_rx < 1 or ch_per_rx < 1 or len(obs) != n_rx * ch_per_rx:
+        raise GpsxError("wobs_pseudoranges_rx takes n_rx * ch_per_rx observables")
+    pr, rx, n_valid = np.zeros(len(obs), np.float64), np.zeros(n_rx, np.float64), np.zeros(n_rx, np.int32)
+    n = load_library().gpsx_wobs_pseudoranges_rx(obs.ctypes.data, n_rx, ch_per_rx, float(offset_ms), pr.ctypes.data, rx.ctypes.data,
+                                                 n_valid.ctypes.data)
+    if n < 0:
+        raise GpsxError(f"gpsx_wobs_pseudoranges_rx -> {n}: no observables, or an offset that is not finite")
+    return pr, rx, n_valid
 
 
 # gpsx_weph_cfg_t / gpsx_weph_state_t / gpsx_weph_t (every channel's broadcast ephemeris from the words) and eph_t (include/gpsx_compat.h)
@@ -327,6 +355,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_track_loop_weighted_aided_dev.argtypes = lib.gpsx_track_loop_weighted_aided.argtypes
     lib.gpsx_track_loop_weighted_sync_aided.argtypes = lib.gpsx_track_loop_weighted_aided.argtypes
     lib.gpsx_track_loop_weighted_sync_aided_dev.argtypes = lib.gpsx_track_loop_weighted_aided.argtypes
+    lib.gpsx_track_loop_weighted_sync_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.gpsx_track_loop_weighted_sync_multi_dev.argtypes = lib.gpsx_track_loop_weighted_sync_multi.argtypes
+    lib.gpsx_wobs_pseudoranges_rx.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gpsx_wnav_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wnav_words_dev.argtypes = lib.gpsx_wnav_words.argtypes
     lib.gpsx_wnav_subframe_image.argtypes = [C.c_void_p, C.c_void_p]
@@ -749,6 +780,22 @@ class Engine:
         rec = np.zeros((wsync_slots(len(blocks), int(cfg["n_coh_search"][0]), int(cfg["n_coh_lock"][0])), n_ch), WSYNC_REC_DTYPE)
         self._chk(self.lib.gpsx_track_loop_weighted_sync_aided(self.h, cfg.ctypes.data, aid.ctypes.data, blocks.ctypes.data, len(blocks),
                                                                C.c_void_p(d_state), n_ch, rec.ctypes.data), "gpsx_track_loop_weighted_sync_aided")
+        return rec
+
+    def track_loop_weighted_sync_multi(self, streams_2bit: np.ndarray, d_state: int, ch_per_rx: int, cfg: np.ndarray,
+                                       code_per_hz: float | None = None) -> np.ndarray:
+        """EXTENSION: track_loop_weighted_sync(_aided) for n_rx receivers in one launch, one IF stream each: streams_2bit is uint8
+        [n_rx, n_blocks, 4092]; the n_rx * ch_per_rx WSYNC_STATE_DTYPE states at device address d_state, channel r * ch_per_rx + j
+        slot j of receiver r (a slot without a satellite: prn = PRN_NONE).  code_per_hz None: unaided.
+        -> WSYNC_REC_DTYPE [slots, n_rx * ch_per_rx], receiver r's columns the single-stream call's on its stream"""
+        streams = np.ascontiguousarray(streams_2bit, np.uint8)
+        assert streams.ndim == 3 and streams.shape[2] == BYTES_PER_MS_2BIT and cfg.dtype == WSYNC_CFG_DTYPE and cfg.size == 1
+        n_rx, n_blocks = streams.shape[:2]
+        rx, aid = wmulti(n_rx, ch_per_rx, n_blocks), (None if code_per_hz is None else waid(code_per_hz))
+        rec = np.zeros((wsync_slots(n_blocks, int(cfg["n_coh_search"][0]), int(cfg["n_coh_lock"][0])), n_rx * ch_per_rx), WSYNC_REC_DTYPE)
+        self._chk(self.lib.gpsx_track_loop_weighted_sync_multi(self.h, cfg.ctypes.data, None if aid is None else aid.ctypes.data, rx.ctypes.data,
+                                                               streams.ctypes.data, n_blocks, C.c_void_p(d_state), rec.ctypes.data),
+                  "gpsx_track_loop_weighted_sync_multi")
         return rec
 
     def wnav_words(self, d_rec: int, n_slots: int, n_blocks: int, d_state: int, n_ch: int, max_bad_words: int = 3) -> np.ndarray:

@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -110,14 +110,21 @@ int track_epl_weighted(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void
 
 // ---- the closed loops: DLL / PLL / FLL, K blocks per launch; the second with a bit synchroniser and bit-aligned windows -------------
 // what a host call of either stages: the capture into the arena, room for the records.  The state is device memory in both variants.
+// n_rx > 1 (the _multi call): n_rx streams of n_blocks blocks, rx_stride_blocks apart in host memory, packed n_blocks apart in the
+// arena -- only the blocks themselves are read.
 template <typename Rec>
-int stage_loop_call(gpsx_ctx *ctx, const uint8_t *if_blocks_2bit, int n_blocks, size_t rec_bytes, const uint8_t **d_blocks, Rec **d_rec)
+int stage_loop_call(gpsx_ctx *ctx, const uint8_t *if_blocks_2bit, int n_blocks, size_t rec_bytes, const uint8_t **d_blocks, Rec **d_rec,
+                    int n_rx = 1, int rx_stride_blocks = 0)
 {
-  const size_t if_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT;
+  const size_t rx_bytes = (size_t)n_blocks * GPSX_BYTES_PER_MS_2BIT, if_bytes = (size_t)n_rx * rx_bytes;
   if (int rc = arena_reset(ctx, arena_size(if_bytes + 2) + arena_size(rec_bytes))) return rc;
   uint8_t *d_if = arena_take<uint8_t>(ctx, if_bytes + 2);
   *d_rec = arena_take<Rec>(ctx, rec_bytes / sizeof(Rec));
-  HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (n_rx == 1 || rx_stride_blocks == n_blocks)
+    HIPCHK(ctx, hipMemcpyAsync(d_if, if_blocks_2bit, if_bytes, hipMemcpyHostToDevice, ctx->stream));
+  else
+    HIPCHK(ctx, hipMemcpy2DAsync(d_if, rx_bytes, if_blocks_2bit, (size_t)rx_stride_blocks * GPSX_BYTES_PER_MS_2BIT, rx_bytes, (size_t)n_rx,
+                                 hipMemcpyHostToDevice, ctx->stream));
   *d_blocks = d_if;
   return GPSX_OK;
 }
@@ -157,12 +164,9 @@ int track_loop_weighted(gpsx_ctx *ctx, const gpsx_wloop_cfg_t *cfg, bool aided, 
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
-int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, bool aided, const gpsx_waid_t *aid, const void *if_blocks_2bit,
-                             int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec, bool host)
+// the sync loop's clauses on cfg and n_blocks, in the order both of its callers report them (between "null argument" and the channel counts)
+int check_wsync_cfg(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, int n_blocks)
 {
-  if (int rc = use_device(ctx)) return rc;
-  if (!cfg || (aided && !aid) || !if_blocks_2bit || !d_state || !rec)
-    return fail(ctx, GPSX_EINVAL, "null argument");
   if (int rc = check_weights_spacing(ctx, cfg->weights, cfg->spacing)) return rc;
   for (int n : {cfg->n_coh_search, cfg->n_coh_lock})
     if (n < 1 || n > 20 || 20 % n != 0)
@@ -173,12 +177,25 @@ int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, bool ai
     return fail(ctx, GPSX_EINVAL, "sync_num and sync_den must be 1..1024");
   if (cfg->sync_num < cfg->sync_den)
     return fail(ctx, GPSX_EINVAL, "sync_num must not be below sync_den");
-  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
-  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  return check_n_blocks(ctx, n_blocks);
+}
+// ... and behind the channel counts: the gains, the aiding factor
+int check_wsync_gains(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid)
+{
   for (const gpsx_wsync_gains_t *g : {&cfg->search, &cfg->lock})
     if (int rc = check_gains(ctx, {g->dll_c1, g->dll_c2, g->pll_c1, g->pll_c2, g->fll_c})) return rc;
-  if (aided)
-    if (int rc = check_aid(ctx, aid)) return rc;
+  return aid ? check_aid(ctx, aid) : GPSX_OK;
+}
+
+int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, bool aided, const gpsx_waid_t *aid, const void *if_blocks_2bit,
+                             int n_blocks, gpsx_wsync_state_t *d_state, int n_ch, gpsx_wsync_rec_t *rec, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || (aided && !aid) || !if_blocks_2bit || !d_state || !rec)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (int rc = check_wsync_cfg(ctx, cfg, n_blocks)) return rc;
+  if (int rc = check_n_ch(ctx, n_ch)) return rc;
+  if (int rc = check_wsync_gains(ctx, cfg, aided ? aid : nullptr)) return rc;
   const int span = cfg->n_coh_search < cfg->n_coh_lock ? cfg->n_coh_search : cfg->n_coh_lock;
   size_t rec_bytes = 0;
   if (records_overflow((size_t)((n_blocks + span - 1) / span), n_ch, sizeof(gpsx_wsync_rec_t), &rec_bytes))
@@ -194,6 +211,49 @@ int track_loop_weighted_sync(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, bool ai
           launch_track_loop_weighted_sync_aided(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, aid->code_per_hz, d_state, n_ch, ctx->d_trk_rep, d_rec, flag);
         else
           launch_track_loop_weighted_sync(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, d_state, n_ch, ctx->d_trk_rep, d_rec, flag);
+      },
+      [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
+// n_rx receivers, one stream each, in one launch (k_track_wsync_multi).  aid NULL: unaided -- the one kernel with a factor of 0, which
+// by the aided call's definition gives the unaided bytes.  The single-stream call's clauses in its order, rx's in the place of n_ch's.
+int track_loop_weighted_sync_multi(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const gpsx_wmulti_t *rx,
+                                   const void *if_blocks_2bit, int n_blocks, gpsx_wsync_state_t *d_state, gpsx_wsync_rec_t *rec, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !rx || !if_blocks_2bit || !d_state || !rec)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (int rc = check_wsync_cfg(ctx, cfg, n_blocks)) return rc;
+  if (rx->n_rx < 1 || rx->n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (rx->ch_per_rx < 1 || rx->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (rx->rx_stride_blocks < n_blocks)
+    return fail(ctx, GPSX_EINVAL, "rx_stride_blocks must not be below n_blocks");
+  if (rx->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  int n_ch = 0;
+  if (__builtin_mul_overflow(rx->n_rx, rx->ch_per_rx, &n_ch))
+    return fail(ctx, GPSX_EINVAL, "n_rx x ch_per_rx must not exceed INT32_MAX");
+  if (int rc = check_wsync_gains(ctx, cfg, aid)) return rc;
+  const int span = cfg->n_coh_search < cfg->n_coh_lock ? cfg->n_coh_search : cfg->n_coh_lock;
+  size_t rec_bytes = 0, bytes = 0;
+  if (records_overflow((size_t)((n_blocks + span - 1) / span), n_ch, sizeof(gpsx_wsync_rec_t), &rec_bytes) ||
+      records_overflow(1, n_ch, sizeof(gpsx_wsync_state_t), &bytes) ||
+      records_overflow((size_t)rx->rx_stride_blocks, rx->n_rx, GPSX_BYTES_PER_MS_2BIT, &bytes))
+    return fail(ctx, GPSX_EINVAL, "slots x n_ch records, states or streams overflow a size");
+  const uint8_t *d_if = static_cast<const uint8_t *>(if_blocks_2bit);
+  gpsx_wsync_rec_t *d_rec = rec;
+  int stride = rx->rx_stride_blocks;
+  if (host) {
+    if (int rc = stage_loop_call(ctx, d_if, n_blocks, rec_bytes, &d_if, &d_rec, rx->n_rx, stride)) return rc;
+    stride = n_blocks;   // (packed in the arena)
+  }
+  return launch_and_report(
+      ctx, host, "k_track_wsync_multi", nullptr,
+      [&](uint32_t *flag) {
+        launch_track_loop_weighted_sync_multi(ctx->stream, d_if, n_blocks, ctx->if_hz, *cfg, aid ? aid->code_per_hz : 0.0f, rx->n_rx, rx->ch_per_rx,
+                                              stride, d_state, ctx->d_trk_rep, d_rec, flag);
       },
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
@@ -389,6 +449,18 @@ int gpsx_track_loop_weighted_sync_aided(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *c
   return track_loop_weighted_sync(ctx, cfg, true, aid, if_blocks_2bit, n_blocks, d_state, n_ch, rec, true);
 }
 
+int gpsx_track_loop_weighted_sync_multi_dev(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const gpsx_wmulti_t *rx,
+                                            const void *d_if_blocks_2bit, int n_blocks, gpsx_wsync_state_t *d_state, gpsx_wsync_rec_t *d_rec)
+{
+  return track_loop_weighted_sync_multi(ctx, cfg, aid, rx, d_if_blocks_2bit, n_blocks, d_state, d_rec, false);
+}
+
+int gpsx_track_loop_weighted_sync_multi(gpsx_ctx *ctx, const gpsx_wsync_cfg_t *cfg, const gpsx_waid_t *aid, const gpsx_wmulti_t *rx,
+                                        const uint8_t *if_blocks_2bit, int n_blocks, gpsx_wsync_state_t *d_state, gpsx_wsync_rec_t *rec)
+{
+  return track_loop_weighted_sync_multi(ctx, cfg, aid, rx, if_blocks_2bit, n_blocks, d_state, rec, true);
+}
+
 int gpsx_wnav_words_dev(gpsx_ctx *ctx, const gpsx_wnav_cfg_t *cfg, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks,
                         gpsx_wnav_state_t *d_state, int n_ch, gpsx_wnav_word_t *d_words)
 {
@@ -491,6 +563,20 @@ int gpsx_wobs_pseudoranges(const gpsx_wobs_t *obs, int n, double offset_ms, doub
   const double rx = ((double)obs[ref].tx_ms - (double)obs[ref].code_phase_fine / 16368.0 + offset_ms) / 1000.0;
   *rx_tow_s = rx >= 604800.0 ? rx - 604800.0 : (rx < 0.0 ? rx + 604800.0 : rx);
   return count;
+}
+
+int gpsx_wobs_pseudoranges_rx(const gpsx_wobs_t *obs, int n_rx, int ch_per_rx, double offset_ms, double *pr_m, double *rx_tow_s, int *n_valid)
+{
+  int n_ch = 0, total = 0;
+  if (!obs || !pr_m || !rx_tow_s || !n_valid || n_rx < 1 || ch_per_rx < 1 || __builtin_mul_overflow(n_rx, ch_per_rx, &n_ch) ||
+      !(offset_ms - offset_ms == 0.0))
+    return GPSX_EINVAL;
+  for (int r = 0; r < n_rx; r++) {   // (the arguments are good: a slice's call returns its count)
+    const size_t at = (size_t)r * (size_t)ch_per_rx;
+    n_valid[r] = gpsx_wobs_pseudoranges(obs + at, ch_per_rx, offset_ms, pr_m + at, rx_tow_s + r);
+    total += n_valid[r];
+  }
+  return total;
 }
 
 }  // extern "C"

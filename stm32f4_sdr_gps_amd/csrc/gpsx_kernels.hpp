@@ -155,6 +155,13 @@ void launch_track_loop_weighted_aided(hipStream_t s, const uint8_t *d_if_blocks_
 void launch_track_loop_weighted_sync_aided(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
                                            float code_per_hz, gpsx_wsync_state_t *d_st, int n_ch, const uint32_t *d_trk_rep,
                                            gpsx_wsync_rec_t *d_rec, uint32_t *d_bad_prn);
+// extension: gpsx_track_loop_weighted_sync_multi (k_track_loop_weighted_sync_multi.hip: k_track_wsync_multi, the sync kernel's text a
+// third time) -- n_rx receivers with ch_per_rx (1 .. 64) channel slots each in one launch, a workgroup per receiver: receiver r reads
+// the n_blocks blocks that start rx_stride_blocks (>= n_blocks) 4092-byte blocks behind receiver r - 1's.  d_st [n_rx ch_per_rx] and
+// d_rec [slots][n_rx ch_per_rx] are the single-stream launch's arrays; code_per_hz 0: the unaided bytes.
+void launch_track_loop_weighted_sync_multi(hipStream_t s, const uint8_t *d_if_blocks_2bit, int n_blocks, int if_hz, const gpsx_wsync_cfg_t &cfg,
+                                           float code_per_hz, int n_rx, int ch_per_rx, int rx_stride_blocks, gpsx_wsync_state_t *d_st,
+                                           const uint32_t *d_trk_rep, gpsx_wsync_rec_t *d_rec, uint32_t *d_bad_prn);
 // extension: gpsx_wnav_words (k_wnav_words.hip: k_wnav_words) -- LNAV frame sync and parity-checked words from the [n_slots][n_ch]
 // records launch_track_loop_weighted_sync wrote for n_blocks blocks: one channel per lane, 64-byte frame states in HBM,
 // d_words [n_blocks / 600 + 2][n_ch], every byte of it written.  d_bad_state (may be null): set to 1 by a channel whose state

@@ -23,4 +23,16 @@ inline TrackLoopWeightedPlan plan_track_loop_weighted(int n_ch)
   return TrackLoopWeightedPlan{(int)cpw, groups};
 }
 
+// k_track_wsync_multi (k_track_loop_weighted_sync_multi.hip): one workgroup of four waves per receiver, wave w serves the receiver's
+// slots w cpw .. + cpw - 1 below ch_per_rx.  Four waves of sixteen quads: 64 slots at most.  ch_per_rx outside 1 .. 64 or n_rx < 1:
+// {0, 0}, no launch.  tests/test_track_loop_weighted_multi_plan.py checks it as the plan above is checked.
+constexpr int kTrackLoopWeightedMultiMaxSlots = 4 * kTrackLoopWeightedMaxCpw;
+
+inline TrackLoopWeightedPlan plan_track_loop_weighted_multi(int n_rx, int ch_per_rx)
+{
+  if (n_rx < 1 || ch_per_rx < 1 || ch_per_rx > kTrackLoopWeightedMultiMaxSlots)
+    return TrackLoopWeightedPlan{0, 0u};
+  return TrackLoopWeightedPlan{(ch_per_rx + 3) / 4, (unsigned)n_rx};
+}
+
 }  // namespace gpsx

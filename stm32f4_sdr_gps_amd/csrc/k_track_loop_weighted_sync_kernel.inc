@@ -1,7 +1,11 @@
 // k_track_loop_weighted_sync_kernel.inc -- the text of k_track_wsync and of its carrier-aided twin k_track_waid_sync:
 // k_track_loop_weighted_sync.hip includes it twice,
 // with GPSX_WSYNC_KERNEL the kernel's name and GPSX_WSYNC_AIDED 0 / 1.  One copy of the block loop; the aided kernel has one more
-// argument (code_per_hz) and window_update's aiding clause (gpsx_track_wloop_parts.hpp), nothing else.  A text, not a template
+// argument (code_per_hz) and window_update's aiding clause (gpsx_track_wloop_parts.hpp), nothing else.
+// k_track_loop_weighted_sync_multi.hip includes it a third time, as k_track_wsync_multi, with GPSX_WSYNC_AIDED 1 and GPSX_WSYNC_MULTI
+// defined: two more arguments and other PLACES -- a workgroup is a receiver, its lanes' channels come from that file's lanes_of_rx, the
+// blocks are the receiver's own -- and no other line.  There n_ch is the record pitch alone (n_rx ch_per_rx), not the lanes' bound.
+// A text, not a template
 // function that two thin kernels call: inlined into a kernel that form changed k_track_wsync's block loop (other exec-mask
 // handling around the record stores; profiles/r16_waid_unaided_isa.txt), and this one leaves both unaided kernels as they were.
 __global__ __launch_bounds__(256, 4) void GPSX_WSYNC_KERNEL(const uint8_t *__restrict__ if_blocks, int n_blocks, int if_hz, gpsx_wsync_cfg_t cfg,
@@ -10,6 +14,9 @@ __global__ __launch_bounds__(256, 4) void GPSX_WSYNC_KERNEL(const uint8_t *__res
                                                      u32 *__restrict__ bad_prn
 #if GPSX_WSYNC_AIDED
                                                      , float code_per_hz
+#endif
+#ifdef GPSX_WSYNC_MULTI
+                                                     , int ch_per_rx, size_t rx_stride_bytes
 #endif
 )
 {
@@ -20,7 +27,12 @@ __global__ __launch_bounds__(256, 4) void GPSX_WSYNC_KERNEL(const uint8_t *__res
   using namespace trkwloop;
   __shared__ __attribute__((aligned(16))) u32 s_x[2][512], s_m[2][512];   // this and the next block's planes
   __shared__ uint2 s_carrier[4];
+#ifdef GPSX_WSYNC_MULTI
+  const Lanes l = lanes_of_rx(ch_per_rx, cpw);   // ch_l counts over all receivers: the state and record bases are in it
+  if_blocks += (size_t)blockIdx.x * rx_stride_bytes;
+#else
   const Lanes l = lanes_of(n_ch, cpw);   // gpsx_track_wloop_parts.hpp, like everything the two loops share
+#endif
   const int lane = l.lane, k_l = l.k_l, n_here = l.n_here, ch_l = l.ch_l;
   const bool in_wave = l.in_wave(), mine = l.mine();
   const int use_magnitude = cfg.weights == GPSX_WEIGHTS_SIGN_MAGNITUDE;

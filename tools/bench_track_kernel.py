@@ -61,7 +61,16 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       beside (1) a device-to-device hipMemcpyAsync of the record array -- the bar: the
                                                       kernel takes no longer -- and (2) gpsx_wobs_dev on the same lines (no bar: it
                                                       reads 16 bytes of a record where this reads 32), the calls taking turns in one
-                                                      process"""
+                                                      process
+  bench_track_kernel.py --weighted-multi [--single-only] [--parent-rows FILE] [N_RXxCH_PER_RX ...]
+                                                      gpsx_track_loop_weighted_sync_multi_dev (EXTENSION: many receivers per launch, one
+                                                      IF stream each; k_track_wsync_multi) at (n_rx, ch_per_rx) = (16384, 4), (8192, 8),
+                                                      (5461, 12), (1024, 64), 64 blocks, every channel LOCKED at n_coh_lock = 20, beside
+                                                      gpsx_track_loop_weighted_sync_aided_dev on ONE stream with the same n_ch, the
+                                                      calls taking turns: time, ns per channel-ms, the ratio, and the IF bytes the
+                                                      launch must read from HBM.  --single-only: the single-stream rows alone, for a
+                                                      library without the new call (the parent commit's, in a neighbouring process);
+                                                      --parent-rows: such rows, against which the ratio is formed too"""
 import ctypes as C
 import json
 import os
@@ -327,6 +336,64 @@ def weighted_sync(counts, k_loop=200):
             print(json.dumps({"scenario_wall_clock": True, "channels": n, "blocks": 10 * k_loop, "launches": 10, "n_coh_search": 4, "n_coh_lock": 20,
                               "seconds": round(wall, 4), "record_bytes_per_launch": capi.wsync_slots(k_loop, 4, 20) * n * 48}), flush=True)
         eng.free(d_sync["c_search"])
+
+
+MULTI_SHAPES = [(16384, 4), (8192, 8), (5461, 12), (1024, 64)]
+
+
+def weighted_multi(shapes, n_blocks=64, single_only=False, parent_rows=None):
+    """gpsx_track_loop_weighted_sync_multi_dev (k_track_wsync_multi: a workgroup per receiver, one IF stream each) per shape
+    (n_rx, ch_per_rx), every channel LOCKED at n_coh_lock = 20 with edges spread, GPSX_WAID_L1CA, beside
+    gpsx_track_loop_weighted_sync_aided_dev (k_track_waid_sync) on ONE stream with the same n_ch and n_blocks, the calls taking
+    turns.  single_only: the single-stream rows alone (a library without the new call: the parent commit's, in a neighbouring
+    process); parent_rows: a file of such rows, against which the ratios are formed as well"""
+    from stm32f4_sdr_gps_amd import capi
+    eng = capi.Engine(0)
+    gains = dict(dll=(1.0, 300.0), pll=(4.0, 3000.0), fll=0.1)
+    cfg, aid = capi.wsync_cfg(20, 20, gains, gains, 20, (1024, 1)), capi.waid()
+    parent = {}
+    if parent_rows:
+        for line in open(parent_rows):
+            row = json.loads(line)
+            if row.get("call", "").startswith("weighted_sync_aided_single"):
+                parent[row["channels"]] = row["us_median"]
+    chunk_rx = 256
+    chunk = np.random.default_rng(7).integers(0, 256, (chunk_rx, n_blocks, 4092), dtype=np.uint8)      # (receivers beyond 256 repeat these bytes)
+    for n_rx, ch in shapes:
+        n = n_rx * ch
+        trk = _bench_states(n)
+        st = np.zeros(n, capi.WSYNC_STATE_DTYPE)
+        for f in ("prn", "code_phase_fine", "if_freq_offset_hz"):
+            st["loop"][f] = trk[f]
+        st["mode"], st["edge"] = capi.WSYNC_LOCKED, np.arange(n) % 20
+        d_single, d_rec = eng.malloc(st.nbytes), eng.malloc(capi.wsync_slots(n_blocks, 20, 20) * n * 48)
+        eng.h2d(d_single, st)
+        d_one = eng.malloc(chunk[0].nbytes)
+        eng.h2d(d_one, chunk[0])
+        calls = {f"weighted_sync_aided_single_k{n_blocks}": (n_blocks, lambda: eng.lib.gpsx_track_loop_weighted_sync_aided_dev(
+            eng.h, cfg.ctypes.data, aid.ctypes.data, C.c_void_p(d_one), n_blocks, C.c_void_p(d_single), n, C.c_void_p(d_rec)))}
+        ptrs = [d_single, d_rec, d_one]
+        if not single_only:
+            rx = capi.wmulti(n_rx, ch, n_blocks)
+            d_multi, d_if = eng.malloc(st.nbytes), eng.malloc(n_rx * chunk[0].nbytes)
+            ptrs += [d_multi, d_if]
+            eng.h2d(d_multi, st)
+            for r in range(0, n_rx, chunk_rx):
+                eng.h2d(d_if + r * chunk[0].nbytes, chunk[:min(chunk_rx, n_rx - r)])
+            calls[f"weighted_sync_multi_k{n_blocks}"] = (n_blocks, lambda: eng.lib.gpsx_track_loop_weighted_sync_multi_dev(
+                eng.h, cfg.ctypes.data, aid.ctypes.data, rx.ctypes.data, C.c_void_p(d_if), n_blocks, C.c_void_p(d_multi), C.c_void_p(d_rec)))
+            calls[f"weighted_sync_aided_single_k{n_blocks}_again"] = calls[f"weighted_sync_aided_single_k{n_blocks}"]
+        med = _timed_rows(eng, calls, {"channels": n, "n_rx": n_rx, "ch_per_rx": ch})
+        if not single_only:
+            single, multi = med[f"weighted_sync_aided_single_k{n_blocks}"], med[f"weighted_sync_multi_k{n_blocks}"]
+            print(json.dumps({"ratio": "k_track_wsync_multi over k_track_waid_sync on one stream", "n_rx": n_rx, "ch_per_rx": ch, "channels": n,
+                              "blocks": n_blocks, "multi_us": round(multi, 3), "ns_per_channel_ms": round(multi / n_blocks / n * 1e3, 4),
+                              "over_single": round(multi / single, 4),
+                              "single_again": round(med[f"weighted_sync_aided_single_k{n_blocks}_again"] / single, 4),
+                              **({"over_parent_single": round(multi / parent[n], 4), "parent_single_us": parent[n]} if n in parent else {}),
+                              "if_bytes_from_hbm": n_rx * n_blocks * 4092, "gb_per_s_of_if": round(n_rx * n_blocks * 4092 / multi / 1e3, 2)}), flush=True)
+        for p in ptrs:
+            eng.free(p)
 
 
 def weighted_nav(counts, n_blocks=4000, span=20):
@@ -718,6 +785,20 @@ def main():
             WINDOW_S = float(args.pop(at + 1))
             args.pop(at)
         return weighted_lock([int(a) for a in args] or [65536, 212992])
+    if "--weighted-multi" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-multi"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        parent_rows = None
+        if "--parent-rows" in args:
+            at = args.index("--parent-rows")
+            parent_rows = args.pop(at + 1)
+            args.pop(at)
+        single_only = "--single-only" in args
+        shapes = [tuple(int(v) for v in a.split("x")) for a in args if a != "--single-only"]
+        return weighted_multi(shapes or MULTI_SHAPES, single_only=single_only, parent_rows=parent_rows)
     if "--weighted-eph" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-eph"]
         if "--window-s" in args:
