@@ -31,7 +31,8 @@
 //     impulses of -1 / +1 in the vector at entries 1021 and 1022 (not in their wrap-around copies) per step;
 //   * the terms "PRN flag x per-offset value" (chip 1022: quirk Q5 and the tail word of Q3; chip 1021: the tail word) are
 //     one more K step of the GEMM: A column 0 of lane half 0 = chip 1022 of the PRN, of half 1 = chip 1021, B = the
-//     per-offset deltas (0, +-1, +-2) read as one byte per lane;
+//     per-offset deltas (0, +-1, +-2) read as one byte per lane -- in the single-block form they ride in chip columns 1021 / 1022
+//     of the main GEMM instead (MxFold, gpsx_fold_codes.hpp);
 //   * at the switch from even to odd byte offsets (t0 = 8) every such term jumps; that one step is patched into the
 //     accumulators by the vector ALU (mx_half_switch).
 // The epilogue of a sample offset is then: clip, square, add, correctly rounded root, truncate, (add the running sum of
@@ -57,6 +58,7 @@
 
 #include "gpsx_anchor_codes.hpp"
 #include "gpsx_device.hpp"
+#include "gpsx_fold_codes.hpp"
 #include "gpsx_kernels.hpp"
 
 namespace gpsx {
@@ -98,6 +100,13 @@ struct MxShared {
   alignas(16) u32 part[8][32][2][32];              // (packed best key, sum) per bit shift, PRN and lane of the wave half that holds the
                                          // PRN: every lane folds its own results in with LDS atomics (no return value, no
                                          // conflicts), the 32 lanes meet once, when the workgroup writes its triplets
+};
+
+// The single-block form alone (k_acq_mx<0>; behind MxShared in its LDS block): the quirk terms of a recurrence pass as code pairs
+// for chip columns 1021 / 1022 of the main GEMM instead of sh.corr and the extra K step (gpsx_fold_codes.hpp)
+struct MxFold {
+  u32 pair[2][2][1024];                  // [buffer][stream][q]: the pair of chip offset q where the fragment dword has it, bits 20..27
+  v4i lut[2][32];                        // [late][plane bits 4 j - 2 .. 4 j + 2] -> the pairs of q = 4 j .. 4 j + 3, q >= 2
 };
 
 __device__ __forceinline__ v8i widen(v4i x) { return v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0}; }
@@ -380,7 +389,11 @@ __device__ __forceinline__ u32 mx_patch_wrap(u32 packed, u32 w9, bool patch)
   return patch ? patched : packed;
 }
 
-__device__ __forceinline__ void mx_vector_build(MxShared &sh, int p_vec, int tid)
+// FOLD (the single-block form): in place of the extra K step's vectors thread (stream, j) writes the code pairs of chip offsets
+// 4 j .. 4 j + 3 (MxFold): one table look-up by the five plane bits they depend on; q = 0 and q = 1 of sample offsets 9..15 have
+// pairs of their own.  (Sample offset 8, the half switch: its pass reads no pairs.)
+template <bool FOLD = false>
+__device__ __forceinline__ void mx_vector_build(MxShared &sh, int p_vec, int tid, MxFold *fold = nullptr)
 {
   const int t0 = p_vec - 1, buf = p_vec & 1;
   const bool late = t0 >= 9;
@@ -388,25 +401,44 @@ __device__ __forceinline__ void mx_vector_build(MxShared &sh, int p_vec, int tid
   const u32 *pl = sh.plane[iq][p_vec - 2];
   // 17 plane bits from 8 j: the 9-bit windows of dwords j and j + 1
   const u32 x = __builtin_amdgcn_alignbit(pl[(j >> 2) + 1], pl[j >> 2], 8u * (u32)(j & 3));
-  // bits 8 dwc - 1 .. 8 dwc + 7 (bit -1 = 0) for the extra K step: d[q] = bit k + 1, d[q - 1] = bit k of the dword's eight q
-  const int pos = dwc ? 8 * dwc - 1 : 0;
-  const u32 y = __builtin_amdgcn_alignbit(pl[(pos >> 5) + 1], pl[pos >> 5], (u32)(pos & 31));
-  const u32 cw = (dwc ? y : y << 1) & 0x1FFu;
+  u32 cw = 0, v = 0;
+  if constexpr (!FOLD) {
+    // bits 8 dwc - 1 .. 8 dwc + 7 (bit -1 = 0) for the extra K step: d[q] = bit k + 1, d[q - 1] = bit k of the dword's eight q
+    const int pos = dwc ? 8 * dwc - 1 : 0;
+    const u32 y = __builtin_amdgcn_alignbit(pl[(pos >> 5) + 1], pl[pos >> 5], (u32)(pos & 31));
+    cw = (dwc ? y : y << 1) & 0x1FFu;
+  }
   u32 lo = sh.t_lut[x & 0x1FFu], hi = sh.t_lut[(x >> 8) & 0x1FFu];
   // term 0: A' deltas: 2 d - 1 before the half switch, 2 (d - dm) after it; term 1: B' deltas 2 dm - 1 (after it only)
-  u32 v = sh.t_lut[which ? 512u + (cw & 0xFFu) : (late ? cw : 512u + (cw >> 1))];
+  if constexpr (!FOLD)
+    v = sh.t_lut[which ? 512u + (cw & 0xFFu) : (late ? cw : 512u + (cw >> 1))];
   if (late) {
     lo = mx_patch_wrap(lo, x & 0x1FFu, j == 127);
     hi = mx_patch_wrap(hi, (x >> 8) & 0x1FFu, j == 126);
-    if (which == 0)
-      v ^= (v & 0x44444444u) << 1;                         // -2 (d - dm) -> 2 (d - dm): the sign of the non-zero codes
-    if (dwc == 0)                                          // q = 0 has no tail word: A' grows by 2 d - 1, B' stays
-      v = (v & ~0xFu) | (which ? 0u : ((cw & 2u) ? 0x2u : 0xAu));
+    if constexpr (!FOLD) {
+      if (which == 0)
+        v ^= (v & 0x44444444u) << 1;                       // -2 (d - dm) -> 2 (d - dm): the sign of the non-zero codes
+      if (dwc == 0)                                        // q = 0 has no tail word: A' grows by 2 d - 1, B' stays
+        v = (v & ~0xFu) | (which ? 0u : ((cw & 2u) ? 0x2u : 0xAu));
+    }
   }
-  v &= dwc == 127 ? 0x0FFFFFFFu : 0xFFFFFFFFu;             // q = 1023 does not exist
-  if ((which && !late) || t0 == 8)
-    v = 0;
-  sh.corr[buf][iq][which][dwc] = v;
+  if constexpr (!FOLD) {
+    v &= dwc == 127 ? 0x0FFFFFFFu : 0xFFFFFFFFu;           // q = 1023 does not exist
+    if ((which && !late) || t0 == 8)
+      v = 0;
+    sh.corr[buf][iq][which][dwc] = v;
+  } else {
+    // plane bits 4 j - 2 .. 4 j + 2, from the circular extension (at + 1023): bits i and i + 1 are d[q - 2] and d[q - 1] of
+    // q = 4 j + i.  (q = 1023 does not exist: its pair meets an accumulator that clips to zero whatever is added.)
+    const int pos = 4 * j + kChips - 2;
+    const u32 z = __builtin_amdgcn_alignbit(pl[(pos >> 5) + 1], pl[pos >> 5], (u32)(pos & 31)) & 31u;
+    v4i pr = fold->lut[late][z];
+    if (late && j == 0) {
+      pr.x = (int)(gpsx_fold_pair(true, 0, (int)(z & 1u), (int)((z >> 1) & 1u)) << kGpsxFoldShift);
+      pr.y = (int)(gpsx_fold_pair(true, 1, (int)((z >> 1) & 1u), (int)((z >> 2) & 1u)) << kGpsxFoldShift);
+    }
+    *reinterpret_cast<v4i *>(&fold->pair[buf][iq][4 * j]) = pr;
+  }
   u32 *dst = &sh.e8[buf][iq][0][j];
 #pragma unroll
   for (int c = 0; c < 8; c++)
@@ -417,34 +449,65 @@ __device__ __forceinline__ void mx_vector_build(MxShared &sh, int p_vec, int tid
 // The sched_group_barriers pin that order -- the DS reads first, (8 MFMAs = 260 cycles ahead of their use) -- which the
 // scheduler, short of registers, would otherwise turn into "requested one MFMA before the wait": the LDS is kept busy by
 // the four waves of the other role, a wave that waits for it at every step loses a third of the matrix pipe's time.
-template <int S, int NT, u32 SCALE_A = kScaleA>
+//
+// FOLD (the single-block form, MxFold): chips 992..1023 -- kappa = 15, lane half 1 -- sit in the fragment of steps S = 15..18, where
+// tile S - 15 alone is at kappa = 15.  Its MFMAs go last in the step, and in front of them the lane's code pair of that tile
+// (requested a step ahead, with the fragments) replaces bits 20..27 of the fragment's fourth dword in place: one v_bfi_b32 per
+// stream, issued under the other tiles' MFMAs.  mask = 0 (lane half 0; a pass without quirk terms) leaves the dword as it is.
+struct MxFoldRegs {
+  lds_cu32 *w;                           // pair[buffer][0][q of tile 0]: tile j at + 64 j, the Q stream at + 1024
+  u32 mask, pi, pq;
+};
+template <int S, int NT, u32 SCALE_A = kScaleA, bool FOLD = false>
 __device__ __forceinline__ void mx_pass_step(lds_cu32 *wi, lds_cu32 *wq, const v4i *ca, v4i (&a)[16], v4i &fi, v4i &fq,
-                                             v16f (&acc)[2][NT], u32 scale_b)
+                                             v16f (&acc)[2][NT], u32 scale_b, MxFoldRegs *fold = nullptr)
 {
   constexpr int kSteps = 16 + NT - 1;
   constexpr bool more = S + 1 < kSteps;
+  constexpr bool pair_next = FOLD && more && S + 1 >= 15, patched = FOLD && S >= 15;
   v4i fi_next = fi, fq_next = fq;
+  u32 pi_next = 0, pq_next = 0;
   if constexpr (more) {
     fi_next = lds_frag(wi, 8 * (S + 1));
     fq_next = lds_frag(wq, 8 * (S + 1));
     if constexpr (S + 1 < 16)
       a[S + 1] = ca[(S + 1) * 64];                         // chips_a[S + 1][h][n]
+    if constexpr (pair_next) {
+      pi_next = fold->w[64 * (S + 1 - 15)];
+      pq_next = fold->w[64 * (S + 1 - 15) + 1024];
+    }
   }
   constexpr int j_lo = S - 15 > 0 ? S - 15 : 0, j_hi = S < NT - 1 ? S : NT - 1;
 #pragma unroll
-  for (int j = j_lo; j <= j_hi; j++) {
+  for (int j = j_lo + (patched ? 1 : 0); j <= j_hi; j++) {
     acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), widen(fi), acc[0][j], 4, 4, 0, SCALE_A, 0, scale_b);
     acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), widen(fq), acc[1][j], 4, 4, 0, SCALE_A, 0, scale_b);
   }
+  if constexpr (patched) {
+    fi.w = (int)((fold->mask & fold->pi) | (~fold->mask & (u32)fi.w));
+    fq.w = (int)((fold->mask & fold->pq) | (~fold->mask & (u32)fq.w));
+    acc[0][j_lo] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[15]), widen(fi), acc[0][j_lo], 4, 4, 0, SCALE_A, 0, scale_b);
+    acc[1][j_lo] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[15]), widen(fq), acc[1][j_lo], 4, 4, 0, SCALE_A, 0, scale_b);
+  }
   if constexpr (more) {
-    __builtin_amdgcn_sched_group_barrier(0x100, S + 1 < 16 ? 5 : 4, 0);   // DS reads
-    __builtin_amdgcn_sched_group_barrier(0x008, 2 * (j_hi - j_lo + 1), 0);   // MFMAs
+    __builtin_amdgcn_sched_group_barrier(0x100, (S + 1 < 16 ? 5 : 4) + (pair_next ? 2 : 0), 0);   // DS reads
+    if constexpr (patched) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * (j_hi - j_lo), 0);    // MFMAs of the tiles below kappa = 15
+      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);                    // the two patches
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                    // MFMAs of tile S - 15
+    } else {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * (j_hi - j_lo + 1), 0);   // MFMAs
+    }
   }
   __builtin_amdgcn_sched_barrier(0);
   fi = fi_next;
   fq = fq_next;
+  if constexpr (FOLD) {
+    fold->pi = pi_next;
+    fold->pq = pq_next;
+  }
   if constexpr (more)
-    mx_pass_step<S + 1, NT, SCALE_A>(wi, wq, ca, a, fi, fq, acc, scale_b);
+    mx_pass_step<S + 1, NT, SCALE_A, FOLD>(wi, wq, ca, a, fi, fq, acc, scale_b, fold);
 }
 
 // The same without a second set of fragment registers (the walk forms, whose prefetched sums leave none): the I fragment of the
@@ -486,10 +549,12 @@ __device__ __forceinline__ void mx_pass_step_inplace(lds_cu32 *wi, lds_cu32 *wq,
 // AHEAD = false (the walk forms): mx_pass_step_inplace
 // NT = q-tiles of this call (q0_tile + 2 j, j < NT): four everywhere but in the byte-phase form, which works in tile pairs
 // SCALE_A: the A operand's block scale (the weighted extension keeps plain integers in its accumulators: 2^0; AHEAD only)
-template <bool AHEAD, int NT, u32 SCALE_A = kScaleA>
+// FOLD: no extra K step; with_corr says whether the pairs of fold_pair (MxFold::pair[buf]) are patched in (mx_pass_step)
+template <bool AHEAD, int NT, u32 SCALE_A = kScaleA, bool FOLD = false>
 __device__ __forceinline__ void mx_pass(const MxShared &sh, int buf, int lane, int q0_tile, v16f (&acc)[2][NT],
-                                        u32 scale_b, v4i a_corr, bool with_corr)
+                                        u32 scale_b, v4i a_corr, bool with_corr, const u32 *fold_pair = nullptr)
 {
+  static_assert(!FOLD || (AHEAD && NT == kMxTiles), "the fold is the single-block form's");
   const int n = lane & 31, h = lane >> 5;
   const u32 *e8 = &sh.e8[buf][0][0][0];
   lds_cu32 *wi = lds_opaque(e8 + (n & 7) * kCopyDwords + 4 * (q0_tile + h) + (n >> 3));
@@ -499,14 +564,19 @@ __device__ __forceinline__ void mx_pass(const MxShared &sh, int buf, int lane, i
   if constexpr (AHEAD) {
     v4i fi = lds_frag(wi, 0), fq = lds_frag(wq, 0);
     a[0] = ca[0];
-    mx_pass_step<0, NT, SCALE_A>(wi, wq, ca, a, fi, fq, acc, scale_b);
+    if constexpr (FOLD) {
+      MxFoldRegs fold{lds_opaque(fold_pair + 32 * q0_tile + n), h && with_corr ? kGpsxFoldMask : 0u, 0u, 0u};
+      mx_pass_step<0, NT, SCALE_A, true>(wi, wq, ca, a, fi, fq, acc, scale_b, &fold);
+    } else {
+      mx_pass_step<0, NT, SCALE_A>(wi, wq, ca, a, fi, fq, acc, scale_b);
+    }
   } else {
     static_assert(SCALE_A == kScaleA, "the in-place walk is the sign-only grid's");
     v4i fi = lds_frag(wi, 0), fq = lds_frag(wq, 0);
     a[0] = ca[0];
     mx_pass_step_inplace<0, NT>(wi, wq, ca, a, fi, fq, acc, scale_b);
   }
-  if (with_corr) {   // wave-uniform
+  if (!FOLD && with_corr) {   // wave-uniform
     // the extra K step: only column 0 of each lane half of A is set (chip 1022 / chip 1021 of the PRN), so only the first
     // nibble of a lane's B window counts: the step's delta for (stream, term h, q)
     // (dword q >> 3 = 4 (q0_tile + 2 j) + n / 8 of the term's vector: one address, constant offsets per tile and stream)

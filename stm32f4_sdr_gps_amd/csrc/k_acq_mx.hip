@@ -575,7 +575,27 @@ __device__ __forceinline__ void mx_epilogue_store(int lane, int q0_tile, int t0,
 //   vector of pass 1 (e8[0], over the anchor): all, 2   pass 1, half steps 2 / 3                  the loop's first (half step 2)
 // The barrier of half step 2 is taken twice: once to end the anchor passes and publish the planes, once -- the loop's own --
 // behind the build of pass 1's vector, where the loop goes on to build pass 2's next to pass 1 as in every later step.
-__device__ __forceinline__ void mx_single(MxShared &sh, const AcqParams &prm, int cluster_lo,
+//
+// The quirk terms ride in chip columns 1021 / 1022 of the recurrence passes (MxFold, gpsx_fold_codes.hpp): no extra K step here.
+// The pairs of a pass are built with its vector and published with it; their look-up table is one more piece of role 1's half
+// step 0, published like t_lut.
+struct MxSingleShared {
+  MxShared mx;
+  MxFold fold;
+};
+__device__ __forceinline__ void mx_fill_fold_lut(MxFold &fold, int t)   // threads 0..63
+{
+  if (t < 64) {
+    const int late = t >> 5, z = t & 31;
+    v4i e;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      e[i] = (int)(gpsx_fold_pair(late != 0, 2, (z >> i) & 1, (z >> (i + 1)) & 1) << kGpsxFoldShift);
+    fold.lut[late][z] = e;
+  }
+}
+
+__device__ __forceinline__ void mx_single(MxShared &sh, MxFold &fold, const AcqParams &prm, int cluster_lo,
                                           const uint8_t *__restrict__ if_blocks, const u32 *__restrict__ mx_a,
                                           const u32 *__restrict__ mx_t, gpsx_peak_t *__restrict__ peaks)
 {
@@ -612,8 +632,6 @@ __device__ __forceinline__ void mx_single(MxShared &sh, const AcqParams &prm, in
   mx_load_block(sh, block0, prm.if_format, tid);
 
   __syncthreads();
-  // A operand of the extra K step: column 0 of lane half 0 = chip 1022 of PRN (lane & 31), of half 1 = chip 1021
-  const v4i a_corr = v4i{(int)(((sh.chip_t[(lane >> 5 ? 1021 : 1022) + 1] >> (lane & 31)) & 1u) << 1), 0, 0, 0};
   u32 kq[kMxTiles];   // 2047 - (even byte offset of the lane's chip offset in tile j): the low field of its search keys
 #pragma unroll
   for (int j = 0; j < kMxTiles; j++) {
@@ -645,6 +663,7 @@ __device__ __forceinline__ void mx_single(MxShared &sh, const AcqParams &prm, in
     if (role) {                    // (threads 256..511; all of it is done before role 0, alone on the matrix pipe, ends its pass)
       mx_planes_half(sh, 0, wave & 3, opaque(lane));
       mx_fill_tables(sh, opaque(tid) & 255, 256);
+      mx_fill_fold_lut(fold, opaque(tid) & 255);
       mx_planes_half(sh, 8, wave & 3, opaque(lane));
       mx_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
     }
@@ -652,14 +671,14 @@ __device__ __forceinline__ void mx_single(MxShared &sh, const AcqParams &prm, in
     if (!role)                     // half step 1 of role 0, under role 1's pass
       mx_epilogue_single(sh, lane, kq, 0, acc);
     __syncthreads();               // half step 2: everybody is done with the anchor vector; the planes and t_lut are published
-    mx_vector_build(sh, 2, opaque(tid));
+    mx_vector_build<true>(sh, 2, opaque(tid), &fold);
 #pragma unroll 1
     for (int hs = 2; hs <= 2 * n_pass; hs++) {
       if ((hs & 1) == 0) {
         __syncthreads();
         const int p_vec = (hs >> 1) + 1;   // the next step's pass
         if (p_vec < n_pass)
-          mx_vector_build(sh, p_vec + 1, tid);
+          mx_vector_build<true>(sh, p_vec + 1, tid, &fold);
       }
       const int x = hs - role;   // role-local half step: even = MFMA pass x / 2, odd = epilogue after pass (x - 1) / 2
       const bool active = x >= 0 && x < 2 * n_pass;
@@ -667,7 +686,8 @@ __device__ __forceinline__ void mx_single(MxShared &sh, const AcqParams &prm, in
       //  the compiler schedules the kernel differently: 7728 instructions against 7732)
       const int p = (x >> 1) + 1;
       if (active && (x & 1) == 0) {
-        mx_pass<true>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne, a_corr, p >= 2 && p != 9);
+        mx_pass<true, kMxTiles, kScaleA, true>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne, v4i{0, 0, 0, 0},
+                                               p >= 2 && p != 9, &fold.pair[p & 1][0][0]);
         if (p == 9)
           mx_half_switch(sh, lane, q0_tile, acc, prm.win_start, prm.win_stop);
       }
@@ -975,11 +995,13 @@ __device__ __forceinline__ void mx_unit(MxShared &sh, const AcqParams &prm, int 
 template <int MODE>
 __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mx(GPSX_K_ACQ_MX_PARAMS)
 {
-  __shared__ MxShared sh;
-  if constexpr (MODE == kMxSingle)
-    mx_single(sh, prm, cluster_lo, if_blocks, mx_a, mx_t, peaks);
-  else
+  if constexpr (MODE == kMxSingle) {
+    __shared__ MxSingleShared sh;
+    mx_single(sh.mx, sh.fold, prm, cluster_lo, if_blocks, mx_a, mx_t, peaks);
+  } else {
+    __shared__ MxShared sh;
     mx_unit<MODE>(sh, prm, cluster_lo, if_blocks, mx_a, mx_t, peaks, energy, flags);
+  }
 }
 
 // plan_acq (gpsx_acq_plan.hpp) decides the form, its grids and split_segs (in prm); this issues its launch sequence
