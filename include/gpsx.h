@@ -37,7 +37,8 @@ extern "C" {
                                             * gpsx_weph_to_eph (include/gpsx_compat.h) likewise; so are the four carrier-aided loop
                                             * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t; gpsx_wlock(_dev) and
                                             * gpsx_wlock_cn0_dbhz likewise; gpsx_track_loop_weighted_sync_multi(_dev) with
-                                            * gpsx_wmulti_t and gpsx_wobs_pseudoranges_rx too. */
+                                            * gpsx_wmulti_t and gpsx_wobs_pseudoranges_rx too; gpsx_wfix(_dev) with gpsx_wfix_cfg_t
+                                            * and gpsx_wfix_t likewise. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -1140,6 +1141,93 @@ int gpsx_wlock(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_
  * logarithm in double; 0 for every other record.  (The logarithm stays on the host: what a device logarithm costs in parity is
  * told at snr_value below.)  Returns GPSX_OK, or GPSX_EINVAL for NULL, n < 1 or n_coh_lock outside 1 .. 20. */
 int gpsx_wlock_cn0_dbhz(const gpsx_wlock_t *lock, int n, int n_coh_lock, float *cn0_dbhz);
+
+/* ---- EXTENSION, not in the reference: weighted position fixes -- every receiver's single-point position, on the device -------------
+ * The last step of the weighted chain: gpsx_wfix(_dev) is a stage behind gpsx_wobs_dev and gpsx_weph_dev (and gpsx_wlock_dev, when its
+ * verdict is wanted).  It reads the observables d_obs[n_rx * ch_per_rx] and the ephemeris records d_eph[n_rx * ch_per_rx] where those
+ * stages left them -- receiver r owns slots [r * ch_per_rx, (r + 1) * ch_per_rx), as in gpsx_track_loop_weighted_sync_multi -- and
+ * returns one 128-byte record per receiver: what gpsx_wobs_pseudoranges_rx, gpsx_weph_to_eph per slot and pntpos per receiver
+ * (include/gpsx_compat.h) give on the host, but with every usable satellite of up to 64 slots, not pntpos' four.  It keeps no state.
+ * Nothing existing changes.
+ *
+ * Definition, per receiver; all arithmetic in IEEE double, uncontracted.
+ *   1 usable       a slot is usable if its observable has GPSX_WOBS_VALID, its ephemeris record has GPSX_WEPH_VALID and, when d_lock is
+ *                  given, its lock record has GPSX_WLOCK_CODE.  Fewer than min_sats usable slots: TOO_FEW, no iteration.
+ *   2 ranges       gpsx_wobs_pseudoranges' definition applied to the usable slots alone (the others count as not VALID): ref_slot,
+ *                  pr_m (0 for the others) and rx_tow_s.  Every operation there is an int64 or a single double operation, so the three
+ *                  are the host helper's bit for bit.  (A pr_m or rx_tow_s that is not finite -- only an observable whose code phase
+ *                  is not finite, which gpsx_wobs never writes, gives one -- is written as 0; such an rx_tow_s ends in NONFINITE.)
+ *   3 time         the observation time is gtime_t{315964800 + 604800 week + (int)rx_tow_s, rx_tow_s - (int)rx_tow_s}, week the
+ *                  reference slot's record's.  A week rollover (rx_tow_s within a travel time of the week's end) is NOT handled: the
+ *                  same limit as the host glue's.
+ *   4 solver       then csrc/gpsx_pvt.cpp's solve(), branch for branch, on each usable slot's own record: |toe - time| <= 7201 s or the
+ *                  slot has no satellite; the two time_adds (which never carry into the whole second) to the transmit time; the
+ *                  broadcast clock's two fixed-point passes; the orbit (Kepler's equation to 1e-14 in fewer than 30 steps or no
+ *                  satellite, A <= 0: a satellite at the centre, the URA table with sva outside 0 .. 14 read as 6144 m, the
+ *                  relativistic clock term); per iteration ecef2pos of x (at the origin: latitude -pi / 2, height -Re, hence az = 0,
+ *                  el = pi / 2 and no atmosphere; its fixed point is bounded at 30 steps here, which a finite x never needs), and per
+ *                  slot: no row if the satellite's radius < Re, if rho = range + Sagnac <= 0, if el < 0 or if svh != 0; Klobuchar with
+ *                  cfg's ion[] (all zero: the 2004 default set, as nav_t.ion_gps), Saastamoinen at humidity 0.7, the four variance
+ *                  terms, the slot's own tgd; x += dx until |dx|^2 < 1e-8 over x, y, z, c dt, ten iterations at most.
+ *   5 different from pntpos, on purpose: any number of rows up to 64; FOUR unknowns -- the reference's three tied-down bias unknowns
+ *                  appear in no satellite row, so its 7 x 7 normal matrix is block diagonal and x, y, z, c dt and their covariance
+ *                  are those of the 4 x 4 system, solved here by a Cholesky factorisation (pntpos: Gauss-Jordan with pivoting, so
+ *                  the two agree to round-off, not to the bit); no duplicate-PRN rule (the stage sees no PRNs: the caller gives a
+ *                  receiver distinct satellites); fewer than min_sats rows in an iteration: TOO_FEW; a pivot of the factorisation that
+ *                  is not positive beyond the round-off of its own subtraction (p_k <= 1e-10 N_kk; p_0 <= 0): SINGULAR; a sum of
+ *                  the normal system or a dx that is not finite: NONFINITE.
+ *   6 start        x = d_prev[r].rr, c dt = 0 if that record has FIX, else the origin.  d_prev may be d_fix itself: a receiver reads
+ *                  its own record before it writes it.
+ *   7 output       with FIX: rr, dtr_s = x[3] / c, geo = ecef2pos(rr), qr as pntpos' sol_t.qr (xx, yy, zz, xy, yz, xz of the inverse
+ *                  normal matrix, as floats), and resid_rms_m = sqrt(sum v^2 / n_used) over the unweighted residuals v recomputed at
+ *                  the FINAL x for the slots of used_mask (that still give a row there).  n_iter counts the iterations whose rows
+ *                  were formed, n_used and used_mask are the last one's.  Without FIX every numeric field but flags, n_used, n_iter,
+ *                  ref_slot, used_mask, rx_tow_s and week is zero.  Exactly one of the five flags is set.  Every byte of d_fix (and
+ *                  of d_pr_m if given) is written; no NaN or infinity is ever written (a result that has one: NONFINITE).
+ * Errors: NULL ctx / cfg / d_obs / d_eph / d_fix, an offset_ms or ion[] that is not finite, ch_per_rx outside 1 .. 64, min_sats
+ * outside 4 .. 64, reserved != 0, n_rx outside 1 .. 1 048 576, a d_fix that is not 16-byte aligned (_dev) and a byte count that
+ * overflows return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.  There is no per-channel BAD policy: a bad channel's
+ * all-zero observable and record are simply not usable.
+ * Vector ALU, FP64 (k_wfix: one slot per lane, a receiver a group of W lanes, W the smallest power of two >= ch_per_rx; the 10 + 4
+ * sums of the normal system by xor-butterflies of width W; every loop bounded and every cross-lane operation under wave-uniform
+ * control flow).  On one stream: ..., gpsx_wobs_dev, gpsx_weph_dev (, gpsx_wlock_dev), then gpsx_wfix_dev on their arrays. */
+#define GPSX_WFIX_FIX        1u   /* rr, dtr_s, geo, qr, resid_rms_m hold a converged solution */
+#define GPSX_WFIX_TOO_FEW    2u   /* fewer than min_sats usable slots (before or inside the iteration) */
+#define GPSX_WFIX_SINGULAR   4u   /* the normal matrix had a pivot that was not positive (beyond round-off: 5 above) */
+#define GPSX_WFIX_NO_CONV    8u   /* ten iterations without |dx|^2 < 1e-8 */
+#define GPSX_WFIX_NONFINITE 16u   /* a non-finite number appeared; nothing non-finite is ever written */
+
+typedef struct {                 /* 96 bytes */
+  double   offset_ms;            /* gpsx_wobs_pseudoranges' offset_ms, finite */
+  double   ion[8];               /* Klobuchar a0..a3, b0..b3, finite; all zero: the 2004 default set (nav_t.ion_gps) */
+  int32_t  ch_per_rx;            /* 1 .. 64 */
+  int32_t  min_sats;             /* 4 .. 64 */
+  int32_t  reserved0, reserved1; /* 0 */
+  int32_t  reserved2, reserved3; /* 0 */
+} gpsx_wfix_cfg_t;
+
+typedef struct {                 /* 128 bytes, one per receiver and launch */
+  uint32_t flags;                /*   0 */
+  int32_t  n_used;               /*   4  rows of the last iteration */
+  int32_t  n_iter;               /*   8  iterations run, 0 .. 10 */
+  int32_t  ref_slot;             /*  12  the reference slot within the receiver, -1: none */
+  uint64_t used_mask;            /*  16  bit j: slot j gave a row in the last iteration */
+  double   rr[3];                /*  24  ECEF, m */
+  double   dtr_s;                /*  48  receiver clock term, x[3] / c */
+  double   rx_tow_s;             /*  56  as gpsx_wobs_pseudoranges' *rx_tow_s over the usable slots */
+  double   geo[3];               /*  64  latitude, longitude (rad), height (m) of rr */
+  float    qr[6];                /*  88  pntpos' sol_t.qr */
+  double   resid_rms_m;          /* 112  sqrt(sum v^2 / n_used), residuals recomputed at the FINAL x, unweighted */
+  int32_t  week, reserved;       /* 120  the reference slot's eph week; 0 */
+} gpsx_wfix_t;
+
+/* d_obs, d_eph, d_lock (NULL: not consulted): [n_rx * ch_per_rx], d_prev (NULL: start at the origin) and d_fix: [n_rx], d_pr_m (NULL:
+ * not written): [n_rx * ch_per_rx]; all on the device for _dev, all in host memory (staged through the arena; the call waits for its
+ * kernel) for gpsx_wfix */
+int gpsx_wfix_dev(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                  const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, double *d_pr_m);
+int gpsx_wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+              const gpsx_wfix_t *prev, int n_rx, gpsx_wfix_t *fix, double *pr_m);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

@@ -120,6 +120,8 @@ def check_no_scratch() -> dict:
     # ... and the sync loop for many receivers per launch (check_wmulti below: refused here like the others; not in the table this
     #     returns, whose keys callers search for the single-stream kernels' names, which k_track_wsync_multi's contains)
     check_wmulti()
+    # ... and the position fixes at the chain's end (check_wfix below: FP64 with a dozen libm calls per row, refused here if it spills)
+    check_wfix()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -154,6 +156,18 @@ def check_wmulti() -> dict:
     if bad:
         raise RuntimeError(f"multi-receiver sync loop kernel above 128 VGPRs (four waves per SIMD) or with scratch memory: {bad}")
     return wmulti
+
+
+def check_wfix() -> dict:
+    """k_wfix (every receiver's position fix: a slot per lane, the normal system in registers; an object of its own): exactly one
+    instance and no scratch.  -> {symbol: resources}"""
+    wfix = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wfix.o")).items() if "k_wfix" in k}
+    if len(wfix) != 1:
+        raise RuntimeError(f"expected k_wfix in build/k_wfix.o, found {sorted(wfix)}")
+    bad = {k: v for k, v in wfix.items() if v["scratch_bytes"] != 0}
+    if bad:
+        raise RuntimeError(f"position-fix kernel with scratch memory (register spills): {bad}")
+    return wfix
 
 
 if __name__ == "__main__":

@@ -234,6 +234,25 @@ WLOCK_DTYPE = np.dtype([("flags", "<u4"), ("n_epochs", "<u4"), ("last_k", "<u4")
 assert WLOCK_CFG_DTYPE.itemsize == 40 and WLOCK_STATE_DTYPE.itemsize == 128 and WLOCK_DTYPE.itemsize == 64
 
 
+# gpsx_wfix_cfg_t / gpsx_wfix_t (every receiver's position fix from the observables and ephemeris records)
+WFIX_FLAG_FIX, WFIX_FLAG_TOO_FEW, WFIX_FLAG_SINGULAR, WFIX_FLAG_NO_CONV, WFIX_FLAG_NONFINITE = 1, 2, 4, 8, 16
+WFIX_CFG_DTYPE = np.dtype([("offset_ms", "<f8"), ("ion", "<f8", (8,)), ("ch_per_rx", "<i4"), ("min_sats", "<i4"), ("reserved0", "<i4"),
+                           ("reserved1", "<i4"), ("reserved2", "<i4"), ("reserved3", "<i4")])
+WFIX_DTYPE = np.dtype([("flags", "<u4"), ("n_used", "<i4"), ("n_iter", "<i4"), ("ref_slot", "<i4"), ("used_mask", "<u8"), ("rr", "<f8", (3,)),
+                       ("dtr_s", "<f8"), ("rx_tow_s", "<f8"), ("geo", "<f8", (3,)), ("qr", "<f4", (6,)), ("resid_rms_m", "<f8"), ("week", "<i4"),
+                       ("reserved", "<i4")])
+assert WFIX_CFG_DTYPE.itemsize == 96 and WFIX_DTYPE.itemsize == 128
+
+
+def wfix_cfg(offset_ms: float, ch_per_rx: int, min_sats: int = 4, ion=None) -> np.ndarray:
+    """a gpsx_wfix_cfg_t as a one-element WFIX_CFG_DTYPE array (ion None: all zero, the solver's default Klobuchar set)"""
+    cfg = np.zeros(1, WFIX_CFG_DTYPE)
+    cfg["offset_ms"], cfg["ch_per_rx"], cfg["min_sats"] = offset_ms, ch_per_rx, min_sats
+    if ion is not None:
+        cfg["ion"][0] = ion
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -369,6 +388,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_weph_to_eph.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wlock.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wlock_dev.argtypes = lib.gpsx_wlock.argtypes
+    lib.gpsx_wfix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.gpsx_wfix_dev.argtypes = lib.gpsx_wfix.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -841,6 +862,24 @@ class Engine:
         self._chk(self.lib.gpsx_wlock(self.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_state),
                                       C.c_void_p(d_sync_state) if d_sync_state else None, n_ch, lock.ctypes.data), "gpsx_wlock")
         return lock
+
+    def wfix(self, cfg: np.ndarray, obs: np.ndarray, eph: np.ndarray, n_rx: int, lock: np.ndarray | None = None,
+             prev: np.ndarray | None = None, want_pr: bool = False):
+        """EXTENSION: every receiver's position fix from the WOBS_DTYPE observables and WEPH_DTYPE ephemeris records [n_rx * ch_per_rx]
+        of one launch of the weighted chain (receiver r owns slots r * ch_per_rx ...), host arrays; cfg from wfix_cfg.  lock: WLOCK_DTYPE
+        records, a slot then also needs WLOCK_FLAG_CODE; prev: WFIX_DTYPE [n_rx], the start points (records with WFIX_FLAG_FIX).
+        -> WFIX_DTYPE [n_rx], and with want_pr the pseudoranges float64 [n_rx * ch_per_rx] as well"""
+        assert cfg.dtype == WFIX_CFG_DTYPE and cfg.size == 1
+        n_ch = n_rx * int(cfg["ch_per_rx"][0])
+        obs, eph = np.ascontiguousarray(obs, WOBS_DTYPE).reshape(-1), np.ascontiguousarray(eph, WEPH_DTYPE).reshape(-1)
+        assert len(obs) == n_ch and len(eph) == n_ch
+        lock = None if lock is None else np.ascontiguousarray(lock).view(WLOCK_DTYPE).reshape(n_ch)      # (any 64-byte record dtype)
+        prev = None if prev is None else np.ascontiguousarray(prev, WFIX_DTYPE).reshape(n_rx)
+        fix, pr = np.zeros(n_rx, WFIX_DTYPE), np.zeros(n_ch, np.float64)
+        self._chk(self.lib.gpsx_wfix(self.h, cfg.ctypes.data, obs.ctypes.data, eph.ctypes.data, None if lock is None else lock.ctypes.data,
+                                     None if prev is None else prev.ctypes.data, n_rx, fix.ctypes.data, pr.ctypes.data if want_pr else None),
+                  "gpsx_wfix")
+        return (fix, pr) if want_pr else fix
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -385,9 +385,91 @@ int wlock(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(lock, d_lock, lock_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
+// ---- the position fixes (host: every array is host memory, staged through the arena; _dev: all device memory) ------------------------
+int wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock, const gpsx_wfix_t *prev,
+         int n_rx, gpsx_wfix_t *fix, double *pr_m, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !obs || !eph || !fix)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (!(cfg->offset_ms - cfg->offset_ms == 0.0))   // (not finite: the difference is a NaN)
+    return fail(ctx, GPSX_EINVAL, "offset_ms is not finite");
+  for (double v : cfg->ion)
+    if (!(v - v == 0.0))
+      return fail(ctx, GPSX_EINVAL, "an ionosphere coefficient is not finite");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->min_sats < 4 || cfg->min_sats > 64)
+    return fail(ctx, GPSX_EINVAL, "min_sats must be 4..64");
+  if (cfg->reserved0 != 0 || cfg->reserved1 != 0 || cfg->reserved2 != 0 || cfg->reserved3 != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (!host && (reinterpret_cast<uintptr_t>(fix) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_fix must be 16-byte aligned");
+  size_t obs_bytes = 0, eph_bytes = 0, lock_bytes = 0, fix_bytes = 0, pr_bytes = 0;
+  if (records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wobs_t), &obs_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_weph_t), &eph_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wlock_t), &lock_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(double), &pr_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wfix_t), &fix_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x ch_per_rx records overflow a size");
+  const size_t n_ch = (size_t)n_rx * (size_t)cfg->ch_per_rx;
+  const gpsx_wobs_t *d_obs = obs;
+  const gpsx_weph_t *d_eph = eph;
+  const gpsx_wlock_t *d_lock = lock;
+  const gpsx_wfix_t *d_prev = prev;
+  gpsx_wfix_t *d_fix = fix;
+  double *d_pr = pr_m;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) +
+                                      (prev ? arena_size(fix_bytes) : 0) + arena_size(fix_bytes) + (pr_m ? arena_size(pr_bytes) : 0)))
+      return rc;
+    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
+    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
+    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_obs = s_obs;
+    d_eph = s_eph;
+    if (lock) {
+      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
+      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_lock = s_lock;
+    }
+    if (prev) {
+      gpsx_wfix_t *s_prev = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
+      HIPCHK(ctx, hipMemcpyAsync(s_prev, prev, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_prev = s_prev;
+    }
+    d_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
+    if (pr_m)
+      d_pr = arena_take<double>(ctx, n_ch);
+  }
+  return launch_and_report(
+      ctx, host, "k_wfix", "k_wfix raised the bad-state flag, which it never does",
+      [&](uint32_t *) { launch_wfix(ctx->stream, *cfg, d_obs, d_eph, d_lock, d_prev, n_rx, d_fix, d_pr); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(fix, d_fix, fix_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (pr_m)
+          HIPCHK(ctx, hipMemcpyAsync(pr_m, d_pr, pr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wfix_dev(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                  const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, double *d_pr_m)
+{
+  return wfix(ctx, cfg, d_obs, d_eph, d_lock, d_prev, n_rx, d_fix, d_pr_m, false);
+}
+
+int gpsx_wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+              const gpsx_wfix_t *prev, int n_rx, gpsx_wfix_t *fix, double *pr_m)
+{
+  return wfix(ctx, cfg, obs, eph, lock, prev, n_rx, fix, pr_m, true);
+}
 
 int gpsx_track_epl_weighted_dev(gpsx_ctx *ctx, const gpsx_trk_weighted_t *cfg, const void *d_if_blocks_2bit, int n_blocks,
                                 gpsx_trk_state_t *d_st, int n_ch, int32_t *d_iq_out)

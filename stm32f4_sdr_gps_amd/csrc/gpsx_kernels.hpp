@@ -184,6 +184,12 @@ void launch_weph(hipStream_t s, const gpsx_wnav_word_t *d_words, int n_blocks, g
 // a channel whose state is out of range.
 void launch_wlock(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots, int n_blocks, const gpsx_wlock_cfg_t &cfg, gpsx_wlock_state_t *d_st,
                   gpsx_wsync_state_t *d_sync_st, int n_ch, gpsx_wlock_t *d_lock, uint32_t *d_bad_state);
+// extension: gpsx_wfix (k_wfix.hip: k_wfix) -- every receiver's position fix from the [n_rx * ch_per_rx] observables and ephemeris
+// records (and lock records, d_lock may be null) of the stages above: one slot per lane, a receiver a group of lanes, no state;
+// d_prev (may be null, may be d_fix) [n_rx] start points, d_fix [n_rx] 128-byte records and d_pr_m (may be null) [n_rx * ch_per_rx],
+// every byte of them written.  cfg as the host checked it.
+void launch_wfix(hipStream_t s, const gpsx_wfix_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                 const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, double *d_pr_m);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

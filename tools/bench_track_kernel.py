@@ -70,7 +70,15 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       calls taking turns: time, ns per channel-ms, the ratio, and the IF bytes the
                                                       launch must read from HBM.  --single-only: the single-stream rows alone, for a
                                                       library without the new call (the parent commit's, in a neighbouring process);
-                                                      --parent-rows: such rows, against which the ratio is formed too"""
+                                                      --parent-rows: such rows, against which the ratio is formed too
+  bench_track_kernel.py --weighted-fix [N_RXxCH_PER_RX ...]
+                                                      gpsx_wfix_dev (EXTENSION: every receiver's position fix; k_wfix) at (n_rx,
+                                                      ch_per_rx) = (16384, 4), (8192, 8), (4096, 12), (1024, 64), every slot usable (16
+                                                      distinct skies of tests/weighted_fix_cases.py, tiled), cold start, beside a
+                                                      device-to-device hipMemcpyAsync of the bytes the kernel reads (288 per slot); then,
+                                                      for the 4-slot shape, the wall time of the host path on records already in host
+                                                      memory: gpsx_wobs_pseudoranges_rx, gpsx_weph_to_eph per slot and pntpos per
+                                                      receiver, called through ctypes (the interpreter's share is in it)"""
 import ctypes as C
 import json
 import os
@@ -776,8 +784,76 @@ def weighted_lock(counts, n_blocks=4000, span=20):
             eng.free(p)
 
 
+FIX_SHAPES = [(16384, 4), (8192, 8), (4096, 12), (1024, 64)]
+
+
+def weighted_fix(shapes):
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fix_cases as W
+    from pvt_types import UNIX2GPS, Eph, GTime, Nav, Obsd, Sol
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    lib = capi.load_library()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    eng = capi.Engine(0, stream=stream.value)
+    names = sorted(W.SITES)
+    for n_rx, ch in shapes:
+        pool = [W.receiver(names[k % len(names)], ch, 3 * k) for k in range(16)]
+        obs, eph = W.pack([pool[r % 16] for r in range(n_rx)], ch)
+        cfg = capi.wfix_cfg(W.OFFSET_MS, ch)
+        read_bytes = obs.nbytes + eph.nbytes
+        d_obs, d_eph, d_fix, d_src, d_dst = eng.malloc(obs.nbytes), eng.malloc(eph.nbytes), eng.malloc(n_rx * 128), eng.malloc(read_bytes), eng.malloc(read_bytes)
+        eng.h2d(d_obs, obs)
+        eng.h2d(d_eph, eph)
+        calls = {"d2d_copy_of_the_bytes_read": (1, lambda: hip.hipMemcpyAsync(d_dst, d_src, read_bytes, 3, stream)),
+                 "wfix": (1, lambda: eng.lib.gpsx_wfix_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_obs), C.c_void_p(d_eph), None, None, n_rx, C.c_void_p(d_fix), None))}
+        med = _timed_rows(eng, calls, {"channels": n_rx * ch, "n_rx": n_rx, "ch_per_rx": ch, "read_bytes": read_bytes})
+        fix = np.zeros(n_rx, capi.WFIX_DTYPE)
+        eng.d2h(fix, d_fix)
+        print(json.dumps({"wfix_check": "records after the timed launches", "n_rx": n_rx, "ch_per_rx": ch, "fixed": int((fix["flags"] == 1).sum()),
+                          "n_iter_max": int(fix["n_iter"].max()), "n_used_min": int(fix["n_used"].min())}), flush=True)
+        print(json.dumps({"ratio": "k_wfix over a device-to-device copy of the bytes it reads", "n_rx": n_rx, "ch_per_rx": ch,
+                          "value": round(med["wfix"] / med["d2d_copy_of_the_bytes_read"], 2), "ns_per_receiver": round(med["wfix"] / n_rx * 1e3, 2),
+                          "read_GBps": round(read_bytes / med["wfix"] / 1e3, 2)}), flush=True)
+        if ch == 4:      # the host path on the same records
+            lib.pntpos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            lib.gpsx_weph_to_eph.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            t0 = time.perf_counter()
+            pr, rx_tow = capi.wobs_pseudoranges_rx(obs, n_rx, ch, W.OFFSET_MS)[:2]
+            ephs = np.zeros(n_rx * ch, capi.EPH_DTYPE)
+            n_fix = 0
+            for r in range(n_rx):
+                nav, od, sol = Nav(), (Obsd * ch)(), Sol()
+                nav.n = ch
+                whole = int(rx_tow[r])
+                for k in range(ch):
+                    at = r * ch + k
+                    lib.gpsx_weph_to_eph(eph[at:at + 1].ctypes.data, k + 1, ephs[at:at + 1].ctypes.data)
+                    nav.eph[k] = C.cast(ephs[at:at + 1].ctypes.data, C.POINTER(Eph))
+                    od[k].time = GTime(UNIX2GPS + 604800 * int(ephs["week"][at]) + whole, float(rx_tow[r]) - whole)
+                    od[k].sat, od[k].rcv, od[k].code[0], od[k].P[0] = k + 1, 1, 1, float(pr[at])
+                n_fix += lib.pntpos(od, ch, C.byref(nav), C.byref(sol)) == 1
+            host_us = (time.perf_counter() - t0) * 1e6
+            print(json.dumps({"call": "host_path_pseudoranges_rx_weph_to_eph_pntpos", "n_rx": n_rx, "ch_per_rx": ch, "fixed": int(n_fix),
+                              "wall_us": round(host_us, 1), "us_per_receiver": round(host_us / n_rx, 2),
+                              "ratio_to_wfix": round(host_us / med["wfix"], 1), "note": "through ctypes from Python, one process, one thread"}), flush=True)
+        for p in (d_obs, d_eph, d_fix, d_src, d_dst):
+            eng.free(p)
+
+
 def main():
     global WINDOW_S
+    if "--weighted-fix" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-fix"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_fix([tuple(int(v) for v in a.split("x")) for a in args] or FIX_SHAPES)
     if "--weighted-lock" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-lock"]
         if "--window-s" in args:
