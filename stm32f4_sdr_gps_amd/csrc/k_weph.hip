@@ -17,6 +17,7 @@
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wstage_parts.hpp"
 
 namespace gpsx {
 
@@ -32,9 +33,6 @@ static_assert(sizeof(gpsx_weph_state_t) == 192 && offsetof(gpsx_weph_state_t, bl
 static_assert(sizeof(gpsx_weph_t) == 256 && offsetof(gpsx_weph_t, flags) == 0 && offsetof(gpsx_weph_t, iode) == 4 && offsetof(gpsx_weph_t, flag) == 28 &&
               offsetof(gpsx_weph_t, toe_time) == 32 && offsetof(gpsx_weph_t, toe_sec) == 56 && offsetof(gpsx_weph_t, A) == 80 &&
               offsetof(gpsx_weph_t, tgd) == 240 && offsetof(gpsx_weph_t, n_sets) == 248 && offsetof(gpsx_weph_t, have) == 252, "gpsx_weph_t layout");
-static_assert(sizeof(gpsx_wnav_word_t) == 16 && offsetof(gpsx_wnav_word_t, end_block) == 0 && offsetof(gpsx_wnav_word_t, word) == 4 &&
-              offsetof(gpsx_wnav_word_t, index) == 8 && offsetof(gpsx_wnav_word_t, flags) == 9 && offsetof(gpsx_wnav_word_t, subframe_id) == 10 &&
-              offsetof(gpsx_wnav_word_t, aux) == 12, "gpsx_wnav_word_t layout");
 
 constexpr int kMaxWords = 4096 / 600 + 2;    // word slots of the longest launch
 constexpr long long kMaxCount = 1ll << 62;

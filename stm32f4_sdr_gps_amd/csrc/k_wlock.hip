@@ -14,6 +14,7 @@
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wstage_parts.hpp"
 
 namespace gpsx {
 
@@ -32,8 +33,6 @@ static_assert(sizeof(gpsx_wlock_t) == 64 && offsetof(gpsx_wlock_t, flags) == 0 &
               offsetof(gpsx_wlock_t, age_blocks) == 12 && offsetof(gpsx_wlock_t, code_ratio) == 16 && offsetof(gpsx_wlock_t, snr) == 24 &&
               offsetof(gpsx_wlock_t, n_range) == 28 && offsetof(gpsx_wlock_t, p) == 32 && offsetof(gpsx_wlock_t, n_lost_code) == 40 &&
               offsetof(gpsx_wlock_t, n_rearm) == 48 && offsetof(gpsx_wlock_t, reserved) == 52, "gpsx_wlock_t layout");
-static_assert(sizeof(gpsx_wsync_rec_t) == 48 && offsetof(gpsx_wsync_rec_t, w) == 0 && offsetof(gpsx_wloop_rec_t, iq) == 0 &&
-              offsetof(gpsx_wsync_rec_t, end_block) == 36 && offsetof(gpsx_wsync_rec_t, flags) == 40, "gpsx_wsync_rec_t layout");
 static_assert(sizeof(gpsx_wsync_state_t) == 448 && offsetof(gpsx_wsync_state_t, loop) == 0 && offsetof(gpsx_wloop_state_t, n_updates) == 32 &&
               offsetof(gpsx_wsync_state_t, win_iq) == 40 && offsetof(gpsx_wsync_state_t, win_n) == 64 && offsetof(gpsx_wsync_state_t, mode) == 72 &&
               offsetof(gpsx_wsync_state_t, bit_ip) == 80 && offsetof(gpsx_wsync_state_t, search_n) == 84 &&
@@ -162,32 +161,17 @@ __global__ __launch_bounds__(64) void k_wlock(const gpsx_wsync_rec_t *__restrict
     epoch_n = 0;
   };
 
-  // kAhead slots from slot `from` on; slots past the launch's last repeat it (in bounds, and not stepped through)
-  auto load = [&](Win (&to)[kAhead], int from) {
-#pragma unroll
-    for (int u = 0; u < kAhead; u++) {
-      const char *r = reinterpret_cast<const char *>(rec + ((size_t)min(from + u, n_slots - 1) * (size_t)n_ch + (size_t)ch));
-      const Quad q = *reinterpret_cast<const Quad *>(r);
-      const Pair l = *reinterpret_cast<const Pair *>(r + 16), ef = *reinterpret_cast<const Pair *>(r + 36);
-      to[u] = Win{q.a, q.b, q.c, q.d, l.a, l.b, ef.a, (u32)ef.b};
-    }
+  auto load_one = [&](int slot) {
+    const char *r = reinterpret_cast<const char *>(rec + ((size_t)slot * (size_t)n_ch + (size_t)ch));
+    const Quad q = *reinterpret_cast<const Quad *>(r);
+    const Pair l = *reinterpret_cast<const Pair *>(r + 16), ef = *reinterpret_cast<const Pair *>(r + 36);
+    return Win{q.a, q.b, q.c, q.d, l.a, l.b, ef.a, (u32)ef.b};
   };
-  auto work = [&](const Win (&from)[kAhead], int at) {
-#pragma unroll
-    for (int u = 0; u < kAhead; u++)
-      if (at + u < n_slots)   // (uniform over the launch)
-        step(from[u]);
-  };
-  // two register sets that take turns, never copied: a copy would have to wait for the loads it copies
   Win even[kAhead], odd[kAhead];
-  load(even, 0);
+  wstage::load_ahead(even, 0, n_slots, load_one);
 #pragma unroll 1
-  for (int at = 0; at < n_slots; at += 2 * kAhead) {
-    load(odd, at + kAhead);        // (unconditional: a set that is loaded on one path only is merged by copies, which wait)
-    work(even, at);
-    load(even, at + 2 * kAhead);
-    work(odd, at + kAhead);
-  }
+  for (int at = 0; at < n_slots; at += 2 * kAhead)
+    wstage::turn(even, odd, at, n_slots, load_one, step);
 
   if (!run) {
     if (active) {

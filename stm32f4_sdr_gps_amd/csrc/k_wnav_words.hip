@@ -17,6 +17,7 @@
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wstage_parts.hpp"
 
 namespace gpsx {
 
@@ -29,11 +30,6 @@ static_assert(sizeof(gpsx_wnav_state_t) == 64 && offsetof(gpsx_wnav_state_t, his
               offsetof(gpsx_wnav_state_t, bit_idx) == 40 && offsetof(gpsx_wnav_state_t, bad_run) == 44 &&
               offsetof(gpsx_wnav_state_t, ok_mask) == 48 && offsetof(gpsx_wnav_state_t, n_sync) == 52 && offsetof(gpsx_wnav_state_t, n_drop) == 56 &&
               offsetof(gpsx_wnav_state_t, n_subframes) == 60, "gpsx_wnav_state_t layout");
-static_assert(sizeof(gpsx_wnav_word_t) == 16 && offsetof(gpsx_wnav_word_t, end_block) == 0 && offsetof(gpsx_wnav_word_t, word) == 4 &&
-              offsetof(gpsx_wnav_word_t, index) == 8 && offsetof(gpsx_wnav_word_t, flags) == 9 && offsetof(gpsx_wnav_word_t, subframe_id) == 10 &&
-              offsetof(gpsx_wnav_word_t, zero) == 11 && offsetof(gpsx_wnav_word_t, aux) == 12, "gpsx_wnav_word_t layout");
-static_assert(sizeof(gpsx_wsync_rec_t) == 48 && offsetof(gpsx_wsync_rec_t, end_block) == 36 && offsetof(gpsx_wsync_rec_t, flags) == 40 &&
-              offsetof(gpsx_wsync_rec_t, bit_ip) == 44, "gpsx_wsync_rec_t layout");
 
 constexpr int kAhead = 8;                    // slots a lane's loads run ahead of its recurrence
 constexpr u32 kWord30 = 0x3FFFFFFFu;
@@ -188,30 +184,15 @@ __global__ __launch_bounds__(64) void k_wnav_words(const gpsx_wsync_rec_t *__res
     emit(b.end_block, d << 6 | (x & 63u), (u32)index, flags, id_out, aux);
   };
 
-  // kAhead slots from slot `from` on; slots past the launch's last repeat it (in bounds, and not stepped through)
-  auto load = [&](Bit3 (&to)[kAhead], int from) {
-#pragma unroll
-    for (int u = 0; u < kAhead; u++) {
-      const gpsx_wsync_rec_t &r = rec[(size_t)min(from + u, n_slots - 1) * (size_t)n_ch + (size_t)ch];
-      to[u] = Bit3{r.end_block, r.flags, r.bit_ip};
-    }
+  auto load_one = [&](int slot) {
+    const gpsx_wsync_rec_t &r = rec[(size_t)slot * (size_t)n_ch + (size_t)ch];
+    return Bit3{r.end_block, r.flags, r.bit_ip};
   };
-  auto work = [&](const Bit3 (&from)[kAhead], int base) {
-#pragma unroll
-    for (int u = 0; u < kAhead; u++)
-      if (base + u < n_slots)   // (uniform over the launch)
-        step(from[u]);
-  };
-  // two register sets that take turns, never copied: a copy would have to wait for the loads it copies
   Bit3 even[kAhead], odd[kAhead];
-  load(even, 0);
+  wstage::load_ahead(even, 0, n_slots, load_one);
 #pragma unroll 1
-  for (int base = 0; base < n_slots; base += 2 * kAhead) {
-    load(odd, base + kAhead);        // (unconditional: a set that is loaded on one path only is merged by copies, which wait)
-    work(even, base);
-    load(even, base + 2 * kAhead);
-    work(odd, base + kAhead);
-  }
+  for (int at = 0; at < n_slots; at += 2 * kAhead)
+    wstage::turn(even, odd, at, n_slots, load_one, step);
 
   if (active) {
 #pragma unroll 1

@@ -14,6 +14,7 @@
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wstage_parts.hpp"
 
 namespace gpsx {
 
@@ -29,11 +30,6 @@ static_assert(sizeof(gpsx_wobs_state_t) == 80 && offsetof(gpsx_wobs_state_t, blo
 static_assert(sizeof(gpsx_wobs_t) == 32 && offsetof(gpsx_wobs_t, tx_ms) == 0 && offsetof(gpsx_wobs_t, code_phase_fine) == 8 &&
               offsetof(gpsx_wobs_t, if_freq_offset_hz) == 12 && offsetof(gpsx_wobs_t, flags) == 16 && offsetof(gpsx_wobs_t, age_blocks) == 20 &&
               offsetof(gpsx_wobs_t, n_wraps) == 24 && offsetof(gpsx_wobs_t, reserved) == 28, "gpsx_wobs_t layout");
-static_assert(sizeof(gpsx_wsync_rec_t) == 48 && offsetof(gpsx_wsync_rec_t, w) == 0 && offsetof(gpsx_wloop_rec_t, code_phase_fine) == 24 &&
-              offsetof(gpsx_wloop_rec_t, if_freq_offset_hz) == 28 && offsetof(gpsx_wsync_rec_t, end_block) == 36 && offsetof(gpsx_wsync_rec_t, flags) == 40,
-              "gpsx_wsync_rec_t layout");
-static_assert(sizeof(gpsx_wnav_word_t) == 16 && offsetof(gpsx_wnav_word_t, end_block) == 0 && offsetof(gpsx_wnav_word_t, index) == 8 &&
-              offsetof(gpsx_wnav_word_t, flags) == 9 && offsetof(gpsx_wnav_word_t, aux) == 12, "gpsx_wnav_word_t layout");
 
 constexpr int kAhead = 8;                    // slots a lane's loads run ahead of its recurrence
 constexpr int kMaxWords = 4096 / 600 + 2;    // word slots of the longest launch
@@ -122,31 +118,16 @@ __global__ __launch_bounds__(64) void k_wobs(const gpsx_wsync_rec_t *__restrict_
     }
   };
 
-  // kAhead slots from slot `from` on; slots past the launch's last repeat it (in bounds, and not stepped through)
-  auto load = [&](Win (&to)[kAhead], int from) {
-#pragma unroll
-    for (int u = 0; u < kAhead; u++) {
-      const char *r = reinterpret_cast<const char *>(rec + ((size_t)min(from + u, n_slots - 1) * (size_t)n_ch + (size_t)ch));
-      const Pair pf = *reinterpret_cast<const Pair *>(r + 24), ef = *reinterpret_cast<const Pair *>(r + 36);
-      to[u] = Win{__uint_as_float(pf.a), __uint_as_float(pf.b), (int)ef.a, ef.b};
-    }
+  auto load_one = [&](int slot) {
+    const char *r = reinterpret_cast<const char *>(rec + ((size_t)slot * (size_t)n_ch + (size_t)ch));
+    const Pair pf = *reinterpret_cast<const Pair *>(r + 24), ef = *reinterpret_cast<const Pair *>(r + 36);
+    return Win{__uint_as_float(pf.a), __uint_as_float(pf.b), (int)ef.a, ef.b};
   };
-  auto work = [&](const Win (&from)[kAhead], int at) {
-#pragma unroll
-    for (int u = 0; u < kAhead; u++)
-      if (at + u < n_slots)   // (uniform over the launch)
-        step(from[u]);
-  };
-  // two register sets that take turns, never copied: a copy would have to wait for the loads it copies
   Win even[kAhead], odd[kAhead];
-  load(even, 0);
+  wstage::load_ahead(even, 0, n_slots, load_one);
 #pragma unroll 1
-  for (int at = 0; at < n_slots; at += 2 * kAhead) {
-    load(odd, at + kAhead);        // (unconditional: a set that is loaded on one path only is merged by copies, which wait)
-    work(even, at);
-    load(even, at + 2 * kAhead);
-    work(odd, at + kAhead);
-  }
+  for (int at = 0; at < n_slots; at += 2 * kAhead)
+    wstage::turn(even, odd, at, n_slots, load_one, step);
 
   // the word records, all in flight before the first is looked at (loaded here, not beside pass 1: their 24 registers there cost
   // the fourth wave per SIMD, and one round trip per wave at the end costs a hundredth of the kernel)

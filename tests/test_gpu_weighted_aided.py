@@ -6,38 +6,21 @@ both loops and both variants, with code phases that the aiding step carries acro
 the unaided calls on the device; a stream cut into launches; bad channels; refusals; and the two scenarios the CPU test measures --
 one satellite at +-4500 Hz over 2200 blocks and the first 8192 blocks of the orbit stream (the restatement of 4 x 8192 channel blocks
 runs in four processes) -- which carry its numbers over to the device."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import weighted_aided_cases as W
 import weighted_aided_ref as A
+import weighted_gpu as G
 import weighted_loop_cases as S
 import weighted_loop_ref as L
 import weighted_pvt_cases as P
 import weighted_sync_cases as K
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
+from weighted_gpu import sync_cfg as _sync_cfg
 
 pytestmark = pytest.mark.gpu
-
-EINVAL = -22
-GUARD = 4096
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
-
-def _sync_cfg(c):
-    from stm32f4_sdr_gps_amd import capi
-    gains = {name: dict(dll=(c[name]["dll_c1"], c[name]["dll_c2"]), pll=(c[name]["pll_c1"], c[name]["pll_c2"]), fll=c[name]["fll_c"]) for name in ("search", "lock")}
-    return capi.wsync_cfg(c["n_coh_search"], c["n_coh_lock"], gains["search"], gains["lock"], c["sync_bits"], (c["sync_num"], c["sync_den"]),
-                          c["use_magnitude"], c["spacing"])
 
 
 def _loop_cfg(c):
@@ -50,66 +33,38 @@ def _call(eng, sync, aided, dev):
     return name, getattr(eng.lib, name)
 
 
-def _gpu(eng, blocks, st, cfg, code_per_hz, dev, pieces=None):
-    """the library on a copy of `st` in device memory, canaries around states and records -> ([(first block, records)], states
-    after).  cfg: a restatement's dict, of either loop (told by the states' dtype); code_per_hz None: the unaided call; dev: blocks
-    and records in device memory too"""
+def _stage(eng, blocks, st, cfg, code_per_hz, dev, pieces=None):
+    """the library on a copy of `st` in device memory -> ([(first block, records)], states after, [return codes]).  cfg: a
+    restatement's dict, of either loop (told by the states' dtype); code_per_hz None: the unaided call; dev: blocks and records in
+    device memory too"""
     from stm32f4_sdr_gps_amd import capi
-    blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 4092)
     sync = st.dtype == Y.STATE_DTYPE
     assert sync or st.dtype == L.STATE_DTYPE
     n_ch = len(st)
     c = _sync_cfg(cfg) if sync else _loop_cfg(cfg)
     aid = None if code_per_hz is None else capi.waid(code_per_hz)
-    name, fn = _call(eng, sync, aid is not None, dev)
+    _, fn = _call(eng, sync, aid is not None, dev)
     kernel = ("k_track_waid_sync" if sync else "k_track_waid_loop") if aid is not None else ("k_track_wsync" if sync else "k_track_wloop")
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0xA5, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = np.ascontiguousarray(st).view(np.uint8)
-    d_st = eng.malloc(h_st.nbytes)
-    recs = []
-    try:
-        eng.h2d(d_st, h_st)
-        at = 0
-        for k in pieces or [len(blocks)]:
-            part = blocks[at:at + k]
-            shape = (Y.slots(k, cfg) if sync else k // cfg["n_coh"], n_ch)
-            dtype = Y.REC_DTYPE if sync else L.REC_DTYPE
-            size = shape[0] * n_ch * dtype.itemsize
-            h_rec = np.full(GUARD + size + GUARD, 0x5A, np.uint8)
-            args = [eng.h, c.ctypes.data] + ([aid.ctypes.data] if aid is not None else [])
-            if dev:
-                d_if, d_rec = eng.malloc(part.nbytes), eng.malloc(h_rec.nbytes)
-                try:
-                    eng.h2d(d_if, part)
-                    eng.h2d(d_rec, h_rec)
-                    eng._chk(fn(*args, C.c_void_p(d_if), k, C.c_void_p(d_st + GUARD), n_ch, C.c_void_p(d_rec + GUARD)), name)
-                    eng.synchronize()
-                    eng.d2h(h_rec, d_rec)
-                finally:
-                    eng.free(d_if)
-                    eng.free(d_rec)
-            else:
-                eng._chk(fn(*args, part.ctypes.data, k, C.c_void_p(d_st + GUARD), n_ch, h_rec[GUARD:].ctypes.data), name)
-            assert eng.lib.gpsx_last_kernel(eng.h) == kernel.encode()
-            assert (h_rec[:GUARD] == 0x5A).all() and (h_rec[GUARD + size:] == 0x5A).all(), "canary around the records"
-            recs.append((at, h_rec[GUARD:GUARD + size].view(dtype).reshape(shape).copy()))
-            at += k
-        eng.d2h(h_st, d_st)
-    finally:
-        eng.free(d_st)
-    assert (h_st[:GUARD] == 0xA5).all() and (h_st[GUARD + st.nbytes:] == 0xA5).all(), "canary around the states"
-    return recs, h_st[GUARD:GUARD + st.nbytes].view(st.dtype).copy()
+    launches, firsts = G.block_launches(blocks, pieces, Y.REC_DTYPE if sync else L.REC_DTYPE,
+                                        lambda k: (Y.slots(k, cfg) if sync else k // cfg["n_coh"], n_ch))
+
+    def call(ins, sts, out, k):
+        args = [eng.h, c.ctypes.data] + ([aid.ctypes.data] if aid is not None else [])
+        return fn(*args, ins[0], len(launches[k][0][0]), sts[0], n_ch, out)
+    recs, after, codes = G.run_stage(eng, call, kernel.encode(), st, launches, dev, host_inputs=True)
+    return list(zip(firsts, recs)), after, codes
+
+
+def _gpu(eng, blocks, st, cfg, code_per_hz, dev, pieces=None):
+    """_stage where no channel is bad -> ([(first block, records)], states after)"""
+    recs, after, codes = _stage(eng, blocks, st, cfg, code_per_hz, dev, pieces)
+    assert not any(codes), (codes, eng.lib.gpsx_last_error(eng.h))
+    return recs, after
 
 
 def _same(rec, after, want_rec, want_st, what):
-    assert rec.dtype == want_rec.dtype and rec.shape == want_rec.shape, what
-    if rec.tobytes() != want_rec.tobytes():
-        bad = [c for c in range(rec.shape[1]) if rec[:, c].tobytes() != want_rec[:, c].tobytes()]
-        slot = [u for u in range(rec.shape[0]) if rec[u, bad[0]].tobytes() != want_rec[u, bad[0]].tobytes()][0]
-        assert not bad, (what, "records", bad[:4], slot, rec[slot, bad[0]], want_rec[slot, bad[0]])
-    if after.tobytes() != want_st.tobytes():
-        bad = [c for c in range(len(after)) if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-        assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    G.same_columns(rec, want_rec, (what, "records"))
+    G.same_rows(after, want_st, (what, "states"))
 
 
 # ---- 6: records and whole states, every lane geometry, both loops, both variants ---------------------------------------------------
@@ -172,50 +127,31 @@ def test_bad_channels_take_no_step(eng, oracle, sync):
     """a PRN out of range, a NaN code phase and (sync) out-of-range sync words among good channels: the good channels are the
     restatement's, the bad ones keep every float -- no aiding step -- and advance their accumulator; GPSX_EINVAL comes from the host
     variant itself and from the next synchronize after the device variant"""
-    from stm32f4_sdr_gps_amd import capi
     blocks = K.strong_blocks(40)
     if sync:
         st0, bad = K.bad_channel_states()
         cfg = Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 1, (5, 4))
         want_st = st0.copy()
         want = A.run_sync(oracle, blocks, want_st, cfg, A.WAID_L1CA)
-        c, rec_dtype, n_slots = _sync_cfg(cfg), Y.REC_DTYPE, Y.slots(40, cfg)
         loop0, loop1 = st0["loop"], want_st["loop"]
     else:
         st0, bad = W.bad_loop_states()
         cfg = W.loop_cfg(S.PULL_IN)
         want_st = st0.copy()
         want = A.run(oracle, blocks, want_st, cfg, A.WAID_L1CA)
-        c, rec_dtype, n_slots = _loop_cfg(cfg), L.REC_DTYPE, 10
         loop0, loop1 = st0, want_st
     for ch in bad:      # (on the restatement: nothing but the accumulator moved)
         for f in L.STATE_DTYPE.names:
             same = loop0[f][ch:ch + 1].tobytes() == loop1[f][ch:ch + 1].tobytes()
             assert same == (f != "if_freq_accum"), (ch, f)
-    n_ch = len(st0)
-    aid = capi.waid()
     for dev in (False, True):
-        name, fn = _call(eng, sync, True, dev)
-        rec = np.zeros((n_slots, n_ch), rec_dtype)
-        after = st0.copy()
-        d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(rec.nbytes)
-        try:
-            eng.h2d(d_st, st0)
-            eng.h2d(d_if, blocks)
-            eng.synchronize()
-            if dev:
-                assert fn(eng.h, c.ctypes.data, aid.ctypes.data, C.c_void_p(d_if), 40, C.c_void_p(d_st), n_ch, C.c_void_p(d_rec)) == 0
-                assert eng.lib.gpsx_synchronize(eng.h) == EINVAL
-                assert eng.lib.gpsx_synchronize(eng.h) == 0
-                eng.d2h(rec, d_rec)
-            else:
-                rc = fn(eng.h, c.ctypes.data, aid.ctypes.data, blocks.ctypes.data, 40, C.c_void_p(d_st), n_ch, rec.ctypes.data)
-                assert rc == EINVAL and b"prn" in eng.lib.gpsx_last_error(eng.h)
-            eng.d2h(after, d_st)
-        finally:
-            for p in (d_st, d_if, d_rec):
-                eng.free(p)
-        _same(rec, after, want, want_st, (name, "bad channels"))
+        recs, after, codes = _stage(eng, blocks, st0, cfg, A.WAID_L1CA, dev)
+        assert codes == [EINVAL], dev
+        if dev:
+            assert eng.lib.gpsx_synchronize(eng.h) == 0
+        else:
+            assert b"prn" in eng.lib.gpsx_last_error(eng.h)
+        _same(recs[0][1], after, want, want_st, (sync, dev, "bad channels"))
 
 
 # ---- 10: refusals --------------------------------------------------------------------------------------------------------------------
@@ -237,43 +173,29 @@ def test_argument_checks_write_nothing(eng, sync):
         b"spacing must be 1..15 samples": [dict(spacing=0), dict(spacing=16, aid=(nan, 0))],        # (the unaided calls' clauses come first)
         b"n_blocks must be 1..4096": [dict(n_blocks=0, aid=(nan, 3)), dict(n_blocks=4097)],
     }
-    n_rec = 2 * 4 * (48 if sync else 36)
-    d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(n_rec)
-    try:
-        eng.h2d(d_if, blocks)
+    n_rec = 2 * 4 * (Y.REC_DTYPE if sync else L.REC_DTYPE).itemsize
+
+    def cfg_of(spacing=8):
+        cfg = _sync_cfg(Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 20, (5, 4))) if sync else _loop_cfg(W.loop_cfg(S.PULL_IN))
+        cfg["spacing"] = spacing
+        return cfg
+    with G.Pool() as pool:
+        d_st, d_if = pool.add(G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0)), pool.add(G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks))
+        outs = {True: pool.add(G.Guarded(eng, n_rec)), False: pool.add(G.Guarded(None, n_rec))}
+
+        def call(a, dev):
+            cfg, aid = cfg_of(a["spacing"]), capi.waid(a["aid"][0])
+            aid["reserved"] = a["aid"][1]
+            return _call(eng, sync, True, dev)[1](eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_aid"] else aid.ctypes.data,
+                                                  d_if.ptr if dev else blocks.ctypes.data, a["n_blocks"], d_st.ptr, 4, outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
+        # the limits themselves are accepted
         for dev in (False, True):
             name, fn = _call(eng, sync, True, dev)
-            for message, changes in by_message.items():
-                for change in changes:
-                    a = {**good, **change}
-                    cfg = _sync_cfg(Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 20, (5, 4))) if sync else _loop_cfg(W.loop_cfg(S.PULL_IN))
-                    cfg["spacing"] = a["spacing"]
-                    aid = capi.waid(a["aid"][0])
-                    aid["reserved"] = a["aid"][1]
-                    rec = np.full(n_rec, 0xA5, np.uint8)
-                    eng.h2d(d_st, st0)
-                    eng.h2d(d_rec, rec)
-                    rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_aid"] else aid.ctypes.data,
-                            C.c_void_p(d_if) if dev else blocks.ctypes.data, a["n_blocks"], C.c_void_p(d_st), 4,
-                            C.c_void_p(d_rec) if dev else rec.ctypes.data)
-                    assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (name, change, eng.lib.gpsx_last_error(eng.h))
-                    eng.synchronize()   # nothing was enqueued, nothing is pending
-                    st, dr = st0.copy(), np.zeros_like(rec)
-                    eng.d2h(st, d_st)
-                    eng.d2h(dr, d_rec)
-                    assert (rec == 0xA5).all() and (dr == 0xA5).all() and st.tobytes() == st0.tobytes(), (name, change)
-            # the limits themselves are accepted
             for k in (1.0, -1.0):
-                aid = capi.waid(k)
-                cfg = _sync_cfg(Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 20, (5, 4))) if sync else _loop_cfg(W.loop_cfg(S.PULL_IN))
-                eng.h2d(d_st, st0)
-                rec = np.zeros(n_rec, np.uint8)
-                eng._chk(fn(eng.h, cfg.ctypes.data, aid.ctypes.data, C.c_void_p(d_if) if dev else blocks.ctypes.data, 8, C.c_void_p(d_st), 4,
-                            C.c_void_p(d_rec) if dev else rec.ctypes.data), name)
+                d_st.refill()
+                eng._chk(fn(eng.h, cfg_of().ctypes.data, capi.waid(k).ctypes.data, d_if.ptr if dev else blocks.ctypes.data, 8, d_st.ptr, 4, outs[dev].ptr), name)
                 eng.synchronize()
-    finally:
-        for p in (d_st, d_if, d_rec):
-            eng.free(p)
 
 
 # ---- 11: the scenarios the CPU test measures, on the device ------------------------------------------------------------------------

@@ -5,27 +5,17 @@ to the library's host decoder and to the reference's recorded outputs).  Every c
 fabricated (tests/weighted_eph_cases.py: 32 distinct streams tiled over the channels -- frames from subframe 1, 2 and 3, failed words,
 a missing record, a word out of order, re-syncs, a cutover, HOWs that do not pass, all-ones and all-zeros sets, a week that ends;
 initial states from the restatement's run over the stream's earlier blocks); the last test puts the word layer's kernel in front."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import weighted_eph_cases as X
 import weighted_eph_ref as E
+import weighted_gpu as G
+from weighted_gpu import EINVAL, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -22
-GUARD = 4096
 VALID, NEW = E.F_VALID, E.F_NEW
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
 
 
 def _cfg(reserved0=0, reserved1=0):
@@ -36,52 +26,20 @@ def _cfg(reserved0=0, reserved1=0):
 
 def _gpu(eng, launches, st, dev=True):
     """the library on a copy of `st` in device memory, launch after launch.  launches: [(words [n_blocks // 600 + 2][n_ch], n_blocks)].
-    States and records sit between canaries, the records are prefilled with 0xA5.  -> ([records per launch], states after, [codes])"""
-    n_ch = len(st)
-    cfg = _cfg()
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0x5A, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = np.ascontiguousarray(st).view(np.uint8)
-    d_st = eng.malloc(h_st.nbytes)
-    out, codes = [], []
-    try:
-        eng.h2d(d_st, h_st)
-        for words, n_blocks in launches:
-            words = np.ascontiguousarray(words)
-            assert words.dtype == E.WORD_DTYPE and words.shape == (E.max_words(n_blocks), n_ch)
-            size = n_ch * 256
-            h_eph = np.full(GUARD + size + GUARD, 0xA5, np.uint8)
-            d_words, d_eph = eng.malloc(words.nbytes), eng.malloc(h_eph.nbytes)
-            try:
-                eng.h2d(d_words, words)
-                if dev:
-                    eng.h2d(d_eph, h_eph)
-                    rc = eng.lib.gpsx_weph_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, C.c_void_p(d_st + GUARD), n_ch,
-                                               C.c_void_p(d_eph + GUARD))
-                    assert rc == 0 and eng.lib.gpsx_last_kernel(eng.h) == b"k_weph"
-                    codes.append(eng.lib.gpsx_synchronize(eng.h))
-                    eng.d2h(h_eph, d_eph)
-                else:
-                    codes.append(eng.lib.gpsx_weph(eng.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, C.c_void_p(d_st + GUARD), n_ch,
-                                                   h_eph[GUARD:].ctypes.data))
-                    assert eng.lib.gpsx_last_kernel(eng.h) == b"k_weph"
-            finally:
-                for p in (d_words, d_eph):
-                    eng.free(p)
-            assert (h_eph[:GUARD] == 0xA5).all() and (h_eph[GUARD + size:] == 0xA5).all(), "canary around the records"
-            out.append(h_eph[GUARD:GUARD + size].view(E.EPH_DTYPE).copy())
-        eng.d2h(h_st, d_st)
-    finally:
-        eng.free(d_st)
-    assert (h_st[:GUARD] == 0x5A).all() and (h_st[GUARD + st.nbytes:] == 0x5A).all(), "canary around the states"
-    return out, h_st[GUARD:GUARD + st.nbytes].view(E.STATE_DTYPE).copy(), codes
+    -> ([records per launch], states after, [codes])"""
+    n_ch, cfg = len(st), _cfg()
+    fn = eng.lib.gpsx_weph_dev if dev else eng.lib.gpsx_weph
+
+    def call(ins, sts, out, k):
+        return fn(eng.h, cfg.ctypes.data, ins[0], launches[k][1], sts[0], n_ch, out)
+    for words, n_blocks in launches:
+        assert words.dtype == E.WORD_DTYPE and words.shape == (E.max_words(n_blocks), n_ch)
+    return G.run_stage(eng, call, b"k_weph", st, [([np.ascontiguousarray(words)], E.EPH_DTYPE, (n_ch,)) for words, _ in launches], dev)
 
 
 def _same(eph, after, want, want_st, what):
-    assert eph.shape == want.shape and after.shape == want_st.shape, what
-    bad = [c for c in range(len(eph)) if eph[c:c + 1].tobytes() != want[c:c + 1].tobytes()]
-    assert not bad, (what, "records", bad[:4], eph[bad[0]], want[bad[0]])
-    bad = [c for c in range(len(after)) if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    G.same_rows(eph, want, (what, "records"))
+    G.same_rows(after, want_st, (what, "states"))
 
 
 @pytest.mark.parametrize("i", range(len(X.CASES)))
@@ -246,28 +204,16 @@ def test_argument_checks_write_nothing(eng):
         b"n_blocks must be 1..4096": [dict(n_blocks=0), dict(n_blocks=-40), dict(n_blocks=4097), dict(n_blocks=0, n_ch=0)],
         b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3)],
     }
-    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
-    d_words, d_st, d_eph = eng.malloc(words.nbytes), eng.malloc(st0.nbytes), eng.malloc(n_ch * 256)
-    try:
-        eng.h2d(d_words, words)
-        for dev, fn in ((False, eng.lib.gpsx_weph), (True, eng.lib.gpsx_weph_dev)):
-            for message, change in refusals:
-                a = {**good, **change}
-                cfg = _cfg(a["r0"], a["r1"])
-                host = np.full(n_ch * 256, 0xA5, np.uint8)
-                eng.h2d(d_st, st0)
-                eng.h2d(d_eph, host)
-                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_words"] else C.c_void_p(d_words), a["n_blocks"],
-                        None if a["null_st"] else C.c_void_p(d_st), a["n_ch"], None if a["null_out"] else (C.c_void_p(d_eph) if dev else host.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                eng.synchronize()      # nothing was enqueued, nothing is pending
-                st, dw = st0.copy(), np.zeros_like(host)
-                eng.d2h(st, d_st)
-                eng.d2h(dw, d_eph)
-                assert (host == 0xA5).all() and (dw == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
-    finally:
-        for p in (d_words, d_st, d_eph):
-            eng.free(p)
+    with G.Pool() as pool:
+        d_words, d_st = pool.add(G.Guarded(eng, words.nbytes, G.STATE_FILL, words)), pool.add(G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0))
+        outs = {True: pool.add(G.Guarded(eng, n_ch * E.EPH_DTYPE.itemsize)), False: pool.add(G.Guarded(None, n_ch * E.EPH_DTYPE.itemsize))}
+
+        def call(a, dev):
+            cfg = _cfg(a["r0"], a["r1"])
+            fn = eng.lib.gpsx_weph_dev if dev else eng.lib.gpsx_weph
+            return fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_words"] else d_words.ptr, a["n_blocks"],
+                      None if a["null_st"] else d_st.ptr, a["n_ch"], None if a["null_out"] else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
 
 
 def test_bits_to_ephemerides_on_the_device(eng):
@@ -277,7 +223,7 @@ def test_bits_to_ephemerides_on_the_device(eng):
     VALID with the payload that was encoded"""
     import weighted_nav_cases as W
     import weighted_nav_ref as N
-    from stm32f4_sdr_gps_amd import capi, synth
+    from stm32f4_sdr_gps_amd import synth
     rng = np.random.default_rng(11)
     gen = np.random.Generator(np.random.PCG64(12))
     sets, specs = [], []
@@ -292,36 +238,21 @@ def test_bits_to_ephemerides_on_the_device(eng):
         specs.append((edge + 19 + 20 * np.arange(len(bits), dtype=np.int64), bits))
     n, n_launch, n_slots = 4096, 5, 205
     assert max(int(ends[-1]) for ends, _ in specs) < n * n_launch
-    nav_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
-    nav_cfg["max_bad_words"] = 3
-    cfg = _cfg()
-    nav, st = np.zeros(3, N.STATE_DTYPE), np.zeros(3, E.STATE_DTYPE)
-    want_st = st.copy()
-    d_nav, d_st = eng.malloc(nav.nbytes), eng.malloc(st.nbytes)
-    d_rec, d_words, d_eph = eng.malloc(n_slots * 3 * 48), eng.malloc(E.max_words(n) * 3 * 16), eng.malloc(3 * 256)
+    want_st = np.zeros(3, E.STATE_DTYPE)
     seen_new = np.zeros(3, np.uint32)
-    try:
-        eng.h2d(d_nav, nav)
-        eng.h2d(d_st, st)
+    with G.Chain(eng, None, dict(nav=np.zeros(3, N.STATE_DTYPE), eph=want_st.copy()), n, max_slots=n_slots) as chain:
         for k in range(n_launch):
             rec = W.launch_records(specs, np.arange(3), k * n, n, 20, filler=False)
             assert rec.shape == (n_slots, 3)
-            eng.h2d(d_rec, rec)
-            eng._chk(eng.lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_nav), 3, C.c_void_p(d_words)),
-                     "gpsx_wnav_words_dev")
-            eng._chk(eng.lib.gpsx_weph_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_words), n, C.c_void_p(d_st), 3, C.c_void_p(d_eph)), "gpsx_weph_dev")
+            chain.records(rec, n)
+            chain.words()
+            chain.eph()
             eng.synchronize()
-            words, eph = np.zeros((E.max_words(n), 3), E.WORD_DTYPE), np.zeros(3, E.EPH_DTYPE)
-            eng.d2h(words, d_words)
-            eng.d2h(eph, d_eph)
-            eng.d2h(st, d_st)
+            words, eph, st = chain.read("words"), chain.read("e"), chain.read("eph")
             want, bad = E.run(words, n, want_st)
             assert not bad
             _same(eph, st, want, want_st, ("launch", k))
             seen_new |= eph["flags"] & NEW
-    finally:
-        for p in (d_nav, d_st, d_rec, d_words, d_eph):
-            eng.free(p)
     assert (eph["flags"] & VALID).all() and (seen_new == NEW).all() and st["n_sets"].tolist() == [1, 1, 1] and st["n_subframes"].tolist() == [3, 3, 3]
     for ch in range(3):
         for k in range(3):      # (d23, d24 of word 10 are solved for parity: not the payload's)

@@ -9,49 +9,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import weighted_eph_ref as E
 import weighted_fix_cases as W
 import weighted_fix_ref as F
-import weighted_nav_ref as N
-import weighted_obs_ref as O
+import weighted_gpu as G
+from weighted_gpu import EINVAL, GUARD, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096
-EINVAL = -22
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
-
-class _Guarded:
-    """`nbytes` of device memory between two canaries of GUARD bytes; the payload starts as `content` or as the fill byte"""
-
-    def __init__(self, eng, nbytes, fill=0xA5, content=None):
-        self.eng, self.nbytes, self.fill = eng, nbytes, fill
-        self.host = np.full(GUARD + nbytes + GUARD, fill, np.uint8)
-        if content is not None:
-            self.host[GUARD:GUARD + nbytes] = np.ascontiguousarray(content).view(np.uint8).reshape(-1)
-        self.base = eng.malloc(self.host.nbytes)
-        eng.h2d(self.base, self.host)
-        self.ptr = C.c_void_p(self.base + GUARD)
-
-    def get(self, dtype, count):
-        self.eng.d2h(self.host, self.base)
-        assert (self.host[:GUARD] == self.fill).all() and (self.host[GUARD + self.nbytes:] == self.fill).all(), "a canary was written"
-        return self.host[GUARD:GUARD + count * np.dtype(dtype).itemsize].view(dtype).copy()
-
-    def untouched(self):
-        self.eng.d2h(self.host, self.base)
-        return bool((self.host == self.fill).all())
-
-    def free(self):
-        self.eng.free(self.base)
 
 
 class _Launch:
@@ -59,9 +22,9 @@ class _Launch:
 
     def __init__(self, eng, cfg, obs, eph, n_rx, lock=None):
         self.eng, self.cfg, self.n_rx, self.n_ch = eng, cfg, n_rx, len(obs)
-        self.obs, self.eph = _Guarded(eng, obs.nbytes, 0x5A, obs), _Guarded(eng, eph.nbytes, 0x5A, eph)
-        self.lock = None if lock is None else _Guarded(eng, lock.nbytes, 0x5A, lock)
-        self.fix, self.pr = _Guarded(eng, n_rx * 128), _Guarded(eng, self.n_ch * 8)
+        self.obs, self.eph = G.Guarded(eng, obs.nbytes, 0x5A, obs), G.Guarded(eng, eph.nbytes, 0x5A, eph)
+        self.lock = None if lock is None else G.Guarded(eng, lock.nbytes, 0x5A, lock)
+        self.fix, self.pr = G.Guarded(eng, n_rx * 128), G.Guarded(eng, self.n_ch * 8)
         self.bufs = [b for b in (self.obs, self.eph, self.lock, self.fix, self.pr) if b is not None]
 
     def call(self, prev=None, fix=None, want_pr=True, cfg=None, n_rx=None):
@@ -122,7 +85,7 @@ def test_host_arrays_equal_device_arrays_and_the_lock_and_pr_arguments(eng):
                 host, host_pr = eng.wfix(cfg, case["obs"], case["eph"], n_rx, lock=lock, want_pr=True)
                 assert got.tobytes() == host.tobytes() and got_pr.tobytes() == host_pr.tobytes()
                 assert eng.wfix(cfg, case["obs"], case["eph"], n_rx, lock=lock).tobytes() == got.tobytes()
-                quiet = _Guarded(eng, n_rx * 128)
+                quiet = G.Guarded(eng, n_rx * 128)
                 eng._chk(run.call(fix=quiet.ptr, want_pr=False), "gpsx_wfix_dev")
                 eng.synchronize()
                 assert quiet.get(F.FIX_DTYPE, n_rx).tobytes() == got.tobytes()
@@ -141,10 +104,10 @@ def test_warm_start_in_place(eng):
     run = _Launch(eng, cfg, case["obs"], case["eph"], n_rx, case["lock"])
     try:
         cold, _ = run.run()
-        copy = _Guarded(eng, cold.nbytes, 0x5A, cold)
+        copy = G.Guarded(eng, cold.nbytes, 0x5A, cold)
         apart, _ = run.run(prev=copy.ptr)
         copy.free()
-        eng.h2d(run.fix.base + GUARD, cold)
+        run.fix.put(cold)
         in_place, _ = run.run(prev=run.fix.ptr)
     finally:
         run.free()
@@ -216,28 +179,20 @@ def test_behind_the_five_device_stages(eng):
     blocks = P.blocks()
     d_if = eng.malloc(blocks.nbytes)
     eng.h2d(d_if, blocks)
-    sync = P.sync_cfg_dev(P.MOVING)
-    nav_cfg, obs_cfg, eph_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE), np.zeros(1, O.CFG_DTYPE), np.zeros(1, E.CFG_DTYPE)
-    nav_cfg["max_bad_words"], obs_cfg["edge_guard"] = P.MAX_BAD_WORDS, P.EDGE_GUARD
-    lock_cfg = capi.wlock_cfg(25, 10, 1.5, 0.3, 1.0, 2, 2)
     st0 = dict(P.fresh_states(), sync=P.handover(), lock=np.zeros(n_ch, capi.WLOCK_STATE_DTYPE))
-    big = max(P.LAUNCHES)
-    bufs = {k: _Guarded(eng, v.nbytes, 0x5A, v) for k, v in st0.items()}
-    bufs.update(rec=_Guarded(eng, capi.wsync_slots(big, P.K.N_COH_SEARCH, P.K.N_COH_LOCK) * n_ch * 48), words=_Guarded(eng, N.max_words(big) * n_ch * 16),
-                o=_Guarded(eng, n_ch * 32), e=_Guarded(eng, n_ch * 256), l=_Guarded(eng, n_ch * 64), fix=_Guarded(eng, 128), pr=_Guarded(eng, n_ch * 8))
+    chain = G.Chain(eng, P.sync_cfg_dev(P.MOVING), st0, max(P.LAUNCHES), P.MAX_BAD_WORDS, P.EDGE_GUARD, capi.wlock_cfg(25, 10, 1.5, 0.3, 1.0, 2, 2))
+    bufs = dict(chain.buf, fix=G.Guarded(eng, F.FIX_DTYPE.itemsize), pr=G.Guarded(eng, n_ch * 8))
     try:
         at = 0
         for n in P.LAUNCHES:
-            n_slots = capi.wsync_slots(n, P.K.N_COH_SEARCH, P.K.N_COH_LOCK)
-            eng._chk(lib.gpsx_track_loop_weighted_sync_dev(eng.h, sync.ctypes.data, C.c_void_p(d_if + at * 4092), n, bufs["sync"].ptr, n_ch, bufs["rec"].ptr),
-                     "gpsx_track_loop_weighted_sync_dev")
-            eng._chk(lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["nav"].ptr, n_ch, bufs["words"].ptr), "gpsx_wnav_words_dev")
-            eng._chk(lib.gpsx_wobs_dev(eng.h, obs_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["words"].ptr, bufs["obs"].ptr, n_ch, bufs["o"].ptr), "gpsx_wobs_dev")
-            eng._chk(lib.gpsx_weph_dev(eng.h, eph_cfg.ctypes.data, bufs["words"].ptr, n, bufs["eph"].ptr, n_ch, bufs["e"].ptr), "gpsx_weph_dev")
-            eng._chk(lib.gpsx_wlock_dev(eng.h, lock_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["lock"].ptr, None, n_ch, bufs["l"].ptr), "gpsx_wlock_dev")
+            chain.sync(d_if + at * 4092, n)
+            chain.words()
+            chain.obs()
+            chain.eph()
+            chain.lock()
             eng.synchronize()
             at += n
-        obs, eph, lock = bufs["o"].get(O.OBS_DTYPE, n_ch), bufs["e"].get(E.EPH_DTYPE, n_ch), bufs["l"].get(capi.WLOCK_DTYPE, n_ch)
+        obs, eph, lock = chain.read("o"), chain.read("e"), chain.read("l")
         assert P.flags_ok(obs) and (lock["flags"] & capi.WLOCK_FLAG_CODE).all(), (obs["flags"], lock["flags"])
         for offset in P.OFFSETS_MS:
             cfg = capi.wfix_cfg(offset, 4)

@@ -6,89 +6,39 @@ tests/test_weighted_forced_reference.py -- through gpsx_track_loop_weighted_sync
 canaries around both: the table at one channel per wave; at 2, 7 and 16 channels per wave with the rows moving through the lanes;
 the host variant; and the same targets reached over two launches, the open window passing through HBM between them.  Every launch
 runs one or two blocks; the restatement runs the distinct rows only."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import weighted_forced_cases as W
+import weighted_gpu as G
 import weighted_loop_cases as S
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -22
-GUARD = 4096
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
-
-def _cfg(c):
-    from stm32f4_sdr_gps_amd import capi
-    gains = {name: dict(dll=(c[name]["dll_c1"], c[name]["dll_c2"]), pll=(c[name]["pll_c1"], c[name]["pll_c2"]), fll=c[name]["fll_c"]) for name in ("search", "lock")}
-    return capi.wsync_cfg(c["n_coh_search"], c["n_coh_lock"], gains["search"], gains["lock"], c["sync_bits"], (c["sync_num"], c["sync_den"]),
-                          c["use_magnitude"], c["spacing"])
-
 
 def _launches(eng, pieces, st, cfg, has_bad, host=False):
-    """the library on a copy of `st` in device memory, canaries around states and records, one launch per entry of `pieces`
-    (arrays of blocks) -> ([records per launch], [states after each launch]).  has_bad: GPSX_EINVAL is due (from the next
-    synchronize after the device variant, from the host variant itself)"""
-    n_ch = len(st)
-    c = _cfg(cfg)
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0xA5, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = st.view(np.uint8)
-    d_st = eng.malloc(h_st.nbytes)
-    recs, states = [], []
-    try:
-        eng.h2d(d_st, h_st)
-        for part in pieces:
-            part = np.ascontiguousarray(part, np.uint8).reshape(-1, 4092)
-            k, n_slots = len(part), Y.slots(len(part), cfg)
-            rec_bytes = n_slots * n_ch * 48
-            h_rec = np.full(GUARD + rec_bytes + GUARD, 0x5A, np.uint8)
-            d_if, d_rec = eng.malloc(part.nbytes), eng.malloc(h_rec.nbytes)
-            try:
-                eng.h2d(d_if, part)
-                eng.h2d(d_rec, h_rec)
-                eng.synchronize()
-                if host:
-                    rc = eng.lib.gpsx_track_loop_weighted_sync(eng.h, c.ctypes.data, part.ctypes.data, k, C.c_void_p(d_st + GUARD), n_ch,
-                                                               h_rec[GUARD:].ctypes.data)
-                    assert rc == (EINVAL if has_bad else 0), eng.lib.gpsx_last_error(eng.h)
-                else:
-                    rc = eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st + GUARD), n_ch,
-                                                                   C.c_void_p(d_rec + GUARD))
-                    assert rc == 0, eng.lib.gpsx_last_error(eng.h)
-                    assert eng.lib.gpsx_synchronize(eng.h) == (EINVAL if has_bad else 0)
-                    assert eng.lib.gpsx_synchronize(eng.h) == 0
-                    eng.d2h(h_rec, d_rec)
-                assert eng.lib.gpsx_last_kernel(eng.h) == b"k_track_wsync"
-            finally:
-                eng.free(d_if)
-                eng.free(d_rec)
-            assert (h_rec[:GUARD] == 0x5A).all() and (h_rec[GUARD + rec_bytes:] == 0x5A).all(), "canary around the records"
-            recs.append(h_rec[GUARD:GUARD + rec_bytes].view(Y.REC_DTYPE).reshape(n_slots, n_ch).copy())
-            eng.d2h(h_st, d_st)
-            assert (h_st[:GUARD] == 0xA5).all() and (h_st[GUARD + st.nbytes:] == 0xA5).all(), "canary around the states"
-            states.append(h_st[GUARD:GUARD + st.nbytes].view(Y.STATE_DTYPE).copy())
-    finally:
-        eng.free(d_st)
+    """the library on a copy of `st` in device memory, one launch per entry of `pieces` (arrays of blocks) -> ([records per launch],
+    [states after each launch]).  has_bad: GPSX_EINVAL is due (from the next synchronize after the device variant, from the host
+    variant itself)"""
+    n_ch, c = len(st), G.sync_cfg(cfg)
+    fn = eng.lib.gpsx_track_loop_weighted_sync if host else eng.lib.gpsx_track_loop_weighted_sync_dev
+    parts = [np.ascontiguousarray(part, np.uint8).reshape(-1, 4092) for part in pieces]
+
+    def call(ins, sts, out, k):
+        return fn(eng.h, c.ctypes.data, ins[0], len(parts[k]), sts[0], n_ch, out)
+    recs, states, codes = G.run_stage(eng, call, b"k_track_wsync", st, [([part], Y.REC_DTYPE, (Y.slots(len(part), cfg), n_ch)) for part in parts],
+                                      not host, host_inputs=True, after_each=True)
+    assert codes == [EINVAL if has_bad else 0] * len(parts), (codes, eng.lib.gpsx_last_error(eng.h))
+    assert eng.lib.gpsx_synchronize(eng.h) == 0
     return recs, states
 
 
 def _same(rec, after, want_rec, want_st, channels, names, what):
-    assert rec.dtype == Y.REC_DTYPE and rec.shape == want_rec.shape, what
-    for c in channels:
-        for u in range(rec.shape[0]):
-            assert rec[u, c].tobytes() == want_rec[u, c].tobytes(), (what, "record", int(c), names[c], u, rec[u, c], want_rec[u, c])
-        assert after[c:c + 1].tobytes() == want_st[c:c + 1].tobytes(), (what, "state", int(c), names[c], after[c], want_st[c])
+    assert rec.dtype == Y.REC_DTYPE, what
+    G.same_columns(rec, want_rec, (what, "record"), list(channels), names)
+    G.same_rows(after, want_st, (what, "state"), list(channels), names)
 
 
 def _group(oracle, group, n_ch, cpw):

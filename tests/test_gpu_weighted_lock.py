@@ -3,93 +3,38 @@ ALU, one channel per lane) against its exact CPU restatement (tests/weighted_loc
 tests/test_weighted_lock_reference.py).  Every comparison is for equality, byte for byte, on the 64-byte records, the 128-byte lock
 states and the 448-byte sync states.  The sync loop's records are fabricated (tests/weighted_lock_cases.py: 32 distinct streams
 tiled over the channels, sync states in all three modes behind them); only the last test starts from IF samples."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import weighted_gpu as G
 import weighted_lock_cases as X
 import weighted_lock_ref as R
 import weighted_nav_ref as N
 import weighted_obs_ref as O
 import weighted_sync_cases as K
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-EINVAL = -22
-GUARD = 4096
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
-
-def _between_canaries(eng, a, fill):
-    h = np.full(GUARD + a.nbytes + GUARD, fill, np.uint8)
-    h[GUARD:GUARD + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    d = eng.malloc(h.nbytes)
-    eng.h2d(d, h)
-    return h, d
-
-
-def _back(eng, h, d, nbytes, fill, what):
-    eng.d2h(h, d)
-    assert (h[:GUARD] == fill).all() and (h[GUARD + nbytes:] == fill).all(), "canary around " + what
-    return h[GUARD:GUARD + nbytes]
 
 
 def _gpu(eng, launches, st, cfg, sync=None, dev=True):
     """the library on copies of `st` (and of `sync`, the sync loop's states; None: a NULL pointer) in device memory, launch after
-    launch.  launches: [(records [n_slots][n_ch], n_blocks)].  States and records sit between canaries, the records are prefilled
-    with 0xA5.  -> ([lock records per launch], lock states after, sync states after or None, [return codes])"""
-    n_ch = len(st)
-    c = R.cfg_array(cfg)
-    h_st, d_st = _between_canaries(eng, st, 0x5A)
-    h_sync, d_sync = _between_canaries(eng, sync, 0x3C) if sync is not None else (None, 0)
-    p_sync = C.c_void_p(d_sync + GUARD) if sync is not None else None
-    out, codes = [], []
-    try:
-        for rec, n_blocks in launches:
-            rec = np.ascontiguousarray(rec)
-            assert rec.dtype == Y.REC_DTYPE and rec.shape[1] == n_ch
-            size = n_ch * 64
-            h_lock = np.full(GUARD + size + GUARD, 0xA5, np.uint8)
-            d_rec, d_lock = eng.malloc(rec.nbytes), eng.malloc(h_lock.nbytes)
-            try:
-                eng.h2d(d_rec, rec)
-                if dev:
-                    eng.h2d(d_lock, h_lock)
-                    rc = eng.lib.gpsx_wlock_dev(eng.h, c.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_st + GUARD), p_sync, n_ch,
-                                                C.c_void_p(d_lock + GUARD))
-                    assert rc == 0 and eng.lib.gpsx_last_kernel(eng.h) == b"k_wlock"
-                    codes.append(eng.lib.gpsx_synchronize(eng.h))
-                    eng.d2h(h_lock, d_lock)
-                else:
-                    codes.append(eng.lib.gpsx_wlock(eng.h, c.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_st + GUARD), p_sync, n_ch,
-                                                    h_lock[GUARD:].ctypes.data))
-            finally:
-                eng.free(d_rec)
-                eng.free(d_lock)
-            assert (h_lock[:GUARD] == 0xA5).all() and (h_lock[GUARD + size:] == 0xA5).all(), "canary around the records"
-            out.append(h_lock[GUARD:GUARD + size].view(R.LOCK_DTYPE).copy())
-        after = _back(eng, h_st, d_st, st.nbytes, 0x5A, "the lock states").view(R.STATE_DTYPE).copy()
-        sync_after = _back(eng, h_sync, d_sync, sync.nbytes, 0x3C, "the sync states").view(Y.STATE_DTYPE).copy() if sync is not None else None
-    finally:
-        eng.free(d_st)
-        if sync is not None:
-            eng.free(d_sync)
+    launch.  launches: [(records [n_slots][n_ch], n_blocks)].
+    -> ([lock records per launch], lock states after, sync states after or None, [return codes])"""
+    n_ch, c = len(st), R.cfg_array(cfg)
+    fn = eng.lib.gpsx_wlock_dev if dev else eng.lib.gpsx_wlock
+
+    def call(ins, sts, out, k):
+        return fn(eng.h, c.ctypes.data, ins[0], launches[k][0].shape[0], launches[k][1], sts[0], sts[1], n_ch, out)
+    for rec, _ in launches:
+        assert rec.dtype == Y.REC_DTYPE and rec.shape[1] == n_ch
+    out, (after, sync_after), codes = G.run_stage(eng, call, b"k_wlock", [st, sync],
+                                                  [([np.ascontiguousarray(rec)], R.LOCK_DTYPE, (n_ch,)) for rec, _ in launches], dev)
     return out, after, sync_after, codes
 
 
-def _same(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    bad = [c for c in range(len(got)) if got[c:c + 1].tobytes() != want[c:c + 1].tobytes()]
-    assert not bad, (what, bad[:4], got[bad[0]], want[bad[0]])
+_same = G.same_rows
 
 
 @pytest.mark.parametrize("n_slots", [1, X.AHEAD - 1, X.AHEAD, 2 * X.AHEAD + 1])
@@ -235,54 +180,33 @@ def test_argument_checks_write_nothing(eng):
         b"n_slots must be 1..n_blocks": [dict(n_slots=0), dict(n_slots=-1), dict(n_slots=n_blocks + 1), dict(n_slots=0, n_ch=0)],
         b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3)],
     }
-    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
-    d_rec, d_st, d_sync, d_lock = eng.malloc(rec.nbytes), eng.malloc(st0.nbytes), eng.malloc(sync0.nbytes), eng.malloc(n_ch * 64)
-    try:
-        eng.h2d(d_rec, rec)
-        for dev, fn in ((False, eng.lib.gpsx_wlock), (True, eng.lib.gpsx_wlock_dev)):
-            for message, change in refusals:
-                a = {**good, **change}
-                cfg = R.cfg_array({**X.FAB, **{k: v for k, v in change.items() if k in X.FAB}}, a["reserved"])
-                host = np.full(n_ch * 64, 0xA5, np.uint8)
-                eng.h2d(d_st, st0)
-                eng.h2d(d_sync, sync0)
-                eng.h2d(d_lock, host)
-                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else C.c_void_p(d_rec), a["n_slots"], a["n_blocks"],
-                        None if a["null_st"] else C.c_void_p(d_st), None if a["null_sync"] else C.c_void_p(d_sync), a["n_ch"],
-                        None if a["null_out"] else (C.c_void_p(d_lock) if dev else host.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                eng.synchronize()      # nothing was enqueued, nothing is pending
-                st, sync, dw = st0.copy(), sync0.copy(), np.zeros_like(host)
-                eng.d2h(st, d_st)
-                eng.d2h(sync, d_sync)
-                eng.d2h(dw, d_lock)
-                assert (host == 0xA5).all() and (dw == 0xA5).all() and st.tobytes() == st0.tobytes() and sync.tobytes() == sync0.tobytes(), (dev, change)
+    with G.Pool() as pool:
+        d_rec, d_st, d_sync = (pool.add(G.Guarded(eng, a.nbytes, G.STATE_FILL, a)) for a in (rec, st0, sync0))
+        outs = {True: pool.add(G.Guarded(eng, n_ch * R.LOCK_DTYPE.itemsize)), False: pool.add(G.Guarded(None, n_ch * R.LOCK_DTYPE.itemsize))}
+
+        def call(a, dev):
+            cfg = R.cfg_array({**X.FAB, **{k: v for k, v in a.items() if k in X.FAB}}, a["reserved"])
+            fn = eng.lib.gpsx_wlock_dev if dev else eng.lib.gpsx_wlock
+            return fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else d_rec.ptr, a["n_slots"], a["n_blocks"],
+                      None if a["null_st"] else d_st.ptr, None if a["null_sync"] else d_sync.ptr, a["n_ch"], None if a["null_out"] else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, d_sync, *outs.values()])
         # the ends of the ranges are in range
         for change in (dict(epoch_search=1024, epoch_lock=1024, n_good=255, n_bad=255, patience=2**31 - 1), dict(epoch_search=1, epoch_lock=1, n_good=1, n_bad=1),
                        dict(code_min=-3.0e38, snr_min=3.0e38)):
-            assert eng.lib.gpsx_wlock_dev(eng.h, R.cfg_array({**X.FAB, **change}).ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_st),
-                                          C.c_void_p(d_sync), n_ch, C.c_void_p(d_lock)) == 0
+            assert eng.lib.gpsx_wlock_dev(eng.h, R.cfg_array({**X.FAB, **change}).ctypes.data, d_rec.ptr, n_slots, n_blocks, d_st.ptr, d_sync.ptr, n_ch,
+                                          outs[True].ptr) == 0
         eng.synchronize()
-    finally:
-        for p in (d_rec, d_st, d_sync, d_lock):
-            eng.free(p)
 
 
 def test_the_engine_convenience(eng):
     st0, sync0, launches, want_st, want_sync = X.fab_run([12], 40)
     rec, n_blocks, want = launches[0]
     from stm32f4_sdr_gps_amd import capi
-    d_rec, d_st, d_sync = eng.malloc(rec.nbytes), eng.malloc(st0.nbytes), eng.malloc(sync0.nbytes)
-    try:
-        eng.h2d(d_rec, np.ascontiguousarray(rec))
-        eng.h2d(d_st, st0)
-        eng.h2d(d_sync, sync0)
+    with G.Pool() as pool:
+        d_rec, d_st, d_sync = (pool.add(G.Guarded(eng, a.nbytes, G.STATE_FILL, a)).ptr.value for a in (rec, st0, sync0))
         f = X.FAB
         cfg = capi.wlock_cfg(f["epoch_search"], f["epoch_lock"], f["code_min"], f["car_min"], f["snr_min"], f["n_good"], f["n_bad"], f["rearm"], f["patience"])
         lock = eng.wlock(cfg, d_rec, rec.shape[0], n_blocks, d_st, 40, d_sync)
-    finally:
-        for p in (d_rec, d_st, d_sync):
-            eng.free(p)
     _same(lock, want, "Engine.wlock")
     assert capi.wlock_cn0_dbhz(lock, 20).tobytes() == R.cn0_dbhz(want, 20).tobytes()
 
@@ -295,40 +219,20 @@ def test_if_samples_to_lock_flags_on_the_device(eng):
     seed, n_ch = 1, X.N_CH
     blocks = X.scenario_blocks(seed)
     sync_cfg = capi.wsync_cfg(K.N_COH_SEARCH, K.N_COH_LOCK, K.S.PULL_IN, K.S.STEADY, K.SYNC_BITS, K.RATIO)
-    nav_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
-    nav_cfg["max_bad_words"] = 3
-    obs_cfg = np.zeros(1, capi.WOBS_CFG_DTYPE)
-    obs_cfg["edge_guard"] = 512.0
     cfg = X.scenario_cfg(1)
-    lock_cfg = R.cfg_array(cfg)
-    sync_st = X.scenario_states(seed)
-    nav, obs_st, lock_st = np.zeros(n_ch, N.STATE_DTYPE), np.zeros(n_ch, O.STATE_DTYPE), np.zeros(n_ch, R.STATE_DTYPE)
-    max_slots = capi.wsync_slots(X.LAUNCH, K.N_COH_SEARCH, K.N_COH_LOCK)
-    sizes = (blocks.nbytes, sync_st.nbytes, nav.nbytes, obs_st.nbytes, lock_st.nbytes, max_slots * n_ch * 48, N.max_words(X.LAUNCH) * n_ch * 16, n_ch * 32, n_ch * 64)
-    ptrs = [eng.malloc(s) for s in sizes]
-    d_if, d_sync, d_nav, d_obs_st, d_lock_st, d_rec, d_words, d_obs, d_lock = ptrs
-    want_st = lock_st.copy()
+    states = dict(sync=X.scenario_states(seed), nav=np.zeros(n_ch, N.STATE_DTYPE), obs=np.zeros(n_ch, O.STATE_DTYPE), lock=np.zeros(n_ch, R.STATE_DTYPE))
+    want_st = states["lock"].copy()
     flags, modes, snr, obs_flags, search_after = [], [], [], [], None
-    try:
-        for d, a in ((d_if, blocks), (d_sync, sync_st), (d_nav, nav), (d_obs_st, obs_st), (d_lock_st, lock_st)):
-            eng.h2d(d, a)
+    with G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks) as d_if, G.Chain(eng, sync_cfg, states, X.LAUNCH, lock_cfg=R.cfg_array(cfg)) as chain:
         for at, n in X.launches():
-            n_slots = capi.wsync_slots(n, K.N_COH_SEARCH, K.N_COH_LOCK)
-            eng._chk(eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, sync_cfg.ctypes.data, C.c_void_p(d_if + at * 4092), n, C.c_void_p(d_sync), n_ch,
-                                                               C.c_void_p(d_rec)), "gpsx_track_loop_weighted_sync_dev")
+            chain.sync(d_if.ptr.value + at * 4092, n)
             eng.synchronize()
-            before = sync_st.copy()
-            eng.d2h(before, d_sync)        # what the sync launch left: the restatement's re-arm starts from it
-            eng._chk(eng.lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_nav), n_ch, C.c_void_p(d_words)),
-                     "gpsx_wnav_words_dev")
-            eng._chk(eng.lib.gpsx_wobs_dev(eng.h, obs_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_words), C.c_void_p(d_obs_st), n_ch,
-                                           C.c_void_p(d_obs)), "gpsx_wobs_dev")
-            eng._chk(eng.lib.gpsx_wlock_dev(eng.h, lock_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_lock_st), C.c_void_p(d_sync), n_ch,
-                                            C.c_void_p(d_lock)), "gpsx_wlock_dev")
+            before = chain.read("sync")        # what the sync launch left: the restatement's re-arm starts from it
+            chain.words()
+            chain.obs()
+            chain.lock(rearm_on_sync=True)
             eng.synchronize()
-            rec, lock, obs = np.zeros((n_slots, n_ch), Y.REC_DTYPE), np.zeros(n_ch, R.LOCK_DTYPE), np.zeros(n_ch, O.OBS_DTYPE)
-            for a, d in ((rec, d_rec), (lock, d_lock), (obs, d_obs), (lock_st, d_lock_st), (sync_st, d_sync)):
-                eng.d2h(a, d)
+            rec, lock, obs, lock_st, sync_st = (chain.read(name) for name in ("rec", "l", "o", "lock", "sync"))
             want, bad = R.run(rec, n, want_st, cfg, before)
             assert not bad
             _same(lock, want, ("records of the launch at", at))
@@ -343,9 +247,6 @@ def test_if_samples_to_lock_flags_on_the_device(eng):
             elif search_after == len(flags) - 1:
                 col = rec[:, X.VANISHING]
                 assert (col["flags"] & Y.F_WINDOW).any() and not (col["flags"] & Y.F_LOCKED).any()      # the launch after the loss ran in SEARCH
-    finally:
-        for p in ptrs:
-            eng.free(p)
     flags = np.array(flags)
     both = R.F_CODE | R.F_CARRIER
     for ch in X.HEALTHY:

@@ -7,28 +7,18 @@ weights, spacings 1 / 8 / 15, a non-default IF, a few hundred blocks; with gains
 gpsx_track_epl_weighted_dev on every channel (GPU against GPU); split launches against one; the device against the host variant;
 the exact handover from a coherent grid's record; bad channels and refusals, with canaries; the pull-in scenario, truncated; and
 the branches of the update that the state alone can force (tests/weighted_forced_cases.py wloop_table)."""
-import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
 import weighted_forced_cases as W
+import weighted_gpu as G
 import weighted_loop_cases as S
 import weighted_loop_ref as L
+from weighted_gpu import EINVAL, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-EINVAL = -22
-GUARD = 4096
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
 
 
 def _blocks(n, amp=0.3, seed=3):
@@ -66,50 +56,29 @@ def _cfg(c):
     return capi.wloop_cfg(c["n_coh"], c["use_magnitude"], c["spacing"], (c["dll_c1"], c["dll_c2"]), (c["pll_c1"], c["pll_c2"]), c["fll_c"])
 
 
+def _stage(eng, blocks, st, cfg, dev=False, pieces=None):
+    """the library on a copy of `st` in device memory -> (records, states after, [return codes]); dev: blocks and records in device memory too"""
+    n_ch, c = len(st), _cfg(cfg)
+    fn = eng.lib.gpsx_track_loop_weighted_dev if dev else eng.lib.gpsx_track_loop_weighted
+    launches, _ = G.block_launches(blocks, pieces, L.REC_DTYPE, lambda k: (k // cfg["n_coh"], n_ch))
+
+    def call(ins, sts, out, k):
+        return fn(eng.h, c.ctypes.data, ins[0], len(launches[k][0][0]), sts[0], n_ch, out)
+    recs, after, codes = G.run_stage(eng, call, b"k_track_wloop", st, launches, dev, host_inputs=True)
+    return np.concatenate(recs), after, codes
+
+
 def _gpu(eng, blocks, st, cfg, dev=False, pieces=None):
-    """the library on a copy of `st` in device memory -> (records, states after); dev: blocks and records in device memory too"""
-    blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 4092)
-    n_ch, n_coh = len(st), cfg["n_coh"]
-    after = st.copy()
-    d_st = eng.malloc(st.nbytes)
-    recs = []
-    try:
-        eng.h2d(d_st, st)
-        at = 0
-        for k in pieces or [len(blocks)]:
-            part = blocks[at:at + k]
-            at += k
-            if not dev:
-                recs.append(eng.track_loop_weighted(part, d_st, n_ch, n_coh, cfg["use_magnitude"], cfg["spacing"], (cfg["dll_c1"], cfg["dll_c2"]),
-                                                    (cfg["pll_c1"], cfg["pll_c2"]), cfg["fll_c"]))
-                assert eng.lib.gpsx_last_kernel(eng.h) == b"k_track_wloop"
-                continue
-            rec = np.zeros((k // n_coh, n_ch), L.REC_DTYPE)
-            d_if, d_rec = eng.malloc(part.nbytes), eng.malloc(rec.nbytes)
-            try:
-                eng.h2d(d_if, part)
-                c = _cfg(cfg)
-                eng._chk(eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st), n_ch,
-                                                              C.c_void_p(d_rec)), "gpsx_track_loop_weighted_dev")
-                eng.synchronize()
-                eng.d2h(rec, d_rec)
-            finally:
-                eng.free(d_if)
-                eng.free(d_rec)
-            recs.append(rec)
-        eng.d2h(after, d_st)
-    finally:
-        eng.free(d_st)
-    return np.concatenate(recs), after
+    """_stage where no channel is bad -> (records, states after)"""
+    rec, after, codes = _stage(eng, blocks, st, cfg, dev, pieces)
+    assert not any(codes), (codes, eng.lib.gpsx_last_error(eng.h))
+    return rec, after
 
 
 def _same(rec, after, want_rec, want_st, channels, what):
-    ch = list(channels)
-    assert rec.dtype == L.REC_DTYPE and rec.shape == want_rec.shape, what
-    bad = [c for c in ch if rec[:, c].tobytes() != want_rec[:, c].tobytes()]
-    assert not bad, (what, "records", bad[:4], rec[:, bad[0]][:2], want_rec[:, bad[0]][:2])
-    bad = [c for c in ch if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    assert rec.dtype == L.REC_DTYPE, what
+    G.same_columns(rec, want_rec, (what, "records"), list(channels))
+    G.same_rows(after, want_st, (what, "states"), list(channels))
 
 
 MOVING = dict(dll=(1.0, 100.0), pll=(56.0, 1600.0), fll=0.1)
@@ -148,38 +117,16 @@ def test_every_channels_per_wave_value(eng, oracle, n_ch):
     sample = sorted({0, 1, cpw - 1, cpw, 4 * cpw - 1, 4 * cpw, n_ch - 1, n_ch - last, max(0, n_ch - last - 1)} | {int(c) for c in rng.integers(0, n_ch, 15)})
     for gains in (MOVING, dict(dll=(0.0, 0.0), pll=(0.0, 0.0), fll=0.0)):
         cfg = L.make_cfg(n_coh, use_mag, spacing, gains["dll"], gains["pll"], gains["fll"])
-        rec_bytes = (k // n_coh) * n_ch * 36
-        h_rec = np.full(GUARD + rec_bytes + GUARD, 0xA5, np.uint8)
-        h_st = np.full(GUARD + st.nbytes + GUARD, 0xA5, np.uint8)
-        h_st[GUARD:GUARD + st.nbytes] = st.view(np.uint8)
+        rec, after = _gpu(eng, blocks, st, cfg, dev=True)
         trk = np.zeros(n_ch, capi.TRK_DTYPE)
         for f in trk.dtype.names:
             trk[f] = st[f]
-        iq = np.zeros((k, n_ch, 6), np.int32)
-        d_if, d_rec, d_st, d_trk, d_iq = (eng.malloc(x.nbytes) for x in (blocks, h_rec, h_st, trk, iq))
-        try:
-            eng.h2d(d_if, blocks)
-            eng.h2d(d_rec, h_rec)
-            eng.h2d(d_st, h_st)
-            eng.h2d(d_trk, trk)
-            c = _cfg(cfg)
-            eng._chk(eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st + GUARD), n_ch,
-                                                          C.c_void_p(d_rec + GUARD)), "gpsx_track_loop_weighted_dev")
-            ocfg = np.array([1 if use_mag else 0, spacing], np.int32)
-            eng._chk(eng.lib.gpsx_track_epl_weighted_dev(eng.h, ocfg.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_trk), n_ch,
-                                                         C.c_void_p(d_iq)), "gpsx_track_epl_weighted_dev")
+        ocfg = np.array([1 if use_mag else 0, spacing], np.int32)
+        with G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks) as d_if, G.Guarded(eng, trk.nbytes, G.STATE_FILL, trk) as d_trk, \
+                G.Guarded(eng, k * n_ch * 6 * 4) as d_iq:
+            eng._chk(eng.lib.gpsx_track_epl_weighted_dev(eng.h, ocfg.ctypes.data, d_if.ptr, k, d_trk.ptr, n_ch, d_iq.ptr), "gpsx_track_epl_weighted_dev")
             eng.synchronize()
-            eng.d2h(h_rec, d_rec)
-            eng.d2h(h_st, d_st)
-            eng.d2h(iq, d_iq)
-            eng.d2h(trk, d_trk)
-        finally:
-            for p in (d_if, d_rec, d_st, d_trk, d_iq):
-                eng.free(p)
-        for h, size in ((h_rec, rec_bytes), (h_st, st.nbytes)):
-            assert (h[:GUARD] == 0xA5).all() and (h[GUARD + size:] == 0xA5).all(), (n_ch, "canary")
-        rec = h_rec[GUARD:GUARD + rec_bytes].view(L.REC_DTYPE).reshape(k // n_coh, n_ch)
-        after = h_st[GUARD:GUARD + st.nbytes].view(L.STATE_DTYPE)
+            iq, trk = d_iq.get(np.int32, (k, n_ch, 6)), d_trk.get(trk.dtype, trk.shape)
         want_st = st.copy()
         want = L.run(oracle, blocks, want_st, cfg, channels=sample)
         _same(rec, after, want, want_st, sample, (n_ch, cpw, gains is MOVING))
@@ -259,32 +206,19 @@ def test_argument_checks_write_nothing(eng):
         b"a loop gain is not finite": [dict(cfg=dict(n_coh=4, dll=(nan, 1.0))), dict(cfg=dict(n_coh=4, dll=(1.0, inf))), dict(cfg=dict(n_coh=4, pll=(-inf, 1.0))),
                                        dict(cfg=dict(n_coh=4, pll=(1.0, nan))), dict(cfg=dict(n_coh=4, fll=inf))],
     }
-    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
-    d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(2 * 4 * 36)
-    try:
-        eng.h2d(d_if, blocks)
-        for dev, fn in ((False, eng.lib.gpsx_track_loop_weighted), (True, eng.lib.gpsx_track_loop_weighted_dev)):
-            for message, change in refusals:
-                a = {**good, **change}
-                c = a["cfg"]
-                cfg = capi.wloop_cfg(c["n_coh"], True, c.get("spacing", 8), c.get("dll", (1.0, 100.0)), c.get("pll", (56.0, 1600.0)), c.get("fll", 0.1))
-                if "weights" in c:
-                    cfg["weights"] = c["weights"]
-                rec = np.full((2, 4), 0xA5, np.uint8).repeat(36, axis=1).view(np.uint8)
-                eng.h2d(d_st, st0)
-                eng.h2d(d_rec, rec)
-                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (C.c_void_p(d_if) if dev else blocks.ctypes.data),
-                        a["n_blocks"], None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
-                        None if a["null_out"] else (C.c_void_p(d_rec) if dev else rec.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                eng.synchronize()   # nothing was enqueued, nothing is pending
-                st, dr = st0.copy(), np.zeros_like(rec)
-                eng.d2h(st, d_st)
-                eng.d2h(dr, d_rec)
-                assert (rec == 0xA5).all() and (dr == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
-    finally:
-        for p in (d_st, d_if, d_rec):
-            eng.free(p)
+    with G.Pool() as pool:
+        d_st, d_if = pool.add(G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0)), pool.add(G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks))
+        outs = {True: pool.add(G.Guarded(eng, 2 * 4 * L.REC_DTYPE.itemsize)), False: pool.add(G.Guarded(None, 2 * 4 * L.REC_DTYPE.itemsize))}
+
+        def call(a, dev):
+            c = a["cfg"]
+            cfg = capi.wloop_cfg(c["n_coh"], True, c.get("spacing", 8), c.get("dll", (1.0, 100.0)), c.get("pll", (56.0, 1600.0)), c.get("fll", 0.1))
+            if "weights" in c:
+                cfg["weights"] = c["weights"]
+            fn = eng.lib.gpsx_track_loop_weighted_dev if dev else eng.lib.gpsx_track_loop_weighted
+            return fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (d_if.ptr if dev else blocks.ctypes.data),
+                      a["n_blocks"], None if a["null_st"] else d_st.ptr, a["n_ch"], None if a["null_out"] else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
 
 
 def test_bad_channels(eng, oracle):
@@ -305,37 +239,13 @@ def test_bad_channels(eng, oracle):
         for f in ("code_phase_fine", "if_freq_offset_hz", "dll_err", "pll_err", "prev_ip", "prev_qp", "n_updates"):
             assert want_st[f][ch:ch + 1].tobytes() == st0[f][ch:ch + 1].tobytes()
         assert want_st["if_freq_accum"][ch] != st0["if_freq_accum"][ch]
-    c = _cfg(cfg)
-    rec_bytes = 3 * 12 * 36
     for dev in (False, True):
-        h_st = np.full(GUARD + st0.nbytes + GUARD, 0xA5, np.uint8)
-        h_st[GUARD:GUARD + st0.nbytes] = st0.view(np.uint8)
-        h_rec = np.full(GUARD + rec_bytes + GUARD, 0x5A, np.uint8)
-        d_st, d_if, d_rec = eng.malloc(h_st.nbytes), eng.malloc(blocks.nbytes), eng.malloc(h_rec.nbytes)
-        try:
-            eng.h2d(d_st, h_st)
-            eng.h2d(d_if, blocks)
-            eng.h2d(d_rec, h_rec)
-            eng.synchronize()
-            if dev:
-                rc = eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), 12, C.c_void_p(d_st + GUARD), 12,
-                                                          C.c_void_p(d_rec + GUARD))
-                assert rc == 0
-                assert eng.lib.gpsx_synchronize(eng.h) == EINVAL
-                assert eng.lib.gpsx_synchronize(eng.h) == 0
-                eng.d2h(h_rec, d_rec)
-            else:
-                rc = eng.lib.gpsx_track_loop_weighted(eng.h, c.ctypes.data, blocks.ctypes.data, 12, C.c_void_p(d_st + GUARD), 12,
-                                                      h_rec[GUARD:].ctypes.data)
-                assert rc == EINVAL and b"prn" in eng.lib.gpsx_last_error(eng.h)
-            eng.d2h(h_st, d_st)
-        finally:
-            for p in (d_st, d_if, d_rec):
-                eng.free(p)
-        for h, size, v in ((h_rec, rec_bytes, 0x5A), (h_st, st0.nbytes, 0xA5)):
-            assert (h[:GUARD] == v).all() and (h[GUARD + size:] == v).all(), dev
-        rec = h_rec[GUARD:GUARD + rec_bytes].view(L.REC_DTYPE).reshape(3, 12)
-        after = h_st[GUARD:GUARD + st0.nbytes].view(L.STATE_DTYPE)
+        rec, after, codes = _stage(eng, blocks, st0, cfg, dev)
+        assert codes == [EINVAL], dev
+        if dev:
+            assert eng.lib.gpsx_synchronize(eng.h) == 0
+        else:
+            assert b"prn" in eng.lib.gpsx_last_error(eng.h)
         _same(rec, after, want, want_st, range(12), ("device" if dev else "host"))
     rec, after = _gpu(eng, blocks, st0[good].copy(), cfg)      # the same channels without the bad ones: no error
     assert rec.tobytes() == np.ascontiguousarray(want[:, good]).tobytes() and after.tobytes() == want_st[good].tobytes()
@@ -350,14 +260,10 @@ def test_the_pull_in_scenario_truncated(eng, oracle):
     st = np.concatenate([S.handover_state(seed) for seed in S.SEEDS])
     want_st = st.copy()
     want = [L.run(oracle, blocks[:S.PULL_IN_MS], want_st, L.make_cfg(**S.PULL_IN)), L.run(oracle, blocks[S.PULL_IN_MS:], want_st, L.make_cfg(**S.STEADY))]
-    d_st = eng.malloc(st.nbytes)
-    try:
-        eng.h2d(d_st, st)
-        got = [eng.track_loop_weighted(blocks[:S.PULL_IN_MS], d_st, 3, **S.PULL_IN), eng.track_loop_weighted(blocks[S.PULL_IN_MS:], d_st, 3, **S.STEADY)]
-        after = st.copy()
-        eng.d2h(after, d_st)
-    finally:
-        eng.free(d_st)
+    with G.Guarded(eng, st.nbytes, G.STATE_FILL, st) as d_st:
+        got = [eng.track_loop_weighted(blocks[:S.PULL_IN_MS], d_st.ptr.value, 3, **S.PULL_IN),
+               eng.track_loop_weighted(blocks[S.PULL_IN_MS:], d_st.ptr.value, 3, **S.STEADY)]
+        after = d_st.get(st.dtype, st.shape)
     for g, w in zip(got, want):
         assert g.tobytes() == w.tobytes()
     assert after.tobytes() == want_st.tobytes()

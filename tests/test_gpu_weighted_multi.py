@@ -12,135 +12,68 @@ import numpy as np
 import pytest
 
 import weighted_aided_ref as A
+import weighted_gpu as G
 import weighted_lock_cases as X
 import weighted_lock_ref as R
 import weighted_multi_cases as M
 import weighted_nav_ref as N
 import weighted_sync_cases as K
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
+from weighted_gpu import sync_cfg as _cfg
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -22
-GUARD = 4096
 L1CA = float(A.WAID_L1CA)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
-
-def _cfg(c):
-    from stm32f4_sdr_gps_amd import capi
-    gains = {name: dict(dll=(c[name]["dll_c1"], c[name]["dll_c2"]), pll=(c[name]["pll_c1"], c[name]["pll_c2"]), fll=c[name]["fll_c"]) for name in ("search", "lock")}
-    return capi.wsync_cfg(c["n_coh_search"], c["n_coh_lock"], gains["search"], gains["lock"], c["sync_bits"], (c["sync_num"], c["sync_den"]),
-                          c["use_magnitude"], c["spacing"])
-
-
-def _run(eng, call, st, n_ch, cfg, launches, dev, codes=None):
-    """`call(d_if_or_host_pointer_offset, n_blocks, state pointer, record pointer)` launch after launch on a copy of `st` in device
-    memory, guards around states and records (the records prefilled) -> ([(first block, records)], states after).  launches:
-    [(first block, n_blocks, host array or device address of the launch's first byte)]; codes: a list that gets what every call and
-    the synchronize behind it returned, instead of an assertion that both are 0"""
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0xA5, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = np.ascontiguousarray(st).view(np.uint8)
-    d_st = eng.malloc(h_st.nbytes)
-    recs = []
-    try:
-        eng.h2d(d_st, h_st)
-        for at, k, where in launches:
-            shape = (Y.slots(k, cfg), n_ch)
-            size = shape[0] * n_ch * Y.REC_DTYPE.itemsize
-            h_rec = np.full(GUARD + size + GUARD, 0x5A, np.uint8)
-            if dev:
-                d_rec = eng.malloc(h_rec.nbytes)
-                try:
-                    eng.h2d(d_rec, h_rec)
-                    rc = call(C.c_void_p(where), k, C.c_void_p(d_st + GUARD), C.c_void_p(d_rec + GUARD))
-                    sync = eng.lib.gpsx_synchronize(eng.h)
-                    eng.d2h(h_rec, d_rec)
-                finally:
-                    eng.free(d_rec)
-            else:
-                rc, sync = call(where, k, C.c_void_p(d_st + GUARD), h_rec[GUARD:].ctypes.data), 0
-            if codes is None:
-                assert (rc, sync) == (0, 0), (rc, sync, eng.lib.gpsx_last_error(eng.h))
-            else:
-                codes.append((rc, sync))
-            assert (h_rec[:GUARD] == 0x5A).all() and (h_rec[GUARD + size:] == 0x5A).all(), "guards around the records"
-            recs.append((at, h_rec[GUARD:GUARD + size].view(Y.REC_DTYPE).reshape(shape).copy()))
-        eng.d2h(h_st, d_st)
-    finally:
-        eng.free(d_st)
-    assert (h_st[:GUARD] == 0xA5).all() and (h_st[GUARD + st.nbytes:] == 0xA5).all(), "guards around the states"
-    return recs, h_st[GUARD:GUARD + st.nbytes].view(Y.STATE_DTYPE).copy()
-
-
 def _multi(eng, streams, st, ch_per_rx, cfg, aid, dev, pieces=None, n_blocks=M.N_BLOCKS, codes=None):
-    """gpsx_track_loop_weighted_sync_multi(_dev) on streams [n_rx][stride][4092] (receiver r's blocks are streams[r, :n_blocks]).
-    aid: None (a NULL pointer) or the factor; pieces: launch lengths, each launch starting from the pointer advanced by its
-    predecessors' blocks with the stride unchanged"""
+    """gpsx_track_loop_weighted_sync_multi(_dev) on streams [n_rx][stride][4092] (receiver r's blocks are streams[r, :n_blocks]), launch
+    after launch on a copy of `st` in device memory -> ([(first block, records)], states after).  aid: None (a NULL pointer) or the
+    factor; pieces: launch lengths, each launch starting from the pointer advanced by its predecessors' blocks with the stride
+    unchanged; codes: a list that gets every launch's return code (the synchronize's behind the _dev call), instead of an assertion
+    that all are 0"""
     from stm32f4_sdr_gps_amd import capi
     streams = np.ascontiguousarray(streams, np.uint8)
     n_rx, stride = streams.shape[:2]
-    rx, c = capi.wmulti(n_rx, ch_per_rx, stride), _cfg(cfg)
+    n_ch, rx, c = n_rx * ch_per_rx, capi.wmulti(n_rx, ch_per_rx, stride), _cfg(cfg)
     a = None if aid is None else capi.waid(aid)
     fn = eng.lib.gpsx_track_loop_weighted_sync_multi_dev if dev else eng.lib.gpsx_track_loop_weighted_sync_multi
-    d_if = eng.malloc(streams.nbytes) if dev else 0
-    try:
-        if dev:
-            eng.h2d(d_if, streams)
-        base = d_if if dev else streams.ctypes.data
-        launches, at = [], 0
-        for k in pieces or [n_blocks]:
-            launches.append((at, k, base + at * 4092))
-            at += k
-        assert at == n_blocks <= stride
+    cuts = pieces or [n_blocks]
+    firsts = [sum(cuts[:i]) for i in range(len(cuts))]
+    assert sum(cuts) == n_blocks <= stride
+    with G.Guarded(eng if dev else None, streams.nbytes, G.STATE_FILL, streams) as d_if:
 
-        def call(where, k, p_st, p_rec):
-            rc = fn(eng.h, c.ctypes.data, None if a is None else a.ctypes.data, rx.ctypes.data, where, k, p_st, p_rec)
-            if rc == 0 or codes is not None:
-                assert eng.lib.gpsx_last_kernel(eng.h) == b"k_track_wsync_multi"
-            return rc
-        return _run(eng, call, st, n_rx * ch_per_rx, cfg, launches, dev, codes)
-    finally:
-        if dev:
-            eng.free(d_if)
+        def call(ins, sts, out, i):
+            return fn(eng.h, c.ctypes.data, None if a is None else a.ctypes.data, rx.ctypes.data, C.c_void_p(ins[0]), cuts[i], sts[0], out)
+        recs, after, got = G.run_stage(eng, call, b"k_track_wsync_multi", st,
+                                       [([d_if.ptr.value + at * 4092], Y.REC_DTYPE, (Y.slots(k, cfg), n_ch)) for at, k in zip(firsts, cuts)], dev)
+    if codes is None:
+        assert not any(got), (got, eng.lib.gpsx_last_error(eng.h))
+    else:
+        codes.extend(got)
+    return list(zip(firsts, recs)), after
 
 
 def _single(eng, blocks, st, cfg, aid):
     """gpsx_track_loop_weighted_sync_dev (aid None) or gpsx_track_loop_weighted_sync_aided_dev on one stream"""
     from stm32f4_sdr_gps_amd import capi
     blocks = np.ascontiguousarray(blocks, np.uint8)
-    c = _cfg(cfg)
-    a = None if aid is None else capi.waid(aid)
-    d_if = eng.malloc(blocks.nbytes)
-    try:
-        eng.h2d(d_if, blocks)
+    c, a = _cfg(cfg), None if aid is None else capi.waid(aid)
 
-        def call(where, k, p_st, p_rec):
-            if a is None:
-                return eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, c.ctypes.data, where, k, p_st, len(st), p_rec)
-            return eng.lib.gpsx_track_loop_weighted_sync_aided_dev(eng.h, c.ctypes.data, a.ctypes.data, where, k, p_st, len(st), p_rec)
-        recs, after = _run(eng, call, st, len(st), cfg, [(0, len(blocks), d_if)], True)
-        return recs[0][1], after
-    finally:
-        eng.free(d_if)
+    def call(ins, sts, out, k):
+        if a is None:
+            return eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, c.ctypes.data, ins[0], len(blocks), sts[0], len(st), out)
+        return eng.lib.gpsx_track_loop_weighted_sync_aided_dev(eng.h, c.ctypes.data, a.ctypes.data, ins[0], len(blocks), sts[0], len(st), out)
+    recs, after, codes = G.run_stage(eng, call, b"k_track_waid_sync" if a is not None else b"k_track_wsync", st,
+                                     [([blocks], Y.REC_DTYPE, (Y.slots(len(blocks), cfg), len(st)))])
+    assert codes == [0]
+    return recs[0], after
 
 
 def _same(rec, after, want_rec, want_st, what):
-    assert rec.dtype == want_rec.dtype and rec.shape == want_rec.shape, what
-    if rec.tobytes() != np.ascontiguousarray(want_rec).tobytes():
-        bad = [c for c in range(rec.shape[1]) if rec[:, c].tobytes() != want_rec[:, c].tobytes()]
-        slot = [u for u in range(rec.shape[0]) if rec[u, bad[0]].tobytes() != want_rec[u, bad[0]].tobytes()][0]
-        assert not bad, (what, "records", bad[:4], slot, rec[slot, bad[0]], want_rec[slot, bad[0]])
-    if after.tobytes() != want_st.tobytes():
-        bad = [c for c in range(len(after)) if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-        assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    G.same_columns(rec, want_rec, (what, "records"))
+    G.same_rows(after, want_st, (what, "states"))
 
 
 SHAPE_IDS = [f"{s[0]}x{s[1]}" for s in M.SHAPES]
@@ -246,7 +179,7 @@ def test_a_bad_channel_in_one_receiver_changes_nothing_elsewhere(eng, oracle, wh
     for dev in (True, False):
         codes = []
         recs, after = _multi(eng, streams, st0, ch, cfg, L1CA, dev, codes=codes)
-        assert codes == [(0, EINVAL) if dev else (EINVAL, 0)], (what, dev, codes)
+        assert codes == [EINVAL], (what, dev, codes)      # (the _dev call itself returned 0: the driver asserts it)
         if not dev:
             assert b"prn" in eng.lib.gpsx_last_error(eng.h)
         assert eng.lib.gpsx_synchronize(eng.h) == 0
@@ -273,64 +206,43 @@ def test_argument_checks_write_nothing(eng):
         b"a loop gain is not finite": [dict(gain=nan), dict(gain=float("inf"), aid=(nan, 0))],
         b"code_per_hz must be finite and -1..1": [dict(aid=(nan, 0)), dict(aid=(1.5, 1))],
     }
-    n_slots = Y.slots(n, Y.make_cfg(4, 20, K.S.PULL_IN, K.S.STEADY, 20, (5, 4)))
-    n_rec = n_slots * n_rx * ch * 48
-    d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(streams.nbytes), eng.malloc(n_rec)
-    try:
-        eng.h2d(d_if, streams)
-        for dev in (False, True):
-            fn = eng.lib.gpsx_track_loop_weighted_sync_multi_dev if dev else eng.lib.gpsx_track_loop_weighted_sync_multi
-            for message, changes in by_message.items():
-                for change in changes:
-                    a = {**good, **change}
-                    cfg = _cfg(Y.make_cfg(4, 20, K.S.PULL_IN, K.S.STEADY, 20, (5, 4)))
-                    cfg["spacing"], cfg["sync_bits"] = a["spacing"], a["sync_bits"]
-                    cfg["lock"]["pll_c2"] = cfg["lock"]["pll_c2"] * np.float32(a["gain"])
-                    aid = capi.waid(a["aid"][0])
-                    aid["reserved"] = a["aid"][1]
-                    rx = capi.wmulti(*a["rx"][:3])
-                    rx["reserved"] = a["rx"][3]
-                    rec = np.full(n_rec, 0xA5, np.uint8)
-                    eng.h2d(d_st, st0)
-                    eng.h2d(d_rec, rec)
-                    null = a["null"]
-                    rc = fn(eng.h, None if null == "cfg" else cfg.ctypes.data, aid.ctypes.data, None if null == "rx" else rx.ctypes.data,
-                            None if null == "blocks" else (C.c_void_p(d_if) if dev else streams.ctypes.data), a["n_blocks"],
-                            None if null == "state" else C.c_void_p(d_st), None if null == "rec" else (C.c_void_p(d_rec) if dev else rec.ctypes.data))
-                    assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                    eng.synchronize()   # nothing was enqueued, nothing is pending
-                    st, dr = st0.copy(), np.zeros_like(rec)
-                    eng.d2h(st, d_st)
-                    eng.d2h(dr, d_rec)
-                    assert (rec == 0xA5).all() and (dr == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
-            # the limits themselves are accepted: a stride of exactly n_blocks, aid NULL (64 slots: the shapes above)
+    n_rec = Y.slots(n, Y.make_cfg(4, 20, K.S.PULL_IN, K.S.STEADY, 20, (5, 4))) * n_rx * ch * Y.REC_DTYPE.itemsize
+    with G.Pool() as pool:
+        d_st, d_if = pool.add(G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0)), pool.add(G.Guarded(eng, streams.nbytes, G.STATE_FILL, streams))
+        outs = {True: pool.add(G.Guarded(eng, n_rec)), False: pool.add(G.Guarded(None, n_rec))}
+        fns = {True: eng.lib.gpsx_track_loop_weighted_sync_multi_dev, False: eng.lib.gpsx_track_loop_weighted_sync_multi}
+
+        def call(a, dev):
             cfg = _cfg(Y.make_cfg(4, 20, K.S.PULL_IN, K.S.STEADY, 20, (5, 4)))
-            rx = capi.wmulti(n_rx, ch, n)
-            packed = np.ascontiguousarray(streams[:, :n])
-            eng.h2d(d_if, packed)
-            eng.h2d(d_st, st0)
-            rec = np.zeros(n_rec, np.uint8)
-            eng._chk(fn(eng.h, cfg.ctypes.data, None, rx.ctypes.data, C.c_void_p(d_if) if dev else packed.ctypes.data, n, C.c_void_p(d_st),
-                        C.c_void_p(d_rec) if dev else rec.ctypes.data), "gpsx_track_loop_weighted_sync_multi")
+            cfg["spacing"], cfg["sync_bits"] = a["spacing"], a["sync_bits"]
+            cfg["lock"]["pll_c2"] = cfg["lock"]["pll_c2"] * np.float32(a["gain"])
+            aid = capi.waid(a["aid"][0])
+            aid["reserved"] = a["aid"][1]
+            rx = capi.wmulti(*a["rx"][:3])
+            rx["reserved"] = a["rx"][3]
+            null = a["null"]
+            return fns[dev](eng.h, None if null == "cfg" else cfg.ctypes.data, aid.ctypes.data, None if null == "rx" else rx.ctypes.data,
+                            None if null == "blocks" else (d_if.ptr if dev else streams.ctypes.data), a["n_blocks"],
+                            None if null == "state" else d_st.ptr, None if null == "rec" else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
+        # the limits themselves are accepted: a stride of exactly n_blocks, aid NULL (64 slots: the shapes above)
+        cfg, rx = _cfg(Y.make_cfg(4, 20, K.S.PULL_IN, K.S.STEADY, 20, (5, 4))), capi.wmulti(n_rx, ch, n)
+        packed = np.ascontiguousarray(streams[:, :n])
+        d_if.put(packed)
+        for dev in (False, True):
+            d_st.refill()
+            eng._chk(fns[dev](eng.h, cfg.ctypes.data, None, rx.ctypes.data, d_if.ptr if dev else packed.ctypes.data, n, d_st.ptr, outs[dev].ptr),
+                     "gpsx_track_loop_weighted_sync_multi")
             eng.synchronize()
-            eng.h2d(d_if, streams)
-    finally:
-        for p in (d_st, d_if, d_rec):
-            eng.free(p)
 
 
 def test_the_engine_convenience(eng):
     n_rx, ch = M.SHAPES[0][:2]
     blocks, st0, cfg = M.shape_inputs(0)
     want_rec, want_st, _ = M.shapes_on_restatement()[(0, L1CA)]
-    d_st = eng.malloc(st0.nbytes)
-    try:
-        eng.h2d(d_st, st0)
-        rec = eng.track_loop_weighted_sync_multi(np.stack(blocks), d_st, ch, _cfg(cfg), L1CA)
-        after = st0.copy()
-        eng.d2h(after, d_st)
-    finally:
-        eng.free(d_st)
+    with G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0) as d_st:
+        rec = eng.track_loop_weighted_sync_multi(np.stack(blocks), d_st.ptr.value, ch, _cfg(cfg), L1CA)
+        after = d_st.get(st0.dtype, st0.shape)
     _same(rec, after, want_rec, want_st, "Engine.track_loop_weighted_sync_multi")
 
 
@@ -347,35 +259,19 @@ def test_two_receivers_from_if_samples_to_words_and_lock_flags(eng):
     both = [M.chain_blocks(r) for r in range(2)]
     stride = M.CHAIN_MS + M.EXTRA
     streams = M.streams_of([b for b, _ in both], stride)
-    sync_cfg, rx = _cfg(K.sync_cfg()), capi.wmulti(2, M.CHAIN_CH, stride)
-    nav_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
-    nav_cfg["max_bad_words"] = 3
     cfg = X.scenario_cfg(0)
-    lock_cfg = R.cfg_array(cfg)
-    sync_st = M.chain_states()
-    nav, lock_st = np.zeros(n_ch, N.STATE_DTYPE), np.zeros(n_ch, R.STATE_DTYPE)
-    want_nav, want_lock_st = nav.copy(), lock_st.copy()
-    max_slots = capi.wsync_slots(M.CHAIN_LAUNCH, K.N_COH_SEARCH, K.N_COH_LOCK)
-    sizes = (streams.nbytes, sync_st.nbytes, nav.nbytes, lock_st.nbytes, max_slots * n_ch * 48, N.max_words(M.CHAIN_LAUNCH) * n_ch * 16, n_ch * 64)
-    ptrs = [eng.malloc(s) for s in sizes]
-    d_if, d_sync, d_nav, d_lock_st, d_rec, d_words, d_lock = ptrs
+    states = dict(sync=M.chain_states(), nav=np.zeros(n_ch, N.STATE_DTYPE), lock=np.zeros(n_ch, R.STATE_DTYPE))
+    want_nav, want_lock_st = states["nav"].copy(), states["lock"].copy()
     recs, flags = [], []
-    try:
-        for d, a in ((d_if, streams), (d_sync, sync_st), (d_nav, nav), (d_lock_st, lock_st)):
-            eng.h2d(d, a)
+    with G.Guarded(eng, streams.nbytes, G.STATE_FILL, streams) as d_if, \
+            G.Chain(eng, _cfg(K.sync_cfg()), states, M.CHAIN_LAUNCH, lock_cfg=R.cfg_array(cfg), rx=capi.wmulti(2, M.CHAIN_CH, stride)) as chain:
         at = 0
         for i, n in enumerate(M.chain_launches()):
-            n_slots = capi.wsync_slots(n, K.N_COH_SEARCH, K.N_COH_LOCK)
-            eng._chk(eng.lib.gpsx_track_loop_weighted_sync_multi_dev(eng.h, sync_cfg.ctypes.data, None, rx.ctypes.data, C.c_void_p(d_if + at * 4092), n,
-                                                                     C.c_void_p(d_sync), C.c_void_p(d_rec)), "gpsx_track_loop_weighted_sync_multi_dev")
-            eng._chk(eng.lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_nav), n_ch, C.c_void_p(d_words)),
-                     "gpsx_wnav_words_dev")
-            eng._chk(eng.lib.gpsx_wlock_dev(eng.h, lock_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_lock_st), None, n_ch, C.c_void_p(d_lock)),
-                     "gpsx_wlock_dev")
+            chain.sync(d_if.ptr.value + at * 4092, n)
+            chain.words()
+            chain.lock()
             eng.synchronize()       # (0: the empty slots are not bad channels)
-            rec, words, lock = np.zeros((n_slots, n_ch), Y.REC_DTYPE), np.zeros((N.max_words(n), n_ch), N.WORD_DTYPE), np.zeros(n_ch, R.LOCK_DTYPE)
-            for a, d in ((rec, d_rec), (words, d_words), (lock, d_lock), (nav, d_nav), (lock_st, d_lock_st), (sync_st, d_sync)):
-                eng.d2h(a, d)
+            rec, words, lock, nav, lock_st, sync_st = (chain.read(name) for name in ("rec", "words", "l", "nav", "lock", "sync"))
             assert rec.tobytes() == np.ascontiguousarray(want_recs[i]).tobytes(), ("sync records of the launch at", at)
             w_words, bad = N.run(rec, n, want_nav, 3)
             assert not bad and words.tobytes() == w_words.tobytes() and nav.tobytes() == want_nav.tobytes(), ("words of the launch at", at)
@@ -384,9 +280,6 @@ def test_two_receivers_from_if_samples_to_words_and_lock_flags(eng):
             recs.append((at, rec))
             flags.append(lock["flags"].copy())
             at += n
-    finally:
-        for p in ptrs:
-            eng.free(p)
     assert sync_st.tobytes() == want_sync.tobytes()
     flags = np.array(flags)
     code_car = R.F_CODE | R.F_CARRIER

@@ -4,29 +4,19 @@ tests/test_weighted_nav_reference.py).  Every comparison is for equality, byte f
 states.  The sync loop's records are fabricated (tests/weighted_nav_cases.py: 32 distinct bit streams tiled over the channels, with
 bit errors, a slip, a gap, another edge and noise; initial states from the restatement's run over the stream's earlier blocks);
 only the last test starts from IF samples."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
+import weighted_gpu as G
 import weighted_loop_cases as S
 import weighted_nav_cases as W
 import weighted_nav_ref as N
 import weighted_sync_cases as K
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-EINVAL = -22
-GUARD = 4096
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
 
 
 def _cfg(max_bad_words, reserved=0):
@@ -38,53 +28,21 @@ def _cfg(max_bad_words, reserved=0):
 
 def _gpu(eng, launches, st, max_bad_words, dev=True):
     """the library on a copy of `st` in device memory, launch after launch.  launches: [(records [n_slots][n_ch], n_blocks)].
-    States and word records sit between canaries, the word records are prefilled with 0xA5.
     -> ([word records per launch], states after, [return codes])"""
-    n_ch = len(st)
-    cfg = _cfg(max_bad_words)
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0x5A, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = np.ascontiguousarray(st).view(np.uint8)
-    d_st = eng.malloc(h_st.nbytes)
-    words_out, codes = [], []
-    try:
-        eng.h2d(d_st, h_st)
-        for rec, n_blocks in launches:
-            rec = np.ascontiguousarray(rec)
-            assert rec.dtype == Y.REC_DTYPE and rec.shape[1] == n_ch
-            n_words = N.max_words(n_blocks)
-            size = n_words * n_ch * 16
-            h_words = np.full(GUARD + size + GUARD, 0xA5, np.uint8)
-            d_rec, d_words = eng.malloc(rec.nbytes), eng.malloc(h_words.nbytes)
-            try:
-                eng.h2d(d_rec, rec)
-                if dev:
-                    eng.h2d(d_words, h_words)
-                    rc = eng.lib.gpsx_wnav_words_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_st + GUARD), n_ch,
-                                                     C.c_void_p(d_words + GUARD))
-                    assert rc == 0 and eng.lib.gpsx_last_kernel(eng.h) == b"k_wnav_words"
-                    codes.append(eng.lib.gpsx_synchronize(eng.h))
-                    eng.d2h(h_words, d_words)
-                else:
-                    codes.append(eng.lib.gpsx_wnav_words(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_st + GUARD),
-                                                         n_ch, h_words[GUARD:].ctypes.data))
-            finally:
-                eng.free(d_rec)
-                eng.free(d_words)
-            assert (h_words[:GUARD] == 0xA5).all() and (h_words[GUARD + size:] == 0xA5).all(), "canary around the word records"
-            words_out.append(h_words[GUARD:GUARD + size].view(N.WORD_DTYPE).reshape(n_words, n_ch).copy())
-        eng.d2h(h_st, d_st)
-    finally:
-        eng.free(d_st)
-    assert (h_st[:GUARD] == 0x5A).all() and (h_st[GUARD + st.nbytes:] == 0x5A).all(), "canary around the states"
-    return words_out, h_st[GUARD:GUARD + st.nbytes].view(N.STATE_DTYPE).copy(), codes
+    n_ch, cfg = len(st), _cfg(max_bad_words)
+    fn = eng.lib.gpsx_wnav_words_dev if dev else eng.lib.gpsx_wnav_words
+
+    def call(ins, sts, out, k):
+        return fn(eng.h, cfg.ctypes.data, ins[0], launches[k][0].shape[0], launches[k][1], sts[0], n_ch, out)
+    for rec, _ in launches:
+        assert rec.dtype == Y.REC_DTYPE and rec.shape[1] == n_ch
+    return G.run_stage(eng, call, b"k_wnav_words", st,
+                       [([np.ascontiguousarray(rec)], N.WORD_DTYPE, (N.max_words(n), n_ch)) for rec, n in launches], dev)
 
 
 def _same(words, after, want_words, want_st, what):
-    assert words.shape == want_words.shape, what
-    bad = [c for c in range(words.shape[1]) if words[:, c].tobytes() != want_words[:, c].tobytes()]
-    assert not bad, (what, "words", bad[:4], words[:, bad[0]], want_words[:, bad[0]])
-    bad = [c for c in range(len(after)) if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    G.same_columns(words, want_words, (what, "words"))
+    G.same_rows(after, want_st, (what, "states"))
 
 
 @pytest.mark.parametrize("i", range(len(W.CASES)))
@@ -182,29 +140,17 @@ def test_argument_checks_write_nothing(eng):
         b"n_slots must be 1..n_blocks": [dict(n_slots=0), dict(n_slots=-1), dict(n_slots=41), dict(n_blocks=1, n_slots=2), dict(n_slots=0, n_ch=0)],
         b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3)],
     }
-    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
-    n_words = N.max_words(n_blocks) * n_ch * 16
-    d_rec, d_st, d_words = eng.malloc(rec.nbytes), eng.malloc(st0.nbytes), eng.malloc(n_words)
-    try:
-        eng.h2d(d_rec, rec)
-        for dev, fn in ((False, eng.lib.gpsx_wnav_words), (True, eng.lib.gpsx_wnav_words_dev)):
-            for message, change in refusals:
-                a = {**good, **change}
-                cfg = _cfg(a["max_bad"], a["reserved"])
-                host = np.full(n_words, 0xA5, np.uint8)
-                eng.h2d(d_st, st0)
-                eng.h2d(d_words, host)
-                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else C.c_void_p(d_rec), a["n_slots"], a["n_blocks"],
-                        None if a["null_st"] else C.c_void_p(d_st), a["n_ch"], None if a["null_out"] else (C.c_void_p(d_words) if dev else host.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                eng.synchronize()      # nothing was enqueued, nothing is pending
-                st, dw = st0.copy(), np.zeros_like(host)
-                eng.d2h(st, d_st)
-                eng.d2h(dw, d_words)
-                assert (host == 0xA5).all() and (dw == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
-    finally:
-        for p in (d_rec, d_st, d_words):
-            eng.free(p)
+    with G.Pool() as pool:
+        d_rec, d_st = pool.add(G.Guarded(eng, rec.nbytes, G.STATE_FILL, rec)), pool.add(G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0))
+        n_words = N.max_words(n_blocks) * n_ch * N.WORD_DTYPE.itemsize
+        outs = {True: pool.add(G.Guarded(eng, n_words)), False: pool.add(G.Guarded(None, n_words))}
+
+        def call(a, dev):
+            cfg = _cfg(a["max_bad"], a["reserved"])
+            fn = eng.lib.gpsx_wnav_words_dev if dev else eng.lib.gpsx_wnav_words
+            return fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else d_rec.ptr, a["n_slots"], a["n_blocks"],
+                      None if a["null_st"] else d_st.ptr, a["n_ch"], None if a["null_out"] else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
 
 
 def test_records_that_are_no_bits_are_ignored(eng):
@@ -232,33 +178,18 @@ def test_if_samples_to_words_on_the_device(eng):
     from stm32f4_sdr_gps_amd import capi
     blocks, truth = W.e2e_scenario(1)
     sync = capi.wsync_cfg(K.N_COH_SEARCH, K.N_COH_LOCK, S.PULL_IN, S.STEADY, K.SYNC_BITS, K.RATIO)
-    cfg = _cfg(3)
-    st = K.handover_states(1)
-    nav = np.zeros(3, N.STATE_DTYPE)
-    max_slots = capi.wsync_slots(1500, K.N_COH_SEARCH, K.N_COH_LOCK)
-    d_if, d_st, d_nav = eng.malloc(blocks.nbytes), eng.malloc(st.nbytes), eng.malloc(nav.nbytes)
-    d_rec, d_words = eng.malloc(max_slots * 3 * 48), eng.malloc(N.max_words(1500) * 3 * 16)
     word_list, copied, at = [], 0, 0
-    try:
-        eng.h2d(d_if, blocks)
-        eng.h2d(d_st, st)
-        eng.h2d(d_nav, nav)
+    with G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks) as d_if, \
+            G.Chain(eng, sync, dict(sync=K.handover_states(1), nav=np.zeros(3, N.STATE_DTYPE)), 1500) as chain:
         for n in (1000, 1000, 1500):
-            n_slots = capi.wsync_slots(n, K.N_COH_SEARCH, K.N_COH_LOCK)
-            eng._chk(eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, sync.ctypes.data, C.c_void_p(d_if + at * 4092), n, C.c_void_p(d_st), 3,
-                                                               C.c_void_p(d_rec)), "gpsx_track_loop_weighted_sync_dev")
-            eng._chk(eng.lib.gpsx_wnav_words_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_nav), 3, C.c_void_p(d_words)),
-                     "gpsx_wnav_words_dev")
-            words = np.zeros((N.max_words(n), 3), N.WORD_DTYPE)
+            chain.sync(d_if.ptr.value + at * 4092, n)
+            chain.words()
             eng.synchronize()
-            eng.d2h(words, d_words)
+            words = chain.read("words")
             copied += words.nbytes
             word_list.append((at, words))
             at += n
-        eng.d2h(nav, d_nav)
-    finally:
-        for p in (d_if, d_st, d_nav, d_rec, d_words):
-            eng.free(p)
+        nav = chain.read("nav")
     assert copied == 16 * 3 * (3 + 3 + 4)
     words_abs = W.absolute_words(word_list)
     for ch in range(3):

@@ -5,31 +5,19 @@ the word layer's words are fabricated (tests/weighted_obs_cases.py: 32 distinct 
 drift and dither through the seam, sit on either side of mid-block or are no phases at all, SEARCH windows, a gap, another edge, a
 week that ends, a HOW that contradicts; initial states from the restatements' run over the stream's earlier blocks); only the last
 test starts from IF samples."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import weighted_gpu as G
 import weighted_loop_cases as S
 import weighted_nav_ref as N
 import weighted_obs_cases as X
 import weighted_obs_ref as O
 import weighted_sync_cases as K
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-EINVAL = -22
-GUARD = 4096
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
 
 def _cfg(edge_guard, reserved=0):
     cfg = np.zeros(1, O.CFG_DTYPE)
@@ -39,53 +27,21 @@ def _cfg(edge_guard, reserved=0):
 
 def _gpu(eng, launches, st, edge_guard=X.EDGE_GUARD, dev=True):
     """the library on a copy of `st` in device memory, launch after launch.  launches: [(records [n_slots][n_ch], words
-    [n_blocks // 600 + 2][n_ch], n_blocks)].  States and observables sit between canaries, the observables are prefilled with 0xA5.
-    -> ([observables per launch], states after, [return codes])"""
-    n_ch = len(st)
-    cfg = _cfg(edge_guard)
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0x5A, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = np.ascontiguousarray(st).view(np.uint8)
-    d_st = eng.malloc(h_st.nbytes)
-    obs_out, codes = [], []
-    try:
-        eng.h2d(d_st, h_st)
-        for rec, words, n_blocks in launches:
-            rec, words = np.ascontiguousarray(rec), np.ascontiguousarray(words)
-            assert rec.dtype == Y.REC_DTYPE and words.dtype == N.WORD_DTYPE and rec.shape[1] == n_ch and words.shape == (N.max_words(n_blocks), n_ch)
-            size = n_ch * 32
-            h_obs = np.full(GUARD + size + GUARD, 0xA5, np.uint8)
-            d_rec, d_words, d_obs = eng.malloc(rec.nbytes), eng.malloc(words.nbytes), eng.malloc(h_obs.nbytes)
-            try:
-                eng.h2d(d_rec, rec)
-                eng.h2d(d_words, words)
-                if dev:
-                    eng.h2d(d_obs, h_obs)
-                    rc = eng.lib.gpsx_wobs_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_words),
-                                               C.c_void_p(d_st + GUARD), n_ch, C.c_void_p(d_obs + GUARD))
-                    assert rc == 0 and eng.lib.gpsx_last_kernel(eng.h) == b"k_wobs"
-                    codes.append(eng.lib.gpsx_synchronize(eng.h))
-                    eng.d2h(h_obs, d_obs)
-                else:
-                    codes.append(eng.lib.gpsx_wobs(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), rec.shape[0], n_blocks, C.c_void_p(d_words),
-                                                   C.c_void_p(d_st + GUARD), n_ch, h_obs[GUARD:].ctypes.data))
-            finally:
-                for p in (d_rec, d_words, d_obs):
-                    eng.free(p)
-            assert (h_obs[:GUARD] == 0xA5).all() and (h_obs[GUARD + size:] == 0xA5).all(), "canary around the observables"
-            obs_out.append(h_obs[GUARD:GUARD + size].view(O.OBS_DTYPE).copy())
-        eng.d2h(h_st, d_st)
-    finally:
-        eng.free(d_st)
-    assert (h_st[:GUARD] == 0x5A).all() and (h_st[GUARD + st.nbytes:] == 0x5A).all(), "canary around the states"
-    return obs_out, h_st[GUARD:GUARD + st.nbytes].view(O.STATE_DTYPE).copy(), codes
+    [n_blocks // 600 + 2][n_ch], n_blocks)].  -> ([observables per launch], states after, [return codes])"""
+    n_ch, cfg = len(st), _cfg(edge_guard)
+    fn = eng.lib.gpsx_wobs_dev if dev else eng.lib.gpsx_wobs
+
+    def call(ins, sts, out, k):
+        return fn(eng.h, cfg.ctypes.data, ins[0], launches[k][0].shape[0], launches[k][2], ins[1], sts[0], n_ch, out)
+    for rec, words, n_blocks in launches:
+        assert rec.dtype == Y.REC_DTYPE and words.dtype == N.WORD_DTYPE and rec.shape[1] == n_ch and words.shape == (N.max_words(n_blocks), n_ch)
+    return G.run_stage(eng, call, b"k_wobs", st,
+                       [([np.ascontiguousarray(rec), np.ascontiguousarray(words)], O.OBS_DTYPE, (n_ch,)) for rec, words, _ in launches], dev)
 
 
 def _same(obs, after, want_obs, want_st, what):
-    assert obs.shape == want_obs.shape and after.shape == want_st.shape, what
-    bad = [c for c in range(len(obs)) if obs[c:c + 1].tobytes() != want_obs[c:c + 1].tobytes()]
-    assert not bad, (what, "observables", bad[:4], obs[bad[0]], want_obs[bad[0]])
-    bad = [c for c in range(len(after)) if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    G.same_rows(obs, want_obs, (what, "observables"))
+    G.same_rows(after, want_st, (what, "states"))
 
 
 @pytest.mark.parametrize("i", range(len(X.CASES)))
@@ -216,35 +172,20 @@ def test_argument_checks_write_nothing(eng):
         b"n_slots must be 1..n_blocks": [dict(n_slots=0), dict(n_slots=-1), dict(n_slots=41), dict(n_blocks=1, n_slots=2), dict(n_slots=0, n_ch=0)],
         b"n_ch must be at least 1": [dict(n_ch=0), dict(n_ch=-3)],
     }
-    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
-    d_rec, d_words, d_st, d_obs = eng.malloc(rec.nbytes), eng.malloc(words.nbytes), eng.malloc(st0.nbytes), eng.malloc(n_ch * 32)
-    try:
-        eng.h2d(d_rec, rec)
-        eng.h2d(d_words, words)
-        for dev, fn in ((False, eng.lib.gpsx_wobs), (True, eng.lib.gpsx_wobs_dev)):
-            for message, change in refusals:
-                a = {**good, **change}
-                cfg = _cfg(a["guard"], a["reserved"])
-                host = np.full(n_ch * 32, 0xA5, np.uint8)
-                eng.h2d(d_st, st0)
-                eng.h2d(d_obs, host)
-                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else C.c_void_p(d_rec), a["n_slots"], a["n_blocks"],
-                        None if a["null_words"] else C.c_void_p(d_words), None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
-                        None if a["null_out"] else (C.c_void_p(d_obs) if dev else host.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                eng.synchronize()      # nothing was enqueued, nothing is pending
-                st, dw = st0.copy(), np.zeros_like(host)
-                eng.d2h(st, d_st)
-                eng.d2h(dw, d_obs)
-                assert (host == 0xA5).all() and (dw == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
+    with G.Pool() as pool:
+        d_rec, d_words, d_st = (pool.add(G.Guarded(eng, a.nbytes, G.STATE_FILL, a)) for a in (rec, words, st0))
+        outs = {True: pool.add(G.Guarded(eng, n_ch * O.OBS_DTYPE.itemsize)), False: pool.add(G.Guarded(None, n_ch * O.OBS_DTYPE.itemsize))}
+
+        def call(a, dev):
+            cfg = _cfg(a["guard"], a["reserved"])
+            fn = eng.lib.gpsx_wobs_dev if dev else eng.lib.gpsx_wobs
+            return fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_rec"] else d_rec.ptr, a["n_slots"], a["n_blocks"],
+                      None if a["null_words"] else d_words.ptr, None if a["null_st"] else d_st.ptr, a["n_ch"], None if a["null_out"] else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
         # the ends of the guard's range are in range
         for guard in (0.0, 8184.0):
-            assert eng.lib.gpsx_wobs_dev(eng.h, _cfg(guard).ctypes.data, C.c_void_p(d_rec), n_slots, n_blocks, C.c_void_p(d_words), C.c_void_p(d_st), n_ch,
-                                         C.c_void_p(d_obs)) == 0
+            assert eng.lib.gpsx_wobs_dev(eng.h, _cfg(guard).ctypes.data, d_rec.ptr, n_slots, n_blocks, d_words.ptr, d_st.ptr, n_ch, outs[True].ptr) == 0
         eng.synchronize()
-    finally:
-        for p in (d_rec, d_words, d_st, d_obs):
-            eng.free(p)
 
 
 def test_records_and_words_that_do_not_count_are_ignored(eng):
@@ -303,42 +244,20 @@ def test_if_samples_to_observables_on_the_device(eng):
     from stm32f4_sdr_gps_amd import capi
     blocks = X.seam_scenario(1)
     sync = capi.wsync_cfg(K.N_COH_SEARCH, K.N_COH_LOCK, S.PULL_IN, S.STEADY, K.SYNC_BITS, K.RATIO)
-    nav_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE)
-    nav_cfg["max_bad_words"] = 3
-    cfg = _cfg(X.EDGE_GUARD)
-    st = X.seam_handover(1)
-    nav, obs_st = np.zeros(3, N.STATE_DTYPE), np.zeros(3, O.STATE_DTYPE)
-    max_slots = capi.wsync_slots(1500, K.N_COH_SEARCH, K.N_COH_LOCK)
-    d_if, d_st, d_nav, d_obs_st = eng.malloc(blocks.nbytes), eng.malloc(st.nbytes), eng.malloc(nav.nbytes), eng.malloc(obs_st.nbytes)
-    d_rec, d_words, d_obs = eng.malloc(max_slots * 3 * 48), eng.malloc(N.max_words(1500) * 3 * 16), eng.malloc(3 * 32)
-    want_st = obs_st.copy()
+    states = dict(sync=X.seam_handover(1), nav=np.zeros(3, N.STATE_DTYPE), obs=np.zeros(3, O.STATE_DTYPE))
+    want_st = states["obs"].copy()
     at = 0
-    try:
-        eng.h2d(d_if, blocks)
-        eng.h2d(d_st, st)
-        eng.h2d(d_nav, nav)
-        eng.h2d(d_obs_st, obs_st)
+    with G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks) as d_if, G.Chain(eng, sync, states, 1500, edge_guard=X.EDGE_GUARD) as chain:
         for n in X.LAUNCHES:
-            n_slots = capi.wsync_slots(n, K.N_COH_SEARCH, K.N_COH_LOCK)
-            eng._chk(eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, sync.ctypes.data, C.c_void_p(d_if + at * 4092), n, C.c_void_p(d_st), 3,
-                                                               C.c_void_p(d_rec)), "gpsx_track_loop_weighted_sync_dev")
-            eng._chk(eng.lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_nav), 3, C.c_void_p(d_words)),
-                     "gpsx_wnav_words_dev")
-            eng._chk(eng.lib.gpsx_wobs_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_rec), n_slots, n, C.c_void_p(d_words), C.c_void_p(d_obs_st), 3,
-                                           C.c_void_p(d_obs)), "gpsx_wobs_dev")
+            chain.sync(d_if.ptr.value + at * 4092, n)
+            chain.words()
+            chain.obs()
             eng.synchronize()
-            rec, words, obs = np.zeros((n_slots, 3), Y.REC_DTYPE), np.zeros((N.max_words(n), 3), N.WORD_DTYPE), np.zeros(3, O.OBS_DTYPE)
-            eng.d2h(rec, d_rec)
-            eng.d2h(words, d_words)
-            eng.d2h(obs, d_obs)
-            eng.d2h(obs_st, d_obs_st)
+            rec, words, obs, obs_st = (chain.read(name) for name in ("rec", "words", "o", "obs"))
             want, bad = O.run(rec, n, words, want_st, X.EDGE_GUARD)
             assert not bad
             _same(obs, obs_st, want, want_st, ("launch at", at))
             at += n
-    finally:
-        for p in (d_if, d_st, d_nav, d_obs_st, d_rec, d_words, d_obs):
-            eng.free(p)
     assert int(obs_st["n_wraps"][1]) > 10 and not obs_st["n_break"][:2].any() and (obs_st["blocks_seen"] == 3500).all()
     for ch in (0, 1):
         assert int(obs["flags"][ch]) == O.F_VALID | O.F_PHASE | O.F_EDGE | O.F_TOW, ch

@@ -8,29 +8,18 @@ the restatements, tests/weighted_pvt_cases.py BOUNDS) are the ones used here.
 Cost.  The stream (102 MB) is synthesised once (about 25 s of CPU) and goes to the device once; the device work is a few seconds in
 all.  The byte-for-byte partner, the chain on the CPU restatements, is 35 s of Python per channel in worker processes of their own
 (about 35 s with a CPU per channel for the MOVING gains; the still-code gains run only the first and the last launch: 7 s)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import weighted_eph_ref as E
-import weighted_nav_ref as N
-import weighted_obs_ref as O
+import weighted_gpu as G
 import weighted_pvt_cases as P
 import weighted_sync_ref as Y
+from weighted_gpu import eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
 SYNC_FIELDS = [("w", f) for f in Y.REC_DTYPE.fields["w"][0].names] + ["end_block", "flags", "bit_ip"]
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
 
 
 @pytest.fixture(scope="module")
@@ -43,87 +32,42 @@ def d_if(eng):
     eng.free(d)
 
 
-class _Guarded:
-    """`nbytes` of device memory between two canaries of GUARD bytes; the payload starts as `content` or as the fill byte"""
-
-    def __init__(self, eng, nbytes, fill, content=None):
-        self.eng, self.nbytes, self.fill = eng, nbytes, fill
-        self.host = np.full(GUARD + nbytes + GUARD, fill, np.uint8)
-        if content is not None:
-            self.host[GUARD:GUARD + nbytes] = np.ascontiguousarray(content).view(np.uint8).reshape(-1)
-        self.base = eng.malloc(self.host.nbytes)
-        eng.h2d(self.base, self.host)
-        self.ptr = C.c_void_p(self.base + GUARD)
-
-    def refill(self):
-        self.host[:] = self.fill
-        self.eng.h2d(self.base, self.host)
-
-    def get(self, dtype, shape):
-        self.eng.d2h(self.host, self.base)
-        assert (self.host[:GUARD] == self.fill).all() and (self.host[GUARD + self.nbytes:] == self.fill).all(), "a canary was written"
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        assert n <= self.nbytes
-        return self.host[GUARD:GUARD + n].view(dtype).reshape(shape).copy()
-
-    def free(self):
-        self.eng.free(self.base)
-
-
 def _chain(eng, d_if, sync0, lock, cuts, host_last=0, first_block=0, states=None):
     """the five stages over consecutive launches of `cuts` blocks from `first_block`, states in device memory between canaries, every
     output prefilled with 0xA5 between canaries.  The last `host_last` launches run the four stages' host variants (blocks and
     outputs in host memory, one wait per stage).  -> ([(first block, n, records, words, observables, ephemeris records)], states)"""
-    from stm32f4_sdr_gps_amd import capi
     lib, n_ch = eng.lib, len(sync0)
-    sync = P.sync_cfg_dev(lock)
-    nav_cfg, obs_cfg, eph_cfg = np.zeros(1, capi.WNAV_CFG_DTYPE), np.zeros(1, O.CFG_DTYPE), np.zeros(1, E.CFG_DTYPE)
-    nav_cfg["max_bad_words"], obs_cfg["edge_guard"] = P.MAX_BAD_WORDS, P.EDGE_GUARD
     st0 = dict(P.fresh_states(), sync=sync0) if states is None else states
-    big = max(cuts)
-    max_slots = capi.wsync_slots(big, P.K.N_COH_SEARCH, P.K.N_COH_LOCK)
-    bufs = {k: _Guarded(eng, st0[k].nbytes, 0x5A, st0[k]) for k in ("sync", "nav", "obs", "eph")}
-    bufs.update(rec=_Guarded(eng, max_slots * n_ch * 48, 0xA5), words=_Guarded(eng, N.max_words(big) * n_ch * 16, 0xA5),
-                o=_Guarded(eng, n_ch * 32, 0xA5), e=_Guarded(eng, n_ch * 256, 0xA5))
     out, at = [], first_block
-    try:
+    with G.Chain(eng, P.sync_cfg_dev(lock), {k: st0[k] for k in ("sync", "nav", "obs", "eph")}, max(cuts), P.MAX_BAD_WORDS, P.EDGE_GUARD) as chain:
+        bufs = chain.buf
         for k, n in enumerate(cuts):
-            n_slots, n_words = capi.wsync_slots(n, P.K.N_COH_SEARCH, P.K.N_COH_LOCK), N.max_words(n)
-            for name in ("rec", "words", "o", "e"):
-                bufs[name].refill()
+            chain.refill()
             if k < len(cuts) - host_last:
-                eng._chk(lib.gpsx_track_loop_weighted_sync_dev(eng.h, sync.ctypes.data, C.c_void_p(d_if + at * 4092), n, bufs["sync"].ptr, n_ch,
-                                                               bufs["rec"].ptr), "gpsx_track_loop_weighted_sync_dev")
-                eng._chk(lib.gpsx_wnav_words_dev(eng.h, nav_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["nav"].ptr, n_ch, bufs["words"].ptr),
-                         "gpsx_wnav_words_dev")
-                eng._chk(lib.gpsx_wobs_dev(eng.h, obs_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["words"].ptr, bufs["obs"].ptr, n_ch,
-                                           bufs["o"].ptr), "gpsx_wobs_dev")
-                eng._chk(lib.gpsx_weph_dev(eng.h, eph_cfg.ctypes.data, bufs["words"].ptr, n, bufs["eph"].ptr, n_ch, bufs["e"].ptr), "gpsx_weph_dev")
+                chain.sync(d_if + at * 4092, n)
+                chain.words()
+                chain.obs()
+                chain.eph()
                 eng.synchronize()
-                rec, words = bufs["rec"].get(Y.REC_DTYPE, (n_slots, n_ch)), bufs["words"].get(N.WORD_DTYPE, (n_words, n_ch))
-                obs, eph = bufs["o"].get(O.OBS_DTYPE, (n_ch,)), bufs["e"].get(E.EPH_DTYPE, (n_ch,))
+                rec, words, obs, eph = (chain.read(name) for name in ("rec", "words", "o", "e"))
             else:
-                rec = np.frombuffer(bytearray(b"\xa5" * (n_slots * n_ch * 48)), Y.REC_DTYPE).reshape(n_slots, n_ch)
-                words = np.frombuffer(bytearray(b"\xa5" * (n_words * n_ch * 16)), N.WORD_DTYPE).reshape(n_words, n_ch)
-                obs = np.frombuffer(bytearray(b"\xa5" * (n_ch * 32)), O.OBS_DTYPE)
-                eph = np.frombuffer(bytearray(b"\xa5" * (n_ch * 256)), E.EPH_DTYPE)
+                chain.begin(n)
+                rec, words, obs, eph = (np.full(int(np.prod(chain.shape(name))) * chain.OUT[name].itemsize, 0xA5, np.uint8).view(chain.OUT[name])
+                                        .reshape(chain.shape(name)) for name in ("rec", "words", "o", "e"))
                 blocks = np.ascontiguousarray(P.blocks()[at:at + n])
-                eng._chk(lib.gpsx_track_loop_weighted_sync(eng.h, sync.ctypes.data, blocks.ctypes.data, n, bufs["sync"].ptr, n_ch, rec.ctypes.data),
+                eng._chk(lib.gpsx_track_loop_weighted_sync(eng.h, chain.sync_cfg.ctypes.data, blocks.ctypes.data, n, bufs["sync"].ptr, n_ch, rec.ctypes.data),
                          "gpsx_track_loop_weighted_sync")
-                eng.h2d(bufs["rec"].base + GUARD, rec)
-                eng._chk(lib.gpsx_wnav_words(eng.h, nav_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["nav"].ptr, n_ch, words.ctypes.data),
+                bufs["rec"].put(rec)
+                eng._chk(lib.gpsx_wnav_words(eng.h, chain.nav_cfg.ctypes.data, bufs["rec"].ptr, chain.n_slots, n, bufs["nav"].ptr, n_ch, words.ctypes.data),
                          "gpsx_wnav_words")
-                eng.h2d(bufs["words"].base + GUARD, words)
-                eng._chk(lib.gpsx_wobs(eng.h, obs_cfg.ctypes.data, bufs["rec"].ptr, n_slots, n, bufs["words"].ptr, bufs["obs"].ptr, n_ch,
+                bufs["words"].put(words)
+                eng._chk(lib.gpsx_wobs(eng.h, chain.obs_cfg.ctypes.data, bufs["rec"].ptr, chain.n_slots, n, bufs["words"].ptr, bufs["obs"].ptr, n_ch,
                                        obs.ctypes.data), "gpsx_wobs")
-                eng._chk(lib.gpsx_weph(eng.h, eph_cfg.ctypes.data, bufs["words"].ptr, n, bufs["eph"].ptr, n_ch, eph.ctypes.data), "gpsx_weph")
+                eng._chk(lib.gpsx_weph(eng.h, chain.eph_cfg.ctypes.data, bufs["words"].ptr, n, bufs["eph"].ptr, n_ch, eph.ctypes.data), "gpsx_weph")
                 bufs["rec"].get(np.uint8, (1,)), bufs["words"].get(np.uint8, (1,))      # (the canaries around what was uploaded)
             out.append((at, n, rec, words, obs, eph))
             at += n
-        states = {k: bufs[k].get(st0[k].dtype, st0[k].shape) for k in ("sync", "nav", "obs", "eph")}
-    finally:
-        for b in bufs.values():
-            b.free()
+        states = {k: chain.read(k) for k in ("sync", "nav", "obs", "eph")}
     return out, states
 
 

@@ -6,83 +6,44 @@ modes, both weights, spacings 1 / 8 / 15, four (n_coh_search, n_coh_lock) pairs;
 channel leaving WAIT -- asserted on the restatement); the ragged sixteen-channels-per-wave shape with canaries; GPU against GPU where
 the call must reduce to gpsx_track_loop_weighted_dev; split launches and the device variant; bad channels; refusals; and the
 three-satellite scenario, truncated."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import weighted_gpu as G
 import weighted_loop_cases as S
 import weighted_loop_ref as L
 import weighted_sync_cases as K
 import weighted_sync_ref as Y
+from weighted_gpu import EINVAL, eng  # noqa: F401
+from weighted_gpu import sync_cfg as _cfg
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -22
-GUARD = 4096
 
+def _stage(eng, blocks, st, cfg, dev=False, pieces=None):
+    """the library on a copy of `st` in device memory -> ([(first block, records)], states after, [return codes]); dev: blocks and
+    records in device memory too"""
+    n_ch, c = len(st), _cfg(cfg)
+    fn = eng.lib.gpsx_track_loop_weighted_sync_dev if dev else eng.lib.gpsx_track_loop_weighted_sync
+    launches, firsts = G.block_launches(blocks, pieces, Y.REC_DTYPE, lambda k: (Y.slots(k, cfg), n_ch))
 
-@pytest.fixture(scope="module")
-def eng():
-    from stm32f4_sdr_gps_amd import capi
-    e = capi.Engine(0)
-    yield e
-    e.close()
-
-
-def _cfg(c):
-    from stm32f4_sdr_gps_amd import capi
-    gains = {name: dict(dll=(c[name]["dll_c1"], c[name]["dll_c2"]), pll=(c[name]["pll_c1"], c[name]["pll_c2"]), fll=c[name]["fll_c"]) for name in ("search", "lock")}
-    return capi.wsync_cfg(c["n_coh_search"], c["n_coh_lock"], gains["search"], gains["lock"], c["sync_bits"], (c["sync_num"], c["sync_den"]),
-                          c["use_magnitude"], c["spacing"])
+    def call(ins, sts, out, k):
+        return fn(eng.h, c.ctypes.data, ins[0], len(launches[k][0][0]), sts[0], n_ch, out)
+    recs, after, codes = G.run_stage(eng, call, b"k_track_wsync", st, launches, dev, host_inputs=True)
+    return list(zip(firsts, recs)), after, codes
 
 
 def _gpu(eng, blocks, st, cfg, dev=False, pieces=None):
-    """the library on a copy of `st` in device memory -> ([(first block, records)], states after); dev: blocks and records in device
-    memory too"""
-    blocks = np.ascontiguousarray(blocks, np.uint8).reshape(-1, 4092)
-    n_ch = len(st)
-    after = st.copy()
-    c = _cfg(cfg)
-    d_st = eng.malloc(st.nbytes)
-    recs = []
-    try:
-        eng.h2d(d_st, st)
-        at = 0
-        for k in pieces or [len(blocks)]:
-            part = blocks[at:at + k]
-            if not dev:
-                recs.append((at, eng.track_loop_weighted_sync(part, d_st, n_ch, c)))
-                assert eng.lib.gpsx_last_kernel(eng.h) == b"k_track_wsync"
-            else:
-                rec = np.zeros((Y.slots(k, cfg), n_ch), Y.REC_DTYPE)
-                d_if, d_rec = eng.malloc(part.nbytes), eng.malloc(rec.nbytes)
-                try:
-                    eng.h2d(d_if, part)
-                    eng._chk(eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st), n_ch,
-                                                                       C.c_void_p(d_rec)), "gpsx_track_loop_weighted_sync_dev")
-                    eng.synchronize()
-                    eng.d2h(rec, d_rec)
-                finally:
-                    eng.free(d_if)
-                    eng.free(d_rec)
-                recs.append((at, rec))
-            at += k
-        eng.d2h(after, d_st)
-    finally:
-        eng.free(d_st)
+    """_stage where no channel is bad -> ([(first block, records)], states after)"""
+    recs, after, codes = _stage(eng, blocks, st, cfg, dev, pieces)
+    assert not any(codes), (codes, eng.lib.gpsx_last_error(eng.h))
     return recs, after
 
 
 def _same(rec, after, want_rec, want_st, channels, what):
-    ch = list(channels)
-    assert rec.dtype == Y.REC_DTYPE and rec.shape == want_rec.shape, what
-    bad = [c for c in ch if rec[:, c].tobytes() != want_rec[:, c].tobytes()]
-    if bad:
-        slot = [u for u in range(rec.shape[0]) if rec[u, bad[0]].tobytes() != want_rec[u, bad[0]].tobytes()][0]
-        assert not bad, (what, "records", bad[:4], slot, rec[slot, bad[0]], want_rec[slot, bad[0]])
-    bad = [c for c in ch if after[c:c + 1].tobytes() != want_st[c:c + 1].tobytes()]
-    assert not bad, (what, "states", bad[:4], after[bad[0]], want_st[bad[0]])
+    assert rec.dtype == Y.REC_DTYPE, what
+    G.same_columns(rec, want_rec, (what, "records"), list(channels))
+    G.same_rows(after, want_st, (what, "states"), list(channels))
 
 
 @pytest.mark.parametrize("i", range(len(K.CASES)))
@@ -111,29 +72,9 @@ def test_the_ragged_sixteen_channels_per_wave_shape(eng, oracle):
     st, _ = K.tiled_states(n_ch, 61, period)
     st["search_n"] = np.where((st["mode"] == Y.SEARCH) & (st["search_n"] == 0), 30, st["search_n"])     # (fresh searches decide at block 9)
     cfg = Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 1, (5, 4))
-    c = _cfg(cfg)
     n_slots = Y.slots(k, cfg)
-    rec_bytes = n_slots * n_ch * 48
-    h_rec = np.full(GUARD + rec_bytes + GUARD, 0xA5, np.uint8)
-    h_st = np.full(GUARD + st.nbytes + GUARD, 0xA5, np.uint8)
-    h_st[GUARD:GUARD + st.nbytes] = st.view(np.uint8)
-    d_if, d_rec, d_st = (eng.malloc(x.nbytes) for x in (blocks, h_rec, h_st))
-    try:
-        eng.h2d(d_if, blocks)
-        eng.h2d(d_rec, h_rec)
-        eng.h2d(d_st, h_st)
-        eng._chk(eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), k, C.c_void_p(d_st + GUARD), n_ch,
-                                                           C.c_void_p(d_rec + GUARD)), "gpsx_track_loop_weighted_sync_dev")
-        eng.synchronize()
-        eng.d2h(h_rec, d_rec)
-        eng.d2h(h_st, d_st)
-    finally:
-        for p in (d_if, d_rec, d_st):
-            eng.free(p)
-    for h, size in ((h_rec, rec_bytes), (h_st, st.nbytes)):
-        assert (h[:GUARD] == 0xA5).all() and (h[GUARD + size:] == 0xA5).all(), "canary"
-    rec = h_rec[GUARD:GUARD + rec_bytes].view(Y.REC_DTYPE).reshape(n_slots, n_ch)
-    after = h_st[GUARD:GUARD + st.nbytes].view(Y.STATE_DTYPE)
+    recs, after = _gpu(eng, blocks, st, cfg, dev=True)
+    rec = recs[0][1]
     last = S.ROWS[n_ch][2]
     rng = np.random.default_rng(n_ch)
     sample = sorted({0, 1, 15, 16, 63, 64, n_ch - 1, n_ch - last, n_ch - last - 1} | {int(x) for x in rng.integers(0, n_ch, 15)})
@@ -160,21 +101,12 @@ def _wloop(eng, blocks, loop_st, n_coh, gains):
     """gpsx_track_loop_weighted_dev on a copy of the 40-byte states -> (records, states after)"""
     from stm32f4_sdr_gps_amd import capi
     c = capi.wloop_cfg(n_coh, True, 8, gains["dll"], gains["pll"], gains["fll"])
-    rec = np.zeros((len(blocks) // n_coh, len(loop_st)), L.REC_DTYPE)
-    after = loop_st.copy()
-    d_if, d_st, d_rec = eng.malloc(blocks.nbytes), eng.malloc(loop_st.nbytes), eng.malloc(rec.nbytes)
-    try:
-        eng.h2d(d_if, blocks)
-        eng.h2d(d_st, np.ascontiguousarray(loop_st))
-        eng._chk(eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), len(blocks), C.c_void_p(d_st), len(loop_st),
-                                                      C.c_void_p(d_rec)), "gpsx_track_loop_weighted_dev")
-        eng.synchronize()
-        eng.d2h(rec, d_rec)
-        eng.d2h(after, d_st)
-    finally:
-        for p in (d_if, d_st, d_rec):
-            eng.free(p)
-    return rec, after
+
+    def call(ins, sts, out, k):
+        return eng.lib.gpsx_track_loop_weighted_dev(eng.h, c.ctypes.data, ins[0], len(blocks), sts[0], len(loop_st), out)
+    recs, after, codes = G.run_stage(eng, call, b"k_track_wloop", loop_st, [([blocks], L.REC_DTYPE, (len(blocks) // n_coh, len(loop_st)))])
+    assert codes == [0]
+    return recs[0], after
 
 
 @pytest.mark.parametrize("n,gains", [(1, S.REFERENCE_1MS), (4, S.PULL_IN), (20, S.STEADY)])
@@ -230,39 +162,14 @@ def test_bad_channels(eng, oracle):
     want_st = st0.copy()
     want = Y.run(oracle, blocks, want_st, cfg)
     assert (want["flags"][:, sorted(bad)] == 0).all() and (want["flags"][:, good] != 0).any(axis=0).all()
-    c = _cfg(cfg)
-    n_slots = Y.slots(45, cfg)
-    rec_bytes = n_slots * n_ch * 48
     for dev in (False, True):
-        h_st = np.full(GUARD + st0.nbytes + GUARD, 0xA5, np.uint8)
-        h_st[GUARD:GUARD + st0.nbytes] = st0.view(np.uint8)
-        h_rec = np.full(GUARD + rec_bytes + GUARD, 0x5A, np.uint8)
-        d_st, d_if, d_rec = eng.malloc(h_st.nbytes), eng.malloc(blocks.nbytes), eng.malloc(h_rec.nbytes)
-        try:
-            eng.h2d(d_st, h_st)
-            eng.h2d(d_if, blocks)
-            eng.h2d(d_rec, h_rec)
-            eng.synchronize()
-            if dev:
-                rc = eng.lib.gpsx_track_loop_weighted_sync_dev(eng.h, c.ctypes.data, C.c_void_p(d_if), 45, C.c_void_p(d_st + GUARD), n_ch,
-                                                               C.c_void_p(d_rec + GUARD))
-                assert rc == 0
-                assert eng.lib.gpsx_synchronize(eng.h) == EINVAL
-                assert eng.lib.gpsx_synchronize(eng.h) == 0
-                eng.d2h(h_rec, d_rec)
-            else:
-                rc = eng.lib.gpsx_track_loop_weighted_sync(eng.h, c.ctypes.data, blocks.ctypes.data, 45, C.c_void_p(d_st + GUARD), n_ch,
-                                                           h_rec[GUARD:].ctypes.data)
-                assert rc == EINVAL and b"prn" in eng.lib.gpsx_last_error(eng.h)
-            eng.d2h(h_st, d_st)
-        finally:
-            for p in (d_st, d_if, d_rec):
-                eng.free(p)
-        for h, size, v in ((h_rec, rec_bytes, 0x5A), (h_st, st0.nbytes, 0xA5)):
-            assert (h[:GUARD] == v).all() and (h[GUARD + size:] == v).all(), dev
-        rec = h_rec[GUARD:GUARD + rec_bytes].view(Y.REC_DTYPE).reshape(n_slots, n_ch)
-        after = h_st[GUARD:GUARD + st0.nbytes].view(Y.STATE_DTYPE)
-        _same(rec, after, want, want_st, range(n_ch), ("device" if dev else "host"))
+        recs, after, codes = _stage(eng, blocks, st0, cfg, dev)
+        assert codes == [EINVAL], dev
+        if dev:
+            assert eng.lib.gpsx_synchronize(eng.h) == 0
+        else:
+            assert b"prn" in eng.lib.gpsx_last_error(eng.h)
+        _same(recs[0][1], after, want, want_st, range(n_ch), ("device" if dev else "host"))
     recs, after = _gpu(eng, blocks, st0[good].copy(), cfg)      # the same channels without the bad ones: no error
     assert recs[0][1].tobytes() == np.ascontiguousarray(want[:, good]).tobytes() and after.tobytes() == want_st[good].tobytes()
 
@@ -289,35 +196,22 @@ def test_argument_checks_write_nothing(eng):
         b"a loop gain is not finite": [dict(cfg={(which, field): value}) for which in ("search", "lock")
                                        for field, value in (("dll_c1", nan), ("dll_c2", inf), ("pll_c1", -inf), ("pll_c2", nan), ("fll_c", inf))],
     }
-    refusals = [(message, change) for message, changes in by_message.items() for change in changes]
-    n_slots = 2
-    d_st, d_if, d_rec = eng.malloc(st0.nbytes), eng.malloc(blocks.nbytes), eng.malloc(n_slots * 4 * 48)
-    try:
-        eng.h2d(d_if, blocks)
-        for dev, fn in ((False, eng.lib.gpsx_track_loop_weighted_sync), (True, eng.lib.gpsx_track_loop_weighted_sync_dev)):
-            for message, change in refusals:
-                a = {**good, **change}
-                cfg = _cfg(Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 20, (5, 4)))
-                for key, value in a["cfg"].items():
-                    if isinstance(key, tuple):
-                        cfg[key[0]][key[1]] = value
-                    else:
-                        cfg[key] = value
-                rec = np.full(n_slots * 4 * 48, 0xA5, np.uint8)
-                eng.h2d(d_st, st0)
-                eng.h2d(d_rec, rec)
-                rc = fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (C.c_void_p(d_if) if dev else blocks.ctypes.data),
-                        a["n_blocks"], None if a["null_st"] else C.c_void_p(d_st), a["n_ch"],
-                        None if a["null_out"] else (C.c_void_p(d_rec) if dev else rec.ctypes.data))
-                assert rc == EINVAL and eng.lib.gpsx_last_error(eng.h) == message, (dev, change, eng.lib.gpsx_last_error(eng.h))
-                eng.synchronize()   # nothing was enqueued, nothing is pending
-                st, dr = st0.copy(), np.zeros_like(rec)
-                eng.d2h(st, d_st)
-                eng.d2h(dr, d_rec)
-                assert (rec == 0xA5).all() and (dr == 0xA5).all() and st.tobytes() == st0.tobytes(), (dev, change)
-    finally:
-        for p in (d_st, d_if, d_rec):
-            eng.free(p)
+    n_rec = 2 * 4 * Y.REC_DTYPE.itemsize
+    with G.Pool() as pool:
+        d_st, d_if = pool.add(G.Guarded(eng, st0.nbytes, G.STATE_FILL, st0)), pool.add(G.Guarded(eng, blocks.nbytes, G.STATE_FILL, blocks))
+        outs = {True: pool.add(G.Guarded(eng, n_rec)), False: pool.add(G.Guarded(None, n_rec))}
+
+        def call(a, dev):
+            cfg = _cfg(Y.make_cfg(4, 20, S.PULL_IN, S.STEADY, 20, (5, 4)))
+            for key, value in a["cfg"].items():
+                if isinstance(key, tuple):
+                    cfg[key[0]][key[1]] = value
+                else:
+                    cfg[key] = value
+            fn = eng.lib.gpsx_track_loop_weighted_sync_dev if dev else eng.lib.gpsx_track_loop_weighted_sync
+            return fn(eng.h, None if a["null_cfg"] else cfg.ctypes.data, None if a["null_if"] else (d_if.ptr if dev else blocks.ctypes.data),
+                      a["n_blocks"], None if a["null_st"] else d_st.ptr, a["n_ch"], None if a["null_out"] else outs[dev].ptr)
+        G.refusals(eng, by_message, good, call, [d_st, *outs.values()])
 
 
 def test_the_scenario_truncated(eng, oracle):
@@ -332,7 +226,13 @@ def test_the_scenario_truncated(eng, oracle):
     for k in pieces:
         want.append((at, Y.run(oracle, blocks[at:at + k], want_st, cfg)))
         at += k
-    recs, after = _gpu(eng, blocks, K.handover_states(1), cfg, pieces=pieces)
+    st, recs, at = K.handover_states(1), [], 0
+    with G.Guarded(eng, st.nbytes, G.STATE_FILL, st) as d_st:      # (the host variant as Engine.track_loop_weighted_sync makes it)
+        for k in pieces:
+            recs.append((at, eng.track_loop_weighted_sync(blocks[at:at + k], d_st.ptr.value, 3, _cfg(cfg))))
+            assert eng.lib.gpsx_last_kernel(eng.h) == b"k_track_wsync"
+            at += k
+        after = d_st.get(st.dtype, st.shape)
     for (at, g), (_, w) in zip(recs, want):
         assert g.tobytes() == w.tobytes(), at
     assert after.tobytes() == want_st.tobytes()
