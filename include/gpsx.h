@@ -38,7 +38,7 @@ extern "C" {
                                             * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t; gpsx_wlock(_dev) and
                                             * gpsx_wlock_cn0_dbhz likewise; gpsx_track_loop_weighted_sync_multi(_dev) with
                                             * gpsx_wmulti_t and gpsx_wobs_pseudoranges_rx too; gpsx_wfix(_dev) with gpsx_wfix_cfg_t
-                                            * and gpsx_wfix_t likewise. */
+                                            * and gpsx_wfix_t likewise; gpsx_wfde(_dev) with gpsx_wfde_cfg_t and gpsx_wfde_t too. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -1228,6 +1228,77 @@ int gpsx_wfix_dev(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *
                   const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, double *d_pr_m);
 int gpsx_wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
               const gpsx_wfix_t *prev, int n_rx, gpsx_wfix_t *fix, double *pr_m);
+
+/* ---- EXTENSION, not in the reference: weighted fixes with millisecond repair and fault detection / exclusion, on the device --------
+ * gpsx_wfix uses every usable slot as it stands: a slot whose tx_ms is the 1 ms off that GPSX_WOBS_AMBIGUOUS warns of (300 km of
+ * range), or whose range is wrong by a few hundred metres, goes into the fix and moves it.  gpsx_wfde(_dev) is gpsx_wfix with both
+ * looked after: it repairs the ambiguous millisecond from a fix over the unambiguous slots, then tests the residuals of the full fix
+ * and excludes the worst slot until the test passes.  Same inputs, same gpsx_wfix_t per receiver, one 64-byte gpsx_wfde_t beside it.
+ * It keeps no state.  gpsx_wfix and everything else stay as they are.
+ *
+ * Definition, per receiver.  A ROUND on an active set S is gpsx_wfix's definition above, steps 1 - 7, with "usable" replaced by S
+ * and every slot's tx_ms replaced by tx_ms + k_j; the reference slot, rx_tow_s, the week and the satellites are those of the round.
+ * The same arithmetic, IEEE double, uncontracted.
+ *   1 sets         U: gpsx_wfix's usable set (d_lock included); A: the slots of U whose observable has GPSX_WOBS_AMBIGUOUS; C = U \ A.
+ *                  k_j = 0 for every slot and excl_mask = 0 to begin with.
+ *   2 repair       only if cfg.repair is set, A is not empty and |C| >= min_sats: one round on C, started from d_prev as in step 6.
+ *                  If it ends in FIX at x_C, then for every j of A: pr_j by step 2's formula against C's reference slot, j's
+ *                  satellite at its transmit time, v_j exactly the solver's row at x_C (clock term included).  No row: k_j = 0 and j
+ *                  stays active.  Otherwise k_j = (int)rint(v_j / 299792.458); |k_j| <= 1 is kept (the plus or minus bit is set when it
+ *                  is not zero); |k_j| > 1 or a v_j that is not finite puts j into excl_mask.  If the round does not end in FIX,
+ *                  or the repair did not run while A is not empty: UNRESOLVED.
+ *   3 detection    S = U minus excl_mask.  Every round starts as step 6 from the preceding round's record (its rr with FIX, else
+ *     and          the origin); for the first round of all that is d_prev.  A round without FIX ends the receiver with NOFIX.  After
+ *     exclusion    FIX, the residual pass at the final x: the rows counted are row AND used_mask, as resid_rms_m counts them;
+ *                  dof = n_counted - 4, y_j = v_j / sig_j, T = sum y_j^2.  dof < 1: UNCHECKED, done.  Otherwise the limit is the
+ *                  Wilson-Hilferty chi-square quantile, in doubles as written: t = 1 - 2 / (9 dof) + z_global sqrt(2 / (9 dof)),
+ *                  limit = dof t t t.  T <= limit: PASSED.  Otherwise FAULT when the statistical exclusions so far equal max_excl,
+ *                  when n_counted - 1 < min_sats, or when no slot can be named.  Naming: the counted rows' normal matrix is
+ *                  factorised as in step 5 (a pivot fails: no name); h_jj = |M a_j|^2, w_j^2 = y_j^2 / (1 - h_jj), 0 where
+ *                  1 - h_jj <= 1e-10; the named slot has the largest w_j^2 > 0, the lowest slot among equals.  It goes into
+ *                  excl_mask and the next round runs: at most 1 + (max_excl + 1) rounds per receiver.  (The w-test, not the
+ *                  largest |y_j|: a faulty row with leverage pulls the fix towards itself and hides its own residual.)
+ *   4 output       d_fix[r] is the last round's gpsx_wfix_t, under the same byte rules (every byte written, nothing non-finite);
+ *                  d_pr_m, if given, that round's pseudoranges, 0 for the slots not active in it; every byte of d_fde[r] is
+ *                  written.  A T that is not finite (no finite record gives one) counts as a failed test and is written as 0.
+ * Hence: with repair = 0 and max_excl = 0, d_fix and d_pr_m are gpsx_wfix_dev's on the same inputs, byte for byte; with four usable
+ * slots the verdict is UNCHECKED and the record gpsx_wfix's.
+ * Errors: all of gpsx_wfix's (on cfg.fix), and: d_fde NULL or not 16-byte aligned (_dev), z_global not finite or outside 0 .. 10,
+ * max_excl outside 0 .. 8, repair outside 0 / 1, reserved != 0: GPSX_EINVAL with a gpsx_last_error text, nothing written.
+ * Vector ALU, FP64 (k_wfde: k_wfix's lane layout with a loop over rounds around the pass loop; a group that is finished masks its
+ * updates, the groups of one wave may sit in different rounds; the arg-max of w^2 is a butterfly on (value, slot)). */
+#define GPSX_WFDE_PASSED      1u   /* the last round has FIX and its test passed */
+#define GPSX_WFDE_UNCHECKED   2u   /* FIX with dof < 1: nothing to test with */
+#define GPSX_WFDE_FAULT       4u   /* FIX, but the test failed and no further exclusion was possible or allowed */
+#define GPSX_WFDE_NOFIX       8u   /* the last round has no FIX (d_fix tells why) */
+#define GPSX_WFDE_EXCLUDED   16u   /* modifier: excl_mask is not zero */
+#define GPSX_WFDE_REPAIRED   32u   /* modifier: a plus or minus bit is set */
+#define GPSX_WFDE_UNRESOLVED 64u   /* modifier: AMBIGUOUS usable slots went in unrepaired */
+
+typedef struct {                 /* 128 bytes */
+  gpsx_wfix_cfg_t fix;           /*   0  as gpsx_wfix's, same rules */
+  double   z_global;             /*  96  finite, 0 .. 10: the normal quantile of the global test (3.09: alpha = 1e-3) */
+  int32_t  max_excl;             /* 104  0 .. 8: statistical exclusions allowed per receiver */
+  int32_t  repair;               /* 108  0 / 1: run the millisecond repair */
+  int32_t  reserved[4];          /* 112  0 */
+} gpsx_wfde_cfg_t;
+
+typedef struct {                 /* 64 bytes, one per receiver and launch */
+  uint32_t flags;                /*  0  exactly one of PASSED / UNCHECKED / FAULT / NOFIX, and the modifiers */
+  int32_t  n_rounds;             /*  4  solver rounds run, the repair round included */
+  int32_t  n_excluded;           /*  8  popcount(excl_mask) */
+  int32_t  dof;                  /* 12  rows counted in the last residual pass - 4 (0 without FIX) */
+  uint64_t excl_mask;            /* 16  slots taken out, by the w-test or for |k| > 1 */
+  uint64_t plus_mask, minus_mask;/* 24  slots whose tx_ms was corrected by +1 / -1 ms */
+  double   t_stat, t_limit;      /* 40  the last round's T and its limit (0 where no test ran) */
+  uint64_t reserved;             /* 56  0 */
+} gpsx_wfde_t;
+
+/* arrays as gpsx_wfix's; d_fde: [n_rx].  On one stream: ..., gpsx_wobs_dev, gpsx_weph_dev (, gpsx_wlock_dev), then gpsx_wfde_dev */
+int gpsx_wfde_dev(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                  const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, gpsx_wfde_t *d_fde, double *d_pr_m);
+int gpsx_wfde(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+              const gpsx_wfix_t *prev, int n_rx, gpsx_wfix_t *fix, gpsx_wfde_t *fde, double *pr_m);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

@@ -122,6 +122,8 @@ def check_no_scratch() -> dict:
     check_wmulti()
     # ... and the position fixes at the chain's end (check_wfix below: FP64 with a dozen libm calls per row, refused here if it spills)
     check_wfix()
+    # ... and the fixes with millisecond repair and fault exclusion (check_wfde below: k_wfix's solver inside a loop over rounds)
+    check_wfde()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -168,6 +170,18 @@ def check_wfix() -> dict:
     if bad:
         raise RuntimeError(f"position-fix kernel with scratch memory (register spills): {bad}")
     return wfix
+
+
+def check_wfde() -> dict:
+    """k_wfde (the fixes with millisecond repair and fault exclusion: k_wfix's lane layout, rounds of the solver; an object of its
+    own): exactly one instance and no scratch.  -> {symbol: resources}"""
+    wfde = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wfde.o")).items() if "k_wfde" in k}
+    if len(wfde) != 1:
+        raise RuntimeError(f"expected k_wfde in build/k_wfde.o, found {sorted(wfde)}")
+    bad = {k: v for k, v in wfde.items() if v["scratch_bytes"] != 0}
+    if bad:
+        raise RuntimeError(f"fault-exclusion kernel with scratch memory (register spills): {bad}")
+    return wfde
 
 
 if __name__ == "__main__":

@@ -253,6 +253,24 @@ def wfix_cfg(offset_ms: float, ch_per_rx: int, min_sats: int = 4, ion=None) -> n
     return cfg
 
 
+# gpsx_wfde_cfg_t / gpsx_wfde_t (the fixes with the ambiguous millisecond repaired and faulty slots detected and excluded)
+WFDE_FLAG_PASSED, WFDE_FLAG_UNCHECKED, WFDE_FLAG_FAULT, WFDE_FLAG_NOFIX = 1, 2, 4, 8
+WFDE_FLAG_EXCLUDED, WFDE_FLAG_REPAIRED, WFDE_FLAG_UNRESOLVED = 16, 32, 64
+WFDE_CFG_DTYPE = np.dtype([("fix", WFIX_CFG_DTYPE), ("z_global", "<f8"), ("max_excl", "<i4"), ("repair", "<i4"), ("reserved", "<i4", (4,))])
+WFDE_DTYPE = np.dtype([("flags", "<u4"), ("n_rounds", "<i4"), ("n_excluded", "<i4"), ("dof", "<i4"), ("excl_mask", "<u8"), ("plus_mask", "<u8"),
+                       ("minus_mask", "<u8"), ("t_stat", "<f8"), ("t_limit", "<f8"), ("reserved", "<u8")])
+assert WFDE_CFG_DTYPE.itemsize == 128 and WFDE_DTYPE.itemsize == 64
+
+
+def wfde_cfg(offset_ms: float, ch_per_rx: int, min_sats: int = 4, ion=None, z_global: float = 3.09, max_excl: int = 2, repair: bool = True) -> np.ndarray:
+    """a gpsx_wfde_cfg_t as a one-element WFDE_CFG_DTYPE array: wfix_cfg's fields, the global test's normal quantile (3.09: a false
+    alarm in a thousand), the statistical exclusions allowed per receiver (0 .. 8) and whether the ambiguous millisecond is repaired"""
+    cfg = np.zeros(1, WFDE_CFG_DTYPE)
+    cfg["fix"] = wfix_cfg(offset_ms, ch_per_rx, min_sats, ion)
+    cfg["z_global"], cfg["max_excl"], cfg["repair"] = z_global, max_excl, int(repair)
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -390,6 +408,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wlock_dev.argtypes = lib.gpsx_wlock.argtypes
     lib.gpsx_wfix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.gpsx_wfix_dev.argtypes = lib.gpsx_wfix.argtypes
+    lib.gpsx_wfde.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gpsx_wfde_dev.argtypes = lib.gpsx_wfde.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -880,6 +900,23 @@ class Engine:
                                      None if prev is None else prev.ctypes.data, n_rx, fix.ctypes.data, pr.ctypes.data if want_pr else None),
                   "gpsx_wfix")
         return (fix, pr) if want_pr else fix
+
+    def wfde(self, cfg: np.ndarray, obs: np.ndarray, eph: np.ndarray, n_rx: int, lock: np.ndarray | None = None,
+             prev: np.ndarray | None = None, want_pr: bool = False):
+        """EXTENSION: wfix with the ambiguous millisecond repaired and faulty slots detected and excluded (include/gpsx.h gpsx_wfde);
+        the same host arrays, cfg from wfde_cfg.
+        -> (WFIX_DTYPE [n_rx], WFDE_DTYPE [n_rx]), and with want_pr the last round's pseudoranges float64 [n_rx * ch_per_rx] as well"""
+        assert cfg.dtype == WFDE_CFG_DTYPE and cfg.size == 1
+        n_ch = n_rx * int(cfg["fix"]["ch_per_rx"][0])
+        obs, eph = np.ascontiguousarray(obs, WOBS_DTYPE).reshape(-1), np.ascontiguousarray(eph, WEPH_DTYPE).reshape(-1)
+        assert len(obs) == n_ch and len(eph) == n_ch
+        lock = None if lock is None else np.ascontiguousarray(lock).view(WLOCK_DTYPE).reshape(n_ch)      # (any 64-byte record dtype)
+        prev = None if prev is None else np.ascontiguousarray(prev, WFIX_DTYPE).reshape(n_rx)
+        fix, fde, pr = np.zeros(n_rx, WFIX_DTYPE), np.zeros(n_rx, WFDE_DTYPE), np.zeros(n_ch, np.float64)
+        self._chk(self.lib.gpsx_wfde(self.h, cfg.ctypes.data, obs.ctypes.data, eph.ctypes.data, None if lock is None else lock.ctypes.data,
+                                     None if prev is None else prev.ctypes.data, n_rx, fix.ctypes.data, fde.ctypes.data,
+                                     pr.ctypes.data if want_pr else None), "gpsx_wfde")
+        return (fix, fde, pr) if want_pr else (fix, fde)
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -455,9 +455,108 @@ int wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, cons
       });
 }
 
+// ---- the position fixes with millisecond repair and fault exclusion (staged as wfix stages its arrays) --------------------------------
+int wfde(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *fc, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock, const gpsx_wfix_t *prev,
+         int n_rx, gpsx_wfix_t *fix, gpsx_wfde_t *fde, double *pr_m, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!fc || !obs || !eph || !fix || !fde)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  const gpsx_wfix_cfg_t *cfg = &fc->fix;
+  if (!(cfg->offset_ms - cfg->offset_ms == 0.0))   // (not finite: the difference is a NaN)
+    return fail(ctx, GPSX_EINVAL, "offset_ms is not finite");
+  for (double v : cfg->ion)
+    if (!(v - v == 0.0))
+      return fail(ctx, GPSX_EINVAL, "an ionosphere coefficient is not finite");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->min_sats < 4 || cfg->min_sats > 64)
+    return fail(ctx, GPSX_EINVAL, "min_sats must be 4..64");
+  if (cfg->reserved0 != 0 || cfg->reserved1 != 0 || cfg->reserved2 != 0 || cfg->reserved3 != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (!(fc->z_global >= 0.0 && fc->z_global <= 10.0))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "z_global must be finite and 0..10");
+  if (fc->max_excl < 0 || fc->max_excl > 8)
+    return fail(ctx, GPSX_EINVAL, "max_excl must be 0..8");
+  if (fc->repair != 0 && fc->repair != 1)
+    return fail(ctx, GPSX_EINVAL, "repair must be 0 or 1");
+  for (int32_t v : fc->reserved)
+    if (v != 0)
+      return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (!host && (reinterpret_cast<uintptr_t>(fix) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_fix must be 16-byte aligned");
+  if (!host && (reinterpret_cast<uintptr_t>(fde) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_fde must be 16-byte aligned");
+  size_t obs_bytes = 0, eph_bytes = 0, lock_bytes = 0, fix_bytes = 0, fde_bytes = 0, pr_bytes = 0;
+  if (records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wobs_t), &obs_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_weph_t), &eph_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wlock_t), &lock_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(double), &pr_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wfix_t), &fix_bytes) ||
+      records_overflow((size_t)n_rx, 1, sizeof(gpsx_wfde_t), &fde_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x ch_per_rx records overflow a size");
+  const size_t n_ch = (size_t)n_rx * (size_t)cfg->ch_per_rx;
+  const gpsx_wobs_t *d_obs = obs;
+  const gpsx_weph_t *d_eph = eph;
+  const gpsx_wlock_t *d_lock = lock;
+  const gpsx_wfix_t *d_prev = prev;
+  gpsx_wfix_t *d_fix = fix;
+  gpsx_wfde_t *d_fde = fde;
+  double *d_pr = pr_m;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) +
+                                      (prev ? arena_size(fix_bytes) : 0) + arena_size(fix_bytes) + arena_size(fde_bytes) +
+                                      (pr_m ? arena_size(pr_bytes) : 0)))
+      return rc;
+    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
+    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
+    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_obs = s_obs;
+    d_eph = s_eph;
+    if (lock) {
+      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
+      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_lock = s_lock;
+    }
+    if (prev) {
+      gpsx_wfix_t *s_prev = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
+      HIPCHK(ctx, hipMemcpyAsync(s_prev, prev, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_prev = s_prev;
+    }
+    d_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
+    d_fde = arena_take<gpsx_wfde_t>(ctx, (size_t)n_rx);
+    if (pr_m)
+      d_pr = arena_take<double>(ctx, n_ch);
+  }
+  return launch_and_report(
+      ctx, host, "k_wfde", "k_wfde raised the bad-state flag, which it never does",
+      [&](uint32_t *) { launch_wfde(ctx->stream, *fc, d_obs, d_eph, d_lock, d_prev, n_rx, d_fix, d_fde, d_pr); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(fix, d_fix, fix_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(fde, d_fde, fde_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (pr_m)
+          HIPCHK(ctx, hipMemcpyAsync(pr_m, d_pr, pr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wfde_dev(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                  const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, gpsx_wfde_t *d_fde, double *d_pr_m)
+{
+  return wfde(ctx, cfg, d_obs, d_eph, d_lock, d_prev, n_rx, d_fix, d_fde, d_pr_m, false);
+}
+
+int gpsx_wfde(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+              const gpsx_wfix_t *prev, int n_rx, gpsx_wfix_t *fix, gpsx_wfde_t *fde, double *pr_m)
+{
+  return wfde(ctx, cfg, obs, eph, lock, prev, n_rx, fix, fde, pr_m, true);
+}
 
 int gpsx_wfix_dev(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                   const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, double *d_pr_m)

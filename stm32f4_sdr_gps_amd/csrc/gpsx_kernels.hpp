@@ -190,6 +190,11 @@ void launch_wlock(hipStream_t s, const gpsx_wsync_rec_t *d_rec, int n_slots, int
 // every byte of them written.  cfg as the host checked it.
 void launch_wfix(hipStream_t s, const gpsx_wfix_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                  const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, double *d_pr_m);
+// extension: gpsx_wfde (k_wfde.hip: k_wfde) -- launch_wfix's fixes with the ambiguous millisecond repaired and faulty slots excluded:
+// the same arrays and lane layout, rounds of the solver per receiver; d_fde [n_rx] 64-byte records, every byte of them written.
+// cfg as the host checked it.
+void launch_wfde(hipStream_t s, const gpsx_wfde_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                 const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, gpsx_wfde_t *d_fde, double *d_pr_m);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

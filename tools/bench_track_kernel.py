@@ -78,7 +78,13 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       device-to-device hipMemcpyAsync of the bytes the kernel reads (288 per slot); then,
                                                       for the 4-slot shape, the wall time of the host path on records already in host
                                                       memory: gpsx_wobs_pseudoranges_rx, gpsx_weph_to_eph per slot and pntpos per
-                                                      receiver, called through ctypes (the interpreter's share is in it)"""
+                                                      receiver, called through ctypes (the interpreter's share is in it)
+  bench_track_kernel.py --weighted-fde [N_RXxCH_PER_RX ...]
+                                                      gpsx_wfde_dev (EXTENSION: the fixes with millisecond repair and fault exclusion;
+                                                      k_wfde) at --weighted-fix's four shapes, 2 m of noise: on clean records beside
+                                                      gpsx_wfix_dev on the same arrays (the ratio of one round to k_wfix), and on records
+                                                      with one 300 m fault per receiver (the cost of a second round), the calls taking
+                                                      turns in one process; the lines also go to profiles/r21_weighted_fde_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -845,8 +851,91 @@ def weighted_fix(shapes):
             eng.free(p)
 
 
+FDE_OUT = os.path.join(ROOT, "profiles", "r21_weighted_fde_bench.jsonl")
+
+
+class _Tee:
+    """stdout, and every line of it into a file as well"""
+
+    def __init__(self, path):
+        self.out, self.file = sys.stdout, open(path, "w")
+
+    def write(self, text):
+        self.out.write(text)
+        self.file.write(text)
+
+    def flush(self):
+        self.out.flush()
+        self.file.flush()
+
+
+def weighted_fde(shapes, out=FDE_OUT):
+    """k_wfde at k_wfix's shapes: on clean records (one round; beside k_wfix on the same arrays, the calls taking turns) and on records
+    with one 300 m fault per receiver (two rounds); the lines go to stdout and to `out`"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fde_cases as X
+    import weighted_fix_cases as W
+    from stm32f4_sdr_gps_amd import capi
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0)
+    names = sorted(W.SITES)
+    try:
+        for n_rx, ch in shapes:
+            rng = np.random.default_rng(ch)
+            clean, faulty = [], []
+            for k in range(16):      # --weighted-fix's sixteen skies, every slot usable, 2 m of noise; the fault at slot k
+                site, noise = names[k % len(names)], rng.normal(0.0, 2.0, ch)
+                clean.append(X.receiver(site, ch, 3 * k, noise))
+                noise[k % ch] += 300.0
+                faulty.append(X.receiver(site, ch, 3 * k, noise))
+            cfg, fix_cfg = capi.wfde_cfg(W.OFFSET_MS, ch), capi.wfix_cfg(W.OFFSET_MS, ch)
+            d_fix, d_fde = eng.malloc(n_rx * 128), eng.malloc(n_rx * 64)
+            dev = {}
+            for name, pool in (("clean", clean), ("one_fault", faulty)):
+                obs, eph = W.pack([pool[r % 16] for r in range(n_rx)], ch)
+                dev[name] = (eng.malloc(obs.nbytes), eng.malloc(eph.nbytes))
+                eng.h2d(dev[name][0], obs)
+                eng.h2d(dev[name][1], eph)
+
+            def fde(which):
+                return eng.lib.gpsx_wfde_dev(eng.h, cfg.ctypes.data, C.c_void_p(dev[which][0]), C.c_void_p(dev[which][1]), None, None, n_rx,
+                                             C.c_void_p(d_fix), C.c_void_p(d_fde), None)
+
+            calls = {"wfix_clean": (1, lambda: eng.lib.gpsx_wfix_dev(eng.h, fix_cfg.ctypes.data, C.c_void_p(dev["clean"][0]), C.c_void_p(dev["clean"][1]), None,
+                                                                     None, n_rx, C.c_void_p(d_fix), None)),
+                     "wfde_clean": (1, lambda: fde("clean")),
+                     "wfde_one_fault": (1, lambda: fde("one_fault"))}
+            med = _timed_rows(eng, calls, {"channels": n_rx * ch, "n_rx": n_rx, "ch_per_rx": ch})
+            rec = np.zeros(n_rx, capi.WFDE_DTYPE)
+            for which in ("clean", "one_fault"):
+                eng._chk(fde(which), "gpsx_wfde_dev")
+                eng.synchronize()
+                eng.d2h(rec, d_fde)
+                print(json.dumps({"wfde_check": which, "n_rx": n_rx, "ch_per_rx": ch, "passed": int((rec["flags"] & 1 != 0).sum()),
+                                  "excluded_one": int((rec["n_excluded"] == 1).sum()), "rounds_min": int(rec["n_rounds"].min()),
+                                  "rounds_max": int(rec["n_rounds"].max())}), flush=True)
+            print(json.dumps({"ratio": "k_wfde over k_wfix on clean records (one round each)", "n_rx": n_rx, "ch_per_rx": ch,
+                              "value": round(med["wfde_clean"] / med["wfix_clean"], 3), "ns_per_receiver": round(med["wfde_clean"] / n_rx * 1e3, 2)}), flush=True)
+            print(json.dumps({"ratio": "k_wfde with one fault per receiver (two rounds) over k_wfde on clean records", "n_rx": n_rx, "ch_per_rx": ch,
+                              "value": round(med["wfde_one_fault"] / med["wfde_clean"], 3),
+                              "second_round_us": round(med["wfde_one_fault"] - med["wfde_clean"], 3)}), flush=True)
+            for p in (d_fix, d_fde) + dev["clean"] + dev["one_fault"]:
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-fde" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-fde"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_fde([tuple(int(v) for v in a.split("x")) for a in args] or FIX_SHAPES)
     if "--weighted-fix" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-fix"]
         if "--window-s" in args:
