@@ -38,7 +38,8 @@ extern "C" {
                                             * calls gpsx_track_loop_weighted(_sync)_aided(_dev) with gpsx_waid_t; gpsx_wlock(_dev) and
                                             * gpsx_wlock_cn0_dbhz likewise; gpsx_track_loop_weighted_sync_multi(_dev) with
                                             * gpsx_wmulti_t and gpsx_wobs_pseudoranges_rx too; gpsx_wfix(_dev) with gpsx_wfix_cfg_t
-                                            * and gpsx_wfix_t likewise; gpsx_wfde(_dev) with gpsx_wfde_cfg_t and gpsx_wfde_t too. */
+                                            * and gpsx_wfix_t likewise; gpsx_wfde(_dev) with gpsx_wfde_cfg_t and gpsx_wfde_t too;
+                                            * gpsx_wvel(_dev) with gpsx_wvel_cfg_t and gpsx_wvel_t likewise. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -1299,6 +1300,102 @@ int gpsx_wfde_dev(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *
                   const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, gpsx_wfde_t *d_fde, double *d_pr_m);
 int gpsx_wfde(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
               const gpsx_wfix_t *prev, int n_rx, gpsx_wfix_t *fix, gpsx_wfde_t *fde, double *pr_m);
+
+/* ---- EXTENSION, not in the reference: weighted velocity fixes -- every receiver's velocity and clock drift, on the device -----------
+ * gpsx_wfix / gpsx_wfde give position and time.  gpsx_wvel(_dev) is a stateless stage behind either: from the carrier frequency that
+ * every observable carries (gpsx_wobs_t.if_freq_offset_hz), the ephemeris records and the position records it solves, per receiver,
+ * the ECEF velocity and the receiver clock's drift by one linear least-squares step, and returns one 112-byte gpsx_wvel_t.  Neither
+ * the reference nor csrc/gpsx_pvt.cpp has a Doppler solver; this text is the definition.  Nothing existing changes.
+ *
+ * Definition, per receiver; all arithmetic in IEEE double, uncontracted.  c = 299792458, we = 7.2921151467e-5, mu = 3.9860050e14.
+ *   1 rows         d_fix[r] has no GPSX_WFIX_FIX: NO_FIX.  Otherwise slot j is a candidate iff bit j of d_fix[r].used_mask is set (so
+ *                  gpsx_wfde's repair and exclusion carry over: an excluded slot gives no Doppler row either), its observable has
+ *                  GPSX_WOBS_VALID, its record has GPSX_WEPH_VALID and svh == 0, its if_freq_offset_hz is finite and, when d_lock is
+ *                  given, its lock record has GPSX_WLOCK_CARRIER.  The records of other slots are not read.
+ *   2 satellite    the satellite clock's reading of the transmit time comes straight from the observable:
+ *                  t_sv = ((double)tx_ms - (double)code_phase_fine / 16368) / 1000, seconds of the week; no pseudorange and no reference
+ *                  slot are needed.  With fold(d) = d > 302400 ? d - 604800 : d < -302400 ? d + 604800 : d (the week's end) and
+ *                  toc = (double)((toc_time - 315964800) mod 604800) + toc_sec: tc = fold(t_sv - toc); tc -= poly(tc) twice (k_wfix's
+ *                  two fixed-point passes, poly(t) = f0 + f1 t + f2 t t); t = t_sv - poly(tc); tk = fold(t - toes).  No row if
+ *                  |tk| > 7201, if A <= 0, or if Kepler's iteration (gpsx_wfix's: to 1e-14) needs 30 steps.  n = sqrt(mu / A^3) + deln.
+ *                  The position ps is gpsx_wfix's (IS-GPS-200 table 20-IV).  The velocity vs is its analytic derivative: with E, nu,
+ *                  phi = nu + omg BEFORE the harmonic corrections and u, r, i after them,
+ *                    E'  = n / (1 - e cos E)                     nu' = E' sqrt(1 - e^2) / (1 - e cos E)
+ *                    u'  = nu' (1 + 2 (cus cos 2phi - cuc sin 2phi))
+ *                    r'  = A e E' sin E + 2 nu' (crs cos 2phi - crc sin 2phi)
+ *                    i'  = idot + 2 nu' (cis cos 2phi - cic sin 2phi)        W' = OMGd - we
+ *                    xo' = r' cos u - r u' sin u                 yo' = r' sin u + r u' cos u
+ *                    vx  = xo' cos W - yo' cos i sin W + yo i' sin i sin W - W' py
+ *                    vy  = xo' sin W + yo' cos i cos W - yo i' sin i cos W + W' px
+ *                    vz  = yo' sin i + yo i' cos i
+ *                  and the satellite clock's rate d' = f1 + 2 f2 fold(t - toc) - 2 sqrt(mu A) e cos E E' / c^2.
+ *                  A slot whose millisecond gpsx_wfde repaired (+- 1 ms) is evaluated at its UNREPAIRED tx_ms: the stage does not see
+ *                  the repair, and 1 ms moves a satellite's velocity by about 6e-4 m/s.
+ *   3 row          l = ps - rr, rr = d_fix[r].rr; s = l.l, rho = sqrt(s); no row if rho == 0; e = l / rho.  With k = we / c, the
+ *                  derivative of gpsx_wfix's range model rho + k (ps_x rr_y - ps_y rr_x) + c dt - c d:
+ *                    y_j = mps_per_hz f_j - (e . vs + k (vs_x rr_y - vs_y rr_x) - c d'_j)
+ *                    a_j = (-e_x - k ps_y, -e_y + k ps_x, -e_z, 1)
+ *                  The signs of the two k terms are the derivative's.  RTKLIB's resdop has both the other way round (+ k (vs_y rr_x -
+ *                  vs_x rr_y) in the rate, + k ps_y and - k ps_x in the row); that is NOT a slip to be corrected here: on Dopplers formed
+ *                  from the travel time's own derivative a receiver at rest comes out 3.6e-3 m/s off with these signs and 2.7e-2 m/s
+ *                  off with resdop's (tests/test_weighted_vel_reference.py).
+ *                  f_j = (double)if_freq_offset_hz.  mps_per_hz is the caller's statement of what a hertz of that field is worth, and
+ *                  it must know the loop: this library's weighted loops rest at fd (1 + 1/1022), not at the Doppler fd (see
+ *                  gpsx_track_loop_weighted above: the NCO mixes 16 352 of a block's 16 368 samples), so their frequencies take
+ *                  GPSX_WVEL_L1CA_WLOOP = GPSX_WVEL_L1CA 1022 / 1023.  GPSX_WVEL_L1CA on them puts 0.1 % of every Doppler into its
+ *                  row, up to 0.75 m/s at 4 kHz: a bias that no averaging removes.  (The tests' IF stream, a receiver at rest on
+ *                  four satellites: 1.05 m/s with GPSX_WVEL_L1CA, 0.07 m/s with GPSX_WVEL_L1CA_WLOOP, the loops' frequencies then being
+ *                  0.04 to 0.35 Hz off the truth.)  The model is linear in x = (v, c drift): one solve, no iteration.  Atmospheric
+ *                  rates are neglected, and so are the terms of second order in 1 / c (the satellite moves on while the range
+ *                  changes: e . vs times the range rate over c, up to 2e-3 m/s per row).  f_j is age_blocks old and is NOT
+ *                  extrapolated to the launch's end: a line-of-sight acceleration stays below 1 Hz/s, times 20 ms.
+ *   4 solve        fewer than min_sats rows: TOO_FEW.  N = sum a a^T, b = sum a y, unweighted.  A row's s counts among the sums: a sum
+ *                  that is not finite: NONFINITE.  Cholesky as gpsx_wfix's with its pivot rule (p_0 <= 0, p_k <= 1e-10 N_kk:
+ *                  SINGULAR), x = N^-1 b, v_j = y_j - a_j . x.  enu = (-sl x0 + cl x1, -sp cl x0 - sp sl x1 + cp x2,
+ *                  cp cl x0 + cp sl x1 + sp x2) with the sines and cosines of d_fix[r].geo[0] (p) and geo[1] (l).  The checks run in
+ *                  this order: NO_FIX, TOO_FEW, NONFINITE (sums), SINGULAR, NONFINITE (a result: x, drift, enu, qv, the rms).
+ *   5 output       with VEL: vel = x[0..2], drift_s_s = x[3] / c, enu, qv = xx, yy, zz, xy, yz, xz of N^-1 as floats,
+ *                  resid_rms_mps = sqrt(sum v^2 / n_used).  n_used and used_mask are the rows (0 with NO_FIX).  Without VEL every
+ *                  numeric field but flags, n_used and used_mask is zero.  Exactly one of the five flags is set.  Every byte of
+ *                  d_vel is written; no NaN or infinity is ever written.
+ * Errors: NULL ctx / cfg / d_obs / d_eph / d_fix / d_vel, an mps_per_hz that is not finite or is 0, ch_per_rx outside 1 .. 64, min_sats
+ * outside 4 .. 64, a reserved word != 0, n_rx outside 1 .. 1 048 576, a d_vel that is not 16-byte aligned (_dev) and a byte count that
+ * overflows return GPSX_EINVAL (with a gpsx_last_error text) and write nothing.
+ * Vector ALU, FP64 (k_wvel: gpsx_wfix's lane layout; the 10 + 4 sums and the sum of squared residuals by xor-butterflies of width W;
+ * no loop but Kepler's).  On one stream: ..., gpsx_wfix_dev or gpsx_wfde_dev, then gpsx_wvel_dev on their arrays. */
+#define GPSX_WVEL_L1CA (-0.19029367279836487)  /* -c / 1575.42e6: m/s of range rate per Hz of a frequency that IS the Doppler */
+#define GPSX_WVEL_L1CA_WLOOP (GPSX_WVEL_L1CA * 1022.0 / 1023.0)   /* ... per Hz of this library's weighted loops' if_freq_offset_hz, which rest at fd (1 + 1/1022) */
+#define GPSX_WVEL_VEL        1u   /* vel, drift_s_s, enu, qv, resid_rms_mps hold a solution */
+#define GPSX_WVEL_NO_FIX     2u   /* d_fix[r] has no GPSX_WFIX_FIX: no position to stand on */
+#define GPSX_WVEL_TOO_FEW    4u   /* fewer than min_sats rows */
+#define GPSX_WVEL_SINGULAR   8u   /* a pivot failed gpsx_wfix's rule (p_0 <= 0, p_k <= 1e-10 N_kk) */
+#define GPSX_WVEL_NONFINITE 16u   /* a sum or a result was not finite; nothing non-finite is ever written */
+
+typedef struct {                 /* 32 bytes */
+  double  mps_per_hz;            /* finite, not 0; negative where the frequency rises as a satellite approaches: GPSX_WVEL_L1CA_WLOOP for this library's weighted loops, GPSX_WVEL_L1CA for a true Doppler (step 3) */
+  int32_t ch_per_rx;             /* 1 .. 64 */
+  int32_t min_sats;              /* 4 .. 64 */
+  int32_t reserved[4];           /* 0 */
+} gpsx_wvel_cfg_t;
+
+typedef struct {                 /* 112 bytes, one per receiver and launch */
+  uint32_t flags;                /*   0  exactly one of the five */
+  int32_t  n_used;               /*   4  rows */
+  uint64_t used_mask;            /*   8  bit j: slot j gave a row */
+  double   vel[3];               /*  16  ECEF, m/s */
+  double   drift_s_s;            /*  40  receiver clock drift, x[3] / c */
+  double   enu[3];               /*  48  vel in the east / north / up frame at d_fix[r].geo */
+  float    qv[6];                /*  72  xx, yy, zz, xy, yz, xz of the inverse normal matrix (unweighted) */
+  double   resid_rms_mps;        /*  96  sqrt(sum v^2 / n_used) */
+  uint64_t reserved;             /* 104  0 */
+} gpsx_wvel_t;
+
+/* d_obs, d_eph, d_lock (NULL: not consulted): [n_rx * ch_per_rx], d_fix and d_vel: [n_rx]; all on the device for _dev, all in host
+ * memory (staged through the arena; the call waits for its kernel) for gpsx_wvel */
+int gpsx_wvel_dev(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                  const gpsx_wfix_t *d_fix, int n_rx, gpsx_wvel_t *d_vel);
+int gpsx_wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+              const gpsx_wfix_t *fix, int n_rx, gpsx_wvel_t *vel);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

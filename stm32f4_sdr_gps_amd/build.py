@@ -124,6 +124,8 @@ def check_no_scratch() -> dict:
     check_wfix()
     # ... and the fixes with millisecond repair and fault exclusion (check_wfde below: k_wfix's solver inside a loop over rounds)
     check_wfde()
+    # ... and the velocity fixes behind either (check_wvel below: one linear solve per receiver, no scratch and no LDS)
+    check_wvel()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -182,6 +184,18 @@ def check_wfde() -> dict:
     if bad:
         raise RuntimeError(f"fault-exclusion kernel with scratch memory (register spills): {bad}")
     return wfde
+
+
+def check_wvel() -> dict:
+    """k_wvel (every receiver's velocity and clock drift: k_wfix's lane layout, one linear solve; an object of its own): exactly one
+    instance, no scratch and no LDS.  -> {symbol: resources}"""
+    wvel = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wvel.o")).items() if "k_wvel" in k}
+    if len(wvel) != 1:
+        raise RuntimeError(f"expected k_wvel in build/k_wvel.o, found {sorted(wvel)}")
+    bad = {k: v for k, v in wvel.items() if v["scratch_bytes"] != 0 or v["lds_bytes"] != 0}
+    if bad:
+        raise RuntimeError(f"velocity-fix kernel with scratch memory (register spills) or LDS: {bad}")
+    return wvel
 
 
 if __name__ == "__main__":

@@ -271,6 +271,24 @@ def wfde_cfg(offset_ms: float, ch_per_rx: int, min_sats: int = 4, ion=None, z_gl
     return cfg
 
 
+# gpsx_wvel_cfg_t / gpsx_wvel_t (every receiver's velocity and clock drift from the carrier frequencies and the position records)
+WVEL_FLAG_VEL, WVEL_FLAG_NO_FIX, WVEL_FLAG_TOO_FEW, WVEL_FLAG_SINGULAR, WVEL_FLAG_NONFINITE = 1, 2, 4, 8, 16
+WVEL_L1CA = -0.19029367279836487      # GPSX_WVEL_L1CA: -c / 1575.42e6, m/s of range rate per Hz of a frequency that is the Doppler
+WVEL_L1CA_WLOOP = WVEL_L1CA * 1022.0 / 1023.0      # GPSX_WVEL_L1CA_WLOOP: per Hz of the weighted loops' if_freq_offset_hz, which rest at fd (1 + 1/1022)
+WVEL_CFG_DTYPE = np.dtype([("mps_per_hz", "<f8"), ("ch_per_rx", "<i4"), ("min_sats", "<i4"), ("reserved", "<i4", (4,))])
+WVEL_DTYPE = np.dtype([("flags", "<u4"), ("n_used", "<i4"), ("used_mask", "<u8"), ("vel", "<f8", (3,)), ("drift_s_s", "<f8"), ("enu", "<f8", (3,)),
+                       ("qv", "<f4", (6,)), ("resid_rms_mps", "<f8"), ("reserved", "<u8")])
+assert WVEL_CFG_DTYPE.itemsize == 32 and WVEL_DTYPE.itemsize == 112
+
+
+def wvel_cfg(ch_per_rx: int, min_sats: int = 4, mps_per_hz: float = WVEL_L1CA) -> np.ndarray:
+    """a gpsx_wvel_cfg_t as a one-element WVEL_CFG_DTYPE array.  mps_per_hz: the default is for frequencies that are the Doppler;
+    observables of this library's weighted loops take WVEL_L1CA_WLOOP"""
+    cfg = np.zeros(1, WVEL_CFG_DTYPE)
+    cfg["mps_per_hz"], cfg["ch_per_rx"], cfg["min_sats"] = mps_per_hz, ch_per_rx, min_sats
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -410,6 +428,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wfix_dev.argtypes = lib.gpsx_wfix.argtypes
     lib.gpsx_wfde.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gpsx_wfde_dev.argtypes = lib.gpsx_wfde.argtypes
+    lib.gpsx_wvel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.gpsx_wvel_dev.argtypes = lib.gpsx_wvel.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -917,6 +937,21 @@ class Engine:
                                      None if prev is None else prev.ctypes.data, n_rx, fix.ctypes.data, fde.ctypes.data,
                                      pr.ctypes.data if want_pr else None), "gpsx_wfde")
         return (fix, fde, pr) if want_pr else (fix, fde)
+
+    def wvel(self, cfg: np.ndarray, obs: np.ndarray, eph: np.ndarray, fix: np.ndarray, n_rx: int, lock: np.ndarray | None = None) -> np.ndarray:
+        """EXTENSION: every receiver's velocity and clock drift (include/gpsx.h gpsx_wvel) from wfix's / wfde's host arrays and their
+        WFIX_DTYPE records fix [n_rx]; cfg from wvel_cfg.  lock: WLOCK_DTYPE records, a slot then also needs WLOCK_FLAG_CARRIER.
+        -> WVEL_DTYPE [n_rx]"""
+        assert cfg.dtype == WVEL_CFG_DTYPE and cfg.size == 1
+        n_ch = n_rx * int(cfg["ch_per_rx"][0])
+        obs, eph = np.ascontiguousarray(obs, WOBS_DTYPE).reshape(-1), np.ascontiguousarray(eph, WEPH_DTYPE).reshape(-1)
+        assert len(obs) == n_ch and len(eph) == n_ch
+        lock = None if lock is None else np.ascontiguousarray(lock).view(WLOCK_DTYPE).reshape(n_ch)      # (any 64-byte record dtype)
+        fix = np.ascontiguousarray(fix, WFIX_DTYPE).reshape(n_rx)
+        vel = np.zeros(n_rx, WVEL_DTYPE)
+        self._chk(self.lib.gpsx_wvel(self.h, cfg.ctypes.data, obs.ctypes.data, eph.ctypes.data, None if lock is None else lock.ctypes.data,
+                                     fix.ctypes.data, n_rx, vel.ctypes.data), "gpsx_wvel")
+        return vel
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

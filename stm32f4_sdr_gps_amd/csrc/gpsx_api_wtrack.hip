@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -542,9 +542,82 @@ int wfde(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *fc, const gpsx_wobs_t *obs, const
       });
 }
 
+// ---- the velocity fixes behind either (staged as wfix stages its arrays; the position records are an input here) ---------------------
+int wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock, const gpsx_wfix_t *fix,
+         int n_rx, gpsx_wvel_t *vel, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !obs || !eph || !fix || !vel)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (!(cfg->mps_per_hz - cfg->mps_per_hz == 0.0) || cfg->mps_per_hz == 0.0)   // (not finite: the difference is a NaN)
+    return fail(ctx, GPSX_EINVAL, "mps_per_hz must be finite and not 0");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->min_sats < 4 || cfg->min_sats > 64)
+    return fail(ctx, GPSX_EINVAL, "min_sats must be 4..64");
+  for (int32_t v : cfg->reserved)
+    if (v != 0)
+      return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (!host && (reinterpret_cast<uintptr_t>(vel) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_vel must be 16-byte aligned");
+  size_t obs_bytes = 0, eph_bytes = 0, lock_bytes = 0, fix_bytes = 0, vel_bytes = 0;
+  if (records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wobs_t), &obs_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_weph_t), &eph_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wlock_t), &lock_bytes) ||
+      records_overflow((size_t)n_rx, 1, sizeof(gpsx_wfix_t), &fix_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wvel_t), &vel_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x ch_per_rx records overflow a size");
+  const size_t n_ch = (size_t)n_rx * (size_t)cfg->ch_per_rx;
+  const gpsx_wobs_t *d_obs = obs;
+  const gpsx_weph_t *d_eph = eph;
+  const gpsx_wlock_t *d_lock = lock;
+  const gpsx_wfix_t *d_fix = fix;
+  gpsx_wvel_t *d_vel = vel;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) + arena_size(fix_bytes) +
+                                      arena_size(vel_bytes)))
+      return rc;
+    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
+    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
+    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_obs = s_obs;
+    d_eph = s_eph;
+    if (lock) {
+      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
+      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_lock = s_lock;
+    }
+    gpsx_wfix_t *s_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
+    HIPCHK(ctx, hipMemcpyAsync(s_fix, fix, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_fix = s_fix;
+    d_vel = arena_take<gpsx_wvel_t>(ctx, (size_t)n_rx);
+  }
+  return launch_and_report(
+      ctx, host, "k_wvel", "k_wvel raised the bad-state flag, which it never does",
+      [&](uint32_t *) { launch_wvel(ctx->stream, *cfg, d_obs, d_eph, d_lock, d_fix, n_rx, d_vel); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(vel, d_vel, vel_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wvel_dev(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                  const gpsx_wfix_t *d_fix, int n_rx, gpsx_wvel_t *d_vel)
+{
+  return wvel(ctx, cfg, d_obs, d_eph, d_lock, d_fix, n_rx, d_vel, false);
+}
+
+int gpsx_wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+              const gpsx_wfix_t *fix, int n_rx, gpsx_wvel_t *vel)
+{
+  return wvel(ctx, cfg, obs, eph, lock, fix, n_rx, vel, true);
+}
 
 int gpsx_wfde_dev(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                   const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, gpsx_wfde_t *d_fde, double *d_pr_m)

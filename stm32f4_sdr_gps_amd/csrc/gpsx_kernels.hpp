@@ -195,6 +195,11 @@ void launch_wfix(hipStream_t s, const gpsx_wfix_cfg_t &cfg, const gpsx_wobs_t *d
 // cfg as the host checked it.
 void launch_wfde(hipStream_t s, const gpsx_wfde_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                  const gpsx_wfix_t *d_prev, int n_rx, gpsx_wfix_t *d_fix, gpsx_wfde_t *d_fde, double *d_pr_m);
+// extension: gpsx_wvel (k_wvel.hip: k_wvel) -- every receiver's velocity and clock drift from the same [n_rx * ch_per_rx] arrays and
+// the [n_rx] position records of launch_wfix / launch_wfde: the same lane layout, one linear solve, no state; d_vel [n_rx] 112-byte
+// records, every byte of them written.  cfg as the host checked it.
+void launch_wvel(hipStream_t s, const gpsx_wvel_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                 const gpsx_wfix_t *d_fix, int n_rx, gpsx_wvel_t *d_vel);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -84,7 +84,13 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       k_wfde) at --weighted-fix's four shapes, 2 m of noise: on clean records beside
                                                       gpsx_wfix_dev on the same arrays (the ratio of one round to k_wfix), and on records
                                                       with one 300 m fault per receiver (the cost of a second round), the calls taking
-                                                      turns in one process; the lines also go to profiles/r21_weighted_fde_bench.jsonl"""
+                                                      turns in one process; the lines also go to profiles/r21_weighted_fde_bench.jsonl
+  bench_track_kernel.py --weighted-vel [N_RXxCH_PER_RX ...]
+                                                      gpsx_wvel_dev (EXTENSION: every receiver's velocity and clock drift; k_wvel) at
+                                                      --weighted-fix's four shapes, receivers at 36 m/s, on the fix records that
+                                                      gpsx_wfix_dev left on the device, beside gpsx_wfix_dev on the same arrays, the
+                                                      calls taking turns in one process; the lines also go to
+                                                      profiles/r22_weighted_vel_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -927,8 +933,62 @@ def weighted_fde(shapes, out=FDE_OUT):
         eng.close()
 
 
+VEL_OUT = os.path.join(ROOT, "profiles", "r22_weighted_vel_bench.jsonl")
+
+
+def weighted_vel(shapes, out=VEL_OUT):
+    """k_wvel at k_wfix's shapes, every slot usable, receivers at 36 m/s: gpsx_wvel_dev on the fix records that gpsx_wfix_dev left on the
+    device, beside gpsx_wfix_dev (cold start) on the same arrays, the calls taking turns; the lines go to stdout and to `out`"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fix_cases as W
+    import weighted_vel_cases as K
+    from stm32f4_sdr_gps_amd import capi
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0)
+    names = sorted(W.SITES)
+    try:
+        for n_rx, ch in shapes:
+            pool = [K.receiver(names[k % len(names)], ch, 3 * k, K.VELOCITIES[1], K.DRIFTS[1]) for k in range(16)]      # --weighted-fix's sixteen skies
+            obs, eph = W.pack([pool[r % 16] for r in range(n_rx)], ch)
+            fix_cfg, vel_cfg = capi.wfix_cfg(W.OFFSET_MS, ch), capi.wvel_cfg(ch)
+            d_obs, d_eph, d_fix, d_fix2, d_vel = eng.malloc(obs.nbytes), eng.malloc(eph.nbytes), eng.malloc(n_rx * 128), eng.malloc(n_rx * 128), eng.malloc(n_rx * 112)
+            eng.h2d(d_obs, obs)
+            eng.h2d(d_eph, eph)
+
+            def wfix(d_out):
+                return eng.lib.gpsx_wfix_dev(eng.h, fix_cfg.ctypes.data, C.c_void_p(d_obs), C.c_void_p(d_eph), None, None, n_rx, C.c_void_p(d_out), None)
+
+            eng._chk(wfix(d_fix), "gpsx_wfix_dev")
+            eng.synchronize()
+            calls = {"wfix": (1, lambda: wfix(d_fix2)),
+                     "wvel": (1, lambda: eng.lib.gpsx_wvel_dev(eng.h, vel_cfg.ctypes.data, C.c_void_p(d_obs), C.c_void_p(d_eph), None, C.c_void_p(d_fix), n_rx,
+                                                               C.c_void_p(d_vel)))}
+            med = _timed_rows(eng, calls, {"channels": n_rx * ch, "n_rx": n_rx, "ch_per_rx": ch, "read_bytes": obs.nbytes + eph.nbytes + n_rx * 128})
+            vel = np.zeros(n_rx, capi.WVEL_DTYPE)
+            eng.d2h(vel, d_vel)
+            err = np.linalg.norm(vel["vel"] - np.array(K.VELOCITIES[1]), axis=1)
+            print(json.dumps({"wvel_check": "records after the timed launches", "n_rx": n_rx, "ch_per_rx": ch, "solved": int((vel["flags"] == capi.WVEL_FLAG_VEL).sum()),
+                              "n_used_min": int(vel["n_used"].min()), "largest_velocity_error_mps": round(float(err.max()), 5)}), flush=True)
+            print(json.dumps({"ratio": "k_wvel over k_wfix on the same arrays", "n_rx": n_rx, "ch_per_rx": ch, "value": round(med["wvel"] / med["wfix"], 3),
+                              "cheaper": bool(med["wvel"] < med["wfix"]), "ns_per_receiver": round(med["wvel"] / n_rx * 1e3, 2),
+                              "read_GBps": round((obs.nbytes + eph.nbytes + n_rx * 128) / med["wvel"] / 1e3, 2)}), flush=True)
+            for p in (d_obs, d_eph, d_fix, d_fix2, d_vel):
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-vel" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-vel"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_vel([tuple(int(v) for v in a.split("x")) for a in args] or FIX_SHAPES)
     if "--weighted-fde" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-fde"]
         if "--window-s" in args:
