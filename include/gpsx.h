@@ -1160,7 +1160,11 @@ int gpsx_wlock_cn0_dbhz(const gpsx_wlock_t *lock, int n, int n_coh_lock, float *
  *                  is not finite, which gpsx_wobs never writes, gives one -- is written as 0; such an rx_tow_s ends in NONFINITE.)
  *   3 time         the observation time is gtime_t{315964800 + 604800 week + (int)rx_tow_s, rx_tow_s - (int)rx_tow_s}, week the
  *                  reference slot's record's.  A week rollover (rx_tow_s within a travel time of the week's end) is NOT handled: the
- *                  same limit as the host glue's.
+ *                  same limit as the host glue's.  The same holds for records of another week than the receive time's -- the
+ *                  previous week's broadcast (toes = 601200) at rx_tow_s = 1800, say: `week` is then that record's, the observation
+ *                  time lies a week off, no slot passes step 4's |toe - time| rule and the receiver ends in TOO_FEW with n_used = 0
+ *                  (pr_m, ref_slot and rx_tow_s are written as always).  gpsx_wvel folds its differences of times and gives
+ *                  such slots rows.
  *   4 solver       then csrc/gpsx_pvt.cpp's solve(), branch for branch, on each usable slot's own record: |toe - time| <= 7201 s or the
  *                  slot has no satellite; the two time_adds (which never carry into the whole second) to the transmit time; the
  *                  broadcast clock's two fixed-point passes; the orbit (Kepler's equation to 1e-14 in fewer than 30 steps or no
