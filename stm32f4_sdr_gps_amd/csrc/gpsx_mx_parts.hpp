@@ -39,10 +39,18 @@
 // earlier blocks,) pack the key, max, sum.
 //
 // A workgroup = 8 waves = one (search, Doppler) pair x 32 PRNs (four 8-PRN sharding units) x all 16 sample offsets.
-// Lane (n, h) of a wave holds, per tile, column q for the 16 PRNs p = (r & 3) + 8 (r >> 2) + 4 h, r = 0..15 -- the
-// per-offset work (corrections, window test) is shared by 16 hypotheses.  The matrix pipe and the vector ALU of a SIMD
-// are separate: waves 0..3 and 4..7 (one of each per SIMD) run half a step apart, one group's MFMA pass under the
-// other's epilogue, with one barrier per step.
+// Lane layout, by form:
+//   * the walk, store, split and byte-phase forms (k_acq_mx<1..5>) and the weighted kernels: chips = A, fragment = B.  Lane (n, h)
+//     of a wave holds, per tile, column q = 32 Q + n for the 16 PRNs p = (r & 3) + 8 (r >> 2) + 4 h, r = 0..15 -- the per-offset
+//     work (corrections, window test) is shared by 16 hypotheses; every lane folds its 16 results per sample offset into its own
+//     LDS slots (MxShared::part), reduced once at the end.
+//   * the single-block form (k_acq_mx<0>), where the fold and the anchor left no per-offset work inside the steps: fragment = A,
+//     chips = B (mx_mfma<true>), each block scale with its operand -- the TRANSPOSED tile (gpsx_mx_transposed.hpp).  Lane (n, h)
+//     holds PRN n, and register r of tile j the chip offset 32 (q0_tile + 2 j) + (r & 3) + 8 (r >> 2) + 4 h: a sample offset's
+//     maximum and sum are register chains of the lane, two LDS atomics per wave, and the result slots (k_acq_mx.hip:
+//     MxSingleShared::part) one word per (bit shift, field, lane half, PRN).  Its LDS block ends with MxSharedCore.
+// The matrix pipe and the vector ALU of a SIMD are separate: waves 0..3 and 4..7 (one of each per SIMD) run half a step apart,
+// one group's MFMA pass under the other's epilogue, with one barrier per step.
 //
 // Forms (k_acq_mx<MODE>; all in k_acq_mx.hip but 4, in k_acq_mx_byte.hip): 0 single block, one workgroup per cluster (the headline
 // sweep); 3 / 1 a workgroup walks the blocks of its search, running sums as 16- / 24-bit records through HBM scratch; 2 a workgroup
@@ -85,7 +93,8 @@ constexpr float kUnscaleSq = 67108864.0f;   // 2^26: scaled squares -> integers
 constexpr u32 kScaleEight = 0x82828282u; // E8M0 130 = 2^3
 constexpr u32 kScaleTwo = 0x80808080u;   // E8M0 128 = 2^1
 
-struct MxShared {
+// (MxSharedCore: everything but the result slots -- the single-block form, whose slots are its own, ends its block here)
+struct MxSharedCore {
   uint16_t x[1024];                      // raw IF block (sign plane)
   u32 d[2][514];                         // wiped I / Q streams (word 511 = wrap-around copy, then zero pad)
   u32 plane[2][16][kPlaneWordsMx];       // d_t0 for the 16 sample offsets, circularly extended
@@ -97,6 +106,8 @@ struct MxShared {
   u32 ones[2];                           // pop(D) per stream
   u32 t_lut[768];                        // [0, 512): 9 adjacent bits -> FP4 codes of -2 (bit k+1 - bit k), k = 0..7;
                                          // [512, 768): 8 bits -> FP4 codes of 2 bit - 1 (mx_fill_tables)
+};
+struct MxShared : MxSharedCore {
   alignas(16) u32 part[8][32][2][32];              // (packed best key, sum) per bit shift, PRN and lane of the wave half that holds the
                                          // PRN: every lane folds its own results in with LDS atomics (no return value, no
                                          // conflicts), the 32 lanes meet once, when the workgroup writes its triplets
@@ -154,14 +165,14 @@ __device__ __forceinline__ u32 mx_step_word(int dopp, int if_hz, int dopp_min_hz
   return nco_step_per_word(freq_hz);
 }
 // mx_a [set][16][2][32][4] -> the A fragments (all the weighted kernels read of the tables); with mx_t [set][1032] -> chip_t
-__device__ __forceinline__ void mx_load_chips_a(MxShared &sh, const u32 *__restrict__ mx_a, int set, int tid)
+__device__ __forceinline__ void mx_load_chips_a(MxSharedCore &sh, const u32 *__restrict__ mx_a, int set, int tid)
 {
   const u32 *src_a = mx_a + (size_t)set * (16 * 2 * 32 * 4);
   u32 *dst_a = reinterpret_cast<u32 *>(&sh.chips_a[0][0][0]);
   for (int i = tid; i < 16 * 2 * 32 * 4; i += kMxThreads)
     dst_a[i] = src_a[i];
 }
-__device__ __forceinline__ void mx_load_tables(MxShared &sh, const u32 *__restrict__ mx_a, const u32 *__restrict__ mx_t, int set, int tid)
+__device__ __forceinline__ void mx_load_tables(MxSharedCore &sh, const u32 *__restrict__ mx_a, const u32 *__restrict__ mx_t, int set, int tid)
 {
   mx_load_chips_a(sh, mx_a, set, tid);
   const u32 *src_t = mx_t + (size_t)set * 1032;
@@ -171,7 +182,7 @@ __device__ __forceinline__ void mx_load_tables(MxShared &sh, const u32 *__restri
 
 // ---- per block: capture -> LDS, wipe-off, polyphase planes -------------------------------------------------------------
 // (in two parts: the block's load goes out together with the cluster's tables -- one global-memory latency, not two)
-__device__ __forceinline__ void mx_load_block(MxShared &sh, const uint8_t *blk, int if_format, int tid)
+__device__ __forceinline__ void mx_load_block(MxSharedCore &sh, const uint8_t *blk, int if_format, int tid)
 {
   for (int i = tid; i < 1024; i += kMxThreads)
     sh.x[i] = i < kWords16 ? load_sign16(blk, i, if_format) : (uint16_t)0;
@@ -182,7 +193,7 @@ __device__ __forceinline__ void mx_load_block(MxShared &sh, const uint8_t *blk, 
 // WRAP_IN_PLACE: the thread of word 511 makes the wrap word itself, from the stream's word 0 as it recomputes it (the NCO's
 // phase at word 0 is 0) -- no barrier and no second step for it; the caller's next barrier publishes everything
 template <bool WRAP_IN_PLACE = false>
-__device__ __forceinline__ void mx_wipe_stream(MxShared &sh, u32 step_word, int tid, int lane)
+__device__ __forceinline__ void mx_wipe_stream(MxSharedCore &sh, u32 step_word, int tid, int lane)
 {
   {
     const u32 *x32 = reinterpret_cast<const u32 *>(sh.x);
@@ -268,7 +279,7 @@ __device__ __forceinline__ u32 fp4_code(int v)
 // The vector builders' lookup tables (once per workgroup): what they replace is the bit -> nibble spreading, a dozen
 // vector instructions per dword of the vectors -- and the vectors are built once per sample offset next to the MFMA passes,
 // by waves that have better things to do.
-__device__ void mx_fill_tables(MxShared &sh, int tid, int nthreads = kMxThreads)
+__device__ void mx_fill_tables(MxSharedCore &sh, int tid, int nthreads = kMxThreads)
 {
   for (int w = tid; w < 512; w += nthreads) {
     const u32 cur = (u32)w & 0xFFu, nxt = ((u32)w >> 1) & 0xFFu;
@@ -393,7 +404,7 @@ __device__ __forceinline__ u32 mx_patch_wrap(u32 packed, u32 w9, bool patch)
 // 4 j .. 4 j + 3 (MxFold): one table look-up by the five plane bits they depend on; q = 0 and q = 1 of sample offsets 9..15 have
 // pairs of their own.  (Sample offset 8, the half switch: its pass reads no pairs.)
 template <bool FOLD = false>
-__device__ __forceinline__ void mx_vector_build(MxShared &sh, int p_vec, int tid, MxFold *fold = nullptr)
+__device__ __forceinline__ void mx_vector_build(MxSharedCore &sh, int p_vec, int tid, MxFold *fold = nullptr)
 {
   const int t0 = p_vec - 1, buf = p_vec & 1;
   const bool late = t0 >= 9;
@@ -458,6 +469,17 @@ struct MxFoldRegs {
   lds_cu32 *w;                           // pair[buffer][0][q of tile 0]: tile j at + 64 j, the Q stream at + 1024
   u32 mask, pi, pq;
 };
+// One MFMA of a pass: chips x fragment.  TR (the single-block form, gpsx_mx_transposed.hpp): the fragment is the A operand and the
+// chips are B, each block scale with its operand -- the same registers, the tile transposed: chip offsets in the rows, one PRN per lane.
+template <bool TR, u32 SCALE_C>
+__device__ __forceinline__ v16f mx_mfma(v4i chips, v4i frag, v16f acc, u32 scale_f)
+{
+  if constexpr (TR)
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(frag), widen(chips), acc, 4, 4, 0, scale_f, 0, SCALE_C);
+  else
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(chips), widen(frag), acc, 4, 4, 0, SCALE_C, 0, scale_f);
+}
+// (FOLD is the single-block form's instantiation, and the transposed one)
 template <int S, int NT, u32 SCALE_A = kScaleA, bool FOLD = false>
 __device__ __forceinline__ void mx_pass_step(lds_cu32 *wi, lds_cu32 *wq, const v4i *ca, v4i (&a)[16], v4i &fi, v4i &fq,
                                              v16f (&acc)[2][NT], u32 scale_b, MxFoldRegs *fold = nullptr)
@@ -480,14 +502,14 @@ __device__ __forceinline__ void mx_pass_step(lds_cu32 *wi, lds_cu32 *wq, const v
   constexpr int j_lo = S - 15 > 0 ? S - 15 : 0, j_hi = S < NT - 1 ? S : NT - 1;
 #pragma unroll
   for (int j = j_lo + (patched ? 1 : 0); j <= j_hi; j++) {
-    acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), widen(fi), acc[0][j], 4, 4, 0, SCALE_A, 0, scale_b);
-    acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), widen(fq), acc[1][j], 4, 4, 0, SCALE_A, 0, scale_b);
+    acc[0][j] = mx_mfma<FOLD, SCALE_A>(a[S - j], fi, acc[0][j], scale_b);
+    acc[1][j] = mx_mfma<FOLD, SCALE_A>(a[S - j], fq, acc[1][j], scale_b);
   }
   if constexpr (patched) {
     fi.w = (int)((fold->mask & fold->pi) | (~fold->mask & (u32)fi.w));
     fq.w = (int)((fold->mask & fold->pq) | (~fold->mask & (u32)fq.w));
-    acc[0][j_lo] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[15]), widen(fi), acc[0][j_lo], 4, 4, 0, SCALE_A, 0, scale_b);
-    acc[1][j_lo] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[15]), widen(fq), acc[1][j_lo], 4, 4, 0, SCALE_A, 0, scale_b);
+    acc[0][j_lo] = mx_mfma<FOLD, SCALE_A>(a[15], fi, acc[0][j_lo], scale_b);
+    acc[1][j_lo] = mx_mfma<FOLD, SCALE_A>(a[15], fq, acc[1][j_lo], scale_b);
   }
   if constexpr (more) {
     __builtin_amdgcn_sched_group_barrier(0x100, (S + 1 < 16 ? 5 : 4) + (pair_next ? 2 : 0), 0);   // DS reads
@@ -551,7 +573,7 @@ __device__ __forceinline__ void mx_pass_step_inplace(lds_cu32 *wi, lds_cu32 *wq,
 // SCALE_A: the A operand's block scale (the weighted extension keeps plain integers in its accumulators: 2^0; AHEAD only)
 // FOLD: no extra K step; with_corr says whether the pairs of fold_pair (MxFold::pair[buf]) are patched in (mx_pass_step)
 template <bool AHEAD, int NT, u32 SCALE_A = kScaleA, bool FOLD = false>
-__device__ __forceinline__ void mx_pass(const MxShared &sh, int buf, int lane, int q0_tile, v16f (&acc)[2][NT],
+__device__ __forceinline__ void mx_pass(const MxSharedCore &sh, int buf, int lane, int q0_tile, v16f (&acc)[2][NT],
                                         u32 scale_b, v4i a_corr, bool with_corr, const u32 *fold_pair = nullptr)
 {
   static_assert(!FOLD || (AHEAD && NT == kMxTiles), "the fold is the single-block form's");

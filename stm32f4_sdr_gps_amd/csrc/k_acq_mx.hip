@@ -3,6 +3,7 @@
 // pieces only they use.
 // (k_acq_mx<4>, the byte-phase form: k_acq_mx_byte.hip; the weighted kernels on the same parts: k_acq_mxw.hip.)
 #include "gpsx_mx_parts.hpp"
+#include "gpsx_mx_transposed.hpp"
 
 namespace gpsx {
 
@@ -57,7 +58,7 @@ constexpr int kAnchorDwords = 392;     // one stream's anchor vector: 2048 six-b
 // inside its pass, would not arrive at.  Lane (t0 = lane & 3, w = lane >> 2 (+ 16)): the four lanes of a word read the same
 // sixteen stream words (LDS broadcast), the sixteen words of a wave in rotated order -- 16 w + (k + w) mod 16: sixteen banks per
 // parity of w -- where the plain order would put all sixteen on two banks.
-__device__ __forceinline__ void mx_planes_half(MxShared &sh, int t0_lo, int v, int lane)
+__device__ __forceinline__ void mx_planes_half(MxSharedCore &sh, int t0_lo, int v, int lane)
 {
   const int iq = v >> 1, t0_first = t0_lo + 4 * (v & 1);
   const int t0 = t0_first + (lane & 3), rot = lane >> 2;
@@ -91,7 +92,7 @@ __device__ __forceinline__ void mx_planes_half(MxShared &sh, int t0_lo, int v, i
 // ONE copy per stream, 2048 codes in 384 dwords: a lane's window starts at bit 6 (32 f + n), dword aligned only every 16 lanes,
 // and is cut out in registers (mx_anchor_pass).  Thread (stream, j): the codes of entries 8 j .. 8 j + 7, 48 bits; the two lanes
 // of a pair write the three dwords they fill.
-__device__ __forceinline__ void mx_anchor_build(MxShared &sh, u32 *dst, int tid)
+__device__ __forceinline__ void mx_anchor_build(MxSharedCore &sh, u32 *dst, int tid)
 {
   const int iq = tid >> 8, j = tid & 255;
   const u32 *dd = sh.d[iq];
@@ -151,8 +152,9 @@ __device__ __forceinline__ void mx_anchor_step(lds_cu32 *wi, lds_cu32 *wq, const
   constexpr int j_lo = S - 15 > 0 ? S - 15 : 0, j_hi = S < NT - 1 ? S : NT - 1;
 #pragma unroll
   for (int j = j_lo; j <= j_hi; j++) {
-    acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), fi, acc[0][j], 4, 3, 0, kScaleA, 0, kScaleTwo);
-    acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[S - j]), fq, acc[1][j], 4, 3, 0, kScaleA, 0, kScaleTwo);
+    // (transposed, as the recurrence passes -- mx_mfma: the E3M2 vector is A, format code 3 in cbsz, its 2^1 on the A side)
+    acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fi, widen(a[S - j]), acc[0][j], 3, 4, 0, kScaleTwo, 0, kScaleA);
+    acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fq, widen(a[S - j]), acc[1][j], 3, 4, 0, kScaleTwo, 0, kScaleA);
   }
   if constexpr (more) {
     __builtin_amdgcn_sched_group_barrier(0x100, S + 1 < 16 ? 9 : 8, 0);      // DS reads
@@ -167,7 +169,7 @@ __device__ __forceinline__ void mx_anchor_step(lds_cu32 *wi, lds_cu32 *wq, const
   }
 }
 template <int NT>
-__device__ __forceinline__ void mx_anchor_pass(const MxShared &sh, const u32 *anchor, int lane, int q0_tile, v16f (&acc)[2][NT])
+__device__ __forceinline__ void mx_anchor_pass(const MxSharedCore &sh, const u32 *anchor, int lane, int q0_tile, v16f (&acc)[2][NT])
 {
   const int n = lane & 31, h = lane >> 5;
   const u32 shift = (u32)(6 * n) & 31u;
@@ -567,11 +569,12 @@ __device__ __forceinline__ void mx_epilogue_store(int lane, int q0_tile, int t0,
 // starts at half step 2.  The preamble builds only what the anchor pass reads and the first epilogue writes; role 1 fills its empty
 // half step 0 with the rest of it, next to a partner that issues MFMAs, LDS reads and the fragments' shifts only:
 //   piece, maker                                    first reader                                  published by the barrier of
-//   anchor vector (in e8[0]), zeroes of sh.part,    the anchor passes; role 0's epilogue of       half step 0
-//   block, pop(D), chips:              all, preamble   offset 0 in half step 1
+//   anchor vector (in e8[0]), zeroes of the result  the anchor passes; role 0's epilogue of       half step 0
+//   slots, block, pop(D), chips:       all, preamble   offset 0 in half step 1
 //   role 1's start values:             role 1, 0    its anchor pass                               (its own)
 //   planes t0 0..7 + extension, t_lut: role 1, 0    mx_vector_build(2), behind that barrier       half step 2
 //   planes t0 8..15 + extension:       role 1, 0    mx_vector_build(10), half step 16             half step 2
+//   the half switch's table hs:        role 1, 0    mxt_half_switch, half steps 16 / 17           half step 2
 //   vector of pass 1 (e8[0], over the anchor): all, 2   pass 1, half steps 2 / 3                  the loop's first (half step 2)
 // The barrier of half step 2 is taken twice: once to end the anchor passes and publish the planes, once -- the loop's own --
 // behind the build of pass 1's vector, where the loop goes on to build pass 2's next to pass 1 as in every later step.
@@ -579,10 +582,229 @@ __device__ __forceinline__ void mx_epilogue_store(int lane, int q0_tile, int t0,
 // The quirk terms ride in chip columns 1021 / 1022 of the recurrence passes (MxFold, gpsx_fold_codes.hpp): no extra K step here.
 // The pairs of a pass are built with its vector and published with it; their look-up table is one more piece of role 1's half
 // step 0, published like t_lut.
+//
+// The accumulator tile is TRANSPOSED here (gpsx_mx_transposed.hpp): the fragment is the MFMA's A operand and the chips are B, so a
+// lane holds ONE PRN, lane & 31, and its 4 x 16 registers 64 chip offsets of it.  The windowed maximum and sum of a sample offset
+// are register chains of the lane that end in two LDS atomics per wave (mxt_epilogue), the result slots are one word per
+// (bit shift, field, lane half, PRN), and what the even-to-odd switch adds per chip offset comes from a table built once per
+// workgroup (mxt_half_switch_build).  The other forms keep one chip offset per lane and 16 PRNs in its registers.
+constexpr int kHsStride = 1026;          // a row of the half switch's table: 1024 entries + 16 bytes, so that the two rows a wave
+                                         // reads at the same chip offset lie in different banks
 struct MxSingleShared {
-  MxShared mx;
+  MxSharedCore mx;
   MxFold fold;
+  alignas(16) u32 part[8][2][2][32];     // [bit shift][best key / sum][lane half][PRN]: a wave's atomic hits 64 different words
+  alignas(16) float2 hs[2][kHsStride];   // [chip 1022 of the PRN][q]: (I, Q) terms of the even-to-odd switch (mxt_half_switch)
 };
+
+// The search window in chip offsets: the even byte offset 2 q of an existing q lies inside for q in [lo0, hi0), the odd one,
+// 2 q + 1, for q in [lo1, hi1); lo1 <= lo0 <= lo1 + 1 and hi1 <= hi0 <= hi1 + 1.
+struct MxtWindow {
+  int lo0, hi0, lo1, hi1;
+};
+__device__ __forceinline__ MxtWindow mxt_window(int win_start, int win_stop)
+{
+  MxtWindow w;
+  w.lo0 = (win_start + 1) >> 1;
+  w.hi0 = min(kChips, (win_stop + 1) >> 1);
+  w.lo1 = win_start >> 1;
+  w.hi1 = min(kChips, win_stop >> 1);
+  return w;
+}
+// Do all 128 chip offsets of this wave exist and lie, with both their byte offsets, inside the search window?  Wave-uniform; true
+// for every wave of an unwindowed search but the one that holds q = 1023.
+__device__ __forceinline__ bool mxt_wave_whole(int q0_tile, int win_start, int win_stop)
+{
+  const MxtWindow w = mxt_window(win_start, win_stop);
+  const int q_lo = 32 * q0_tile, q_hi = 32 * (q0_tile + 2 * (kMxTiles - 1)) + 31;
+  return q_lo >= w.lo0 && q_hi < w.hi1;
+}
+
+// mx_init_acc for the transposed tile: the window test is per register, or -- one test for the wave -- not needed at all
+__device__ __forceinline__ void mxt_init_acc(const u32 *ones, int lane, int q0_tile, v16f (&acc)[2][kMxTiles], int win_start,
+                                             int win_stop, int pass_bias)
+{
+  const float base_i = (float)((int)ones[0] + 8192 - kHalf - pass_bias) * kAccScale,
+              base_q = (float)((int)ones[1] + 8192 - kHalf - pass_bias) * kAccScale;
+  if (mxt_wave_whole(q0_tile, win_start, win_stop)) {
+#pragma unroll
+    for (int j = 0; j < kMxTiles; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        acc[0][j][r] = base_i;
+        acc[1][j][r] = base_q;
+      }
+  } else {
+    const MxtWindow w = mxt_window(win_start, win_stop);
+    const int h = lane >> 5;
+    const u32 span = (u32)max(w.hi0 - w.lo0, 0);
+#pragma unroll
+    for (int j = 0; j < kMxTiles; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int q = 32 * (q0_tile + 2 * j) + gpsx_mxt_row(h, r);
+        const bool in_win = (u32)(q - w.lo0) < span;   // lo0 <= q < hi0
+        acc[0][j][r] = in_win ? base_i : base_i + kOutside;
+        acc[1][j][r] = in_win ? base_q : base_q + kOutside;
+      }
+  }
+}
+
+// The even-to-odd switch (the formula in front of mx_half_switch, at b = 0) per chip offset, once per workgroup: what does not
+// depend on the PRN but through its chip 1022, hs[c22][q] = (fk + c22 fa) / 8192 for both streams.  Thread t of n: the chip offset
+// pairs m = t, t + n, ..: q = 2 m and 2 m + 1 read data bytes 4 m - 1 .. 4 m + 2, one stream word and the one before it, and
+// leave as one 16-byte store per row.  (q = 1023 does not exist: its entry is as small as the others, and its hypothesis, started
+// outside the window, still clips to zero.)
+__device__ __forceinline__ void mxt_half_switch_build(const MxSharedCore &sh, float2 (*hs)[kHsStride], int t, int n)
+{
+  const int popw[2] = {(int)__popc(sh.d[0][0] & 0xFFu), (int)__popc(sh.d[1][0] & 0xFFu)};
+#pragma unroll 1
+  for (int m = t; m < 512; m += n) {
+    float row[2][2][2];   // [c22][q & 1][stream]
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      const u32 w = sh.d[s][m], before = sh.d[s][m > 0 ? m - 1 : 0] >> 24;   // data bytes 4 m .. 4 m + 3; 4 m - 1
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const u32 cur = (w >> (16 * k)) & 0xFFu;                              // data byte 2 q
+        // A_7 of the even offset goes, A_0 = 0 of the odd one comes
+        int fa = -(2 * (int)__popc(cur & 0x7Fu) - 7);
+        int fk = -popw[s];
+        if (2 * m + k > 0) {                                                  // T(q): the tail word, data bytes (2 q - 1, 2 q)
+          const u32 prev = (k ? (w >> 8) & 0xFFu : before) | (cur << 8);
+          fk -= (int)__popc(prev);
+          fa -= 16 - 2 * (int)__popc(prev);
+        }
+        row[0][k][s] = (float)fk * kAccScale;
+        row[1][k][s] = (float)(fk + fa) * kAccScale;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+      *reinterpret_cast<float4 *>(&hs[c][2 * m]) = make_float4(row[c][0][0], row[c][0][1], row[c][1][0], row[c][1][1]);
+  }
+}
+
+// mx_half_switch for the transposed tile.  A lane's chip 1022 picks its row of the table; the entries of four adjacent chip
+// offsets (registers 4 g .. 4 g + 3) are two 16-byte reads, the same address in all lanes of a half and row.  Left per lane: the
+// chip[1022 - q] beta_0 term -- chip 1022 - q of PRN lane & 31 is bit lane & 31 of chip_t[1023 - q], four words per read.
+// Every term is a multiple of 2^-13 below 2^8 in magnitude: the sums are exact in any order.
+__device__ __forceinline__ void mxt_half_switch(const MxSharedCore &sh, const float2 (*hs)[kHsStride], int lane, int q0_tile,
+                                                v16f (&acc)[2][kMxTiles], int win_start, int win_stop)
+{
+  asm volatile("" : "+v"(lane));   // (the addresses below are computed here, not hoisted over the passes into registers they lack)
+  const int prn = lane & 31, h = lane >> 5;
+  const u32 wrap_i = (sh.d[0][0] & 0xFFu) << 8, wrap_q = (sh.d[1][0] & 0xFFu) << 8;
+  const float nbeta_i = -(float)(16 - 2 * (int)__popc(wrap_i)) * kAccScale, nbeta_q = -(float)(16 - 2 * (int)__popc(wrap_q)) * kAccScale;
+  // one address per table, constant offsets per (tile, register quad): the chip words run DOWN with q, so theirs is the last quad's
+  const int q4_first = 32 * q0_tile + 4 * h, q4_last = q4_first + 64 * (kMxTiles - 1) + 24;
+  const float2 *tab = &hs[(sh.chip_t[1022 + 1] >> prn) & 1u][q4_first];
+  const u32 *cw = &sh.chip_t[kChips - 3 - q4_last];          // chip_t[1020 - q4 .. 1023 - q4] of the last quad
+#pragma unroll
+  for (int j = 0; j < kMxTiles; j++) {
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const int dq = 64 * j + 8 * g;                         // registers 4 g + i: chip offsets q4_first + dq + i
+      const float4 t01 = *reinterpret_cast<const float4 *>(&tab[dq]), t23 = *reinterpret_cast<const float4 *>(&tab[dq + 2]);
+      const uint4 w = *reinterpret_cast<const uint4 *>(&cw[64 * (kMxTiles - 1) + 24 - dq]);
+      const float ti[4] = {t01.x, t01.z, t23.x, t23.z}, tq[4] = {t01.y, t01.w, t23.y, t23.w};
+      const u32 wi[4] = {w.w, w.z, w.y, w.x};                  // chip_t[1023 - (q4 + i)]
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const float c1 = (float)((wi[i] >> prn) & 1u);
+        acc[0][j][4 * g + i] += __builtin_fmaf(c1, nbeta_i, ti[i]);
+        acc[1][j][4 * g + i] += __builtin_fmaf(c1, nbeta_q, tq[i]);
+      }
+    }
+  }
+  if (!mxt_wave_whole(q0_tile, win_start, win_stop)) {
+    // A window edge may fall between the two byte offsets of a chip offset; the accumulators were started for the even one's
+    // place.  That happens at two chip offsets at the most: lo1, if only its odd byte offset is inside (an odd win_start), and
+    // hi1, if only its even one is (an odd win_stop).  A tile that holds neither is skipped (wave-uniform).
+    const MxtWindow w = mxt_window(win_start, win_stop);
+    const bool any = win_start < win_stop;
+    const int q_in = any && w.lo1 != w.lo0 ? w.lo1 : -1, q_out = any && w.hi1 != w.hi0 ? w.hi1 : -1;
+#pragma unroll
+    for (int j = 0; j < kMxTiles; j++) {
+      const int tile = q0_tile + 2 * j;
+      if ((q_in >> 5) != tile && (q_out >> 5) != tile)
+        continue;
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int q = 32 * tile + gpsx_mxt_row(h, r);
+        const float edge = (q == q_in ? -kOutside : 0.0f) + (q == q_out ? kOutside : 0.0f);
+        acc[0][j][r] += edge;
+        acc[1][j][r] += edge;
+      }
+    }
+  }
+}
+
+// mx_epilogue_single for the transposed tile: the same groups of eight hypotheses (two tiles x four registers), radius test, small
+// and exact paths and rounding modes.  The keys are LOCAL -- (root bits << 6) | the register's compile-time code, one
+// v_lshl_or_b32 with an inline constant -- and all 64 of a lane belong to ONE (bit shift, PRN): four interleaved chains of
+// v_max3_u32 / v_add3_u32 (register rr of every group feeds chain rr: a chain's links are a whole group apart, as the 16 chains
+// of mx_epilogue_single are), joined at the end; the winner becomes the global key once, and the wave issues one ds_max_u32 and
+// one ds_add_u32, each lane at its own word.  The root bits carry 0x4B000000: it leaves a global key in the shift, and the sum
+// starts at -64 x 0x4B000000 (mod 2^32).
+__device__ __forceinline__ void mxt_epilogue(u32 *part, int lane, int q0_tile, int t0, const v16f (&acc)[2][kMxTiles])
+{
+  const int b = t0 & 7, half = t0 >> 3;
+  u32 best[4], total[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    best[c] = 0;
+    total[c] = c ? 0u : 0u - (u32)kGpsxMxtLocals * kRootBias;
+  }
+  mx_round_toward_zero();
+#pragma unroll
+  for (int jp = 0; jp < kMxTiles; jp += 2) {
+#pragma unroll
+    for (int r0 = 0; r0 < 16; r0 += 4) {
+      float ev[8];
+      u32 e_max = 0;
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        ev[i] = clip_square_sum(acc[0][jp + (i >> 2)][r0 + (i & 3)], acc[1][jp + (i >> 2)][r0 + (i & 3)]);
+        e_max = max(e_max, __float_as_uint(ev[i]));
+      }
+      const bool small = __builtin_amdgcn_ballot_w64(e_max >= 0x3C800000u /* 2^20 / 2^26 as f32 */) == 0;
+      u32 bits[8];
+      if (__builtin_expect(small, 1)) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          bits[i] = root_bits_small(ev[i]);
+      } else {
+        float ci[8], cq[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          ci[i] = acc[0][jp + (i >> 2)][r0 + (i & 3)];
+          cq[i] = acc[1][jp + (i >> 2)][r0 + (i & 3)];
+        }
+        mx_roots_exact<8>(ci, cq, bits);
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          bits[i] += kRootBias;
+      }
+#pragma unroll
+      for (int rr = 0; rr < 4; rr++) {
+        const u32 k0 = gpsx_mxt_local_key(bits[rr], jp, r0 + rr), k1 = gpsx_mxt_local_key(bits[4 + rr], jp + 1, r0 + rr);
+        best[rr] = max(max(best[rr], k0), k1);
+        total[rr] = total[rr] + bits[rr] + bits[4 + rr];
+      }
+      // (pinned in program order, as in mx_epilogue_single)
+#pragma unroll
+      for (int rr = 0; rr < 4; rr++)
+        asm volatile("" : "+v"(best[rr]), "+v"(total[rr]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  mx_round_to_nearest();
+  const u32 key = gpsx_mxt_global_key(max(max(best[0], best[1]), max(best[2], best[3])), 32 * q0_tile + 4 * (lane >> 5), half);
+  u32 *slot = part + (2 * b) * 64 + lane;   // part[b][0][h][PRN]; the sum 64 words on
+  atomicMax(slot, key);
+  atomicAdd(slot + 64, total[0] + total[1] + total[2] + total[3]);
+}
 __device__ __forceinline__ void mx_fill_fold_lut(MxFold &fold, int t)   // threads 0..63
 {
   if (t < 64) {
@@ -595,10 +817,13 @@ __device__ __forceinline__ void mx_fill_fold_lut(MxFold &fold, int t)   // threa
   }
 }
 
-__device__ __forceinline__ void mx_single(MxShared &sh, MxFold &fold, const AcqParams &prm, int cluster_lo,
+__device__ __forceinline__ void mx_single(MxSingleShared &shs, const AcqParams &prm, int cluster_lo,
                                           const uint8_t *__restrict__ if_blocks, const u32 *__restrict__ mx_a,
                                           const u32 *__restrict__ mx_t, gpsx_peak_t *__restrict__ peaks)
 {
+  MxSharedCore &sh = shs.mx;
+  MxFold &fold = shs.fold;
+  u32 *part = &shs.part[0][0][0][0];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform values in SGPRs)
   const int role = wave >> 2;                            // waves w and w + 4 share a SIMD: half a step apart
@@ -625,19 +850,13 @@ __device__ __forceinline__ void mx_single(MxShared &sh, MxFold &fold, const AcqP
     mx_load_tables(sh, mx_a, mx_t, set, tid);   // (t_lut: role 1 fills it in half step 0)
   }
   // (role 0's first epilogue runs in half step 1 -- the zeroes are published by the barrier of half step 0, like the block)
-  for (int i = tid; i < 8 * 32 * 2 * 32 / 4; i += kMxThreads)
-    reinterpret_cast<uint4 *>(&sh.part[0][0][0][0])[i] = make_uint4(0, 0, 0, 0);
+  if (tid < (int)(sizeof(shs.part) / sizeof(uint4)))
+    reinterpret_cast<uint4 *>(part)[tid] = make_uint4(0, 0, 0, 0);
   const size_t block_bytes = prm.if_format == GPSX_IF_2BIT_SM ? GPSX_BYTES_PER_MS_2BIT : kBytes;
   const uint8_t *block0 = if_blocks + (size_t)(search * prm.search_stride_blocks) * block_bytes;
   mx_load_block(sh, block0, prm.if_format, tid);
 
   __syncthreads();
-  u32 kq[kMxTiles];   // 2047 - (even byte offset of the lane's chip offset in tile j): the low field of its search keys
-#pragma unroll
-  for (int j = 0; j < kMxTiles; j++) {
-    kq[j] = (u32)(2047 - 2 * (32 * (q0_tile + 2 * j) + (lane & 31)));
-    asm volatile("" : "+v"(kq[j]));   // (kept in registers, not rebuilt per group)
-  }
   const int n_pass = kPassesAnchor;
   // (One trip.  Inside a loop the compiler hoists the preamble's per-thread address arithmetic above the barriers, as it does in
   //  mx_unit's block loop, which this form used to run once; without it k_acq_mx<0> comes out 14 instructions longer.)
@@ -651,7 +870,7 @@ __device__ __forceinline__ void mx_single(MxShared &sh, MxFold &fold, const AcqP
 
     v16f acc[2][kMxTiles];
     if (role == 0)   // (role 1's start values wait until role 0 is inside pass 0)
-      mx_init_acc(sh.ones, lane, q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
+      mxt_init_acc(sh.ones, lane, q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
 
     // (thread indices made opaque per piece: a piece's per-thread addresses are computed where it runs, not hoisted over the
     //  passes into registers that the passes do not have)
@@ -665,12 +884,13 @@ __device__ __forceinline__ void mx_single(MxShared &sh, MxFold &fold, const AcqP
       mx_fill_tables(sh, opaque(tid) & 255, 256);
       mx_fill_fold_lut(fold, opaque(tid) & 255);
       mx_planes_half(sh, 8, wave & 3, opaque(lane));
-      mx_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
+      mxt_half_switch_build(sh, shs.hs, opaque(tid) & 255, 256);
+      mxt_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
     }
     mx_anchor_pass(sh, &sh.e8[0][0][0][0], lane, q0_tile, acc);
     if (!role)                     // half step 1 of role 0, under role 1's pass
-      mx_epilogue_single(sh, lane, kq, 0, acc);
-    __syncthreads();               // half step 2: everybody is done with the anchor vector; the planes and t_lut are published
+      mxt_epilogue(part, lane, q0_tile, 0, acc);
+    __syncthreads();               // half step 2: everybody is done with the anchor vector; the planes, t_lut and hs are published
     mx_vector_build<true>(sh, 2, opaque(tid), &fold);
 #pragma unroll 1
     for (int hs = 2; hs <= 2 * n_pass; hs++) {
@@ -689,29 +909,20 @@ __device__ __forceinline__ void mx_single(MxShared &sh, MxFold &fold, const AcqP
         mx_pass<true, kMxTiles, kScaleA, true>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne, v4i{0, 0, 0, 0},
                                                p >= 2 && p != 9, &fold.pair[p & 1][0][0]);
         if (p == 9)
-          mx_half_switch(sh, lane, q0_tile, acc, prm.win_start, prm.win_stop);
+          mxt_half_switch(sh, shs.hs, lane, q0_tile, acc, prm.win_start, prm.win_stop);
       }
       if (active && (x & 1) && p >= 1)
-        mx_epilogue_single(sh, lane, kq, p - 1, acc);
+        mxt_epilogue(part, lane, q0_tile, p - 1, acc);
     }
   }
   __syncthreads();
-  // the finished triplets and packed keys, as at the end of mx_unit without its SPLIT half (a copy: as one function called from
-  // both, the same text changes the instruction streams of k_acq_mx<0>, <1> and <3>; profiles/r09_mx_split_isa.txt)
+  // the finished triplets and packed keys, as at the end of mx_unit without its SPLIT half; a (bit shift, PRN) cell is two words
+  // per field, one per lane half, read directly
   {
     const int which = tid >> 8, p = (tid >> 3) & 31, b = tid & 7;
     const int slot = 32 * set + p;
-    const u32 *row = sh.part[b][p][which];
-    u32 vals[32];
-#pragma unroll
-    for (int l = 0; l < 32; l++)
-      vals[l] = row[(l + tid) & 31];   // (rotated start: the threads of a wave spread over the banks)
-    u32 k = 0, t = 0;
-#pragma unroll
-    for (int l = 0; l < 32; l++) {
-      k = vals[l] > k ? vals[l] : k;
-      t += vals[l];
-    }
+    const u32 v0 = shs.part[b][which][0][p], v1 = shs.part[b][which][1][p];
+    const u32 k = v0 > v1 ? v0 : v1, t = v0 + v1;   // (which = 0: the keys' maximum counts, which = 1: the sums' sum)
     if (((group_mask >> (p >> 3)) & 1u) && slot < prm.n_prn && b < prm.n_bits) {
       const size_t idx = ((size_t)(search * prm.n_prn + slot) * prm.n_dopp + dopp) * prm.n_bits + b;
       uint2 *pk = reinterpret_cast<uint2 *>(&peaks[idx]);
@@ -997,7 +1208,7 @@ __global__ __launch_bounds__(kMxThreads, 1) void k_acq_mx(GPSX_K_ACQ_MX_PARAMS)
 {
   if constexpr (MODE == kMxSingle) {
     __shared__ MxSingleShared sh;
-    mx_single(sh.mx, sh.fold, prm, cluster_lo, if_blocks, mx_a, mx_t, peaks);
+    mx_single(sh, prm, cluster_lo, if_blocks, mx_a, mx_t, peaks);
   } else {
     __shared__ MxShared sh;
     mx_unit<MODE>(sh, prm, cluster_lo, if_blocks, mx_a, mx_t, peaks, energy, flags);

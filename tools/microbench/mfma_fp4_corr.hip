@@ -7,7 +7,9 @@
 //                            q + 64 kappa + 32 h -- an UNALIGNED 16-byte LDS read from one of two copies (even / odd start)
 //   fragment reuse: tile (Q, kappa) reads the same bytes as (Q - 2, kappa + 1): a wave owning q-tiles Q0, Q0+2, Q0+4, Q0+6
 //   walks anti-diagonals f = Q + 2 kappa, 19 fragment loads per 64 MFMAs.
-// Part 1 checks operand / result layouts and exactness against the CPU; part 2 times the MFMA part of one bench step
+// Part 1 checks operand / result layouts and exactness against the CPU -- also with the operands swapped (the transposed arm:
+// A = the Toeplitz fragment, B = the chips, each block scale with its operand; register i of lane l then holds chip offset
+// (i & 3) + 8 (i >> 2) + 4 (l >> 5) of its tile for PRN l & 31); part 2 times the MFMA part of one bench step
 // (1344 (search, Doppler) pairs x 17 passes x 2 streams) with 8 waves per workgroup.
 // Build: hipcc --offload-arch=gfx950 -O3 mfma_fp4_corr.hip -o mfma_fp4_corr
 #include <hip/hip_runtime.h>
@@ -47,9 +49,11 @@ __device__ __forceinline__ v4i lds_read16_unaligned(const uint8_t *p)
   return v;
 }
 
-// One pass: acc[stream][tile] += chips x Toeplitz(e[stream]).  scale_b: E8M0 scale of the data operand.
-template <int MODE>
-__device__ __forceinline__ void toeplitz_pass(const Lds &L, int lane, int q0_tile, v16f (&acc)[2][kTiles], u32 scale_b)
+// One pass: acc[stream][tile] += chips x Toeplitz(e[stream]).  scale_b: E8M0 scale of the data operand, scale_c: of the chips.
+// TR: the fragment goes in as A and the chips as B (the same registers, the scales with them): the tile comes out transposed.
+template <int MODE, bool TR = false>
+__device__ __forceinline__ void toeplitz_pass(const Lds &L, int lane, int q0_tile, v16f (&acc)[2][kTiles], u32 scale_b,
+                                              u32 scale_c = kScaleOne)
 {
   const int n = lane & 31, h = lane >> 5;
   const u32 *wi = &L.e8[0][n & 7][4 * (q0_tile + h) + (n >> 3)];
@@ -83,8 +87,13 @@ __device__ __forceinline__ void toeplitz_pass(const Lds &L, int lane, int q0_til
       const int kappa = s - j;
       if (kappa < 0 || kappa >= 16)
         continue;
-      acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[kappa]), widen(fi), acc[0][j], 4, 4, 0, kScaleOne, 0, scale_b);
-      acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[kappa]), widen(fq), acc[1][j], 4, 4, 0, kScaleOne, 0, scale_b);
+      if constexpr (TR) {
+        acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(fi), widen(a[kappa]), acc[0][j], 4, 4, 0, scale_b, 0, scale_c);
+        acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(fq), widen(a[kappa]), acc[1][j], 4, 4, 0, scale_b, 0, scale_c);
+      } else {
+        acc[0][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[kappa]), widen(fi), acc[0][j], 4, 4, 0, scale_c, 0, scale_b);
+        acc[1][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(a[kappa]), widen(fq), acc[1][j], 4, 4, 0, scale_c, 0, scale_b);
+      }
     }
   }
 }
@@ -119,8 +128,9 @@ __device__ void stage_chips(Lds &L, const uint8_t *chipnib, int tid, int nthread
 }
 
 // Part 1: one workgroup, n_pass passes over the same vectors (scale alternates to test the x4 path), full result out.
+template <bool TR>
 __global__ __launch_bounds__(64 * kWaves, 1) void k_check(const uint8_t *vec, const uint8_t *chipnib, float *out /* [2][1024 q][32 prn] */,
-                                                          int n_pass, u32 scale_b)
+                                                          int n_pass, u32 scale_b, u32 scale_c)
 {
   __shared__ Lds L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -134,13 +144,15 @@ __global__ __launch_bounds__(64 * kWaves, 1) void k_check(const uint8_t *vec, co
       for (int r = 0; r < 16; r++)
         acc[st][j][r] = 0.f;
   for (int p = 0; p < n_pass; p++)
-    toeplitz_pass<0>(L, lane, q0_tile, acc, scale_b);
+    toeplitz_pass<0, TR>(L, lane, q0_tile, acc, scale_b, scale_c);
   const int n = lane & 31, h = lane >> 5;
   for (int st = 0; st < 2; st++)
     for (int j = 0; j < kTiles; j++)
       for (int r = 0; r < 16; r++) {
-        const int q = 32 * (q0_tile + 2 * j) + n;
-        const int prn = (r & 3) + 8 * (r >> 2) + 4 * h;
+        // register r of lane (n, h): row (r & 3) + 8 (r >> 2) + 4 h of D, column n; the rows are the A operand's
+        const int sub = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int q = 32 * (q0_tile + 2 * j) + (TR ? sub : n);
+        const int prn = TR ? n : sub;
         out[(st * 1024 + q) * 32 + prn] = acc[st][j][r];
       }
 }
@@ -214,12 +226,22 @@ int main()
   CHECK(hipMemcpy(d_chips, chipnib.data(), chipnib.size(), hipMemcpyHostToDevice));
 
   // ---- part 1: layout + exactness ------------------------------------------------------------------------------
-  for (int variant = 0; variant < 3; variant++) {
+  long part1_bad = 0;
+  // (variants 3..5: the grid kernel's own scales, 2^-13 on the chips and 2^0 / 2^1 / 2^3 on the vector; every value stays on the
+  //  result's 2^-13 grid and below 2^24 of it, so the f32 comparison is still exact)
+  for (int tr = 0; tr < 2; tr++)
+  for (int variant = 0; variant < 6; variant++) {
+    static const u32 kVecScale[6] = {kScaleOne, kScaleOne, 0x81818181u /* 2^2 */, kScaleOne, 0x80808080u /* 2^1 */, 0x82828282u /* 2^3 */};
+    static const float kVecMult[6] = {1.f, 1.f, 4.f, 1.f, 2.f, 8.f};
     const int n_pass = variant == 0 ? 1 : 17;
-    const u32 scale_b = variant == 2 ? 0x81818181u : kScaleOne;   // E8M0 129 = 2^2
-    const float mult = (variant == 2 ? 4.f : 1.f) * n_pass;
+    const u32 scale_b = kVecScale[variant];
+    const u32 scale_c = variant >= 3 ? 0x72727272u : kScaleOne;   // E8M0 114 = 2^-13
+    const float mult = kVecMult[variant] * (variant >= 3 ? 1.f / 8192.f : 1.f) * n_pass;
     CHECK(hipMemset(d_out, 0, 2 * 1024 * 32 * 4));
-    hipLaunchKernelGGL(k_check, dim3(1), dim3(64 * kWaves), 0, 0, d_vec, d_chips, d_out, n_pass, scale_b);
+    if (tr)
+      hipLaunchKernelGGL(k_check<true>, dim3(1), dim3(64 * kWaves), 0, 0, d_vec, d_chips, d_out, n_pass, scale_b, scale_c);
+    else
+      hipLaunchKernelGGL(k_check<false>, dim3(1), dim3(64 * kWaves), 0, 0, d_vec, d_chips, d_out, n_pass, scale_b, scale_c);
     CHECK(hipDeviceSynchronize());
     std::vector<float> out(2 * 1024 * 32);
     CHECK(hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost));
@@ -240,9 +262,13 @@ int main()
           }
           if (fabs(want) > maxabs) maxabs = fabs(want);
         }
-    printf("part 1 variant %d (%d passes, data scale %s): %ld mismatches of %d, max |value| %.0f\n", variant, n_pass,
-           variant == 2 ? "2^2" : "2^0", bad, 2 * 1024 * 32, maxabs);
+    static const char *kVecName[6] = {"2^0", "2^0", "2^2", "2^0", "2^1", "2^3"};
+    printf("part 1%s variant %d (%d passes, data scale %s, chip scale %s%s): %ld mismatches of %d, max |value| %g\n", tr ? "T" : "",
+           variant, n_pass, kVecName[variant], variant >= 3 ? "2^-13" : "2^0", tr ? "; fragment = A, chips = B" : "", bad,
+           2 * 1024 * 32, maxabs);
+    part1_bad += bad;
   }
+  printf(part1_bad == 0 ? "part 1: layouts and exactness hold in both operand orders\n" : "part 1: MISMATCHES\n");
 
   // ---- part 2: throughput ----------------------------------------------------------------------------------------
   auto time_mode = [&](int mode, int n_wg, int n_pass) {
@@ -278,5 +304,5 @@ int main()
     for (int n_wg : {256, 1344})
       time_mode(mode, n_wg, 17);
   time_mode(2, 2688, 9);
-  return 0;
+  return part1_bad == 0 ? 0 : 1;
 }

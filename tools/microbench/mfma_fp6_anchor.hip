@@ -9,6 +9,10 @@
 //         scales with all four bytes equal and with only byte 0 set (pins which byte the opsel = 0 call reads)
 // Part 3  the kernel's way of feeding B: ONE packed six-bit stream per vector, lane (n, h) of fragment f takes the 192 bits at bit
 //         6 (32 (f + h) + n) with seven dword reads and six v_alignbit_b32 -- a Toeplitz product against the CPU
+// Transposed arm (parts 1T, 2T, 3T): the same three parts with the operands swapped -- A = the E3M2 vector (cbsz 3, the same six
+//         dwords per lane, dwords 6, 7 ignored, its scale on the A side), B = the FP4 chips (blgp 4, 2^-13 on the B side) -- so
+//         that D comes out transposed: register i of lane l = D[row (i & 3) + 8 (i >> 2) + 4 (l >> 5)][col l & 31], rows = the
+//         vector's columns (chip offsets), the lane = the PRN
 // Every part must print 0 mismatches for the hypothesis; the program's exit status says so.
 // Build: hipcc --offload-arch=gfx950 -O3 mfma_fp6_anchor.hip -o mfma_fp6_anchor
 #include <hip/hip_runtime.h>
@@ -29,7 +33,8 @@ typedef unsigned int u32;
 constexpr float kStart = 3.0f;       // accumulator start of every case: on the result's 2^-12 grid, every sum stays below 2^24 of it
 
 // One wave per case: acc = start; n_step MFMAs over a[case][step][lane][4] and b[case][step][lane][6]; out[case][lane][16].
-template <int BLGP>
+// TR: the operands swapped (b as A with format code BLGP in cbsz, a as B), the scales with them
+template <int BLGP, bool TR = false>
 __global__ __launch_bounds__(64) void k_cases(const u32 *a, const u32 *b, float *out, int n_step, u32 scale_a, u32 scale_b)
 {
   const int lane = threadIdx.x, cs = blockIdx.x;
@@ -41,7 +46,10 @@ __global__ __launch_bounds__(64) void k_cases(const u32 *a, const u32 *b, float 
     const u32 *pb = b + ((size_t)(cs * n_step + s) * 64 + lane) * 6;
     const v8i fa = {(int)pa[0], (int)pa[1], (int)pa[2], (int)pa[3], 0, 0, 0, 0};
     const v8i fb = {(int)pb[0], (int)pb[1], (int)pb[2], (int)pb[3], (int)pb[4], (int)pb[5], -1, -1};   // dwords 6, 7 must not matter
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fa, fb, acc, 4, BLGP, 0, scale_a, 0, scale_b);
+    if constexpr (TR)
+      acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb, fa, acc, BLGP, 4, 0, scale_b, 0, scale_a);
+    else
+      acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fa, fb, acc, 4, BLGP, 0, scale_a, 0, scale_b);
   }
   for (int r = 0; r < 16; r++)
     out[((size_t)cs * 64 + lane) * 16 + r] = acc[r];
@@ -50,6 +58,8 @@ __global__ __launch_bounds__(64) void k_cases(const u32 *a, const u32 *b, float 
 constexpr int kStreamDwords = 384 + 8;   // 2048 six-bit codes + slack for the seventh dword of the last window
 
 // Part 3: one workgroup of 8 waves, wave w owns q-tiles w, w + 8, w + 16, w + 24; out[q][prn] = sum_c chip[prn][c] * val[q + c].
+// TR: the fragment is A, the chips are B: lane (n, h) then holds PRN n at chip offsets 32 tile + (r & 3) + 8 (r >> 2) + 4 h
+template <bool TR>
 __global__ __launch_bounds__(512) void k_toeplitz(const u32 *stream, const u32 *chips /* [16][64 lanes][4] */, float *out, u32 scale_a, u32 scale_b)
 {
   __shared__ u32 s6[kStreamDwords];
@@ -74,10 +84,18 @@ __global__ __launch_bounds__(512) void k_toeplitz(const u32 *stream, const u32 *
         fb[i] = (int)__builtin_amdgcn_alignbit(d[i + 1], d[i], sh);      // ({hi, lo} >> sh)[31:0]; sh = 0 passes d[i]
       const u32 *pa = chips + ((size_t)kappa * 64 + lane) * 4;
       const v8i fa = {(int)pa[0], (int)pa[1], (int)pa[2], (int)pa[3], 0, 0, 0, 0};
-      acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fa, fb, acc, 4, 3, 0, scale_a, 0, scale_b);
+      if constexpr (TR)
+        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb, fa, acc, 3, 4, 0, scale_b, 0, scale_a);
+      else
+        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fa, fb, acc, 4, 3, 0, scale_a, 0, scale_b);
     }
-    for (int r = 0; r < 16; r++)
-      out[(size_t)(32 * tile + n) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
+    for (int r = 0; r < 16; r++) {
+      const int sub = (r & 3) + 8 * (r >> 2) + 4 * h;
+      if constexpr (TR)
+        out[(size_t)(32 * tile + sub) * 32 + n] = acc[r];
+      else
+        out[(size_t)(32 * tile + n) * 32 + sub] = acc[r];
+    }
   }
 }
 
@@ -104,7 +122,7 @@ struct Cases {
   std::vector<uint8_t> code;   // [case][step][64 k][32 n]  six-bit codes
 };
 
-static long run_cases(const Cases &c, int blgp, u32 scale_a, u32 scale_b, double mult, const char *what)
+static long run_cases(const Cases &c, int blgp, u32 scale_a, u32 scale_b, double mult, const char *what, bool transposed = false)
 {
   const size_t n_ms = (size_t)c.n_case * c.n_step;
   std::vector<u32> a(n_ms * 64 * 4, 0), b(n_ms * 64 * 6, 0);
@@ -126,7 +144,11 @@ static long run_cases(const Cases &c, int blgp, u32 scale_a, u32 scale_b, double
   CHECK(hipMalloc(&d_out, (size_t)c.n_case * 64 * 16 * 4));
   CHECK(hipMemcpy(d_a, a.data(), a.size() * 4, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-  if (blgp == 3)
+  if (transposed && blgp == 3)
+    hipLaunchKernelGGL((k_cases<3, true>), dim3(c.n_case), dim3(64), 0, 0, d_a, d_b, d_out, c.n_step, scale_a, scale_b);
+  else if (transposed)
+    hipLaunchKernelGGL((k_cases<2, true>), dim3(c.n_case), dim3(64), 0, 0, d_a, d_b, d_out, c.n_step, scale_a, scale_b);
+  else if (blgp == 3)
     hipLaunchKernelGGL(k_cases<3>, dim3(c.n_case), dim3(64), 0, 0, d_a, d_b, d_out, c.n_step, scale_a, scale_b);
   else
     hipLaunchKernelGGL(k_cases<2>, dim3(c.n_case), dim3(64), 0, 0, d_a, d_b, d_out, c.n_step, scale_a, scale_b);
@@ -140,7 +162,9 @@ static long run_cases(const Cases &c, int blgp, u32 scale_a, u32 scale_b, double
   for (int cs = 0; cs < c.n_case; cs++)
     for (int lane = 0; lane < 64; lane++)
       for (int r = 0; r < 16; r++) {
-        const int n = lane & 31, m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        // D[row][col]: register r of lane l holds row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31; rows belong to A
+        const int sub = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int n = transposed ? sub : lane & 31, m = transposed ? lane & 31 : sub;
         double want = 0;
         for (int s = 0; s < c.n_step; s++) {
           const size_t ms = (size_t)cs * c.n_step + s;
@@ -207,6 +231,12 @@ int main()
   hyp_bad += run_cases(p2, 3, 0x7F7F7F72u, 0x7F7F7F80u, mult, "part 2 chained 272 MFMAs, scale in byte 0 only, opsel 0");
   run_cases(p2, 3, 0x727F7F7Fu, 0x807F7F7Fu, mult, "part 2 scale in byte 3 only, opsel 0 (expected to MISMATCH)");
 
+  // ---- the transposed arm of parts 1 and 2: E3M2 as A (cbsz 3), chips as B (blgp 4), each scale with its operand ----------------
+  hyp_bad += run_cases(p1, 3, kA, kB, mult, "part 1T cbsz 3 (E3M2 as A) x blgp 4, 17 values x 32 positions x 64 lanes, D transposed", true);
+  run_cases(p1, 2, kA, kB, mult, "part 1T cbsz 2 (E2M3 as A) on the same bits, for contrast", true);
+  hyp_bad += run_cases(p2, 3, kA, kB, mult, "part 2T chained 272 MFMAs, 2^1 on the A side, 2^-13 on the B side, bytes all equal", true);
+  hyp_bad += run_cases(p2, 3, 0x7F7F7F72u, 0x7F7F7F80u, mult, "part 2T chained 272 MFMAs, scale in byte 0 only, opsel 0", true);
+
   // ---- part 3: one packed stream, windows by funnel shift ---------------------------------------------------------------------
   {
     std::vector<int> sums(2048 + 64, 0);
@@ -236,26 +266,33 @@ int main()
     CHECK(hipMalloc(&d_out, 1024 * 32 * 4));
     CHECK(hipMemcpy(d_s, stream.data(), stream.size() * 4, hipMemcpyHostToDevice));
     CHECK(hipMemcpy(d_a, a.data(), a.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_toeplitz, dim3(1), dim3(512), 0, 0, d_s, d_a, d_out, kA, kB);
-    CHECK(hipDeviceSynchronize());
-    std::vector<float> out(1024 * 32);
-    CHECK(hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost));
-    long bad = 0;
-    for (int q = 0; q < 1024; q++)
-      for (int p = 0; p < 32; p++) {
-        double want = 0;
-        for (int c = 0; c < 1024; c++)
-          want += chip[p * 1024 + c] * (8 - sums[q + c]);
-        want = want * mult + kStart;
-        if (out[q * 32 + p] != (float)want) {
-          if (bad < 4)
-            printf("  mismatch q %d prn %d: got %.6f want %.6f\n", q, p, out[q * 32 + p], want);
-          bad++;
+    for (int tr = 0; tr < 2; tr++) {
+      CHECK(hipMemset(d_out, 0, 1024 * 32 * 4));
+      if (tr)
+        hipLaunchKernelGGL(k_toeplitz<true>, dim3(1), dim3(512), 0, 0, d_s, d_a, d_out, kA, kB);
+      else
+        hipLaunchKernelGGL(k_toeplitz<false>, dim3(1), dim3(512), 0, 0, d_s, d_a, d_out, kA, kB);
+      CHECK(hipDeviceSynchronize());
+      std::vector<float> out(1024 * 32);
+      CHECK(hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost));
+      long bad = 0;
+      for (int q = 0; q < 1024; q++)
+        for (int p = 0; p < 32; p++) {
+          double want = 0;
+          for (int c = 0; c < 1024; c++)
+            want += chip[p * 1024 + c] * (8 - sums[q + c]);
+          want = want * mult + kStart;
+          if (out[q * 32 + p] != (float)want) {
+            if (bad < 4)
+              printf("  mismatch q %d prn %d: got %.6f want %.6f\n", q, p, out[q * 32 + p], want);
+            bad++;
+          }
         }
-      }
-    printf("part 3 Toeplitz from one packed stream, 7 dwords + 6 alignbit per fragment: %ld mismatches of %d\n", bad, 1024 * 32);
-    hyp_bad += bad;
+      printf("part 3%s Toeplitz from one packed stream, 7 dwords + 6 alignbit per fragment%s: %ld mismatches of %d\n", tr ? "T" : "",
+             tr ? ", the fragment as A" : "", bad, 1024 * 32);
+      hyp_bad += bad;
+    }
   }
-  printf(hyp_bad == 0 ? "LAYOUT PINNED: blgp 3, code j at bit 6 j LSB first, scale byte 0 (opsel 0)\n" : "LAYOUT NOT PINNED\n");
+  printf(hyp_bad == 0 ? "LAYOUT PINNED: blgp 3 / cbsz 3, code j at bit 6 j LSB first, scale byte 0 (opsel 0), D transposes with the operands\n" : "LAYOUT NOT PINNED\n");
   return hyp_bad == 0 ? 0 : 1;
 }
