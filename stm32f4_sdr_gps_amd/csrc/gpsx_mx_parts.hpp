@@ -786,7 +786,9 @@ __device__ __forceinline__ void mx_half_switch(const MxShared &sh, int lane, int
 //   sums carry 0x4B000000 per term, four terms per PRN and sample offset: they start at -4 x 0x4B000000 (mod 2^32).
 //   (Tried: taking the small path on trust and checking the best keys afterwards -- one test per 64 hypotheses, a second round
 //   on the exact path for the PRN groups that show a radius >= 1024 -- saves the 5/8: 1 % faster on noise, 2.5 % slower
-//   on the strong test signal, same-box A/B; not kept.)
+//   on the strong test signal, same-box A/B; not kept.  The transposed single-block form, where a lane is one PRN, does it per
+//   wave with a predictor for the strong signal -- mxt_epilogue, k_acq_mx.hip: 7 instructions per hypothesis + 3 per lane and
+//   sample offset on the trusted path, these 7 5/8 on its careful path.)
 constexpr u32 kRootBias = 0x4B000000u;
 template <int NT>
 __device__ __forceinline__ void mx_epilogue_single(MxShared &sh, int lane, const u32 (&kq)[NT], int t0,

@@ -36,5 +36,15 @@ constexpr uint32_t gpsx_mxt_global_key(uint32_t local_key, int q_first, int half
   const int q = gpsx_mxt_q_of_local(q_first, local);
   return ((local_key >> kGpsxMxtKeyShift) << kGpsxKeyShift) | (uint32_t)(2047 - (2 * q + half));
 }
+// The epilogue's trust limit (mxt_epilogue).  The small path's root bits are kGpsxMxtRootBias + magnitude; they are
+// taken for all 64 hypotheses of a lane without a radius test, and the lane's winning local key is compared once with the local key
+// of (magnitude kGpsxMxtTrustRadius, code 0), mod 2^32 as the keys themselves are.  Magnitudes stay below 2^14 (11 585 at the most),
+// so a local key is monotone in (magnitude, code): winner >= limit <=> some hypothesis of the lane has magnitude >= 1024.
+constexpr uint32_t kGpsxMxtRootBias = 0x4B000000u;         // the f32 pattern of 2^23: what the rounding fma leaves above the root
+constexpr int kGpsxMxtTrustRadius = 1024;                  // the small path is used below it (and proven below 1182)
+constexpr int kGpsxMxtHotRadius = 768;                     // a winner from here on sends the wave's NEXT epilogue down the careful path
+constexpr uint32_t gpsx_mxt_limit_key(int radius) { return (kGpsxMxtRootBias + (uint32_t)radius) << kGpsxMxtKeyShift; }
+constexpr uint32_t gpsx_mxt_trust_limit_key() { return gpsx_mxt_limit_key(kGpsxMxtTrustRadius); }
+constexpr uint32_t gpsx_mxt_hot_limit_key() { return gpsx_mxt_limit_key(kGpsxMxtHotRadius); }
 // the 8-PRN sharding group a lane's results belong to (the lane is the PRN)
 constexpr int gpsx_mxt_group(int lane) { return (lane & 31) >> 3; }

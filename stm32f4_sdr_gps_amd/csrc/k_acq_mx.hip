@@ -747,49 +747,105 @@ __device__ __forceinline__ void mxt_half_switch(const MxSharedCore &sh, const fl
 // of mx_epilogue_single are), joined at the end; the winner becomes the global key once, and the wave issues one ds_max_u32 and
 // one ds_add_u32, each lane at its own word.  The root bits carry 0x4B000000: it leaves a global key in the shift, and the sum
 // starts at -64 x 0x4B000000 (mod 2^32).
-__device__ __forceinline__ void mxt_epilogue(u32 *part, int lane, int q0_tile, int t0, const v16f (&acc)[2][kMxTiles])
+//
+// TRUST, VERIFY, REDO.  The radius test costs 5 vector instructions and two branches per group and fires only next to a satellite,
+// so the lane's 64 hypotheses first go down the small path WITHOUT it (TRUST = true: 7 instructions per hypothesis, issued phase
+// by phase -- sixteen clip-squares, eight sums, eight roots, eight fmas, eight keys, the chains -- so that only the chain links
+// follow their producers directly), and the joined winner is compared ONCE with the local key of magnitude 1024
+// (gpsx_mxt_trust_limit_key).  A hypothesis at or beyond radius 1024 leaves root bits >= kRootBias + 1024 on the small path whatever
+// else is wrong with them (the guard factor: the product is never below the true root), and local keys are monotone in the root
+// bits below 2^14, so a winner below the limit says that every hypothesis of the lane was inside the small path's proven range.
+// If any lane of the wave is at or above it, the wave throws the chains away and runs the group-tested code (TRUST = false: the
+// careful path, 7 5/8 per hypothesis) over the same accumulators -- an epilogue changes none of them, and nothing has left the
+// registers before the check.  A satellite's peak region spans some 32 consecutive sample offsets of one lane: `hot`, wave-uniform
+// and carried from one epilogue of the wave to its next, says that some winner reached magnitude kGpsxMxtHotRadius last time, and
+// sends this one down the careful path at once, so a strong signal costs one redo on entry and the careful path's price inside.
+// Results never depend on it.
+static_assert(kGpsxMxtRootBias == kRootBias, "gpsx_mx_transposed.hpp's limit keys carry the small path's bias");
+static_assert(kGpsxMxtHotRadius <= kGpsxMxtTrustRadius, "mxt_epilogue tests the limit only where the predictor's radius is reached");
+// The end of a phase of the trust path: all eight values pass through one empty asm statement, so every instruction of the
+// next phase is behind every instruction of this one (__builtin_amdgcn_sched_barrier alone does not order the arithmetic, which
+// is placed before the scheduler sees it).  With the branch gone the compiler emits the phases in this order by itself; what the
+// statement adds is the s_nop 0 the hazard recogniser puts behind an asm statement, five per group.  Measured, not explained
+// (EXPERIMENTS round 14, same-box A/B on three boxes): without the fences the kernel is 2.0 % faster than the parent at amplitude
+// 0.25 but 0.9 - 1.1 % SLOWER at 1.0; with them 1.6 % faster at 0.25, 1.2 % at 0.5 and 0.2 - 0.4 % at 1.0 -- the form that is
+// never slower is the one kept.
+template <typename T>
+__device__ __forceinline__ void mxt_phase(T (&v)[8])
 {
-  const int b = t0 & 7, half = t0 >> 3;
+  asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <bool TRUST>
+__device__ __forceinline__ u32 mxt_chains(const v16f (&acc)[2][kMxTiles], u32 &sum)
+{
   u32 best[4], total[4];
 #pragma unroll
   for (int c = 0; c < 4; c++) {
     best[c] = 0;
     total[c] = c ? 0u : 0u - (u32)kGpsxMxtLocals * kRootBias;
   }
-  mx_round_toward_zero();
 #pragma unroll
   for (int jp = 0; jp < kMxTiles; jp += 2) {
 #pragma unroll
     for (int r0 = 0; r0 < 16; r0 += 4) {
-      float ev[8];
-      u32 e_max = 0;
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        ev[i] = clip_square_sum(acc[0][jp + (i >> 2)][r0 + (i & 3)], acc[1][jp + (i >> 2)][r0 + (i & 3)]);
-        e_max = max(e_max, __float_as_uint(ev[i]));
-      }
-      const bool small = __builtin_amdgcn_ballot_w64(e_max >= 0x3C800000u /* 2^20 / 2^26 as f32 */) == 0;
       u32 bits[8];
-      if (__builtin_expect(small, 1)) {
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-          bits[i] = root_bits_small(ev[i]);
-      } else {
-        float ci[8], cq[8];
+      if constexpr (TRUST) {
+        float si[8], sq[8], ev[8], rt[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          ci[i] = acc[0][jp + (i >> 2)][r0 + (i & 3)];
-          cq[i] = acc[1][jp + (i >> 2)][r0 + (i & 3)];
+          si[i] = mx_clip_square(acc[0][jp + (i >> 2)][r0 + (i & 3)]);
+          sq[i] = mx_clip_square(acc[1][jp + (i >> 2)][r0 + (i & 3)]);
         }
-        mx_roots_exact<8>(ci, cq, bits);
+        mxt_phase(si);
+        mxt_phase(sq);
 #pragma unroll
         for (int i = 0; i < 8; i++)
-          bits[i] += kRootBias;
+          ev[i] = si[i] + sq[i];
+        mxt_phase(ev);
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          rt[i] = __builtin_amdgcn_sqrtf(ev[i]);
+        mxt_phase(rt);
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          bits[i] = __float_as_uint(__builtin_fmaf(rt[i], kRootGuard, 8388608.0f));   // (root_bits_small, a phase apart)
+        mxt_phase(bits);
+      } else {
+        float ev[8];
+        u32 e_max = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          ev[i] = clip_square_sum(acc[0][jp + (i >> 2)][r0 + (i & 3)], acc[1][jp + (i >> 2)][r0 + (i & 3)]);
+          e_max = max(e_max, __float_as_uint(ev[i]));
+        }
+        const bool small = __builtin_amdgcn_ballot_w64(e_max >= 0x3C800000u /* 2^20 / 2^26 as f32 */) == 0;
+        if (__builtin_expect(small, 1)) {
+#pragma unroll
+          for (int i = 0; i < 8; i++)
+            bits[i] = root_bits_small(ev[i]);
+        } else {
+          float ci[8], cq[8];
+#pragma unroll
+          for (int i = 0; i < 8; i++) {
+            ci[i] = acc[0][jp + (i >> 2)][r0 + (i & 3)];
+            cq[i] = acc[1][jp + (i >> 2)][r0 + (i & 3)];
+          }
+          mx_roots_exact<8>(ci, cq, bits);
+#pragma unroll
+          for (int i = 0; i < 8; i++)
+            bits[i] += kRootBias;
+        }
       }
+      u32 key[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        key[i] = gpsx_mxt_local_key(bits[i], jp + (i >> 2), r0 + (i & 3));
+      if constexpr (TRUST)
+        mxt_phase(key);
 #pragma unroll
       for (int rr = 0; rr < 4; rr++) {
-        const u32 k0 = gpsx_mxt_local_key(bits[rr], jp, r0 + rr), k1 = gpsx_mxt_local_key(bits[4 + rr], jp + 1, r0 + rr);
-        best[rr] = max(max(best[rr], k0), k1);
+        best[rr] = max(max(best[rr], key[rr]), key[4 + rr]);
         total[rr] = total[rr] + bits[rr] + bits[4 + rr];
       }
       // (pinned in program order, as in mx_epilogue_single)
@@ -799,11 +855,37 @@ __device__ __forceinline__ void mxt_epilogue(u32 *part, int lane, int q0_tile, i
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  sum = total[0] + total[1] + total[2] + total[3];
+  return max(max(best[0], best[1]), max(best[2], best[3]));
+}
+// `hot`: in, take the careful path at once; out, some lane's winner reached kGpsxMxtHotRadius (both wave-uniform)
+__device__ __forceinline__ void mxt_epilogue(u32 *part, int lane, int q0_tile, int t0, v16f (&acc)[2][kMxTiles], bool &hot)
+{
+  const int b = t0 & 7, half = t0 >> 3;
+  u32 winner = 0, sum = 0;
+  bool careful = hot;
+  mx_round_toward_zero();
+  if (!careful) {
+    winner = mxt_chains<true>(acc, sum);
+    // (one compare where nothing is near: a winner below the predictor's radius is below the limit)
+    hot = __builtin_amdgcn_ballot_w64(winner >= gpsx_mxt_hot_limit_key()) != 0;
+    careful = hot && __builtin_amdgcn_ballot_w64(winner >= gpsx_mxt_trust_limit_key()) != 0;
+  }
+  if (careful) {
+    // (the accumulators made opaque: left alone, the compiler keeps the trust path's 64 sums of squares for this path -- in scratch)
+#pragma unroll
+    for (int s = 0; s < 2; s++)
+#pragma unroll
+      for (int j = 0; j < kMxTiles; j++)
+        asm volatile("" : "+v"(acc[s][j]));
+    winner = mxt_chains<false>(acc, sum);
+    hot = __builtin_amdgcn_ballot_w64(winner >= gpsx_mxt_hot_limit_key()) != 0;
+  }
   mx_round_to_nearest();
-  const u32 key = gpsx_mxt_global_key(max(max(best[0], best[1]), max(best[2], best[3])), 32 * q0_tile + 4 * (lane >> 5), half);
+  const u32 key = gpsx_mxt_global_key(winner, 32 * q0_tile + 4 * (lane >> 5), half);
   u32 *slot = part + (2 * b) * 64 + lane;   // part[b][0][h][PRN]; the sum 64 words on
   atomicMax(slot, key);
-  atomicAdd(slot + 64, total[0] + total[1] + total[2] + total[3]);
+  atomicAdd(slot + 64, sum);
 }
 __device__ __forceinline__ void mx_fill_fold_lut(MxFold &fold, int t)   // threads 0..63
 {
@@ -888,8 +970,9 @@ __device__ __forceinline__ void mx_single(MxSingleShared &shs, const AcqParams &
       mxt_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
     }
     mx_anchor_pass(sh, &sh.e8[0][0][0][0], lane, q0_tile, acc);
+    bool hot = false;              // (the epilogues' predictor: per wave, clear for its first one)
     if (!role)                     // half step 1 of role 0, under role 1's pass
-      mxt_epilogue(part, lane, q0_tile, 0, acc);
+      mxt_epilogue(part, lane, q0_tile, 0, acc, hot);
     __syncthreads();               // half step 2: everybody is done with the anchor vector; the planes, t_lut and hs are published
     mx_vector_build<true>(sh, 2, opaque(tid), &fold);
 #pragma unroll 1
@@ -912,7 +995,7 @@ __device__ __forceinline__ void mx_single(MxSingleShared &shs, const AcqParams &
           mxt_half_switch(sh, shs.hs, lane, q0_tile, acc, prm.win_start, prm.win_stop);
       }
       if (active && (x & 1) && p >= 1)
-        mxt_epilogue(part, lane, q0_tile, p - 1, acc);
+        mxt_epilogue(part, lane, q0_tile, p - 1, acc, hot);
     }
   }
   __syncthreads();
