@@ -39,7 +39,8 @@ extern "C" {
                                             * gpsx_wlock_cn0_dbhz likewise; gpsx_track_loop_weighted_sync_multi(_dev) with
                                             * gpsx_wmulti_t and gpsx_wobs_pseudoranges_rx too; gpsx_wfix(_dev) with gpsx_wfix_cfg_t
                                             * and gpsx_wfix_t likewise; gpsx_wfde(_dev) with gpsx_wfde_cfg_t and gpsx_wfde_t too;
-                                            * gpsx_wvel(_dev) with gpsx_wvel_cfg_t and gpsx_wvel_t likewise. */
+                                            * gpsx_wvel(_dev) with gpsx_wvel_cfg_t and gpsx_wvel_t likewise;
+                                            * gpsx_wkf(_dev) with gpsx_wkf_cfg_t, gpsx_wkf_state_t and gpsx_wkf_t too. */
 #define GPSX_BYTES_PER_MS       2046       /* PM/config.h:26-27: 16368 one-bit samples                    */
 #define GPSX_PHASES_BYTE        2046       /* code-phase hypotheses at byte (0.5 chip) granularity         */
 #define GPSX_PHASES_FINE        16368      /* byte offset x 8 replica bit shifts (PM/GPS/tracking.c:23)    */
@@ -1400,6 +1401,158 @@ int gpsx_wvel_dev(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *
                   const gpsx_wfix_t *d_fix, int n_rx, gpsx_wvel_t *d_vel);
 int gpsx_wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
               const gpsx_wfix_t *fix, int n_rx, gpsx_wvel_t *vel);
+
+/* ---- EXTENSION, not in the reference: weighted navigation filter -- every receiver's position, velocity and clock, carried from ------
+ *      launch to launch in a resident state, on the device
+ * gpsx_wfix / gpsx_wfde / gpsx_wvel keep no state: every launch's noise goes into that launch's fix, and a receiver with fewer than
+ * four usable slots gets nothing.  gpsx_wkf(_dev) is a STATEFUL stage behind gpsx_wobs_dev and gpsx_weph_dev (and gpsx_wlock_dev,
+ * gpsx_wfix_dev or gpsx_wfde_dev, gpsx_wvel_dev): an eight-state Kalman filter per receiver -- ECEF position, receiver clock term b (m),
+ * velocity, clock drift d (m/s), in that order -- whose 384-byte gpsx_wkf_state_t lives in device memory (all zero: a fresh receiver)
+ * and which returns one 240-byte gpsx_wkf_t per receiver and launch.  It is tightly coupled: its measurements are every slot's
+ * pseudorange and carrier frequency, not the fix records, so it updates with one, two or three satellites too.  It must be called on
+ * every launch of a stream, as gpsx_wobs.  Neither the reference nor csrc/gpsx_pvt.cpp has a filter; this text is the definition.
+ * Nothing existing changes.
+ *
+ * Definition, per receiver; all arithmetic in IEEE double, uncontracted, sums in ascending index order unless a butterfly is named.
+ * c = 299792458, ms = 299792.458 (c per millisecond), W = 604 800 000.  P is symmetric; P_ij below names its element, the state holds
+ * the upper triangle row by row (P_00 .. P_07, P_11 .. P_17, ..., P_77: 36 doubles).
+ *   0 state        BAD if the state has flag bits beyond GPSX_WKF_STATE_INIT, an rcv_ms outside 0 .. W - 1, an x or P element that
+ *                  is not finite, or (with INIT) a P_ii <= 0.  A BAD state stays as it was, its record is all zero but for
+ *                  flags = GPSX_WKF_BAD, and the call reports GPSX_EINVAL (gpsx_wkf after its wait, gpsx_wkf_dev at the next
+ *                  gpsx_synchronize), as gpsx_wobs does.
+ *   1 time base    the filter's clock is the sample count, not gpsx_wfix's reference slot (whose clock term jumps with the
+ *                  reference): rcv_ms is the receiver clock's reading, in ms of the week, of sample 0 of the block that follows
+ *                  the launch, and b = c (receiver clock - GPS time) moves with the oscillator alone.  An initialised receiver
+ *                  first advances: rcv_ms += n_blocks; rcv_ms >= W: rcv_ms -= W, week += 1.  dt = (double)n_blocks * 1e-3.
+ *   2 init         a state without INIT reads d_fix[r] (d_fix NULL: as a record without FIX).  Without GPSX_WFIX_FIX it stays as
+ *                  it is: NOT_INIT, nothing counted, the state not written.  With it: u = 1000 (rx_tow_s - dtr_s), m = rint(u),
+ *                  b = ms (m - u), rcv_ms = (int64)m, week = the record's; rcv_ms >= W: rcv_ms -= W, week += 1; rcv_ms < 0:
+ *                  rcv_ms += W, week -= 1.  x = (rr, b, vel, c drift_s_s) with vel and drift_s_s from d_vel[r] if d_vel is given and
+ *                  that record has GPSX_WVEL_VEL, else zeros.  P = diag(p0_pos^2 x 3, p0_clk^2, p0_vel^2 x 3, p0_drift^2).
+ *                  n_starved = 0, n_init += 1.  No prediction and no update in this call: INIT (an |m| >= 2^53, an rcv_ms still
+ *                  outside 0 .. W - 1, or anything of step 12's x, P or output that is not finite: NOT_INIT instead).  Initialised receivers never read d_fix or d_vel.
+ *   3 prediction   constant velocity, F = [[I4, dt I4], [0, I4]]: x-_i = x_i + dt x_(4+i), x-_(4+i) = x_(4+i), i = 0 .. 3, and
+ *                  P- = F P F^T + Q in three 4 x 4 blocks (i, j = 0 .. 3):
+ *                    P-_(i,j)     = ((P_(i,j) + dt (P_(i,4+j) + P_(j,4+i))) + (dt dt) P_(4+i,4+j)) [+ qpp_i if i == j]
+ *                    P-_(i,4+j)   = (P_(i,4+j) + dt P_(4+i,4+j)) [+ qpv_i if i == j]
+ *                    P-_(4+i,4+j) = P_(4+i,4+j) [+ qvv_i if i == j]
+ *                  with t3 = dt dt dt / 3, t2 = dt dt / 2; position axes i = 0 .. 2: qpp = q_acc t3, qpv = q_acc t2, qvv = q_acc dt;
+ *                  clock i = 3: qpp = q_clk_f dt + q_clk_g t3, qpv = q_clk_g t2, qvv = q_clk_g dt.
+ *   4 slots        slot j is usable as in gpsx_wfix's step 1 without the lock record (observable VALID, record VALID).  It may
+ *                  give a pseudorange row if d_lock is NULL or its lock record has GPSX_WLOCK_CODE, and a Doppler row if d_lock is
+ *                  NULL or that record has GPSX_WLOCK_CARRIER, and its if_freq_offset_hz is finite.  Both need svh == 0.
+ *   5 satellite    one evaluation per slot at the transmit time its own clock reads, gpsx_wvel's step 2 with tx_ms + k_j in tx_ms'
+ *                  place (k_j = 0 at first: step 7): t_sv, tc, t, tk, position ps, velocity vs and clock rate d', no satellite
+ *                  if |tk| > 7201, A <= 0 or Kepler's iteration needs 30 steps.  The clock offset is gpsx_wfix's
+ *                  dts = poly(fold(t - toc)) - 2 sqrt(mu A) e sin E / c^2 (without its "dts == 0" fallback), tgd = c * the record's,
+ *                  the URA variance gpsx_wfix's table (sva outside 0 .. 14: 6144 m), squared.
+ *   6 rows         the pseudorange, gpsx_wobs_pseudoranges' formula with rcv_ms in the reference's place, int64 and single double
+ *                  operations, no reference slot and no offset_ms:
+ *                    pr_j = 299792458e-3 * ((double)fold_ms(rcv_ms - (tx_ms_j + k_j)) + (double)code_phase_fine_j / 16368.0)
+ *                  (fold_ms: gpsx_wobs_pseudoranges' fold into -W/2 .. W/2 - 1).  The pseudorange row is gpsx_wfix's row at x-
+ *                  (step 4 there): no row if |ps| < Re, rho = range + Sagnac <= 0, el < 0; ecef2pos of x-_0..2 (30 steps at most),
+ *                  Klobuchar with cfg.ion[] (all zero: the default set) at tow = (double)rcv_ms / 1000, Saastamoinen at humidity
+ *                  0.7;  v = (pr - tgd) - (rho + dion + dtrp + x-_3 - c dts),  h = (-e, 1) on states 0 .. 3,
+ *                  sig2 = gpsx_wfix's four variance terms (in its order) + sig_pr_m^2.
+ *                  The Doppler row is gpsx_wvel's step 3 with rr = x-_0..2: no row if the range is 0; a_j on states 4 .. 7,
+ *                  y = gpsx_wvel's y_j - (a_j . x-_4..7) (ascending), sig2 = sig_dop_mps^2; f_j and the code phase are age_blocks
+ *                  old and are not extrapolated, as in the solvers.
+ *   7 repair       a slot with GPSX_WOBS_AMBIGUOUS that gives a pseudorange row: k = (int)rint(v / ms).  |k| > 1: the row is
+ *                  rejected (rej_pr_mask).  k = +-1: k_j = k, bit j of plus_mask / minus_mask (gpsx_wfde's convention: tx_ms is
+ *                  corrected by k_j), and steps 5 and 6 are evaluated ONCE more for this slot at tx_ms + k_j -- both rows, without
+ *                  a second repair -- so a repaired slot gives bit for bit what the unshifted observable would.
+ *   8 gate         every row: s = h P- h^T + sig2 (over the row's 4 x 4 block, sum_i h_i (sum_j P-_ij h_j)), rejected if
+ *                  v v > (gate gate) s or if v or s is not finite (rej_pr_mask / rej_dop_mask); the two rows of a slot are judged
+ *                  apart.  n_pr, n_dop, pr_mask, dop_mask: the accepted rows.  nis_pr = sum v v / s over them, nis_dop likewise.
+ *   9 update       information form, independent of the rows' order: with I = sum h^T h / sig2 (the upper-left 4 x 4 block from the
+ *                  pseudorange rows, the lower-right from the Doppler rows: 10 + 10 sums, each term (h_i h_j) / sig2) and
+ *                  g = sum h^T v / sig2 (4 + 4, each term (h_i v) / sig2):  L = (P-)^-1 + I,  P+ = L^-1,  x+ = x- + P+ g.
+ *                  Both inverses by INV below.  No accepted row at all: x+ = x-, P+ = P-, COAST.  Otherwise UPDATED.
+ *                  INV(N), 8 x 8: Cholesky N = L L^T column by column, p_j = N_jj - l_j0^2 - ... - l_j,j-1^2, gpsx_wfix's pivot rule
+ *                  (p_0 <= 0 or p_j <= 1e-10 N_jj fails), l_jj = sqrt(p_j), l_ij = (N_ij - l_i0 l_j0 - ... ) / l_jj; M = L^-1 with
+ *                  m_jj = 1 / l_jj, m_ij = -(l_ij m_jj + ... + l_i,i-1 m_i-1,j) / l_ii; N^-1_ij = the sum over
+ *                  k = max(i, j) .. 7 of m_ki m_kj.  A failed pivot in either: LOST.
+ *  10 starvation   no accepted pseudorange row: n_starved += 1, else n_starved = 0.  n_starved > max_coast: LOST.
+ *  11 steering     x+_3 > ms / 2: x+_3 -= ms, rcv_ms -= 1 (rcv_ms < 0: += W, week -= 1); x+_3 < -ms / 2: x+_3 += ms, rcv_ms += 1
+ *                  (rcv_ms >= W: -= W, week += 1); STEERED; once per call.  The pseudoranges of the next call follow rcv_ms.
+ *  12 output       rr = x+_0..2, clk_m = x+_3, vel = x+_4..6, cdrift_mps = x+_7, geo = ecef2pos(rr), enu = vel in the east / north /
+ *                  up frame at geo (gpsx_wvel's formula), sigma[i] = (float)sqrt(P+_ii), the counts, masks and sums of steps 7 - 9,
+ *                  rcv_ms, week, n_starved.  flags: exactly one of INIT / NOT_INIT / UPDATED / COAST / LOST / BAD, and with UPDATED or
+ *                  COAST the modifiers REPAIRED (a plus or minus bit), REJECTED (a reject bit), STEERED.  INIT fills rr .. sigma,
+ *                  rcv_ms and week.  Anything in x+, P+, geo, enu, sigma, nis_pr or nis_dop that is not finite: LOST.  A LOST,
+ *                  NOT_INIT or BAD record is zero but for its flag.  LOST clears the state to "not initialised": everything zero
+ *                  but n_init and n_lost (+= 1); a later call re-initialises it from d_fix.  Every byte of d_kf is written, the
+ *                  state of a receiver that is neither BAD nor NOT_INIT is written whole, nothing non-finite is written to either.
+ * Errors (GPSX_EINVAL with a gpsx_last_error text, nothing written): NULL ctx / cfg / d_obs / d_eph / d_state / d_kf, ch_per_rx
+ * outside 1 .. 64, n_rx outside 1 .. 1 048 576, n_blocks outside 1 .. 4096, max_coast outside 0 .. 1 000 000, gate not finite or outside
+ * (0, 100], sig_dop_mps not finite or <= 0, sig_pr_m, a q_* or a p0_* not finite or negative, a p0_* of 0, mps_per_hz not finite or 0,
+ * an ion[] not finite, a reserved word != 0, a d_state (both variants: it is device memory in both) or a d_kf (_dev) that is not
+ * 16-byte aligned, a byte count that overflows.
+ * Vector ALU, FP64 (k_wkf: gpsx_wfix's lane layout, a slot per lane; the 28 sums of I and g and the two of the NIS by
+ * xor-butterflies of width W; P-, the two INVs and P+ in every lane of the group, in registers; every loop bounded, every cross-lane
+ * operation under wave-uniform control flow).  On one stream: ..., gpsx_wfix_dev or gpsx_wfde_dev, gpsx_wvel_dev, then gpsx_wkf_dev. */
+#define GPSX_WKF_INIT        1u   /* the state was initialised from d_fix (and d_vel) in this call; no update */
+#define GPSX_WKF_NOT_INIT    2u   /* not initialised and no FIX record offered */
+#define GPSX_WKF_UPDATED     4u   /* prediction and an update with n_pr + n_dop >= 1 rows */
+#define GPSX_WKF_COAST       8u   /* prediction alone: no row was accepted */
+#define GPSX_WKF_LOST       16u   /* a pivot failed, a result was not finite or n_starved > max_coast: the state is cleared */
+#define GPSX_WKF_BAD        32u   /* the state was out of range: it is untouched, the record is otherwise zero */
+#define GPSX_WKF_REPAIRED   64u   /* modifier: a plus or minus bit is set */
+#define GPSX_WKF_REJECTED  128u   /* modifier: a bit of rej_pr_mask or rej_dop_mask is set */
+#define GPSX_WKF_STEERED   256u   /* modifier: rcv_ms moved by a millisecond, clk_m by -+ 299 792.458 m */
+#define GPSX_WKF_STATE_INIT  1u   /* gpsx_wkf_state_t.flags: x, P, rcv_ms and week hold a filter */
+
+typedef struct {                 /* 176 bytes */
+  double   ion[8];               /*   0  Klobuchar a0..a3, b0..b3, finite; all zero: the 2004 default set */
+  double   mps_per_hz;           /*  64  as gpsx_wvel_cfg_t's: finite, not 0 */
+  double   sig_pr_m;             /*  72  >= 0: receiver pseudorange noise, added to gpsx_wfix's variance terms */
+  double   sig_dop_mps;          /*  80  > 0: range-rate noise of a Doppler row */
+  double   gate;                 /*  88  (0, 100]: rows with |v| > gate sqrt(s) are rejected */
+  double   q_acc;                /*  96  >= 0, m^2/s^3 per position axis */
+  double   q_clk_f, q_clk_g;     /* 104  >= 0: clock phase (m^2/s) and frequency (m^2/s^3) noise */
+  double   p0_pos, p0_clk, p0_vel, p0_drift;   /* 120  > 0: the initial standard deviations, m and m/s */
+  int32_t  ch_per_rx;            /* 152  1 .. 64 */
+  int32_t  max_coast;            /* 156  0 .. 1 000 000: launches without a pseudorange row before LOST */
+  int32_t  reserved[4];          /* 160  0 */
+} gpsx_wkf_cfg_t;
+
+typedef struct {                 /* 384 bytes, one per receiver, resident in device memory; all zero: a fresh receiver */
+  double   x[8];                 /*   0  x, y, z, b, vx, vy, vz, d */
+  double   P[36];                /*  64  upper triangle, row by row */
+  int64_t  rcv_ms;               /* 352  0 .. 604 799 999 */
+  int32_t  week;                 /* 360 */
+  uint32_t flags;                /* 364  GPSX_WKF_STATE_INIT */
+  uint32_t n_starved;            /* 368  launches in a row without an accepted pseudorange row */
+  uint32_t n_init, n_lost;       /* 372  counters (mod 2^32): initialisations, losses */
+  uint32_t reserved;             /* 380  0 */
+} gpsx_wkf_state_t;
+
+typedef struct {                 /* 240 bytes, one per receiver and launch */
+  uint32_t flags;                /*   0 */
+  int32_t  n_pr, n_dop;          /*   4  accepted rows */
+  uint32_t n_starved;            /*  12 */
+  uint64_t pr_mask, dop_mask;    /*  16  bit j: slot j's row was accepted */
+  uint64_t rej_pr_mask, rej_dop_mask;   /*  32  bit j: slot j's row was formed and rejected (|k| > 1 or the gate) */
+  uint64_t plus_mask, minus_mask;/*  48  slots whose tx_ms was corrected by +1 / -1 ms */
+  double   rr[3];                /*  64  ECEF, m */
+  double   clk_m;                /*  88  b = c (receiver clock - GPS time), m */
+  double   vel[3];               /*  96  ECEF, m/s */
+  double   cdrift_mps;           /* 120  d, m/s */
+  double   geo[3];               /* 128  latitude, longitude (rad), height (m) of rr */
+  double   enu[3];               /* 152  vel in the east / north / up frame at geo */
+  float    sigma[8];             /* 176  sqrt(P_ii) */
+  double   nis_pr, nis_dop;      /* 208  sum v^2 / s over the accepted rows */
+  int64_t  rcv_ms;               /* 224  the state's, after this call */
+  int32_t  week, reserved;       /* 232  the state's; 0 */
+} gpsx_wkf_t;
+
+/* d_obs, d_eph, d_lock (NULL: not consulted): [n_rx * ch_per_rx]; d_fix, d_vel (NULL: none offered): [n_rx]; d_kf: [n_rx]; all on the
+ * device for _dev, all in host memory (staged through the arena; the call waits for its kernel) for gpsx_wkf.  d_state [n_rx] is
+ * device memory in both.  n_blocks: what this launch's gpsx_wobs_dev call got. */
+int gpsx_wkf_dev(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                 const gpsx_wfix_t *d_fix, const gpsx_wvel_t *d_vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *d_kf);
+int gpsx_wkf(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+             const gpsx_wfix_t *fix, const gpsx_wvel_t *vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *kf);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

@@ -126,6 +126,8 @@ def check_no_scratch() -> dict:
     check_wfde()
     # ... and the velocity fixes behind either (check_wvel below: one linear solve per receiver, no scratch and no LDS)
     check_wvel()
+    # ... and the navigation filter behind them (check_wkf below: two 8 x 8 factorisations per receiver in registers, no scratch, no LDS)
+    check_wkf()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -196,6 +198,18 @@ def check_wvel() -> dict:
     if bad:
         raise RuntimeError(f"velocity-fix kernel with scratch memory (register spills) or LDS: {bad}")
     return wvel
+
+
+def check_wkf() -> dict:
+    """k_wkf (every receiver's navigation filter: k_wfix's lane layout, the 8 x 8 covariance and its two factorisations in
+    registers; an object of its own): exactly one instance, no scratch and no LDS.  -> {symbol: resources}"""
+    wkf = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wkf.o")).items() if "k_wkf" in k}
+    if len(wkf) != 1:
+        raise RuntimeError(f"expected k_wkf in build/k_wkf.o, found {sorted(wkf)}")
+    bad = {k: v for k, v in wkf.items() if v["scratch_bytes"] != 0 or v["lds_bytes"] != 0}
+    if bad:
+        raise RuntimeError(f"navigation-filter kernel with scratch memory (register spills) or LDS: {bad}")
+    return wkf
 
 
 if __name__ == "__main__":

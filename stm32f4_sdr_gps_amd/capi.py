@@ -289,6 +289,37 @@ def wvel_cfg(ch_per_rx: int, min_sats: int = 4, mps_per_hz: float = WVEL_L1CA) -
     return cfg
 
 
+# gpsx_wkf_cfg_t / gpsx_wkf_state_t / gpsx_wkf_t (every receiver's navigation filter: a resident eight-state Kalman filter)
+WKF_FLAG_INIT, WKF_FLAG_NOT_INIT, WKF_FLAG_UPDATED, WKF_FLAG_COAST, WKF_FLAG_LOST, WKF_FLAG_BAD = 1, 2, 4, 8, 16, 32
+WKF_FLAG_REPAIRED, WKF_FLAG_REJECTED, WKF_FLAG_STEERED = 64, 128, 256
+WKF_STATE_INIT = 1
+WKF_CFG_DTYPE = np.dtype([("ion", "<f8", (8,)), ("mps_per_hz", "<f8"), ("sig_pr_m", "<f8"), ("sig_dop_mps", "<f8"), ("gate", "<f8"), ("q_acc", "<f8"),
+                          ("q_clk_f", "<f8"), ("q_clk_g", "<f8"), ("p0_pos", "<f8"), ("p0_clk", "<f8"), ("p0_vel", "<f8"), ("p0_drift", "<f8"),
+                          ("ch_per_rx", "<i4"), ("max_coast", "<i4"), ("reserved", "<i4", (4,))])
+WKF_STATE_DTYPE = np.dtype([("x", "<f8", (8,)), ("P", "<f8", (36,)), ("rcv_ms", "<i8"), ("week", "<i4"), ("flags", "<u4"), ("n_starved", "<u4"),
+                            ("n_init", "<u4"), ("n_lost", "<u4"), ("reserved", "<u4")])
+WKF_DTYPE = np.dtype([("flags", "<u4"), ("n_pr", "<i4"), ("n_dop", "<i4"), ("n_starved", "<u4"), ("pr_mask", "<u8"), ("dop_mask", "<u8"),
+                      ("rej_pr_mask", "<u8"), ("rej_dop_mask", "<u8"), ("plus_mask", "<u8"), ("minus_mask", "<u8"), ("rr", "<f8", (3,)),
+                      ("clk_m", "<f8"), ("vel", "<f8", (3,)), ("cdrift_mps", "<f8"), ("geo", "<f8", (3,)), ("enu", "<f8", (3,)), ("sigma", "<f4", (8,)),
+                      ("nis_pr", "<f8"), ("nis_dop", "<f8"), ("rcv_ms", "<i8"), ("week", "<i4"), ("reserved", "<i4")])
+assert WKF_CFG_DTYPE.itemsize == 176 and WKF_STATE_DTYPE.itemsize == 384 and WKF_DTYPE.itemsize == 240
+
+
+def wkf_cfg(ch_per_rx: int, mps_per_hz: float = WVEL_L1CA, sig_pr_m: float = 3.0, sig_dop_mps: float = 0.1, gate: float = 5.0, q_acc: float = 1.0,
+            q_clk_f: float = 0.04, q_clk_g: float = 0.4, p0=(30.0, 30.0, 10.0, 500.0), max_coast: int = 10, ion=None) -> np.ndarray:
+    """a gpsx_wkf_cfg_t as a one-element WKF_CFG_DTYPE array: the row noises (m, m/s), the gate in standard deviations, the process
+    noise (q_acc m^2/s^3 per axis; the clock's phase and frequency noise), the initial standard deviations p0 = (position, clock,
+    velocity, drift) and the launches a receiver may go without a pseudorange row.  mps_per_hz as wvel_cfg's"""
+    cfg = np.zeros(1, WKF_CFG_DTYPE)
+    for name, v in (("mps_per_hz", mps_per_hz), ("sig_pr_m", sig_pr_m), ("sig_dop_mps", sig_dop_mps), ("gate", gate), ("q_acc", q_acc),
+                    ("q_clk_f", q_clk_f), ("q_clk_g", q_clk_g), ("p0_pos", p0[0]), ("p0_clk", p0[1]), ("p0_vel", p0[2]), ("p0_drift", p0[3]),
+                    ("ch_per_rx", ch_per_rx), ("max_coast", max_coast)):
+        cfg[name] = v
+    if ion is not None:
+        cfg["ion"][0] = ion
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -430,6 +461,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wfde_dev.argtypes = lib.gpsx_wfde.argtypes
     lib.gpsx_wvel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.gpsx_wvel_dev.argtypes = lib.gpsx_wvel.argtypes
+    lib.gpsx_wkf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                             C.c_void_p]
+    lib.gpsx_wkf_dev.argtypes = lib.gpsx_wkf.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -952,6 +986,25 @@ class Engine:
         self._chk(self.lib.gpsx_wvel(self.h, cfg.ctypes.data, obs.ctypes.data, eph.ctypes.data, None if lock is None else lock.ctypes.data,
                                      fix.ctypes.data, n_rx, vel.ctypes.data), "gpsx_wvel")
         return vel
+
+    def wkf(self, cfg: np.ndarray, obs: np.ndarray, eph: np.ndarray, n_rx: int, n_blocks: int, d_state: int, fix: np.ndarray | None = None,
+            vel: np.ndarray | None = None, lock: np.ndarray | None = None) -> np.ndarray:
+        """EXTENSION: every receiver's navigation filter (include/gpsx.h gpsx_wkf), one call per launch of n_blocks blocks, on the n_rx
+        WKF_STATE_DTYPE states at device address d_state (all zero: a fresh receiver); obs / eph / lock as wfix's host arrays, cfg from
+        wkf_cfg.  fix (WFIX_DTYPE [n_rx]) and vel (WVEL_DTYPE [n_rx]) initialise the receivers that are not yet initialised.
+        -> WKF_DTYPE [n_rx]"""
+        assert cfg.dtype == WKF_CFG_DTYPE and cfg.size == 1
+        n_ch = n_rx * int(cfg["ch_per_rx"][0])
+        obs, eph = np.ascontiguousarray(obs, WOBS_DTYPE).reshape(-1), np.ascontiguousarray(eph, WEPH_DTYPE).reshape(-1)
+        assert len(obs) == n_ch and len(eph) == n_ch
+        lock = None if lock is None else np.ascontiguousarray(lock).view(WLOCK_DTYPE).reshape(n_ch)      # (any 64-byte record dtype)
+        fix = None if fix is None else np.ascontiguousarray(fix, WFIX_DTYPE).reshape(n_rx)
+        vel = None if vel is None else np.ascontiguousarray(vel, WVEL_DTYPE).reshape(n_rx)
+        kf = np.zeros(n_rx, WKF_DTYPE)
+        self._chk(self.lib.gpsx_wkf(self.h, cfg.ctypes.data, obs.ctypes.data, eph.ctypes.data, None if lock is None else lock.ctypes.data,
+                                    None if fix is None else fix.ctypes.data, None if vel is None else vel.ctypes.data, n_rx, n_blocks,
+                                    C.c_void_p(d_state), kf.ctypes.data), "gpsx_wkf")
+        return kf
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

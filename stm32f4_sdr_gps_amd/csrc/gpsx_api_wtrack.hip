@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -603,9 +603,107 @@ int wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs, cons
       });
 }
 
+// ---- the navigation filter behind them (staged as wfix stages its arrays; the state is device memory in both variants) ----------------
+int wkf(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock, const gpsx_wfix_t *fix,
+        const gpsx_wvel_t *vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *kf, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !obs || !eph || !d_state || !kf)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (cfg->max_coast < 0 || cfg->max_coast > 1000000)
+    return fail(ctx, GPSX_EINVAL, "max_coast must be 0..1000000");
+  if (!(cfg->gate > 0.0 && cfg->gate <= 100.0))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "gate must be finite, above 0 and at most 100");
+  if (!(cfg->sig_dop_mps - cfg->sig_dop_mps == 0.0) || !(cfg->sig_dop_mps > 0.0))   // (not finite: the difference is a NaN)
+    return fail(ctx, GPSX_EINVAL, "sig_dop_mps must be finite and above 0");
+  for (double v : {cfg->sig_pr_m, cfg->q_acc, cfg->q_clk_f, cfg->q_clk_g, cfg->p0_pos, cfg->p0_clk, cfg->p0_vel, cfg->p0_drift})
+    if (!(v - v == 0.0) || v < 0.0)
+      return fail(ctx, GPSX_EINVAL, "sig_pr_m, q_* and p0_* must be finite and not negative");
+  for (double v : {cfg->p0_pos, cfg->p0_clk, cfg->p0_vel, cfg->p0_drift})
+    if (v == 0.0)
+      return fail(ctx, GPSX_EINVAL, "p0_* must not be 0");
+  if (!(cfg->mps_per_hz - cfg->mps_per_hz == 0.0) || cfg->mps_per_hz == 0.0)
+    return fail(ctx, GPSX_EINVAL, "mps_per_hz must be finite and not 0");
+  for (double v : cfg->ion)
+    if (!(v - v == 0.0))
+      return fail(ctx, GPSX_EINVAL, "an ionosphere coefficient is not finite");
+  for (int32_t v : cfg->reserved)
+    if (v != 0)
+      return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if ((reinterpret_cast<uintptr_t>(d_state) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_state must be 16-byte aligned");
+  if (!host && (reinterpret_cast<uintptr_t>(kf) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_kf must be 16-byte aligned");
+  size_t obs_bytes = 0, eph_bytes = 0, lock_bytes = 0, fix_bytes = 0, vel_bytes = 0, kf_bytes = 0, bytes = 0;
+  if (records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wobs_t), &obs_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_weph_t), &eph_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wlock_t), &lock_bytes) ||
+      records_overflow((size_t)n_rx, 1, sizeof(gpsx_wfix_t), &fix_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wvel_t), &vel_bytes) ||
+      records_overflow((size_t)n_rx, 1, sizeof(gpsx_wkf_state_t), &bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wkf_t), &kf_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x ch_per_rx records overflow a size");
+  const size_t n_ch = (size_t)n_rx * (size_t)cfg->ch_per_rx;
+  const gpsx_wobs_t *d_obs = obs;
+  const gpsx_weph_t *d_eph = eph;
+  const gpsx_wlock_t *d_lock = lock;
+  const gpsx_wfix_t *d_fix = fix;
+  const gpsx_wvel_t *d_vel = vel;
+  gpsx_wkf_t *d_kf = kf;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) +
+                                      (fix ? arena_size(fix_bytes) : 0) + (vel ? arena_size(vel_bytes) : 0) + arena_size(kf_bytes)))
+      return rc;
+    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
+    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
+    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
+    d_obs = s_obs;
+    d_eph = s_eph;
+    if (lock) {
+      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
+      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_lock = s_lock;
+    }
+    if (fix) {
+      gpsx_wfix_t *s_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
+      HIPCHK(ctx, hipMemcpyAsync(s_fix, fix, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_fix = s_fix;
+    }
+    if (vel) {
+      gpsx_wvel_t *s_vel = arena_take<gpsx_wvel_t>(ctx, (size_t)n_rx);
+      HIPCHK(ctx, hipMemcpyAsync(s_vel, vel, vel_bytes, hipMemcpyHostToDevice, ctx->stream));
+      d_vel = s_vel;
+    }
+    d_kf = arena_take<gpsx_wkf_t>(ctx, (size_t)n_rx);
+  }
+  return launch_and_report(
+      ctx, host, "k_wkf", "a receiver's filter state is out of range (its state is untouched, its record is zero but for the flag)",
+      [&](uint32_t *flag) { launch_wkf(ctx->stream, *cfg, d_obs, d_eph, d_lock, d_fix, d_vel, n_rx, n_blocks, d_state, d_kf, flag); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(kf, d_kf, kf_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wkf_dev(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                 const gpsx_wfix_t *d_fix, const gpsx_wvel_t *d_vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *d_kf)
+{
+  return wkf(ctx, cfg, d_obs, d_eph, d_lock, d_fix, d_vel, n_rx, n_blocks, d_state, d_kf, false);
+}
+
+int gpsx_wkf(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
+             const gpsx_wfix_t *fix, const gpsx_wvel_t *vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *kf)
+{
+  return wkf(ctx, cfg, obs, eph, lock, fix, vel, n_rx, n_blocks, d_state, kf, true);
+}
 
 int gpsx_wvel_dev(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                   const gpsx_wfix_t *d_fix, int n_rx, gpsx_wvel_t *d_vel)

@@ -200,6 +200,13 @@ void launch_wfde(hipStream_t s, const gpsx_wfde_cfg_t &cfg, const gpsx_wobs_t *d
 // records, every byte of them written.  cfg as the host checked it.
 void launch_wvel(hipStream_t s, const gpsx_wvel_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                  const gpsx_wfix_t *d_fix, int n_rx, gpsx_wvel_t *d_vel);
+// extension: gpsx_wkf (k_wkf.hip: k_wkf) -- every receiver's navigation filter on the same [n_rx * ch_per_rx] arrays: the same lane
+// layout, a resident 384-byte state per receiver in d_state [n_rx]; d_fix and d_vel (each may be null) [n_rx] are read by receivers
+// that are not initialised; d_kf [n_rx] 240-byte records, every byte of them written.  A state that is out of range raises
+// *d_bad_state.  cfg and n_blocks as the host checked them.
+void launch_wkf(hipStream_t s, const gpsx_wkf_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
+                const gpsx_wfix_t *d_fix, const gpsx_wvel_t *d_vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *d_kf,
+                uint32_t *d_bad_state);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -90,7 +90,14 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       --weighted-fix's four shapes, receivers at 36 m/s, on the fix records that
                                                       gpsx_wfix_dev left on the device, beside gpsx_wfix_dev on the same arrays, the
                                                       calls taking turns in one process; the lines also go to
-                                                      profiles/r22_weighted_vel_bench.jsonl"""
+                                                      profiles/r22_weighted_vel_bench.jsonl
+  bench_track_kernel.py --weighted-kf [N_RXxCH_PER_RX ...]
+                                                      gpsx_wkf_dev (EXTENSION: every receiver's navigation filter; k_wkf) at
+                                                      --weighted-fix's four shapes: one update per receiver from states initialised one
+                                                      launch earlier (a device-to-device copy puts them back before every timed launch;
+                                                      it is timed alone and subtracted), beside gpsx_wfix_dev (warm start) and
+                                                      gpsx_wvel_dev on the same records, the calls taking turns in one process; the
+                                                      lines also go to profiles/r24_weighted_kf_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -980,8 +987,96 @@ def weighted_vel(shapes, out=VEL_OUT):
         eng.close()
 
 
+KF_OUT = os.path.join(ROOT, "profiles", "r24_weighted_kf_bench.jsonl")
+
+
+def weighted_kf(shapes, out=KF_OUT):
+    """k_wkf at k_wfix's shapes, every slot usable, receivers at 36 m/s whose clocks drift by 1e-6: the states are initialised from
+    gpsx_wfix_dev's and gpsx_wvel_dev's records of one launch; the timed call is the update of the NEXT launch (1000 blocks later),
+    and because a filter call advances its state, each timed launch is preceded by a device-to-device copy that puts the initialised
+    states back -- that copy is timed alone beside it and subtracted.  The yardstick is k_wfix (warm start) + k_wvel on the same
+    records, the calls taking turns; the lines go to stdout and to `out`"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fix_cases as W
+    import weighted_kf_cases as K
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0, stream=stream.value)
+    names = sorted(W.SITES)
+    try:
+        for n_rx, ch in shapes:
+            pool = [K.track(names[k % len(names)], ch, 3 * k, K.VELOCITY, 1e-6, 2) for k in range(16)]      # --weighted-fix's sixteen skies
+            obs0, eph = W.pack([(pool[r % 16][0][0]["obs"], pool[r % 16][1]) for r in range(n_rx)], ch)
+            obs1, _ = W.pack([(pool[r % 16][0][1]["obs"], pool[r % 16][1]) for r in range(n_rx)], ch)
+            fix_cfg, vel_cfg, kf_cfg = capi.wfix_cfg(W.OFFSET_MS, ch), capi.wvel_cfg(ch), capi.wkf_cfg(ch)
+            state_bytes = n_rx * capi.WKF_STATE_DTYPE.itemsize
+            d_obs0, d_obs1, d_eph = eng.malloc(obs0.nbytes), eng.malloc(obs1.nbytes), eng.malloc(eph.nbytes)
+            d_fix, d_fix2, d_vel, d_vel2 = eng.malloc(n_rx * 128), eng.malloc(n_rx * 128), eng.malloc(n_rx * 112), eng.malloc(n_rx * 112)
+            d_state, d_state0, d_kf = eng.malloc(state_bytes), eng.malloc(state_bytes), eng.malloc(n_rx * capi.WKF_DTYPE.itemsize)
+            for d, a in ((d_obs0, obs0), (d_obs1, obs1), (d_eph, eph), (d_state0, np.zeros(n_rx, capi.WKF_STATE_DTYPE))):
+                eng.h2d(d, a)
+
+            def wfix(d_o, d_prev, d_out):
+                return eng.lib.gpsx_wfix_dev(eng.h, fix_cfg.ctypes.data, C.c_void_p(d_o), C.c_void_p(d_eph), None, None if d_prev is None else C.c_void_p(d_prev),
+                                             n_rx, C.c_void_p(d_out), None)
+
+            def wvel(d_o, d_f, d_out):
+                return eng.lib.gpsx_wvel_dev(eng.h, vel_cfg.ctypes.data, C.c_void_p(d_o), C.c_void_p(d_eph), None, C.c_void_p(d_f), n_rx, C.c_void_p(d_out))
+
+            def wkf(d_o, d_st):
+                return eng.lib.gpsx_wkf_dev(eng.h, kf_cfg.ctypes.data, C.c_void_p(d_o), C.c_void_p(d_eph), None, C.c_void_p(d_fix), C.c_void_p(d_vel), n_rx, 1000,
+                                            C.c_void_p(d_st), C.c_void_p(d_kf))
+
+            def restore():
+                return hip.hipMemcpyAsync(d_state, d_state0, state_bytes, 3, stream)
+
+            def restore_and_update():
+                restore()
+                return wkf(d_obs1, d_state)
+
+            eng._chk(wfix(d_obs0, None, d_fix), "gpsx_wfix_dev")
+            eng._chk(wvel(d_obs0, d_fix, d_vel), "gpsx_wvel_dev")
+            eng._chk(wkf(d_obs0, d_state0), "gpsx_wkf_dev")      # INIT: what every timed launch starts from
+            eng.synchronize()
+            calls = {"d2d_copy_of_the_states": (1, restore),
+                     "wfix_warm": (1, lambda: wfix(d_obs1, d_fix, d_fix2)),
+                     "wvel": (1, lambda: wvel(d_obs1, d_fix, d_vel2)),
+                     "state_copy_then_wkf": (1, restore_and_update)}
+            med = _timed_rows(eng, calls, {"channels": n_rx * ch, "n_rx": n_rx, "ch_per_rx": ch, "state_bytes": state_bytes,
+                                           "read_bytes": obs1.nbytes + eph.nbytes + state_bytes})
+            kf = np.zeros(n_rx, capi.WKF_DTYPE)
+            eng.d2h(kf, d_kf)
+            truth = np.stack([pool[r % 16][0][1]["rx"] for r in range(n_rx)])
+            print(json.dumps({"wkf_check": "records after the timed launches", "n_rx": n_rx, "ch_per_rx": ch,
+                              "updated": int((kf["flags"] == capi.WKF_FLAG_UPDATED).sum()), "n_pr_min": int(kf["n_pr"].min()), "n_dop_min": int(kf["n_dop"].min()),
+                              "largest_position_error_m": round(float(np.linalg.norm(kf["rr"] - truth, axis=1).max()), 4)}), flush=True)
+            own = med["state_copy_then_wkf"] - med["d2d_copy_of_the_states"]
+            both = med["wfix_warm"] + med["wvel"]
+            print(json.dumps({"ratio": "k_wkf (the timed pair less the state copy) over k_wfix + k_wvel on the same records", "n_rx": n_rx, "ch_per_rx": ch,
+                              "wkf_us": round(own, 3), "wfix_plus_wvel_us": round(both, 3), "value": round(own / both, 3), "cheaper": bool(own < both),
+                              "over_the_state_copy": round(own / med["d2d_copy_of_the_states"], 2), "ns_per_receiver": round(own / n_rx * 1e3, 2)}), flush=True)
+            for p in (d_obs0, d_obs1, d_eph, d_fix, d_fix2, d_vel, d_vel2, d_state, d_state0, d_kf):
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-kf" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-kf"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_kf([tuple(int(v) for v in a.split("x")) for a in args] or FIX_SHAPES)
     if "--weighted-vel" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-vel"]
         if "--window-s" in args:
