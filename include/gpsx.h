@@ -1471,7 +1471,8 @@ int gpsx_wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs,
  *                  INV(N), 8 x 8: Cholesky N = L L^T column by column, p_j = N_jj - l_j0^2 - ... - l_j,j-1^2, gpsx_wfix's pivot rule
  *                  (p_0 <= 0 or p_j <= 1e-10 N_jj fails), l_jj = sqrt(p_j), l_ij = (N_ij - l_i0 l_j0 - ... ) / l_jj; M = L^-1 with
  *                  m_jj = 1 / l_jj, m_ij = -(l_ij m_jj + ... + l_i,i-1 m_i-1,j) / l_ii; N^-1_ij = the sum over
- *                  k = max(i, j) .. 7 of m_ki m_kj.  A failed pivot in either: LOST.
+ *                  k = max(i, j) .. 7 of m_ki m_kj.  A failed pivot in either: LOST -- of an update, that is: without an accepted
+ *                  row nothing is inverted that counts, and a P- that would fail coasts until a row arrives.
  *  10 starvation   no accepted pseudorange row: n_starved += 1, else n_starved = 0.  n_starved > max_coast: LOST.
  *  11 steering     x+_3 > ms / 2: x+_3 -= ms, rcv_ms -= 1 (rcv_ms < 0: += W, week -= 1); x+_3 < -ms / 2: x+_3 += ms, rcv_ms += 1
  *                  (rcv_ms >= W: -= W, week += 1); STEERED; once per call.  The pseudoranges of the next call follow rcv_ms.

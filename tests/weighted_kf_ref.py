@@ -124,7 +124,8 @@ def _poly(e, t):
 
 
 def satellites(e, tx_ms, phase, cand):
-    """step 5: gpsx_wvel's step 2 at tx_ms, with the clock offset and the URA variance -> sat, ps [..., 3], vs [..., 3], rate, clk, svar"""
+    """step 5: gpsx_wvel's step 2 at tx_ms, with the clock offset and the URA variance -> sat, ps [..., 3], vs [..., 3], rate, clk, svar,
+    tk (of every candidate slot, NaN elsewhere: for the tests' margins)"""
     t_sv = (tx_ms.astype(np.float64) - phase.astype(np.float64) / 16368.0) / 1000.0
     toc = ((e["toc_time"] - UNIX_TO_GPS) % 604800).astype(np.float64) + e["toc_sec"]
     tc = _fold(t_sv - toc)
@@ -175,14 +176,14 @@ def satellites(e, tx_ms, phase, cand):
     sva = e["sva"]
     ura = np.where((sva < 0) | (sva > 14), 6144.0, F.URA[np.clip(sva, 0, 14)])
     z = lambda a: np.where(sat, a, 0.0)      # noqa: E731
-    return sat, np.stack([z(px), z(py), z(pz)], -1), np.stack([z(vx), z(vy), z(vz)], -1), z(rate), z(clk), z(ura * ura)
+    return sat, np.stack([z(px), z(py), z(pz)], -1), np.stack([z(vx), z(vy), z(vz)], -1), z(rate), z(clk), z(ura * ura), np.where(cand, tk, np.nan)
 
 
 def rows(x, rcv_ms, obs, e, k_ms, may_pr, may_dop, cfg, ion):
-    """steps 5 and 6 at x- [n, 8] with tx_ms + k_ms -> dict(prow, v, sig2, h [n, ch, 3], drow, y, a [n, ch, 3], el)"""
+    """steps 5 and 6 at x- [n, 8] with tx_ms + k_ms -> dict(prow, v, sig2, h [n, ch, 3], drow, y, a [n, ch, 3], el, tk)"""
     tx = obs["tx_ms"].astype(np.int64) + k_ms
     ph = obs["code_phase_fine"]
-    sat, ps, vs, rate, clk, svar = satellites(e, tx, ph, may_pr | may_dop)
+    sat, ps, vs, rate, clk, svar, tk = satellites(e, tx, ph, may_pr | may_dop)
     lat, lon, hgt = F._geodetic(x[:, :3])
     tow = rcv_ms.astype(np.float64) / 1000.0
     los = ps - x[:, None, :3]
@@ -220,7 +221,7 @@ def rows(x, rcv_ms, obs, e, k_ms, may_pr, may_dop, cfg, ion):
     v_meas = ev * (ev + ev / sin_el)
     v = (pr - C_LIGHT * e["tgd"]) - (rho + dion + dtrp + x[:, None, 3] - C_LIGHT * clk)
     sig2 = (v_meas + svar + v_ion + v_trp) + float(cfg["sig_pr_m"]) * float(cfg["sig_pr_m"])
-    return dict(prow=prow, v=v, sig2=sig2, h=-los, drow=drow, y=y, a=a, el=el)
+    return dict(prow=prow, v=v, sig2=sig2, h=-los, drow=drow, y=y, a=a, el=el, tk=tk)
 
 
 def _gate_s(P, h, off, extra):
@@ -239,7 +240,8 @@ def _mask(b, ch):
 def run(cfg, obs, eph, state, n_rx, n_blocks, lock=None, fix=None, vel=None, detail=None):
     """gpsx_wkf on obs / eph (/ lock) [n_rx * ch_per_rx], the states [n_rx] and fix / vel [n_rx] (or None)
     -> (KF_DTYPE [n_rx], the states after, the code: 0 or -22 when a state was BAD).  detail: a dict that receives the decisions'
-    quantities (gate ratios v^2 / (gate^2 s), the rint arguments, the pivot shares, the elevations of the rows)"""
+    quantities (gate ratios v^2 / (gate^2 s), the rint arguments, the pivot shares, the elevations of the rows, tk of every candidate slot
+    at the transmit time that counts, x+_3 as step 11 finds it, step 2's u of the receivers it initialises)"""
     c = np.asarray(cfg, CFG_DTYPE).reshape(1)[0]
     ch = int(c["ch_per_rx"])
     ion = np.array(c["ion"], np.float64)
@@ -260,7 +262,7 @@ def run(cfg, obs, eph, state, n_rx, n_blocks, lock=None, fix=None, vel=None, det
         n_starved, n_init, n_lost = st["n_starved"].astype(np.int64), st["n_init"].astype(np.int64), st["n_lost"].astype(np.int64)
 
         # ---- step 2: initialisation ----
-        init = np.zeros(n_rx, bool)
+        init, init_u = np.zeros(n_rx, bool), np.full(n_rx, np.nan)
         if fix is not None:
             fx = np.ascontiguousarray(fix, F.FIX_DTYPE).reshape(n_rx)
             cand = ~inited & ~bad & ((fx["flags"] & F.F_FIX) != 0)
@@ -287,7 +289,7 @@ def run(cfg, obs, eph, state, n_rx, n_blocks, lock=None, fix=None, vel=None, det
             x[cand], P[cand], rcv[cand], week[cand] = xi[cand], Pi[cand], mi[cand], wk[cand]
             n_starved[cand] = 0
             n_init[cand] = (n_init[cand] + 1) % (1 << 32)
-            init = cand
+            init, init_u = cand, np.where(cand, u, np.nan)
 
         # ---- steps 1 and 3: the time base, the prediction ----
         rcv = np.where(run_, rcv + n_blocks, rcv)
@@ -356,6 +358,7 @@ def run(cfg, obs, eph, state, n_rx, n_blocks, lock=None, fix=None, vel=None, det
         n_starved = np.where(run_, np.where(n_pr == 0, (n_starved + 1) % (1 << 32), 0), n_starved)
         lost = run_ & ((any_ & ~ok) | (n_starved > int(c["max_coast"])))
         live = run_ & ~lost
+        x3_pre = np.where(live, xp[:, 3], np.nan)
         up_, dn_ = live & (xp[:, 3] > MS / 2.0), live & (xp[:, 3] < -MS / 2.0)
         xp[:, 3] = np.where(up_, xp[:, 3] - MS, np.where(dn_, xp[:, 3] + MS, xp[:, 3]))
         rcv = np.where(up_, rcv - 1, np.where(dn_, rcv + 1, rcv))
@@ -395,8 +398,10 @@ def run(cfg, obs, eph, state, n_rx, n_blocks, lock=None, fix=None, vel=None, det
         st[lost] = np.zeros(int(lost.sum()), STATE_DTYPE)
         st["n_init"][lost], st["n_lost"][lost] = keep_init, keep_lost
     if detail is not None:
-        detail.update(gate_pr=np.where(prow & ~k_out, v * v / (gg * s_pr), np.nan), gate_dop=np.where(drow, y * y / (gg * s_dop), np.nan),
-                      rint_arg=np.where(amb, r0["v"] / MS, np.nan), el=np.where(R["prow"] | (may_pr & ~R["prow"]), R["el"], np.nan),
-                      shares=np.where((run_ & any_)[:, None], np.minimum(sh1, sh2), np.nan), pr_ok=pr_ok, dop_ok=dop_ok, prow=prow, drow=drow,
-                      v=v, y=y, s_pr=s_pr, s_dop=s_dop, xm=xm, Pm=Pm)
+        with np.errstate(all="ignore"):
+            detail.update(gate_pr=np.where(prow & ~k_out, v * v / (gg * s_pr), np.nan), gate_dop=np.where(drow, y * y / (gg * s_dop), np.nan),
+                          rint_arg=np.where(amb, r0["v"] / MS, np.nan), el=np.where(R["prow"] | (may_pr & ~R["prow"]), R["el"], np.nan),
+                          shares=np.where((run_ & any_)[:, None], np.minimum(sh1, sh2), np.nan), pr_ok=pr_ok, dop_ok=dop_ok, prow=prow, drow=drow,
+                          v=v, y=y, s_pr=s_pr, s_dop=s_dop, xm=xm, Pm=Pm, tk=R["tk"], x3_pre=x3_pre, init_u=init_u, may_pr=may_pr, may_dop=may_dop,
+                          pivot_failed=run_ & any_ & ~ok, starved_out=run_ & (n_starved > int(c["max_coast"])), not_finite=(init | run_) & ~fin)
     return out, st, (-22 if bad.any() else 0)
