@@ -164,52 +164,37 @@ def check_wmulti() -> dict:
     return wmulti
 
 
-def check_wfix() -> dict:
-    """k_wfix (every receiver's position fix: a slot per lane, the normal system in registers; an object of its own): exactly one
-    instance and no scratch.  -> {symbol: resources}"""
-    wfix = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wfix.o")).items() if "k_wfix" in k}
-    if len(wfix) != 1:
-        raise RuntimeError(f"expected k_wfix in build/k_wfix.o, found {sorted(wfix)}")
-    bad = {k: v for k, v in wfix.items() if v["scratch_bytes"] != 0}
+def check_wsolver(obj: str, kernel: str, no_lds: bool) -> dict:
+    """One solver kernel at the weighted chain's end (a slot per lane, a receiver's system in registers, the shared parts from
+    csrc/gpsx_wsolve_parts.hpp; an object of its own): exactly one instance in build/`obj`, no scratch and, if `no_lds`, no LDS.
+    -> {symbol: resources}"""
+    found = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", obj)).items() if kernel in k}
+    if len(found) != 1:
+        raise RuntimeError(f"expected {kernel} in build/{obj}, found {sorted(found)}")
+    bad = {k: v for k, v in found.items() if v["scratch_bytes"] != 0 or (no_lds and v["lds_bytes"] != 0)}
     if bad:
-        raise RuntimeError(f"position-fix kernel with scratch memory (register spills): {bad}")
-    return wfix
+        raise RuntimeError(f"{kernel} with scratch memory (register spills){' or LDS' if no_lds else ''}: {bad}")
+    return found
+
+
+def check_wfix() -> dict:
+    """k_wfix, every receiver's position fix"""
+    return check_wsolver("k_wfix.o", "k_wfix", False)
 
 
 def check_wfde() -> dict:
-    """k_wfde (the fixes with millisecond repair and fault exclusion: k_wfix's lane layout, rounds of the solver; an object of its
-    own): exactly one instance and no scratch.  -> {symbol: resources}"""
-    wfde = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wfde.o")).items() if "k_wfde" in k}
-    if len(wfde) != 1:
-        raise RuntimeError(f"expected k_wfde in build/k_wfde.o, found {sorted(wfde)}")
-    bad = {k: v for k, v in wfde.items() if v["scratch_bytes"] != 0}
-    if bad:
-        raise RuntimeError(f"fault-exclusion kernel with scratch memory (register spills): {bad}")
-    return wfde
+    """k_wfde, the fixes with millisecond repair and fault exclusion"""
+    return check_wsolver("k_wfde.o", "k_wfde", False)
 
 
 def check_wvel() -> dict:
-    """k_wvel (every receiver's velocity and clock drift: k_wfix's lane layout, one linear solve; an object of its own): exactly one
-    instance, no scratch and no LDS.  -> {symbol: resources}"""
-    wvel = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wvel.o")).items() if "k_wvel" in k}
-    if len(wvel) != 1:
-        raise RuntimeError(f"expected k_wvel in build/k_wvel.o, found {sorted(wvel)}")
-    bad = {k: v for k, v in wvel.items() if v["scratch_bytes"] != 0 or v["lds_bytes"] != 0}
-    if bad:
-        raise RuntimeError(f"velocity-fix kernel with scratch memory (register spills) or LDS: {bad}")
-    return wvel
+    """k_wvel, every receiver's velocity and clock drift: no LDS either"""
+    return check_wsolver("k_wvel.o", "k_wvel", True)
 
 
 def check_wkf() -> dict:
-    """k_wkf (every receiver's navigation filter: k_wfix's lane layout, the 8 x 8 covariance and its two factorisations in
-    registers; an object of its own): exactly one instance, no scratch and no LDS.  -> {symbol: resources}"""
-    wkf = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wkf.o")).items() if "k_wkf" in k}
-    if len(wkf) != 1:
-        raise RuntimeError(f"expected k_wkf in build/k_wkf.o, found {sorted(wkf)}")
-    bad = {k: v for k, v in wkf.items() if v["scratch_bytes"] != 0 or v["lds_bytes"] != 0}
-    if bad:
-        raise RuntimeError(f"navigation-filter kernel with scratch memory (register spills) or LDS: {bad}")
-    return wkf
+    """k_wkf, every receiver's navigation filter: no LDS either"""
+    return check_wsolver("k_wkf.o", "k_wkf", True)
 
 
 if __name__ == "__main__":

@@ -385,7 +385,21 @@ int wlock(gpsx_ctx *ctx, const gpsx_wlock_cfg_t *cfg, const gpsx_wsync_rec_t *d_
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(lock, d_lock, lock_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
 }
 
-// ---- the position fixes (host: every array is host memory, staged through the arena; _dev: all device memory) ------------------------
+// ---- the solvers at the chain's end (host: every array is host memory, staged through the arena; _dev: all device memory) ------------
+// a host call's input array of n records, which may be absent: room in the arena, the copy enqueued, *d the staged copy (src ==
+// nullptr: nothing is taken, *d stays null).  The takes follow the order of the calls, as arena_reset's sum does.
+template <typename T>
+int stage_in(gpsx_ctx *ctx, const T *src, size_t n, const T **d)
+{
+  if (!src)
+    return GPSX_OK;
+  T *staged = arena_take<T>(ctx, n);
+  HIPCHK(ctx, hipMemcpyAsync(staged, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  *d = staged;
+  return GPSX_OK;
+}
+
+// ---- the position fixes ---------------------------------------------------------------------------------------------------------------
 int wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock, const gpsx_wfix_t *prev,
          int n_rx, gpsx_wfix_t *fix, double *pr_m, bool host)
 {
@@ -424,22 +438,10 @@ int wfix(gpsx_ctx *ctx, const gpsx_wfix_cfg_t *cfg, const gpsx_wobs_t *obs, cons
     if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) +
                                       (prev ? arena_size(fix_bytes) : 0) + arena_size(fix_bytes) + (pr_m ? arena_size(pr_bytes) : 0)))
       return rc;
-    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
-    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
-    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_obs = s_obs;
-    d_eph = s_eph;
-    if (lock) {
-      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
-      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_lock = s_lock;
-    }
-    if (prev) {
-      gpsx_wfix_t *s_prev = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
-      HIPCHK(ctx, hipMemcpyAsync(s_prev, prev, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_prev = s_prev;
-    }
+    if (int rc = stage_in(ctx, obs, n_ch, &d_obs)) return rc;
+    if (int rc = stage_in(ctx, eph, n_ch, &d_eph)) return rc;
+    if (int rc = stage_in(ctx, lock, n_ch, &d_lock)) return rc;
+    if (int rc = stage_in(ctx, prev, (size_t)n_rx, &d_prev)) return rc;
     d_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
     if (pr_m)
       d_pr = arena_take<double>(ctx, n_ch);
@@ -509,22 +511,10 @@ int wfde(gpsx_ctx *ctx, const gpsx_wfde_cfg_t *fc, const gpsx_wobs_t *obs, const
                                       (prev ? arena_size(fix_bytes) : 0) + arena_size(fix_bytes) + arena_size(fde_bytes) +
                                       (pr_m ? arena_size(pr_bytes) : 0)))
       return rc;
-    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
-    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
-    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_obs = s_obs;
-    d_eph = s_eph;
-    if (lock) {
-      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
-      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_lock = s_lock;
-    }
-    if (prev) {
-      gpsx_wfix_t *s_prev = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
-      HIPCHK(ctx, hipMemcpyAsync(s_prev, prev, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_prev = s_prev;
-    }
+    if (int rc = stage_in(ctx, obs, n_ch, &d_obs)) return rc;
+    if (int rc = stage_in(ctx, eph, n_ch, &d_eph)) return rc;
+    if (int rc = stage_in(ctx, lock, n_ch, &d_lock)) return rc;
+    if (int rc = stage_in(ctx, prev, (size_t)n_rx, &d_prev)) return rc;
     d_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
     d_fde = arena_take<gpsx_wfde_t>(ctx, (size_t)n_rx);
     if (pr_m)
@@ -578,20 +568,10 @@ int wvel(gpsx_ctx *ctx, const gpsx_wvel_cfg_t *cfg, const gpsx_wobs_t *obs, cons
     if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) + arena_size(fix_bytes) +
                                       arena_size(vel_bytes)))
       return rc;
-    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
-    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
-    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_obs = s_obs;
-    d_eph = s_eph;
-    if (lock) {
-      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
-      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_lock = s_lock;
-    }
-    gpsx_wfix_t *s_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
-    HIPCHK(ctx, hipMemcpyAsync(s_fix, fix, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_fix = s_fix;
+    if (int rc = stage_in(ctx, obs, n_ch, &d_obs)) return rc;
+    if (int rc = stage_in(ctx, eph, n_ch, &d_eph)) return rc;
+    if (int rc = stage_in(ctx, lock, n_ch, &d_lock)) return rc;
+    if (int rc = stage_in(ctx, fix, (size_t)n_rx, &d_fix)) return rc;
     d_vel = arena_take<gpsx_wvel_t>(ctx, (size_t)n_rx);
   }
   return launch_and_report(
@@ -657,27 +637,11 @@ int wkf(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *obs, const 
     if (int rc = arena_reset(ctx, arena_size(obs_bytes) + arena_size(eph_bytes) + (lock ? arena_size(lock_bytes) : 0) +
                                       (fix ? arena_size(fix_bytes) : 0) + (vel ? arena_size(vel_bytes) : 0) + arena_size(kf_bytes)))
       return rc;
-    gpsx_wobs_t *s_obs = arena_take<gpsx_wobs_t>(ctx, n_ch);
-    gpsx_weph_t *s_eph = arena_take<gpsx_weph_t>(ctx, n_ch);
-    HIPCHK(ctx, hipMemcpyAsync(s_obs, obs, obs_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(s_eph, eph, eph_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_obs = s_obs;
-    d_eph = s_eph;
-    if (lock) {
-      gpsx_wlock_t *s_lock = arena_take<gpsx_wlock_t>(ctx, n_ch);
-      HIPCHK(ctx, hipMemcpyAsync(s_lock, lock, lock_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_lock = s_lock;
-    }
-    if (fix) {
-      gpsx_wfix_t *s_fix = arena_take<gpsx_wfix_t>(ctx, (size_t)n_rx);
-      HIPCHK(ctx, hipMemcpyAsync(s_fix, fix, fix_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_fix = s_fix;
-    }
-    if (vel) {
-      gpsx_wvel_t *s_vel = arena_take<gpsx_wvel_t>(ctx, (size_t)n_rx);
-      HIPCHK(ctx, hipMemcpyAsync(s_vel, vel, vel_bytes, hipMemcpyHostToDevice, ctx->stream));
-      d_vel = s_vel;
-    }
+    if (int rc = stage_in(ctx, obs, n_ch, &d_obs)) return rc;
+    if (int rc = stage_in(ctx, eph, n_ch, &d_eph)) return rc;
+    if (int rc = stage_in(ctx, lock, n_ch, &d_lock)) return rc;
+    if (int rc = stage_in(ctx, fix, (size_t)n_rx, &d_fix)) return rc;
+    if (int rc = stage_in(ctx, vel, (size_t)n_rx, &d_vel)) return rc;
     d_kf = arena_take<gpsx_wkf_t>(ctx, (size_t)n_rx);
   }
   return launch_and_report(

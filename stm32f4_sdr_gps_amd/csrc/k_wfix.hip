@@ -13,132 +13,32 @@
 // finished", from a ballot, eleven passes at most (ten iterations and the pass that takes the residuals at the final x); a group that
 // is finished masks its own updates; nothing returns before the last shuffle.  The lane-local loops are bounded: Kepler at 30 steps as
 // on the host, the geodetic fixed point at 30 (a finite position needs about five).
+//
+// gpsx_wsolve_parts.hpp has what is shared: the constants and models, the lane geometry, the satellite at its transmit time, azimuth
+// and elevation, the row's model terms.  The reference scan, the sums, the Cholesky solve and the record's fill are this file's own
+// text: shared, they cost 0.4 us at 64 slots per receiver (EXPERIMENTS.md, "One parts header for the solver kernels").
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wsolve_parts.hpp"
 
 namespace gpsx {
-
-namespace {
+using namespace wsolve;
 
 static_assert(sizeof(gpsx_wfix_cfg_t) == 96 && offsetof(gpsx_wfix_cfg_t, ion) == 8 && offsetof(gpsx_wfix_cfg_t, ch_per_rx) == 72 &&
               offsetof(gpsx_wfix_cfg_t, min_sats) == 76 && offsetof(gpsx_wfix_cfg_t, reserved0) == 80, "gpsx_wfix_cfg_t layout");
-static_assert(sizeof(gpsx_wfix_t) == 128 && offsetof(gpsx_wfix_t, n_used) == 4 && offsetof(gpsx_wfix_t, n_iter) == 8 &&
-              offsetof(gpsx_wfix_t, ref_slot) == 12 && offsetof(gpsx_wfix_t, used_mask) == 16 && offsetof(gpsx_wfix_t, rr) == 24 &&
-              offsetof(gpsx_wfix_t, dtr_s) == 48 && offsetof(gpsx_wfix_t, rx_tow_s) == 56 && offsetof(gpsx_wfix_t, geo) == 64 &&
-              offsetof(gpsx_wfix_t, qr) == 88 && offsetof(gpsx_wfix_t, resid_rms_m) == 112 && offsetof(gpsx_wfix_t, week) == 120 &&
-              offsetof(gpsx_wfix_t, reserved) == 124, "gpsx_wfix_t layout");
-static_assert(sizeof(gpsx_wobs_t) == 32 && sizeof(gpsx_weph_t) == 256 && sizeof(gpsx_wlock_t) == 64, "the records this stage reads");
-
-constexpr double kC = 299792458.0;
-constexpr double kPi = 3.1415926535897932;
-constexpr double kMu = 3.9860050E14;
-constexpr double kOmegaE = 7.2921151467E-5;
-constexpr double kRe = 6378137.0;
-constexpr double kFe = 1.0 / 298.257223563;
-constexpr int kMaxIter = 10;
-constexpr double kPivot = 1E-10;   // a pivot at or below this share of its diagonal element is round-off: SINGULAR
-constexpr long long kWeekMs = 604800000, kHalfMs = kWeekMs / 2;
-
-__device__ const double kUra[15] = {2.4, 3.4, 4.85, 6.85, 9.65, 13.65, 24.0, 48.0, 96.0, 192.0, 384.0, 768.0, 1536.0, 3072.0, 6144.0};
-__device__ const double kIonDefault[8] = {0.1118E-07, -0.7451E-08, -0.5961E-07, 0.1192E-06, 0.1167E+06, -0.2294E+06, -0.1311E+06, 0.1049E+07};
-
-struct GTime { long long time; double sec; };
-
-__device__ __forceinline__ bool finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }   // (a NaN fails it)
-__device__ __forceinline__ long long fold(long long d) { return ((d + kHalfMs) % kWeekMs + kWeekMs) % kWeekMs - kHalfMs; }
-__device__ __forceinline__ double time_diff(GTime a, GTime b) { return (double)(a.time - b.time) + a.sec - b.sec; }
-__device__ __forceinline__ GTime time_add(GTime t, double sec)   // no carry into t.time, as the host's
-{
-  t.sec += sec;
-  const double whole = floor(t.sec);
-  t.sec += whole;
-  t.sec -= whole;
-  return t;
-}
-__device__ __forceinline__ double clock_poly(const gpsx_weph_t &e, double t) { return e.f0 + e.f1 * t + e.f2 * t * t; }
-__device__ __forceinline__ double sat_clock_bias(const gpsx_weph_t &e, GTime when)
-{
-  double t = time_diff(when, GTime{e.toc_time, e.toc_sec});
-  t -= clock_poly(e, t);
-  t -= clock_poly(e, t);
-  return clock_poly(e, t);
-}
-
-// ecef2pos as the host has it (what it does at the origin included), its fixed point bounded
-__device__ __forceinline__ void geodetic(double x, double y, double zr, double &lat, double &lon, double &hgt)
-{
-  const double e2 = kFe * (2.0 - kFe), r2 = x * x + y * y;
-  double v = kRe, z = zr, zk = 0.0;
-  for (int it = 0; __builtin_fabs(z - zk) >= 1E-4 && it < 30; it++) {
-    zk = z;
-    const double sp = z / sqrt(r2 + z * z);
-    v = kRe / sqrt(1.0 - e2 * sp * sp);
-    z = zr + v * e2 * sp;
-  }
-  lat = r2 > 1E-12 ? atan(z / sqrt(r2)) : (zr > 0.0 ? kPi / 2.0 : -kPi / 2.0);
-  lon = r2 > 1E-12 ? atan2(y, x) : 0.0;
-  hgt = sqrt(r2 + z * z) - v;
-}
-
-__device__ __forceinline__ double klobuchar(double tow, const double *ion, double lat, double lon, double hgt, double az, double el)
-{
-  if (hgt < -1E3 || el <= 0)
-    return 0.0;
-  const double psi = 0.0137 / (el / kPi + 0.11) - 0.022;
-  double phi = lat / kPi + psi * cos(az);
-  phi = phi > 0.416 ? 0.416 : (phi < -0.416 ? -0.416 : phi);
-  const double lam = lon / kPi + psi * sin(az) / cos(phi * kPi);
-  phi += 0.064 * cos((lam - 1.617) * kPi);
-  double tt = 43200.0 * lam + tow;
-  tt -= floor(tt / 86400.0) * 86400.0;
-  const double slant = 1.0 + 16.0 * pow(0.53 - el / kPi, 3.0);
-  double amp = ion[0] + phi * (ion[1] + phi * (ion[2] + phi * ion[3]));
-  double per = ion[4] + phi * (ion[5] + phi * (ion[6] + phi * ion[7]));
-  amp = amp < 0.0 ? 0.0 : amp;
-  per = per < 72000.0 ? 72000.0 : per;
-  const double x = 2.0 * kPi * (tt - 50400.0) / per;
-  return kC * slant * (__builtin_fabs(x) < 1.57 ? 5E-9 + amp * (1.0 + x * x * (-0.5 + x * x / 24.0)) : 5E-9);
-}
-
-__device__ __forceinline__ double saastamoinen(double lat, double h, double el, double humidity)
-{
-  if (h < -100.0 || 1E4 < h || el <= 0)
-    return 0.0;
-  const double hgt = h < 0.0 ? 0.0 : h;
-  const double pres = 1013.25 * pow(1.0 - 2.2557E-5 * hgt, 5.2568);
-  const double temp = 15.0 - 6.5E-3 * hgt + 273.16;
-  const double e = 6.108 * humidity * exp((17.15 * temp - 4684.0) / (temp - 38.45));
-  const double z = kPi / 2.0 - el;
-  const double dry = 0.0022768 * pres / (1.0 - 0.00266 * cos(2.0 * lat) - 0.00028 * hgt / 1E3) / cos(z);
-  const double wet = 0.002277 * (1255.0 / temp + 0.05) * e / cos(z);
-  return dry + wet;
-}
-
-// the sum over a group's w lanes, in every one of them (the same bits in each: an addition commutes)
-__device__ __forceinline__ double group_sum(double v, int w)
-{
-  for (int m = 1; m < w; m <<= 1)   // (w is the launch's: wave-uniform)
-    v += __shfl_xor(v, m);
-  return v;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void k_wfix(gpsx_wfix_cfg_t cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
                                               const gpsx_wfix_t *prev, int n_rx, int w, int log2w, gpsx_wfix_t *fix, double *pr_out)
 {
-  const int lane = (int)(threadIdx.x & 63u);
-  const long long g = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
-  const int j = (int)(g & (long long)(w - 1));
-  const long long r = g >> log2w;
-  const int base = lane & ~(w - 1);
-  const bool in_rx = r < (long long)n_rx;
-  const bool slot = in_rx && j < cfg.ch_per_rx;
-  const size_t at = slot ? (size_t)r * (size_t)cfg.ch_per_rx + (size_t)j : 0;
+  const Lane ln = lane_of(w, log2w, n_rx, cfg.ch_per_rx);
+  const int j = ln.j, base = ln.base;
+  const long long r = ln.r;
+  const bool in_rx = ln.in_rx, slot = ln.slot;
+  const size_t at = ln.at;
 
   // ---- the lane's records; the receiver's start point (read before anything is written: prev may be fix) ----
   gpsx_wobs_t o = {};
@@ -173,7 +73,7 @@ __global__ __launch_bounds__(256) void k_wfix(gpsx_wfix_cfg_t cfg, const gpsx_wo
     const int us_k = __shfl((int)usable, src), week_k = __shfl(e.week, src);
     if (us_k) {
       count++;
-      if (ref < 0 || (double)fold(tx_k - ref_tx) - ((double)ph_k - (double)ref_ph) / 16368.0 > 0.0) {
+      if (ref < 0 || (double)fold_ms(tx_k - ref_tx) - ((double)ph_k - (double)ref_ph) / 16368.0 > 0.0) {
         ref = k;
         ref_tx = tx_k;
         ref_ph = ph_k;
@@ -184,7 +84,7 @@ __global__ __launch_bounds__(256) void k_wfix(gpsx_wfix_cfg_t cfg, const gpsx_wo
   double pr = 0.0, rx_tow = 0.0;
   if (ref >= 0) {
     if (usable)
-      pr = 299792458e-3 * ((double)fold(ref_tx - o.tx_ms) + ((double)o.code_phase_fine - (double)ref_ph) / 16368.0 + cfg.offset_ms);
+      pr = 299792458e-3 * ((double)fold_ms(ref_tx - o.tx_ms) + ((double)o.code_phase_fine - (double)ref_ph) / 16368.0 + cfg.offset_ms);
     const double rx = ((double)ref_tx - (double)ref_ph / 16368.0 + cfg.offset_ms) / 1000.0;
     rx_tow = rx >= 604800.0 ? rx - 604800.0 : (rx < 0.0 ? rx + 604800.0 : rx);
   }
@@ -195,51 +95,12 @@ __global__ __launch_bounds__(256) void k_wfix(gpsx_wfix_cfg_t cfg, const gpsx_wo
     pr_out[at] = finite(pr) ? pr : 0.0;
 
   // ---- the observation time, the satellite at its transmit time (satposs) ----
-  const int whole = (int)rx_tow;
-  const GTime t_obs = {315964800ll + 604800ll * (long long)week + (long long)whole, rx_tow - (double)whole};
-  const double tow = (double)((t_obs.time - 315964800ll) - (long long)(int)((t_obs.time - 315964800ll) / 604800ll) * 604800ll) + t_obs.sec;
+  const GTime t_obs = obs_time(week, rx_tow);
+  const double tow = tow_of(t_obs);
   double px = 0.0, py = 0.0, pz = 0.0, clk = 0.0, svar = 0.0;
   bool cand = false;   // the solver has a satellite record for this slot (health and all)
-  if (usable && __builtin_fabs(time_diff(GTime{e.toe_time, e.toe_sec}, t_obs)) <= 7201.0) {
-    GTime t = time_add(t_obs, -pr / kC);
-    t = time_add(t, -sat_clock_bias(e, t));
-    if (e.A <= 0.0) {
-      cand = true;
-      clk = sat_clock_bias(e, t);   // (clk == 0: "no precise clock")
-    } else {
-      double tk = time_diff(t, GTime{e.toe_time, e.toe_sec});
-      const double mean = e.M0 + (sqrt(kMu / (e.A * e.A * e.A)) + e.deln) * tk;
-      double ecc = mean, was = 0.0;
-      int n = 0;
-      for (; __builtin_fabs(ecc - was) > 1E-14 && n < 30; n++) {
-        was = ecc;
-        ecc -= (ecc - e.e * sin(ecc) - mean) / (1.0 - e.e * cos(ecc));
-      }
-      if (n < 30) {
-        const double se = sin(ecc), ce = cos(ecc);
-        double u = atan2(sqrt(1.0 - e.e * e.e) * se, ce - e.e) + e.omg;
-        double rad = e.A * (1.0 - e.e * ce);
-        double inc = e.i0 + e.idot * tk;
-        const double s2 = sin(2.0 * u), c2 = cos(2.0 * u);
-        u += e.cus * s2 + e.cuc * c2;
-        rad += e.crs * s2 + e.crc * c2;
-        inc += e.cis * s2 + e.cic * c2;
-        const double xo = rad * cos(u), yo = rad * sin(u), ci = cos(inc);
-        const double node = e.OMG0 + (e.OMGd - kOmegaE) * tk - kOmegaE * e.toes;
-        const double sn = sin(node), cn = cos(node);
-        px = xo * cn - yo * ci * sn;
-        py = xo * sn + yo * ci * cn;
-        pz = yo * sin(inc);
-        tk = time_diff(t, GTime{e.toc_time, e.toc_sec});
-        clk = clock_poly(e, tk) - 2.0 * sqrt(kMu * e.A) * e.e * se / (kC * kC);
-        const double ura = (e.sva < 0 || e.sva > 14) ? 6144.0 : kUra[e.sva];
-        svar = ura * ura;
-        cand = true;
-        if (clk == 0.0)
-          clk = sat_clock_bias(e, t);
-      }
-    }
-  }
+  if (usable)
+    cand = sat_at_transmit(e, t_obs, pr, px, py, pz, clk, svar);
   const bool healthy = e.svh == 0;
   const double tgd = kC * e.tgd;
   const double rn = sqrt(px * px + py * py + pz * pz);
@@ -253,7 +114,7 @@ __global__ __launch_bounds__(256) void k_wfix(gpsx_wfix_cfg_t cfg, const gpsx_wo
     ion[i] = ion_sq <= 0.0 ? kIonDefault[i] : cfg.ion[i];
 
   // ---- estpos / rescode ----
-  const u64 group_bits = (w == 64 ? ~0ull : ((1ull << w) - 1ull));
+  const u64 group_bits = group_mask(w);
   u32 flags = 0;
   int mode = 0;   // 0: iterating, 1: converged, the residuals at the final x are due, 2: finished
   if (!in_rx)
@@ -286,28 +147,14 @@ __global__ __launch_bounds__(256) void k_wfix(gpsx_wfix_cfg_t cfg, const gpsx_wo
       l2 /= range;
       const double rho = range + kOmegaE * (px * x1 - py * x0) / kC;
       row = !(rho <= 0.0);
-      double az = 0.0, el = kPi / 2.0;
-      if (hgt > -kRe) {
-        const double sp = sin(lat), cp = cos(lat), sl = sin(lon), cl = cos(lon);
-        const double east = -sl * l0 + cl * l1;
-        const double north = -sp * cl * l0 - sp * sl * l1 + cp * l2;
-        const double up = cp * cl * l0 + cp * sl * l1 + sp * l2;
-        az = east * east + north * north < 1E-12 ? 0.0 : atan2(east, north);
-        if (az < 0.0)
-          az += 2 * kPi;
-        el = asin(up);
-      }
+      double az, el;
+      az_el(l0, l1, l2, lat, lon, hgt, az, el);
       row = row && !(el < 0.0) && healthy;
       if (row) {
-        const double dion = klobuchar(tow, ion, lat, lon, hgt, az, el);
-        const double dtrp = saastamoinen(lat, hgt, el, 0.7);
-        const double v_ion = (dion * 0.5) * (dion * 0.5);
-        const double sin_el = sin(el);
-        const double v_trp = (0.3 / (sin_el + 0.1)) * (0.3 / (sin_el + 0.1));
-        const double ev = 0.003 * 0.003;
-        const double v_meas = ev * (ev + ev / sin_el);
+        double dion, dtrp;
+        const double var = pr_model(tow, ion, lat, lon, hgt, az, el, svar, dion, dtrp);
         v = (pr - tgd) - (rho + dion + dtrp + x3 - kC * clk);
-        const double sig = sqrt(v_meas + svar + v_ion + v_trp);
+        const double sig = sqrt(var);
         a0 = -l0 / sig;
         a1 = -l1 / sig;
         a2 = -l2 / sig;
@@ -421,14 +268,8 @@ void launch_wfix(hipStream_t s, const gpsx_wfix_cfg_t &cfg, const gpsx_wobs_t *d
 {
   if (n_rx < 1 || n_rx > (1 << 20) || cfg.ch_per_rx < 1 || cfg.ch_per_rx > 64)
     return;
-  int w = 1, log2w = 0;
-  while (w < cfg.ch_per_rx) {
-    w <<= 1;
-    log2w++;
-  }
-  const unsigned long long lanes = (unsigned long long)n_rx << log2w;   // at most 2^26
-  hipLaunchKernelGGL(k_wfix, dim3((unsigned)((lanes + 255ull) / 256ull)), dim3(256), 0, s, cfg, d_obs, d_eph, d_lock, d_prev, n_rx, w, log2w, d_fix,
-                     d_pr_m);
+  const Geometry g = geometry_of(n_rx, cfg.ch_per_rx);
+  hipLaunchKernelGGL(k_wfix, dim3(g.grid), dim3(256), 0, s, cfg, d_obs, d_eph, d_lock, d_prev, n_rx, g.w, g.log2w, d_fix, d_pr_m);
 }
 
 }  // namespace gpsx

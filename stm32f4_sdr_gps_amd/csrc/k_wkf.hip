@@ -12,20 +12,23 @@
 // then in every lane, unrolled and in registers, nothing indexed by a run-time value: (P-)^-1 by a Cholesky factorisation, + I, P+ by
 // a second one, x+ = x- + P+ g.  The group's first lane writes the record and the state.  FP64 on the vector ALU; 390 VGPRs (one wave
 // per SIMD, as k_wfix), 106 SGPRs, no LDS, no scratch (build.py check_wkf).
+// The parts it shares with k_wfix, k_wfde and k_wvel are gpsx_wsolve_parts.hpp's; tri and spd_inverse are this file's.
 //
-// Every cross-lane operation runs under wave-uniform control flow: there is no branch around a ballot or a shuffle; a lane without a
-// row adds zeros, a group that does not run (out of range, BAD, not initialised) computes on zeros and masks its result; nothing
-// returns before the last shuffle.  The lane-local loops are bounded: the repair's two passes, Kepler at 30 steps, the geodetic fixed
-// point at 30.  Every store is an ordinary vector store.  The satellite text is this file's own (k_wfix.hip, k_wfde.hip and
-// k_wvel.hip stay instruction for instruction what they were).
+// Every cross-lane operation runs under wave-uniform control flow: there is no branch around a ballot or a shuffle -- the six
+// ballots and every group_sum (a butterfly of width w, w the launch's) stand at the kernel's top level, the sums in loops that are
+// unrolled -- a lane without a row adds zeros, a group that does not run (out of range, BAD, not initialised) computes on zeros and
+// masks its result; nothing returns before the last shuffle.  The lane-local loops are bounded: the repair's two passes, Kepler at
+// 30 steps, the geodetic fixed point at 30.  Every store is an ordinary vector store.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wsolve_parts.hpp"
 
 namespace gpsx {
+using namespace wsolve;
 
 namespace {
 
@@ -45,85 +48,6 @@ static_assert(sizeof(gpsx_wkf_t) == 240 && offsetof(gpsx_wkf_t, n_pr) == 4 && of
               offsetof(gpsx_wkf_t, cdrift_mps) == 120 && offsetof(gpsx_wkf_t, geo) == 128 && offsetof(gpsx_wkf_t, enu) == 152 &&
               offsetof(gpsx_wkf_t, sigma) == 176 && offsetof(gpsx_wkf_t, nis_pr) == 208 && offsetof(gpsx_wkf_t, nis_dop) == 216 &&
               offsetof(gpsx_wkf_t, rcv_ms) == 224 && offsetof(gpsx_wkf_t, week) == 232 && offsetof(gpsx_wkf_t, reserved) == 236, "gpsx_wkf_t layout");
-static_assert(sizeof(gpsx_wobs_t) == 32 && sizeof(gpsx_weph_t) == 256 && sizeof(gpsx_wlock_t) == 64 && sizeof(gpsx_wfix_t) == 128 &&
-              sizeof(gpsx_wvel_t) == 112, "the records this stage reads");
-
-constexpr double kC = 299792458.0;
-constexpr double kMs = 299792.458;   // c per millisecond
-constexpr double kPi = 3.1415926535897932;
-constexpr double kMu = 3.9860050E14;
-constexpr double kOmegaE = 7.2921151467E-5;
-constexpr double kRe = 6378137.0;
-constexpr double kFe = 1.0 / 298.257223563;
-constexpr double kPivot = 1E-10;   // gpsx_wfix's: a pivot at or below this share of its diagonal element is round-off
-constexpr double kHalfWeek = 302400.0, kWeek = 604800.0;
-constexpr long long kWeekMs = 604800000, kHalfMs = kWeekMs / 2;
-
-__device__ const double kUra[15] = {2.4, 3.4, 4.85, 6.85, 9.65, 13.65, 24.0, 48.0, 96.0, 192.0, 384.0, 768.0, 1536.0, 3072.0, 6144.0};
-__device__ const double kIonDefault[8] = {0.1118E-07, -0.7451E-08, -0.5961E-07, 0.1192E-06, 0.1167E+06, -0.2294E+06, -0.1311E+06, 0.1049E+07};
-
-__device__ __forceinline__ bool finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }   // (a NaN fails it)
-__device__ __forceinline__ long long fold_ms(long long d) { return ((d + kHalfMs) % kWeekMs + kWeekMs) % kWeekMs - kHalfMs; }
-__device__ __forceinline__ double fold(double d) { return d > kHalfWeek ? d - kWeek : (d < -kHalfWeek ? d + kWeek : d); }
-__device__ __forceinline__ double clock_poly(const gpsx_weph_t &e, double t) { return e.f0 + e.f1 * t + e.f2 * t * t; }
-
-// ecef2pos as the host has it (what it does at the origin included), its fixed point bounded
-__device__ __forceinline__ void geodetic(double x, double y, double zr, double &lat, double &lon, double &hgt)
-{
-  const double e2 = kFe * (2.0 - kFe), r2 = x * x + y * y;
-  double v = kRe, z = zr, zk = 0.0;
-  for (int it = 0; __builtin_fabs(z - zk) >= 1E-4 && it < 30; it++) {
-    zk = z;
-    const double sp = z / sqrt(r2 + z * z);
-    v = kRe / sqrt(1.0 - e2 * sp * sp);
-    z = zr + v * e2 * sp;
-  }
-  lat = r2 > 1E-12 ? atan(z / sqrt(r2)) : (zr > 0.0 ? kPi / 2.0 : -kPi / 2.0);
-  lon = r2 > 1E-12 ? atan2(y, x) : 0.0;
-  hgt = sqrt(r2 + z * z) - v;
-}
-
-__device__ __forceinline__ double klobuchar(double tow, const double *ion, double lat, double lon, double hgt, double az, double el)
-{
-  if (hgt < -1E3 || el <= 0)
-    return 0.0;
-  const double psi = 0.0137 / (el / kPi + 0.11) - 0.022;
-  double phi = lat / kPi + psi * cos(az);
-  phi = phi > 0.416 ? 0.416 : (phi < -0.416 ? -0.416 : phi);
-  const double lam = lon / kPi + psi * sin(az) / cos(phi * kPi);
-  phi += 0.064 * cos((lam - 1.617) * kPi);
-  double tt = 43200.0 * lam + tow;
-  tt -= floor(tt / 86400.0) * 86400.0;
-  const double slant = 1.0 + 16.0 * pow(0.53 - el / kPi, 3.0);
-  double amp = ion[0] + phi * (ion[1] + phi * (ion[2] + phi * ion[3]));
-  double per = ion[4] + phi * (ion[5] + phi * (ion[6] + phi * ion[7]));
-  amp = amp < 0.0 ? 0.0 : amp;
-  per = per < 72000.0 ? 72000.0 : per;
-  const double x = 2.0 * kPi * (tt - 50400.0) / per;
-  return kC * slant * (__builtin_fabs(x) < 1.57 ? 5E-9 + amp * (1.0 + x * x * (-0.5 + x * x / 24.0)) : 5E-9);
-}
-
-__device__ __forceinline__ double saastamoinen(double lat, double h, double el, double humidity)
-{
-  if (h < -100.0 || 1E4 < h || el <= 0)
-    return 0.0;
-  const double hgt = h < 0.0 ? 0.0 : h;
-  const double pres = 1013.25 * pow(1.0 - 2.2557E-5 * hgt, 5.2568);
-  const double temp = 15.0 - 6.5E-3 * hgt + 273.16;
-  const double e = 6.108 * humidity * exp((17.15 * temp - 4684.0) / (temp - 38.45));
-  const double z = kPi / 2.0 - el;
-  const double dry = 0.0022768 * pres / (1.0 - 0.00266 * cos(2.0 * lat) - 0.00028 * hgt / 1E3) / cos(z);
-  const double wet = 0.002277 * (1255.0 / temp + 0.05) * e / cos(z);
-  return dry + wet;
-}
-
-// the sum over a group's w lanes, in every one of them (the same bits in each: an addition commutes)
-__device__ __forceinline__ double group_sum(double v, int w)
-{
-  for (int m = 1; m < w; m <<= 1)   // (w is the launch's: wave-uniform)
-    v += __shfl_xor(v, m);
-  return v;
-}
 
 // the place of element (i, j) of a symmetric 8 x 8 in its upper triangle, row by row
 __device__ __forceinline__ constexpr int tri(int i, int j) { return i <= j ? i * (17 - i) / 2 + (j - i) : j * (17 - j) / 2 + (i - j); }
@@ -183,14 +107,11 @@ __global__ __launch_bounds__(256) void k_wkf(gpsx_wkf_cfg_t cfg, const gpsx_wobs
                                              const gpsx_wfix_t *fix, const gpsx_wvel_t *vel, int n_rx, int n_blocks, int w, int log2w,
                                              gpsx_wkf_state_t *state, gpsx_wkf_t *kf, u32 *bad_state)
 {
-  const int lane = (int)(threadIdx.x & 63u);
-  const long long g = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
-  const int j = (int)(g & (long long)(w - 1));
-  const long long r = g >> log2w;
-  const int base = lane & ~(w - 1);
-  const bool in_rx = r < (long long)n_rx;
-  const bool slot = in_rx && j < cfg.ch_per_rx;
-  const size_t at = slot ? (size_t)r * (size_t)cfg.ch_per_rx + (size_t)j : 0;
+  const Lane ln = lane_of(w, log2w, n_rx, cfg.ch_per_rx);
+  const int j = ln.j, base = ln.base;
+  const long long r = ln.r;
+  const bool in_rx = ln.in_rx, slot = ln.slot;
+  const size_t at = ln.at;
 
   // ---- the receiver's state, in every lane of its group; what kind of call this is for it ----
   double x[8], P[36];
@@ -322,14 +243,8 @@ __global__ __launch_bounds__(256) void k_wkf(gpsx_wkf_cfg_t cfg, const gpsx_wobs
     may_pr = usable && (lf & GPSX_WLOCK_CODE) != 0;
     may_dop = usable && (lf & GPSX_WLOCK_CARRIER) != 0 && __builtin_fabsf(o.if_freq_offset_hz) <= 3.402823466e+38f;
   }
-  double ion_sq = 0.0;
-#pragma unroll
-  for (int i = 0; i < 8; i++)
-    ion_sq += cfg.ion[i] * cfg.ion[i];
   double ion[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++)
-    ion[i] = ion_sq <= 0.0 ? kIonDefault[i] : cfg.ion[i];
+  choose_ion(cfg.ion, ion);
   double lat, lon, hgt;
   geodetic(x[0], x[1], x[2], lat, lon, hgt);
   const double tow = (double)rcv_ms / 1000.0;
@@ -342,63 +257,12 @@ __global__ __launch_bounds__(256) void k_wkf(gpsx_wkf_cfg_t cfg, const gpsx_wobs
   for (int pass = 0; pass < 2; pass++) {
     prow = false;
     drow = false;
-    double px = 0.0, py = 0.0, pz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0, rate = 0.0, clk = 0.0, svar = 0.0;
+    SatState s = {};
     bool sat = false;
     const long long tx_ms = o.tx_ms + (long long)k_ms;
-    if (may_pr || may_dop) {
-      const double t_sv = ((double)tx_ms - (double)o.code_phase_fine / 16368.0) / 1000.0;
-      const double toc = (double)(((e.toc_time - 315964800ll) % 604800ll + 604800ll) % 604800ll) + e.toc_sec;
-      double tc = fold(t_sv - toc);
-      tc -= clock_poly(e, tc);
-      tc -= clock_poly(e, tc);
-      const double t = t_sv - clock_poly(e, tc);
-      const double tk = fold(t - e.toes);
-      if (__builtin_fabs(tk) <= 7201.0 && e.A > 0.0) {
-        const double n0 = sqrt(kMu / (e.A * e.A * e.A)) + e.deln;
-        const double mean = e.M0 + n0 * tk;
-        double ecc = mean, was = 0.0;
-        int n = 0;
-        for (; __builtin_fabs(ecc - was) > 1E-14 && n < 30; n++) {
-          was = ecc;
-          ecc -= (ecc - e.e * sin(ecc) - mean) / (1.0 - e.e * cos(ecc));
-        }
-        if (n < 30) {
-          const double se = sin(ecc), ce = cos(ecc);
-          const double root = sqrt(1.0 - e.e * e.e), den = 1.0 - e.e * ce;
-          double u = atan2(root * se, ce - e.e) + e.omg;
-          double rad = e.A * den;
-          double inc = e.i0 + e.idot * tk;
-          const double s2 = sin(2.0 * u), c2 = cos(2.0 * u);
-          const double ed = n0 / den;              // E'
-          const double nud = ed * root / den;      // nu'
-          const double ud = nud * (1.0 + 2.0 * (e.cus * c2 - e.cuc * s2));
-          const double rd = e.A * e.e * ed * se + 2.0 * nud * (e.crs * c2 - e.crc * s2);
-          const double id = e.idot + 2.0 * nud * (e.cis * c2 - e.cic * s2);
-          const double od = e.OMGd - kOmegaE;
-          u += e.cus * s2 + e.cuc * c2;
-          rad += e.crs * s2 + e.crc * c2;
-          inc += e.cis * s2 + e.cic * c2;
-          const double su = sin(u), cu = cos(u), si = sin(inc), ci = cos(inc);
-          const double xo = rad * cu, yo = rad * su;
-          const double xd = rd * cu - rad * ud * su, yd = rd * su + rad * ud * cu;
-          const double node = e.OMG0 + od * tk - kOmegaE * e.toes;
-          const double sn = sin(node), cn = cos(node);
-          px = xo * cn - yo * ci * sn;
-          py = xo * sn + yo * ci * cn;
-          pz = yo * si;
-          vx = xd * cn - yd * ci * sn + yo * id * si * sn - od * py;
-          vy = xd * sn + yd * ci * cn - yo * id * si * cn + od * px;
-          vz = yd * si + yo * id * ci;
-          const double tcl = fold(t - toc);
-          rate = e.f1 + 2.0 * e.f2 * tcl - 2.0 * sqrt(kMu * e.A) * e.e * ce * ed / (kC * kC);
-          clk = clock_poly(e, tcl) - 2.0 * sqrt(kMu * e.A) * e.e * se / (kC * kC);
-          const double ura = (e.sva < 0 || e.sva > 14) ? 6144.0 : kUra[e.sva];
-          svar = ura * ura;
-          sat = true;
-        }
-      }
-    }
-    double l0 = px - x[0], l1 = py - x[1], l2 = pz - x[2];
+    if (may_pr || may_dop)
+      sat = sat_at_clock(e, ((double)tx_ms - (double)o.code_phase_fine / 16368.0) / 1000.0, s);
+    double l0 = s.px - x[0], l1 = s.py - x[1], l2 = s.pz - x[2];
     const double range = sqrt(l0 * l0 + l1 * l1 + l2 * l2);
     if (sat && !(range == 0.0)) {
       l0 /= range;
@@ -406,37 +270,23 @@ __global__ __launch_bounds__(256) void k_wkf(gpsx_wkf_cfg_t cfg, const gpsx_wobs
       l2 /= range;
       const double kk = kOmegaE / kC;
       if (may_dop) {
-        a0 = -l0 - kk * py;
-        a1 = -l1 + kk * px;
+        a0 = -l0 - kk * s.py;
+        a1 = -l1 + kk * s.px;
         a2 = -l2;
-        y = cfg.mps_per_hz * (double)o.if_freq_offset_hz - (l0 * vx + l1 * vy + l2 * vz + kk * (vx * x[1] - vy * x[0]) - kC * rate);
+        y = cfg.mps_per_hz * (double)o.if_freq_offset_hz - (l0 * s.vx + l1 * s.vy + l2 * s.vz + kk * (s.vx * x[1] - s.vy * x[0]) - kC * s.rate);
         y = y - (a0 * x[4] + a1 * x[5] + a2 * x[6] + x[7]);
         drow = true;
       }
-      const double rn = sqrt(px * px + py * py + pz * pz);
-      const double rho = range + kOmegaE * (px * x[1] - py * x[0]) / kC;
-      double az = 0.0, el = kPi / 2.0;
-      if (hgt > -kRe) {
-        const double sp = sin(lat), cp = cos(lat), sl = sin(lon), cl = cos(lon);
-        const double east = -sl * l0 + cl * l1;
-        const double north = -sp * cl * l0 - sp * sl * l1 + cp * l2;
-        const double up = cp * cl * l0 + cp * sl * l1 + sp * l2;
-        az = east * east + north * north < 1E-12 ? 0.0 : atan2(east, north);
-        if (az < 0.0)
-          az += 2 * kPi;
-        el = asin(up);
-      }
+      const double rn = sqrt(s.px * s.px + s.py * s.py + s.pz * s.pz);
+      const double rho = range + kOmegaE * (s.px * x[1] - s.py * x[0]) / kC;
+      double az, el;
+      az_el(l0, l1, l2, lat, lon, hgt, az, el);
       if (may_pr && !(rn < kRe) && !(rho <= 0.0) && !(el < 0.0)) {
         const double pr = 299792458e-3 * ((double)fold_ms(rcv_ms - tx_ms) + (double)o.code_phase_fine / 16368.0);
-        const double dion = klobuchar(tow, ion, lat, lon, hgt, az, el);
-        const double dtrp = saastamoinen(lat, hgt, el, 0.7);
-        const double v_ion = (dion * 0.5) * (dion * 0.5);
-        const double sin_el = sin(el);
-        const double v_trp = (0.3 / (sin_el + 0.1)) * (0.3 / (sin_el + 0.1));
-        const double ev = 0.003 * 0.003;
-        const double v_meas = ev * (ev + ev / sin_el);
-        v = (pr - kC * e.tgd) - (rho + dion + dtrp + x[3] - kC * clk);
-        sig2 = (v_meas + svar + v_ion + v_trp) + cfg.sig_pr_m * cfg.sig_pr_m;
+        double dion, dtrp;
+        const double var = pr_model(tow, ion, lat, lon, hgt, az, el, s.svar, dion, dtrp);
+        v = (pr - kC * e.tgd) - (rho + dion + dtrp + x[3] - kC * s.clk);
+        sig2 = var + cfg.sig_pr_m * cfg.sig_pr_m;
         h0 = -l0;
         h1 = -l1;
         h2 = -l2;
@@ -472,7 +322,7 @@ __global__ __launch_bounds__(256) void k_wkf(gpsx_wkf_cfg_t cfg, const gpsx_wobs
   }
   const bool pr_ok = prow && !k_out && finite(v) && finite(s_pr) && !(v * v > gg * s_pr);
   const bool dop_ok = drow && finite(y) && finite(s_dop) && !(y * y > gg * s_dop);
-  const u64 group_bits = (w == 64 ? ~0ull : ((1ull << w) - 1ull));
+  const u64 group_bits = ln.group_bits;
   const u64 pr_mask = (__ballot(pr_ok) >> base) & group_bits, dop_mask = (__ballot(dop_ok) >> base) & group_bits;
   const u64 rej_pr = (__ballot(prow && !pr_ok) >> base) & group_bits, rej_dop = (__ballot(drow && !dop_ok) >> base) & group_bits;
   const u64 plus_mask = (__ballot(k_ms > 0) >> base) & group_bits, minus_mask = (__ballot(k_ms < 0) >> base) & group_bits;
@@ -564,10 +414,8 @@ __global__ __launch_bounds__(256) void k_wkf(gpsx_wkf_cfg_t cfg, const gpsx_wobs
     if (flags & (GPSX_WKF_INIT | GPSX_WKF_UPDATED | GPSX_WKF_COAST)) {
       double glat, glon, ghgt;
       geodetic(x[0], x[1], x[2], glat, glon, ghgt);
-      const double sp = sin(glat), cp = cos(glat), sl = sin(glon), cl = cos(glon);
-      const double east = -sl * x[4] + cl * x[5];
-      const double north = -sp * cl * x[4] - sp * sl * x[5] + cp * x[6];
-      const double up = cp * cl * x[4] + cp * sl * x[5] + sp * x[6];
+      double east, north, up;
+      to_enu(glat, glon, x[4], x[5], x[6], east, north, up);
       bool fin = finite(glat) && finite(glon) && finite(ghgt) && finite(east) && finite(north) && finite(up) && finite(nis_pr) && finite(nis_dop);
       float sg[8];
 #pragma unroll
@@ -647,14 +495,9 @@ void launch_wkf(hipStream_t s, const gpsx_wkf_cfg_t &cfg, const gpsx_wobs_t *d_o
 {
   if (n_rx < 1 || n_rx > (1 << 20) || cfg.ch_per_rx < 1 || cfg.ch_per_rx > 64 || n_blocks < 1 || n_blocks > 4096)
     return;
-  int w = 1, log2w = 0;
-  while (w < cfg.ch_per_rx) {
-    w <<= 1;
-    log2w++;
-  }
-  const unsigned long long lanes = (unsigned long long)n_rx << log2w;   // at most 2^26
-  hipLaunchKernelGGL(k_wkf, dim3((unsigned)((lanes + 255ull) / 256ull)), dim3(256), 0, s, cfg, d_obs, d_eph, d_lock, d_fix, d_vel, n_rx, n_blocks, w,
-                     log2w, d_state, d_kf, d_bad_state);
+  const Geometry g = geometry_of(n_rx, cfg.ch_per_rx);
+  hipLaunchKernelGGL(k_wkf, dim3(g.grid), dim3(256), 0, s, cfg, d_obs, d_eph, d_lock, d_fix, d_vel, n_rx, n_blocks, g.w, g.log2w, d_state, d_kf,
+                     d_bad_state);
 }
 
 }  // namespace gpsx

@@ -11,17 +11,18 @@
 //
 // Every cross-lane operation runs under wave-uniform control flow: there is no branch around a ballot or a shuffle, a lane without a
 // row adds zeros, and nothing returns before the last shuffle.  The only lane-local loop is Kepler's, bounded at 30 steps.
-// The satellite text is this file's own (k_wfix.hip and k_wfde.hip stay instruction for instruction what they were).
+// gpsx_wsolve_parts.hpp has the constants, the small helpers and the lane geometry; everything else is this file's own text, which
+// keeps the kernel instruction for instruction what it was (a shared part moved it by 0.4 % at 4 slots per receiver).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
 #include "gpsx_device.hpp"
 #include "gpsx_kernels.hpp"
+#include "gpsx_wsolve_parts.hpp"
 
 namespace gpsx {
-
-namespace {
+using namespace wsolve;
 
 static_assert(sizeof(gpsx_wvel_cfg_t) == 32 && offsetof(gpsx_wvel_cfg_t, ch_per_rx) == 8 && offsetof(gpsx_wvel_cfg_t, min_sats) == 12 &&
               offsetof(gpsx_wvel_cfg_t, reserved) == 16, "gpsx_wvel_cfg_t layout");
@@ -29,40 +30,15 @@ static_assert(sizeof(gpsx_wvel_t) == 112 && offsetof(gpsx_wvel_t, n_used) == 4 &
               offsetof(gpsx_wvel_t, vel) == 16 && offsetof(gpsx_wvel_t, drift_s_s) == 40 && offsetof(gpsx_wvel_t, enu) == 48 &&
               offsetof(gpsx_wvel_t, qv) == 72 && offsetof(gpsx_wvel_t, resid_rms_mps) == 96 && offsetof(gpsx_wvel_t, reserved) == 104,
               "gpsx_wvel_t layout");
-static_assert(sizeof(gpsx_wobs_t) == 32 && sizeof(gpsx_weph_t) == 256 && sizeof(gpsx_wlock_t) == 64 && sizeof(gpsx_wfix_t) == 128,
-              "the records this stage reads");
-
-constexpr double kC = 299792458.0;
-constexpr double kMu = 3.9860050E14;
-constexpr double kOmegaE = 7.2921151467E-5;
-constexpr double kPivot = 1E-10;   // gpsx_wfix's: a pivot at or below this share of its diagonal element is round-off: SINGULAR
-constexpr double kHalfWeek = 302400.0, kWeek = 604800.0;
-
-__device__ __forceinline__ bool finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }   // (a NaN fails it)
-__device__ __forceinline__ double fold(double d) { return d > kHalfWeek ? d - kWeek : (d < -kHalfWeek ? d + kWeek : d); }
-__device__ __forceinline__ double clock_poly(const gpsx_weph_t &e, double t) { return e.f0 + e.f1 * t + e.f2 * t * t; }
-
-// the sum over a group's w lanes, in every one of them (the same bits in each: an addition commutes)
-__device__ __forceinline__ double group_sum(double v, int w)
-{
-  for (int m = 1; m < w; m <<= 1)   // (w is the launch's: wave-uniform)
-    v += __shfl_xor(v, m);
-  return v;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void k_wvel(gpsx_wvel_cfg_t cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
                                               const gpsx_wfix_t *fix, int n_rx, int w, int log2w, gpsx_wvel_t *vel)
 {
-  const int lane = (int)(threadIdx.x & 63u);
-  const long long g = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
-  const int j = (int)(g & (long long)(w - 1));
-  const long long r = g >> log2w;
-  const int base = lane & ~(w - 1);
-  const bool in_rx = r < (long long)n_rx;
-  const bool slot = in_rx && j < cfg.ch_per_rx;
-  const size_t at = slot ? (size_t)r * (size_t)cfg.ch_per_rx + (size_t)j : 0;
+  const Lane ln = lane_of(w, log2w, n_rx, cfg.ch_per_rx);
+  const int j = ln.j, base = ln.base;
+  const long long r = ln.r;
+  const bool in_rx = ln.in_rx, slot = ln.slot;
+  const size_t at = ln.at;
 
   // ---- the receiver's fix, the lane's records ----
   bool fixed = false;
@@ -98,11 +74,11 @@ __global__ __launch_bounds__(256) void k_wvel(gpsx_wvel_cfg_t cfg, const gpsx_wo
   if (cand) {
     const double t_sv = ((double)o.tx_ms - (double)o.code_phase_fine / 16368.0) / 1000.0;
     const double toc = (double)(((e.toc_time - 315964800ll) % 604800ll + 604800ll) % 604800ll) + e.toc_sec;
-    double tc = fold(t_sv - toc);
+    double tc = fold_s(t_sv - toc);
     tc -= clock_poly(e, tc);
     tc -= clock_poly(e, tc);
     const double t = t_sv - clock_poly(e, tc);
-    const double tk = fold(t - e.toes);
+    const double tk = fold_s(t - e.toes);
     if (__builtin_fabs(tk) <= 7201.0 && e.A > 0.0) {
       const double n0 = sqrt(kMu / (e.A * e.A * e.A)) + e.deln;
       const double mean = e.M0 + n0 * tk;
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(256) void k_wvel(gpsx_wvel_cfg_t cfg, const gpsx_wo
         vx = xd * cn - yd * ci * sn + yo * id * si * sn - od * py;
         vy = xd * sn + yd * ci * cn - yo * id * si * cn + od * px;
         vz = yd * si + yo * id * ci;
-        rate = e.f1 + 2.0 * e.f2 * fold(t - toc) - 2.0 * sqrt(kMu * e.A) * e.e * ce * ed / (kC * kC);
+        rate = e.f1 + 2.0 * e.f2 * fold_s(t - toc) - 2.0 * sqrt(kMu * e.A) * e.e * ce * ed / (kC * kC);
         sat = true;
       }
     }
@@ -163,7 +139,7 @@ __global__ __launch_bounds__(256) void k_wvel(gpsx_wvel_cfg_t cfg, const gpsx_wo
     a2 = -l2;
     a3 = 1.0;
   }
-  const u64 group_bits = (w == 64 ? ~0ull : ((1ull << w) - 1ull));
+  const u64 group_bits = ln.group_bits;
   const u64 rows = (__ballot(row) >> base) & group_bits;
   const u64 wilds = (__ballot(wild) >> base) & group_bits;
   const double n00 = group_sum(a0 * a0, w), n10 = group_sum(a1 * a0, w), n11 = group_sum(a1 * a1, w), n20 = group_sum(a2 * a0, w),
@@ -240,13 +216,8 @@ void launch_wvel(hipStream_t s, const gpsx_wvel_cfg_t &cfg, const gpsx_wobs_t *d
 {
   if (n_rx < 1 || n_rx > (1 << 20) || cfg.ch_per_rx < 1 || cfg.ch_per_rx > 64)
     return;
-  int w = 1, log2w = 0;
-  while (w < cfg.ch_per_rx) {
-    w <<= 1;
-    log2w++;
-  }
-  const unsigned long long lanes = (unsigned long long)n_rx << log2w;   // at most 2^26
-  hipLaunchKernelGGL(k_wvel, dim3((unsigned)((lanes + 255ull) / 256ull)), dim3(256), 0, s, cfg, d_obs, d_eph, d_lock, d_fix, n_rx, w, log2w, d_vel);
+  const Geometry g = geometry_of(n_rx, cfg.ch_per_rx);
+  hipLaunchKernelGGL(k_wvel, dim3(g.grid), dim3(256), 0, s, cfg, d_obs, d_eph, d_lock, d_fix, n_rx, g.w, g.log2w, d_vel);
 }
 
 }  // namespace gpsx
