@@ -1555,6 +1555,98 @@ int gpsx_wkf_dev(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *d_
 int gpsx_wkf(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *obs, const gpsx_weph_t *eph, const gpsx_wlock_t *lock,
              const gpsx_wfix_t *fix, const gpsx_wvel_t *vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *kf);
 
+/* ---- EXTENSION, not in the reference: acquisition decisions and slot hand-over -- a weighted grid's records to channel states ---------
+ * The stage between the front and the middle of the weighted chain: gpsx_wacq(_dev) sits behind a launch of gpsx_acq_grid_weighted
+ * {,_ms,_coh,_hyb}_dev and in front of gpsx_track_loop_weighted_sync_multi_dev (or, with one receiver, the single-stream sync loops).
+ * It reads the grid's records peaks[n_search][n_prn][n_dopp] where they are, decides per receiver which PRNs are there, picks a slot
+ * for each and writes the hand-over into that slot's states -- and it frees the slots whose code the lock monitor has not found, so
+ * that a lost channel is re-acquired by the next grid launch.  No peak record and no channel state crosses to the host.  The stage is
+ * stateless; it changes no existing struct, kernel or definition (GPSX_VERSION stays 110).  Every decision is in integers; its float
+ * arithmetic is two single-precision operations on one value (step 5).
+ *
+ * g is the description the grid call was given: n_search is n_rx (search s IS receiver s: the grid's search_stride_blocks and the
+ * multi loop's rx_stride_blocks describe the same buffer), prns a HOST pointer, the Doppler grid the grid call's.  The channel of
+ * receiver r's slot j is r * ch_per_rx + j, as in gpsx_track_loop_weighted_sync_multi.
+ *
+ * Definition, per receiver r (everything is an integer but step 5):
+ *   1 best record   per PRN index p: d* = the LOWEST bin whose max_val is the row's greatest; M = that max_val, S = that record's
+ *                   sum, tau = that record's phase
+ *   2 detection     a PRN is detected iff M >= max(min_peak, 1) and (uint64)M * 16368 * det_den >= (uint64)det_num * S: the
+ *                   record's own peak over its mean across the 16 368 phases, at least det_num / det_den.  Exact for any uint32
+ *                   pair (the left side stays below 2^56).  `sum` is the grids' sum mod 2^32, so the statistic needs a mean E(tau)
+ *                   below 2^18 = 2^32 / 16 384: noise at n_coh = 20 x n_seg = 128 is about 1.6 x 10^5
+ *   3 slots         slot j holds a channel iff d_sync_state[r * ch_per_rx + j].loop.prn != GPSX_PRN_NONE.  A slot that holds a
+ *                   channel is EVICTED iff evict_after_blocks > 0, its lock state's flags lack GPSX_WLOCK_CODE and its lock
+ *                   state's blocks_seen >= evict_after_blocks (blocks_seen counts since the hand-over, which zeroes it).  KEPT
+ *                   slots hold a channel and are not evicted; FREE slots are empty or evicted
+ *   4 candidates    the detected PRNs that no kept slot holds (the others are TRACKED), ranked by M, greater first; equal M: the
+ *                   lower PRN index first.  The k-th candidate goes to the k-th free slot in ascending slot order; candidates
+ *                   beyond the free slots are DROPPED
+ *   5 hand-over     the whole 448-byte sync state of the slot becomes zero but for loop.prn = the PRN, loop.if_freq_offset_hz =
+ *                   f = (float)(dopp_min_hz + d* x dopp_step_hz), loop.if_freq_accum = 0 and loop.code_phase_fine = p, where
+ *                     p = (float)tau
+ *                     if code_per_hz != 0.0f && lead_blocks != 0:
+ *                       p = p - (code_per_hz * f) * ((float)lead_blocks * 0.001f)     one IEEE single operation each, in the order
+ *                                                                                      written, no contraction
+ *                       one wrap as the loops': + 16368.0f if p < 0, else - 16368.0f if p >= 16368.0f (a sum that rounds onto
+ *                       16368.0f stays, as in the loops' own definition)
+ *                   An evicted slot that receives no candidate becomes the same zeroed state with loop.prn = GPSX_PRN_NONE.  For
+ *                   every slot handed over or evicted the lock, nav, obs and eph states are set to zero, in each of the four
+ *                   arrays that is not NULL (all zero is "a fresh channel" in all four).  Kept slots and empty slots that stay
+ *                   empty are not written at all
+ *   6 records       d_acq[r] is written as the struct says, d_det[r][p] for every p unless d_det is NULL; every byte of both
+ * What lead_blocks is for: a record's phase belongs to the search's first block, the loop starts lead_blocks later (a 10 x 8 hybrid
+ * search handed to a loop that starts behind it: 80), and a Doppler of f Hz has moved the code by f x code_per_hz samples per second
+ * meanwhile.  code_per_hz is gpsx_waid_t's factor (GPSX_WAID_L1CA).
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written: cfg, g, g->prns, the peaks, d_sync_state or d_acq NULL;
+ * ch_per_rx, det_num, det_den, lead_blocks, evict_after_blocks or reserved out of range; code_per_hz not finite or above 1 in
+ * magnitude; d_lock_state NULL while evict_after_blocks != 0; n_search outside 1 .. 1 048 576; n_prn outside 1 .. 64; n_dopp outside 1 .. 1 048 576; a
+ * PRN outside 1 .. 210 or listed twice; a Doppler bin outside int32; |code_per_hz| x max |bin's Hz| x lead_blocks x 0.001 >= 16368
+ * (checked on the host in double: one wrap suffices); size products that overflow.
+ * _dev only enqueues on the context's stream: behind the grid, before the next loop launch.  Vector ALU (k_wacq: a wave per
+ * receiver, four receivers per workgroup; a row's bins strided over the lanes, a 64-bit key (max_val, bin) reduced by butterflies;
+ * slots and PRNs one per lane, matched and ranked with ballots, popcounts and shuffles; states written 8 bytes per lane). */
+#define GPSX_WACQ_DET_DETECTED 1u
+#define GPSX_WACQ_DET_TRACKED  2u    /* detected, but a kept slot of this receiver already holds the PRN */
+#define GPSX_WACQ_DET_ASSIGNED 4u
+#define GPSX_WACQ_DET_DROPPED  8u    /* a candidate that found no free slot */
+#define GPSX_WACQ_ASSIGNED 1u
+#define GPSX_WACQ_EVICTED  2u
+#define GPSX_WACQ_FULL     4u        /* n_dropped > 0 */
+
+typedef struct {                 /* 32 bytes */
+  int32_t  ch_per_rx;            /* 1 .. 64 */
+  int32_t  det_num, det_den;     /* 1 .. 1024, det_num >= det_den */
+  uint32_t min_peak;             /* a detection also needs max_val >= max(min_peak, 1) */
+  int32_t  lead_blocks;          /* 0 .. 4096: blocks from the instant the record's phase belongs to, to the loop's first block */
+  float    code_per_hz;          /* as gpsx_waid_t's; 0: the phase is not projected */
+  int32_t  evict_after_blocks;   /* 0: never; 1 .. 2^30 */
+  int32_t  reserved;             /* 0 */
+} gpsx_wacq_cfg_t;
+
+typedef struct {                 /* 16 bytes, one per (receiver, PRN index) */
+  uint32_t max_val, phase;       /* the PRN's best record */
+  int32_t  dopp_hz;              /* its bin */
+  uint8_t  flags;  int8_t slot;  /* GPSX_WACQ_DET_*; the slot handed over to, else -1 */
+  uint16_t zero;
+} gpsx_wacq_det_t;
+
+typedef struct {                 /* 64 bytes, one per receiver */
+  uint32_t flags, n_detected, n_tracked, n_assigned, n_evicted, n_dropped;   /*  0 */
+  uint64_t assigned_mask, evicted_mask, kept_mask, free_mask;                /* 24: bit j = slot j; free_mask: after the call */
+  uint32_t reserved[2];                                                      /* 56: 0 */
+} gpsx_wacq_t;
+
+/* d_peaks [n_search][n_prn][n_dopp]; the five state arrays [n_search * ch_per_rx], device memory in both variants (d_lock_state NULL
+ * only with evict_after_blocks == 0; d_nav_state, d_obs_state, d_eph_state NULL: not touched); d_acq [n_search], d_det (NULL: not
+ * wanted) [n_search][n_prn].  gpsx_wacq takes peaks, acq and det in host memory (staged through the arena; it waits for its kernel). */
+int gpsx_wacq_dev(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *d_peaks,
+                  gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+                  gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wacq_t *d_acq, gpsx_wacq_det_t *d_det);
+int gpsx_wacq(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *peaks,
+              gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+              gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wacq_t *acq, gpsx_wacq_det_t *det);
+
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,
  *      with gps_tracking_dll / _pll / _fll / _pll_check :175-393 and gps_nav_data_analyse_new_code, PM/GPS/nav_data.c:46-253)

@@ -128,6 +128,8 @@ def check_no_scratch() -> dict:
     check_wvel()
     # ... and the navigation filter behind them (check_wkf below: two 8 x 8 factorisations per receiver in registers, no scratch, no LDS)
     check_wkf()
+    # ... and, between the grids and the loops, the acquisition decisions (check_wacq below: a wave per receiver, no scratch, no LDS)
+    check_wacq()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -195,6 +197,12 @@ def check_wvel() -> dict:
 def check_wkf() -> dict:
     """k_wkf, every receiver's navigation filter: no LDS either"""
     return check_wsolver("k_wkf.o", "k_wkf", True)
+
+
+def check_wacq() -> dict:
+    """k_wacq, acquisition decisions and slot hand-over (not a solver, but the same terms: an object of its own, exactly one instance,
+    no scratch and no LDS)"""
+    return check_wsolver("k_wacq.o", "k_wacq", True)
 
 
 if __name__ == "__main__":

@@ -320,6 +320,29 @@ def wkf_cfg(ch_per_rx: int, mps_per_hz: float = WVEL_L1CA, sig_pr_m: float = 3.0
     return cfg
 
 
+# gpsx_wacq_cfg_t / gpsx_wacq_det_t / gpsx_wacq_t (acquisition decisions and slot hand-over between a weighted grid and the sync loop)
+WACQ_DET_DETECTED, WACQ_DET_TRACKED, WACQ_DET_ASSIGNED, WACQ_DET_DROPPED = 1, 2, 4, 8
+WACQ_FLAG_ASSIGNED, WACQ_FLAG_EVICTED, WACQ_FLAG_FULL = 1, 2, 4
+WACQ_CFG_DTYPE = np.dtype([("ch_per_rx", "<i4"), ("det_num", "<i4"), ("det_den", "<i4"), ("min_peak", "<u4"), ("lead_blocks", "<i4"),
+                           ("code_per_hz", "<f4"), ("evict_after_blocks", "<i4"), ("reserved", "<i4")])
+WACQ_DET_DTYPE = np.dtype([("max_val", "<u4"), ("phase", "<u4"), ("dopp_hz", "<i4"), ("flags", "u1"), ("slot", "i1"), ("zero", "<u2")])
+WACQ_DTYPE = np.dtype([("flags", "<u4"), ("n_detected", "<u4"), ("n_tracked", "<u4"), ("n_assigned", "<u4"), ("n_evicted", "<u4"),
+                       ("n_dropped", "<u4"), ("assigned_mask", "<u8"), ("evicted_mask", "<u8"), ("kept_mask", "<u8"), ("free_mask", "<u8"),
+                       ("reserved", "<u4", (2,))])
+assert WACQ_CFG_DTYPE.itemsize == 32 and WACQ_DET_DTYPE.itemsize == 16 and WACQ_DTYPE.itemsize == 64
+
+
+def wacq_cfg(ch_per_rx: int, det=(4, 1), min_peak: int = 0, lead_blocks: int = 0, code_per_hz: float = 0.0, evict_after_blocks: int = 0) -> np.ndarray:
+    """a gpsx_wacq_cfg_t as a one-element WACQ_CFG_DTYPE array: a PRN is detected when its best record's peak is at least
+    det[0] / det[1] times its mean over the phases (and at least min_peak); lead_blocks and code_per_hz (WAID_L1CA) project the
+    record's phase to the loop's first block; a slot without code lock evict_after_blocks after its hand-over is freed (0: never)"""
+    cfg = np.zeros(1, WACQ_CFG_DTYPE)
+    for name, v in (("ch_per_rx", ch_per_rx), ("det_num", det[0]), ("det_den", det[1]), ("min_peak", min_peak), ("lead_blocks", lead_blocks),
+                    ("code_per_hz", code_per_hz), ("evict_after_blocks", evict_after_blocks)):
+        cfg[name] = v
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -464,6 +487,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wkf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p]
     lib.gpsx_wkf_dev.argtypes = lib.gpsx_wkf.argtypes
+    lib.gpsx_wacq.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p]
+    lib.gpsx_wacq_dev.argtypes = lib.gpsx_wacq.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1005,6 +1031,26 @@ class Engine:
                                     None if fix is None else fix.ctypes.data, None if vel is None else vel.ctypes.data, n_rx, n_blocks,
                                     C.c_void_p(d_state), kf.ctypes.data), "gpsx_wkf")
         return kf
+
+    def wacq(self, cfg: np.ndarray, peaks: np.ndarray, prns, dopp_min_hz: int, dopp_step_hz: int, d_sync_state: int, d_lock_state: int | None = None,
+             d_nav_state: int | None = None, d_obs_state: int | None = None, d_eph_state: int | None = None, want_det: bool = True):
+        """EXTENSION: acquisition decisions and slot hand-over (include/gpsx.h gpsx_wacq) from a weighted grid's records, PEAK_DTYPE
+        [n_rx, n_prn, n_dopp] in host memory (search s is receiver s; prns and the Doppler grid are the grid call's), on the
+        n_rx * ch_per_rx WSYNC_STATE_DTYPE states at device address d_sync_state and, where given, the lock, nav, obs and eph states of
+        the same slots: a detected PRN that no slot tracks is handed to a free slot, whose states start afresh; cfg from wacq_cfg.
+        -> (WACQ_DTYPE [n_rx], WACQ_DET_DTYPE [n_rx, n_prn]), or the first alone without want_det"""
+        assert cfg.dtype == WACQ_CFG_DTYPE and cfg.size == 1
+        peaks = np.ascontiguousarray(peaks, PEAK_DTYPE)
+        prns = np.ascontiguousarray(prns, np.uint8)
+        assert peaks.ndim == 3 and peaks.shape[1] == len(prns)
+        n_rx, n_prn, n_dopp = peaks.shape
+        g = AcqWeightedT(n_rx, 0, n_prn, prns.ctypes.data_as(C.POINTER(C.c_uint8)), dopp_min_hz, dopp_step_hz, n_dopp, 1)
+        acq, det = np.zeros(n_rx, WACQ_DTYPE), np.zeros((n_rx, n_prn), WACQ_DET_DTYPE)
+        opt = lambda d: C.c_void_p(d) if d else None   # noqa: E731
+        self._chk(self.lib.gpsx_wacq(self.h, cfg.ctypes.data, C.addressof(g), peaks.ctypes.data, C.c_void_p(d_sync_state), opt(d_lock_state),
+                                     opt(d_nav_state), opt(d_obs_state), opt(d_eph_state), acq.ctypes.data, det.ctypes.data if want_det else None),
+                  "gpsx_wacq")
+        return (acq, det) if want_det else acq
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -653,9 +653,96 @@ int wkf(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *obs, const 
       });
 }
 
+// ---- acquisition decisions and slot hand-over (host: peaks, acq and det are host memory, staged through the arena; the five state
+//      arrays are device memory in both variants) -----------------------------------------------------------------------------------------
+int wacq(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *peaks, gpsx_wsync_state_t *d_sync_state,
+         gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state, gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state,
+         gpsx_wacq_t *acq, gpsx_wacq_det_t *det, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !g || !g->prns || !peaks || !d_sync_state || !acq)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->det_num < 1 || cfg->det_num > 1024 || cfg->det_den < 1 || cfg->det_den > 1024 || cfg->det_num < cfg->det_den)
+    return fail(ctx, GPSX_EINVAL, "det_num and det_den must be 1..1024, det_num >= det_den");
+  if (cfg->lead_blocks < 0 || cfg->lead_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "lead_blocks must be 0..4096");
+  if (!(__builtin_fabsf(cfg->code_per_hz) <= 1.0f))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "code_per_hz must be finite and -1..1");
+  if (cfg->evict_after_blocks < 0 || cfg->evict_after_blocks > (1 << 30))
+    return fail(ctx, GPSX_EINVAL, "evict_after_blocks must be 0..1073741824");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (cfg->evict_after_blocks != 0 && !d_lock_state)
+    return fail(ctx, GPSX_EINVAL, "evict_after_blocks needs d_lock_state");
+  if (g->n_search < 1 || g->n_search > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_search must be 1..1048576");
+  if (g->n_prn < 1 || g->n_prn > 64)
+    return fail(ctx, GPSX_EINVAL, "n_prn must be 1..64");
+  if (g->n_dopp < 1 || g->n_dopp > (1 << 20))   // (the kernel counts bins in int32, four turns of 64 ahead)
+    return fail(ctx, GPSX_EINVAL, "n_dopp must be 1..1048576");
+  bool listed[GPSX_MAX_PRN + 1] = {};
+  for (int i = 0; i < g->n_prn; i++) {
+    if (g->prns[i] < 1 || g->prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+    if (listed[g->prns[i]])
+      return fail(ctx, GPSX_EINVAL, "a PRN is listed twice");
+    listed[g->prns[i]] = true;
+  }
+  const long long f_first = g->dopp_min_hz, f_last = f_first + (long long)(g->n_dopp - 1) * (long long)g->dopp_step_hz;
+  if (f_last < -2147483647ll - 1 || f_last > 2147483647ll)
+    return fail(ctx, GPSX_EINVAL, "a Doppler bin lies outside int32");
+  const double f_max = (double)std::max(f_first < 0 ? -f_first : f_first, f_last < 0 ? -f_last : f_last);
+  if (std::fabs((double)cfg->code_per_hz) * f_max * (double)cfg->lead_blocks * 0.001 >= 16368.0)
+    return fail(ctx, GPSX_EINVAL, "the projection must stay below one code period (|code_per_hz| x max |Doppler| x lead_blocks x 0.001 < 16368)");
+  size_t peak_bytes = 0, acq_bytes = 0, det_bytes = 0, bytes = 0;
+  if (records_overflow((size_t)g->n_search * (size_t)g->n_prn, g->n_dopp, sizeof(gpsx_peak_t), &peak_bytes) ||
+      records_overflow((size_t)g->n_search, cfg->ch_per_rx, sizeof(gpsx_wsync_state_t), &bytes) ||
+      records_overflow((size_t)g->n_search, g->n_prn, sizeof(gpsx_wacq_det_t), &det_bytes) ||
+      records_overflow((size_t)g->n_search, 1, sizeof(gpsx_wacq_t), &acq_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_search x n_prn x n_dopp records overflow a size");
+  const gpsx_peak_t *d_peaks = peaks;
+  gpsx_wacq_t *d_acq = acq;
+  gpsx_wacq_det_t *d_det = det;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(peak_bytes) + arena_size(acq_bytes) + (det ? arena_size(det_bytes) : 0))) return rc;
+    if (int rc = stage_in(ctx, peaks, peak_bytes / sizeof(gpsx_peak_t), &d_peaks)) return rc;
+    d_acq = arena_take<gpsx_wacq_t>(ctx, (size_t)g->n_search);
+    if (det)
+      d_det = arena_take<gpsx_wacq_det_t>(ctx, det_bytes / sizeof(gpsx_wacq_det_t));
+  }
+  return launch_and_report(
+      ctx, host, "k_wacq", "k_wacq raised the bad-state flag, which it never does",
+      [&](uint32_t *) {
+        launch_wacq(ctx->stream, *cfg, g->n_search, g->n_prn, g->prns, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, d_peaks, d_sync_state, d_lock_state,
+                    d_nav_state, d_obs_state, d_eph_state, d_acq, d_det);
+      },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(acq, d_acq, acq_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (det)
+          HIPCHK(ctx, hipMemcpyAsync(det, d_det, det_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wacq_dev(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *d_peaks,
+                  gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+                  gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wacq_t *d_acq, gpsx_wacq_det_t *d_det)
+{
+  return wacq(ctx, cfg, g, d_peaks, d_sync_state, d_lock_state, d_nav_state, d_obs_state, d_eph_state, d_acq, d_det, false);
+}
+
+int gpsx_wacq(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *peaks,
+              gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+              gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wacq_t *acq, gpsx_wacq_det_t *det)
+{
+  return wacq(ctx, cfg, g, peaks, d_sync_state, d_lock_state, d_nav_state, d_obs_state, d_eph_state, acq, det, true);
+}
 
 int gpsx_wkf_dev(gpsx_ctx *ctx, const gpsx_wkf_cfg_t *cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                  const gpsx_wfix_t *d_fix, const gpsx_wvel_t *d_vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *d_kf)

@@ -207,6 +207,14 @@ void launch_wvel(hipStream_t s, const gpsx_wvel_cfg_t &cfg, const gpsx_wobs_t *d
 void launch_wkf(hipStream_t s, const gpsx_wkf_cfg_t &cfg, const gpsx_wobs_t *d_obs, const gpsx_weph_t *d_eph, const gpsx_wlock_t *d_lock,
                 const gpsx_wfix_t *d_fix, const gpsx_wvel_t *d_vel, int n_rx, int n_blocks, gpsx_wkf_state_t *d_state, gpsx_wkf_t *d_kf,
                 uint32_t *d_bad_state);
+// extension: gpsx_wacq (k_wacq.hip: k_wacq) -- acquisition decisions and slot hand-over between a weighted grid's records d_peaks
+// [n_rx][n_prn][n_dopp] and the [n_rx * ch_per_rx] states of the sync loop and of the four stages behind it (d_lock_st null only
+// with evict_after_blocks == 0; d_nav_st, d_obs_st, d_eph_st may be null): a wave per receiver, no state of its own; prns: the
+// grid's n_prn (<= 64) PRN numbers in HOST memory, passed by value; d_acq [n_rx] 64-byte records and d_det (may be null)
+// [n_rx][n_prn] 16-byte records, every byte of them written.  cfg and the grid as the host checked them: the launcher checks nothing again.
+void launch_wacq(hipStream_t s, const gpsx_wacq_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                 const gpsx_peak_t *d_peaks, gpsx_wsync_state_t *d_sync_st, gpsx_wlock_state_t *d_lock_st, gpsx_wnav_state_t *d_nav_st,
+                 gpsx_wobs_state_t *d_obs_st, gpsx_weph_state_t *d_eph_st, gpsx_wacq_t *d_acq, gpsx_wacq_det_t *d_det);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -97,7 +97,16 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       launch earlier (a device-to-device copy puts them back before every timed launch;
                                                       it is timed alone and subtracted), beside gpsx_wfix_dev (warm start) and
                                                       gpsx_wvel_dev on the same records, the calls taking turns in one process; the
-                                                      lines also go to profiles/r24_weighted_kf_bench.jsonl"""
+                                                      lines also go to profiles/r24_weighted_kf_bench.jsonl
+  bench_track_kernel.py --weighted-acq [N_RXxN_PRNxN_DOPPxCH_PER_RX ...]
+                                                      gpsx_wacq_dev (EXTENSION: acquisition decisions and slot hand-over; k_wacq) at
+                                                      (receivers, PRNs, bins, slots) = (256, 32, 201, 12), (4096, 32, 41, 8), (16384,
+                                                      32, 21, 4): eight of the PRNs detected per receiver, half the slots free, beside
+                                                      (1) a device-to-device hipMemcpyAsync of the peak records it reads and (2)
+                                                      gpsx_memcpy_d2h of those records, the first step of the host path it replaces,
+                                                      the calls taking turns in one process (a hand-over changes the states, so a
+                                                      device-to-device copy puts them back before every timed launch; it is timed alone
+                                                      and subtracted); the lines also go to profiles/r27_weighted_acq_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -170,8 +179,9 @@ def weighted(k_blocks, counts):
             eng.free(p)
 
 
-def _timed_rows(eng, calls, extra):
-    """calls: {name: (blocks per launch, fn)} taking turns, WINDOWS windows each -> {name: median us per launch}, one JSON line each"""
+def _timed_rows(eng, calls, extra, per_channel_ms=True):
+    """calls: {name: (blocks per launch, fn)} taking turns, WINDOWS windows each -> {name: median us per launch}, one JSON line each
+    (per_channel_ms False: a leg whose calls are not per block and channel -- no `blocks`, no `ns_per_channel_ms` in its lines)"""
     e0, e1 = eng.event(), eng.event()
 
     def window(fn, reps):
@@ -194,9 +204,12 @@ def _timed_rows(eng, calls, extra):
     med = {}
     for name, (k, _) in calls.items():
         med[name] = float(np.median(us[name]))
-        print(json.dumps({"call": name, **extra, "blocks": k, "windows": WINDOWS, "launches_per_window": reps[name],
-                          "us_median": round(med[name], 3), "us_min": round(min(us[name]), 3), "us_max": round(max(us[name]), 3),
-                          "ns_per_channel_ms": round(med[name] / k / extra["channels"] * 1e3, 4)}), flush=True)
+        row = {"call": name, **extra, "blocks": k, "windows": WINDOWS, "launches_per_window": reps[name],
+               "us_median": round(med[name], 3), "us_min": round(min(us[name]), 3), "us_max": round(max(us[name]), 3),
+               "ns_per_channel_ms": round(med[name] / k / extra["channels"] * 1e3, 4)}
+        if not per_channel_ms:
+            del row["blocks"], row["ns_per_channel_ms"]
+        print(json.dumps(row), flush=True)
     return med
 
 
@@ -1068,8 +1081,98 @@ def weighted_kf(shapes, out=KF_OUT):
         eng.close()
 
 
+ACQ_OUT = os.path.join(ROOT, "profiles", "r27_weighted_acq_bench.jsonl")
+ACQ_SHAPES = [(256, 32, 201, 12), (4096, 32, 41, 8), (16384, 32, 21, 4)]
+
+
+def weighted_acq(shapes, out=ACQ_OUT):
+    """k_wacq at (receivers, PRNs, bins, slots per receiver): noise records with eight PRNs per receiver standing out, half of a
+    receiver's slots empty and half holding a channel with code lock, so that every receiver hands over ch / 2 PRNs and drops the rest.
+    A call changes the sync states it hands over to, so each timed launch is preceded by a device-to-device copy that puts the sync
+    states back -- timed alone beside it and subtracted.  The yardsticks: a device-to-device copy of the peak records the kernel reads,
+    and gpsx_memcpy_d2h of them into page-locked host memory, the first step of the host path; the calls take turns; the lines go to
+    stdout and to `out`"""
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0, stream=stream.value)
+    try:
+        for n_rx, n_prn, n_dopp, ch in shapes:
+            rng = np.random.default_rng(27)
+            peaks = np.zeros((n_rx, n_prn, n_dopp), capi.PEAK_DTYPE)
+            peaks["max_val"] = rng.integers(15000, 18000, peaks.shape)
+            peaks["sum"] = 138000000
+            peaks["phase"] = rng.integers(0, 16368, peaks.shape)
+            for k in range(8):                   # PRN indices 4 k + (r % 4) stand out in a bin of their own
+                r = np.arange(n_rx)
+                peaks["max_val"][r, (4 * k + r % 4) % n_prn, (37 * k + r) % n_dopp] = 60000 + 1000 * k
+            peaks["avr"] = peaks["sum"] // 16368
+            prns = np.arange(1, n_prn + 1, dtype=np.uint8)
+            n_ch = n_rx * ch
+            sync = np.zeros(n_ch, capi.WSYNC_STATE_DTYPE)
+            sync["loop"]["prn"] = np.where(np.arange(n_ch) % 2 == 0, capi.PRN_NONE, 100 + np.arange(n_ch) % ch)
+            lock = np.zeros(n_ch, capi.WLOCK_STATE_DTYPE)
+            lock["flags"], lock["blocks_seen"] = capi.WLOCK_FLAG_CODE, 5000
+            cfg = capi.wacq_cfg(ch, (4, 1), 0, 80, capi.WAID_L1CA, 1000)
+            g = capi.AcqWeightedT(n_rx, 80, n_prn, prns.ctypes.data_as(C.POINTER(C.c_uint8)), -5000, 10000 // max(n_dopp - 1, 1), n_dopp, 1)
+            sizes = [n_ch * capi.WNAV_STATE_DTYPE.itemsize, n_ch * capi.WOBS_STATE_DTYPE.itemsize, n_ch * capi.WEPH_STATE_DTYPE.itemsize]
+            d_pk, d_copy, d_sync, d_sync0, d_lock = (eng.malloc(b) for b in (peaks.nbytes, peaks.nbytes, sync.nbytes, sync.nbytes, lock.nbytes))
+            d_nav, d_obs, d_eph = (eng.malloc(b) for b in sizes)
+            d_acq, d_det = eng.malloc(n_rx * capi.WACQ_DTYPE.itemsize), eng.malloc(n_rx * n_prn * capi.WACQ_DET_DTYPE.itemsize)
+            host = eng.host_array(peaks.shape, capi.PEAK_DTYPE)
+            for d, a in ((d_pk, peaks), (d_sync0, sync), (d_sync, sync), (d_lock, lock), (d_nav, np.zeros(sizes[0], np.uint8)),
+                         (d_obs, np.zeros(sizes[1], np.uint8)), (d_eph, np.zeros(sizes[2], np.uint8))):
+                eng.h2d(d, a)
+
+            def restore():
+                return hip.hipMemcpyAsync(d_sync, d_sync0, sync.nbytes, 3, stream)
+
+            def wacq():
+                return eng.lib.gpsx_wacq_dev(eng.h, cfg.ctypes.data, C.addressof(g), C.c_void_p(d_pk), C.c_void_p(d_sync), C.c_void_p(d_lock), C.c_void_p(d_nav),
+                                             C.c_void_p(d_obs), C.c_void_p(d_eph), C.c_void_p(d_acq), C.c_void_p(d_det))
+
+            def restore_and_decide():
+                restore()
+                return wacq()
+
+            calls = {"d2d_copy_of_the_sync_states": (1, restore),
+                     "d2d_copy_of_the_peaks": (1, lambda: hip.hipMemcpyAsync(d_copy, d_pk, peaks.nbytes, 3, stream)),
+                     "memcpy_d2h_of_the_peaks": (1, lambda: eng.lib.gpsx_memcpy_d2h(eng.h, host.ctypes.data, C.c_void_p(d_pk), peaks.nbytes)),
+                     "state_copy_then_wacq": (1, restore_and_decide)}
+            med = _timed_rows(eng, calls, {"channels": n_ch, "n_rx": n_rx, "n_prn": n_prn, "n_dopp": n_dopp, "ch_per_rx": ch, "peak_bytes": peaks.nbytes},
+                              per_channel_ms=False)
+            acq = np.zeros(n_rx, capi.WACQ_DTYPE)
+            eng.d2h(acq, d_acq)
+            print(json.dumps({"wacq_check": "records after the timed launches", "n_rx": n_rx, "detected_per_rx": [int(acq["n_detected"].min()), int(acq["n_detected"].max())],
+                              "assigned_per_rx": [int(acq["n_assigned"].min()), int(acq["n_assigned"].max())],
+                              "dropped_per_rx": [int(acq["n_dropped"].min()), int(acq["n_dropped"].max())]}), flush=True)
+            own = med["state_copy_then_wacq"] - med["d2d_copy_of_the_sync_states"]
+            print(json.dumps({"ratio": "k_wacq (the timed pair less the state copy) over the two yardsticks", "n_rx": n_rx, "n_prn": n_prn, "n_dopp": n_dopp,
+                              "ch_per_rx": ch, "wacq_us": round(own, 3), "over_d2d_copy_of_the_peaks": round(own / med["d2d_copy_of_the_peaks"], 3),
+                              "over_memcpy_d2h_of_the_peaks": round(own / med["memcpy_d2h_of_the_peaks"], 4),
+                              "cheaper_than_the_host_copy": bool(own < med["memcpy_d2h_of_the_peaks"]), "ns_per_receiver": round(own / n_rx * 1e3, 2),
+                              "read_GBps": round(peaks.nbytes / own / 1e3, 1)}), flush=True)
+            for p in (d_pk, d_copy, d_sync, d_sync0, d_lock, d_nav, d_obs, d_eph, d_acq, d_det):
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-acq" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-acq"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_acq([tuple(int(v) for v in a.split("x")) for a in args] or ACQ_SHAPES)
     if "--weighted-kf" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-kf"]
         if "--window-s" in args:
