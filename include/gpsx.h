@@ -1647,6 +1647,174 @@ int gpsx_wacq(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted
               gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
               gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wacq_t *acq, gpsx_wacq_det_t *det);
 
+/* ---- EXTENSION, not in the reference: the ephemeris bank -- a receiver's decoded orbits outlive the slots that decoded them ---------
+ * gpsx_weph keeps a satellite's subframes in the state of the slot that tracks it, and gpsx_wacq zeroes that state on every hand-over
+ * and eviction.  A satellite that is lost for ten seconds therefore comes back as a channel without an ephemeris for another 18 .. 30 s,
+ * although its orbit was decoded minutes ago and holds for two hours.  gpsx_wbank(_dev) sits behind gpsx_weph_dev: it keeps, per
+ * receiver and PRN of a list, the newest VALID record any slot has produced, in d_bank[n_rx][n_prn] (device resident, owned by the
+ * caller; all zero = empty), and gives a slot that tracks a listed PRN without a VALID set of its own the bank's in a merged copy of
+ * the launch's records.  The solvers and gpsx_wkf take that copy in d_eph's place.  It changes no existing struct, kernel or
+ * definition (GPSX_VERSION stays 110).  Integers only: records are moved, never evaluated.
+ *
+ * prns is a HOST pointer to n_prn PRN numbers, as gpsx_acq_weighted_t's, passed to the kernel by value; PRN index p is its position
+ * in the list.  The channel of receiver r's slot j is r * ch_per_rx + j.  d_sync_state is only read (for loop.prn).
+ *
+ * Definition, per receiver r:
+ *   1 offer     slot j's PRN is d_sync_state[r * ch_per_rx + j].loop.prn; p_j is its index in prns (GPSX_PRN_NONE and a PRN that
+ *               is not listed have none).  Slot j OFFERS iff it has an index and d_eph[r * ch_per_rx + j].flags has GPSX_WEPH_VALID
+ *   2 store     among the offers for one index p the greatest toe_time wins, among equal toe_time the lowest slot.  d_bank[r][p] is
+ *               replaced by the winner iff the bank's record lacks GPSX_WEPH_VALID or the winner's toe_time >= the bank's: an older
+ *               set never pushes out a newer one; an equal one refreshes ttr (and is counted as stored).  What is stored is the
+ *               slot's record byte for byte but for flags = GPSX_WEPH_VALID (NEW is cleared)
+ *   3 merge     d_eph_out[r * ch_per_rx + j] is d_eph's record unchanged if that has VALID or the slot has no index; otherwise
+ *               d_bank[r][p_j] as step 2 left it, byte for byte, if that has VALID (the slot is FROM THE BANK); otherwise d_eph's
+ *               record unchanged
+ *   4 report    d_rep[r] as the struct says, every byte written
+ * d_eph_out NULL: no merged copy is wanted.  d_eph_out == d_eph: the merge happens in place (only FROM THE BANK records are written).
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written: cfg, prns, d_sync_state, d_eph, d_bank or d_rep NULL;
+ * ch_per_rx outside 1 .. 64; a reserved word != 0; n_rx outside 1 .. 1 048 576; n_prn outside 1 .. 64; a PRN outside 1 .. 210 or
+ * listed twice; d_sync_state not 8-byte aligned, d_bank or (in _dev) d_eph, d_eph_out, d_rep not 16-byte aligned; two of the five
+ * arrays overlapping other than d_eph_out == d_eph; size products that overflow.
+ * _dev only enqueues on the context's stream: behind gpsx_weph_dev, before the solvers.  Vector ALU (k_wbank: a wave per receiver,
+ * four receivers per workgroup, no LDS; slots and PRN indices one per lane, matched with shuffles and ballots; records moved by half
+ * a wave each, 8 bytes per lane, two records a turn; no record is read back in the call that stored it). */
+typedef struct {                 /* 16 bytes */
+  int32_t ch_per_rx;             /* 1 .. 64 */
+  int32_t reserved[3];           /* 0 */
+} gpsx_wbank_cfg_t;
+
+typedef struct {                 /* 32 bytes, one per receiver */
+  uint64_t stored_mask;          /*  0  bit p: d_bank[r][p] was replaced in this call */
+  uint64_t have_mask;            /*  8  bit p: d_bank[r][p] has GPSX_WEPH_VALID after it */
+  uint64_t from_bank_mask;       /* 16  bit j: slot j's merged record is the bank's (also counted when d_eph_out is NULL) */
+  uint16_t n_stored, n_have, n_from_bank, zero;   /* 24  the masks' bit counts; 0 */
+} gpsx_wbank_t;
+
+/* d_sync_state [n_rx * ch_per_rx] and d_bank [n_rx][n_prn]: device memory in both variants.  d_eph, d_eph_out (NULL: not wanted; may be
+ * d_eph itself) [n_rx * ch_per_rx] and d_rep [n_rx]: device memory; gpsx_wbank takes eph, eph_out and rep in host memory (staged
+ * through the arena; it waits for its kernel). */
+int gpsx_wbank_dev(gpsx_ctx *ctx, const gpsx_wbank_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns,
+                   const gpsx_wsync_state_t *d_sync_state, const gpsx_weph_t *d_eph, gpsx_weph_t *d_bank, gpsx_weph_t *d_eph_out,
+                   gpsx_wbank_t *d_rep);
+int gpsx_wbank(gpsx_ctx *ctx, const gpsx_wbank_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns,
+               const gpsx_wsync_state_t *d_sync_state, const gpsx_weph_t *eph, gpsx_weph_t *d_bank, gpsx_weph_t *eph_out,
+               gpsx_wbank_t *rep);
+
+/* ---- EXTENSION, not in the reference: prediction and hot hand-over -- from the filter's state and the bank back to the slots ---------
+ * gpsx_wkf holds every receiver's position, clock, velocity and drift; with an ephemeris that fixes the code phase of any satellite
+ * to a fraction of a sample and its Doppler to a fraction of a hertz.  gpsx_wpred(_dev) sits behind gpsx_wkf_dev and in front of the
+ * next loop launch: for every (receiver, PRN index) of the bank's list it computes elevation, azimuth, pseudorange, code phase and
+ * Doppler at the loop's next block, and hands the satellites that are above el_min_rad, known well enough and tracked by no slot
+ * straight to free slots, with no grid launch; no record and no state crosses to the host.  d_kf_state and d_bank are only read.
+ * The slot bookkeeping (steps 5 - 7) is gpsx_wacq's, so the two stages can be called in either order on one stream.  Nothing existing
+ * changes (GPSX_VERSION stays 110).
+ *
+ * Definition, per receiver r; all arithmetic in IEEE double, uncontracted, with gpsx_wkf's constants (c, ms = 299792.458, W =
+ * 604 800 000, we, Re) and sum orders; P_ij names the state's element as there.
+ *   0 state        without GPSX_WKF_STATE_INIT: NOT_INIT.  A state gpsx_wkf's step 0 would call BAD: BAD.  In either case d_rx[r] and
+ *                  every d_pred[r][p] are zero but for that flag, no slot is read or written, and the call still returns 0: only the
+ *                  filter reports a bad state as an error.
+ *   1 epoch        T = rcv_ms + lead_blocks; T >= W: T -= W, week += 1.  dt = (double)lead_blocks * 1e-3; x^_i = x_i + dt x_(4+i),
+ *                  i = 0 .. 3; x^_4..7 = x_4..7.  P^ is gpsx_wkf step 3's three blocks WITHOUT the q terms (what is known, not what
+ *                  the filter fears): with lead_blocks == 0 it is P.  lat, lon, hgt = ecef2pos of x^_0..2 (30 steps at most).
+ *   2 satellite    for every PRN index p whose bank record has GPSX_WEPH_VALID (HAVE_EPH) and svh == 0, exactly three passes, no
+ *     and range    convergence test.  pr_0 = 72 ms (72 x 299792.458 m).  Pass k = 0, 1, 2:
+ *                    t_sv = ((double)T - pr_k / ms) / 1000, seconds of the week
+ *                    the satellite at its own clock's reading t_sv as in gpsx_wkf's step 5 (ps, vs, d', dts, tgd = c x the
+ *                      record's); the pass fails if |tk| > 7201, A <= 0 or Kepler's iteration needs 30 steps
+ *                    l = ps - x^_0..2, range = |l|; the pass fails if range == 0, |ps| < Re or rho = range + we (ps_x x^_1 - ps_y
+ *                      x^_0) / c <= 0;  e = l / range;  az, el at (lat, lon, hgt) as gpsx_wfix
+ *                    dion = Klobuchar(cfg.ion or the default set, tow = (double)T / 1000), dtrp = Saastamoinen(humidity 0.7); both
+ *                      are 0 where el <= 0 (the models' own rule), so a satellite below the horizon is still predicted
+ *                    pr_(k+1) = (rho + dion + dtrp + x^_3 - c dts) + tgd: the pseudorange for which gpsx_wkf's step 6 has v = 0
+ *                  The last pass's ps, vs, d', e, el, az count.  Why three: pass k+1 is wrong by (range rate / c) <= 3e-6 of what
+ *                  pass k was wrong by (the satellite moves at most 800 m/s along the line of sight during the error in time).  The
+ *                  first guess is off by 20 ms = 6e6 m at most (ranges are 67 .. 86 ms); that leaves 18 m after the first pass,
+ *                  5e-5 m after the second and below 1e-9 m after the third, under the round-off of a 2e7 m range in doubles (4e-9).
+ *   3 observables  u = pr_3 / ms, q = floor(u), code_phase = (u - q) x 16368; tx_ms = (T - q) folded into 0 .. W - 1: gpsx_wobs_t's
+ *                  convention (transmit time at sample 0 = tx_ms - code_phase / 16368 ms).  The Doppler in the loop's units is
+ *                  gpsx_wvel's step 3 read backwards, with rr = x^_0..2, a = (-e_x - k ps_y, -e_y + k ps_x, -e_z, 1), k = we / c:
+ *                    f_hz = ((a_0 x^_4 + a_1 x^_5 + a_2 x^_6 + x^_7) + (e . vs + k (vs_x rr_y - vs_y rr_x) - c d')) / mps_per_hz
+ *                  s_pr = h P^ h^T over states 0 .. 3 with h = (-e, 1), in gpsx_wkf step 8's order (sum_i h_i (sum_j P^_ij h_j),
+ *                  no sig2); s_f = (a P_vv a^T) / (mps_per_hz mps_per_hz) over states 4 .. 7 in the same order.
+ *   4 flags        HAVE_EPH; PREDICTED: three passes that did not fail and pr_3, code_phase, f_hz, el, az, s_pr, s_f and both float
+ *                  sigmas finite (a negative s gives none); VISIBLE: PREDICTED and el >= el_min_rad; CERTAIN: PREDICTED and
+ *                  s_pr <= max_sigma_m^2 and s_f <= max_sigma_hz^2; TRACKED: a kept slot (step 5) holds the PRN, whatever is known
+ *                  of it.  Nothing non-finite is ever written; a PRN without PREDICTED has zeros beside its flags and slot = -1.
+ *   5 slots        gpsx_wacq's step 3, word for word: slot j holds a channel iff its loop.prn != GPSX_PRN_NONE; it is EVICTED iff
+ *                  evict_after_blocks > 0, its lock state's flags lack GPSX_WLOCK_CODE and its blocks_seen >= evict_after_blocks;
+ *                  KEPT slots hold a channel and are not evicted; FREE slots are empty or evicted.
+ *   6 candidates   the PRNs that are VISIBLE and CERTAIN and not TRACKED, ranked by el, greater first; equal el: the lower index
+ *                  first.  handover == 1: the k-th goes to the k-th free slot in ascending order (ASSIGNED, slot), those beyond the
+ *                  free slots are DROPPED.  handover == 0: nothing is assigned, dropped or written; evicted slots stay as they are
+ *                  (evicted_mask still names them, free_mask is the free slots).
+ *   7 hand-over    gpsx_wacq's step 5 with loop.if_freq_offset_hz = (float)f_hz and loop.code_phase_fine = (float)code_phase (a cast
+ *                  that lands on 16368.0f stays, as there) and no projection: step 1 already stands at the loop's first block.  The
+ *                  slot's whole sync state is otherwise zero, its lock, nav, obs and eph states are zeroed where given; an evicted
+ *                  slot without a candidate becomes GPSX_PRN_NONE; kept slots and empty slots that stay empty are not written.
+ *   8 records      d_pred[r][p] (unless NULL) and d_rx[r] as the structs say, every byte of both written.
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written: cfg, prns, d_kf_state, d_bank, d_sync_state or d_rx NULL;
+ * an ion[] not finite; mps_per_hz not finite or 0; el_min_rad not finite or outside +-pi/2; max_sigma_m or max_sigma_hz not finite
+ * or <= 0; ch_per_rx outside 1 .. 64; lead_blocks outside 0 .. 4096; evict_after_blocks outside 0 .. 2^30; handover not 0 or 1; a
+ * reserved word != 0; d_lock_state NULL while evict_after_blocks != 0; n_rx outside 1 .. 1 048 576; n_prn outside 1 .. 64; a PRN
+ * outside 1 .. 210 or listed twice; d_kf_state or d_bank not 16-byte aligned, d_rx or d_pred not 16-byte aligned (_dev); size
+ * products that overflow.
+ * _dev only enqueues.  Vector ALU, FP64 (k_wpred: a wave per receiver, four receivers per workgroup, no LDS; lane p is PRN index p
+ * for steps 2 - 4 -- one satellite evaluation per lane and pass -- and lane j is slot j for steps 5 - 7, with gpsx_wacq's ballots,
+ * shuffles and popcounts; states written 8 bytes per lane).  On one stream: ..., gpsx_weph_dev, gpsx_wbank_dev, the solvers on
+ * d_eph_out, gpsx_wkf_dev, gpsx_wpred_dev, then the next loop launch lead_blocks after the filter's rcv_ms. */
+#define GPSX_WPRED_HAVE_EPH    1u
+#define GPSX_WPRED_PREDICTED   2u
+#define GPSX_WPRED_VISIBLE     4u
+#define GPSX_WPRED_CERTAIN     8u
+#define GPSX_WPRED_TRACKED    16u
+#define GPSX_WPRED_ASSIGNED   32u
+#define GPSX_WPRED_DROPPED    64u
+#define GPSX_WPRED_RX_PREDICTED 1u   /* the state is a filter's: the PRNs were looked at */
+#define GPSX_WPRED_RX_NOT_INIT  2u
+#define GPSX_WPRED_RX_BAD       4u
+#define GPSX_WPRED_RX_ASSIGNED  8u
+#define GPSX_WPRED_RX_EVICTED  16u
+#define GPSX_WPRED_RX_FULL     32u   /* n_dropped > 0 */
+
+typedef struct {                 /* 128 bytes */
+  double  ion[8];                /*   0  as gpsx_wkf_cfg_t's */
+  double  mps_per_hz;            /*  64  as gpsx_wkf_cfg_t's: finite, not 0 */
+  double  el_min_rad;            /*  72  finite, -pi/2 .. pi/2 */
+  double  max_sigma_m;           /*  80  > 0: CERTAIN needs sqrt(s_pr) <= this */
+  double  max_sigma_hz;          /*  88  > 0: ... and sqrt(s_f) <= this */
+  int32_t ch_per_rx;             /*  96  1 .. 64 */
+  int32_t lead_blocks;           /* 100  0 .. 4096: blocks from the filter's rcv_ms to the loop's first block */
+  int32_t evict_after_blocks;    /* 104  0: never; 1 .. 2^30 */
+  int32_t handover;              /* 108  0: predict only; 1: write slots */
+  int32_t reserved[4];           /* 112  0 */
+} gpsx_wpred_cfg_t;
+
+typedef struct {                 /* 64 bytes, one per (receiver, PRN index) */
+  uint32_t flags;  int32_t slot; /*   0  GPSX_WPRED_*; the slot handed over to, else -1 */
+  int64_t  tx_ms;                /*   8  0 .. W - 1 */
+  double   pr_m, code_phase, f_hz, el, az;   /*  16  pr_3 (m), samples 0 .. 16368, the loop's Hz, rad */
+  float    sigma_m, sigma_hz;    /*  56  (float)sqrt(s_pr), (float)sqrt(s_f) */
+} gpsx_wpred_t;
+
+typedef struct {                 /* 64 bytes, one per receiver */
+  uint16_t flags;  int16_t week; /*   0  GPSX_WPRED_RX_*; the week of T */
+  int32_t  t_ms;                 /*   4  T */
+  uint8_t  n_have, n_visible, n_tracked, n_assigned, n_evicted, n_dropped;   /*  8 */
+  uint16_t zero;                 /*  14 */
+  uint64_t visible_mask, have_mask;   /*  16  bit p = PRN index p: VISIBLE; HAVE_EPH.  OR visible_mask over receivers: the next grid's PRNs */
+  uint64_t assigned_mask, evicted_mask, kept_mask, free_mask;   /*  32  bit j = slot j, as gpsx_wacq_t's; free_mask: after the call */
+} gpsx_wpred_rx_t;
+
+/* d_kf_state [n_rx], d_bank [n_rx][n_prn] and the five state arrays [n_rx * ch_per_rx] (NULL rules as gpsx_wacq's): device memory in
+ * both variants.  d_rx [n_rx], d_pred (NULL: not wanted) [n_rx][n_prn]: device memory; gpsx_wpred takes them in host memory. */
+int gpsx_wpred_dev(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
+                   const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+                   gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *d_rx, gpsx_wpred_t *d_pred);
+int gpsx_wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
+               const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+               gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *rx, gpsx_wpred_t *pred);
+
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,
  *      with gps_tracking_dll / _pll / _fll / _pll_check :175-393 and gps_nav_data_analyse_new_code, PM/GPS/nav_data.c:46-253)

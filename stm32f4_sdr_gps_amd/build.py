@@ -130,6 +130,10 @@ def check_no_scratch() -> dict:
     check_wkf()
     # ... and, between the grids and the loops, the acquisition decisions (check_wacq below: a wave per receiver, no scratch, no LDS)
     check_wacq()
+    # ... and, behind the ephemeris stage, the ephemeris bank (check_wbank below: the same terms)
+    check_wbank()
+    # ... and, behind the filter, the prediction and hot hand-over (check_wpred below: FP64, a wave per receiver, the same terms)
+    check_wpred()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -203,6 +207,18 @@ def check_wacq() -> dict:
     """k_wacq, acquisition decisions and slot hand-over (not a solver, but the same terms: an object of its own, exactly one instance,
     no scratch and no LDS)"""
     return check_wsolver("k_wacq.o", "k_wacq", True)
+
+
+def check_wbank() -> dict:
+    """k_wbank, the ephemeris bank (a mover of records, in the solvers' terms: an object of its own, exactly one instance, no scratch
+    and no LDS)"""
+    return check_wsolver("k_wbank.o", "k_wbank", True)
+
+
+def check_wpred() -> dict:
+    """k_wpred, prediction and hot hand-over (the solvers' shared parts on k_wacq's geometry: an object of its own, exactly one
+    instance, no scratch and no LDS)"""
+    return check_wsolver("k_wpred.o", "k_wpred", True)
 
 
 if __name__ == "__main__":

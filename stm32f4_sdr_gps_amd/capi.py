@@ -343,6 +343,47 @@ def wacq_cfg(ch_per_rx: int, det=(4, 1), min_peak: int = 0, lead_blocks: int = 0
     return cfg
 
 
+# gpsx_wbank_cfg_t / gpsx_wbank_t (the ephemeris bank behind gpsx_weph: a receiver's newest VALID record per listed PRN, WEPH_DTYPE [n_rx, n_prn])
+WBANK_CFG_DTYPE = np.dtype([("ch_per_rx", "<i4"), ("reserved", "<i4", (3,))])
+WBANK_DTYPE = np.dtype([("stored_mask", "<u8"), ("have_mask", "<u8"), ("from_bank_mask", "<u8"), ("n_stored", "<u2"), ("n_have", "<u2"),
+                        ("n_from_bank", "<u2"), ("zero", "<u2")])
+assert WBANK_CFG_DTYPE.itemsize == 16 and WBANK_DTYPE.itemsize == 32
+
+
+def wbank_cfg(ch_per_rx: int) -> np.ndarray:
+    """a gpsx_wbank_cfg_t as a one-element WBANK_CFG_DTYPE array"""
+    cfg = np.zeros(1, WBANK_CFG_DTYPE)
+    cfg["ch_per_rx"] = ch_per_rx
+    return cfg
+
+
+# gpsx_wpred_cfg_t / gpsx_wpred_t / gpsx_wpred_rx_t (prediction and hot hand-over behind the navigation filter, from its state and the bank)
+WPRED_HAVE_EPH, WPRED_PREDICTED, WPRED_VISIBLE, WPRED_CERTAIN, WPRED_TRACKED, WPRED_ASSIGNED, WPRED_DROPPED = 1, 2, 4, 8, 16, 32, 64
+WPRED_RX_PREDICTED, WPRED_RX_NOT_INIT, WPRED_RX_BAD, WPRED_RX_ASSIGNED, WPRED_RX_EVICTED, WPRED_RX_FULL = 1, 2, 4, 8, 16, 32
+WPRED_CFG_DTYPE = np.dtype([("ion", "<f8", (8,)), ("mps_per_hz", "<f8"), ("el_min_rad", "<f8"), ("max_sigma_m", "<f8"), ("max_sigma_hz", "<f8"),
+                            ("ch_per_rx", "<i4"), ("lead_blocks", "<i4"), ("evict_after_blocks", "<i4"), ("handover", "<i4"), ("reserved", "<i4", (4,))])
+WPRED_DTYPE = np.dtype([("flags", "<u4"), ("slot", "<i4"), ("tx_ms", "<i8"), ("pr_m", "<f8"), ("code_phase", "<f8"), ("f_hz", "<f8"), ("el", "<f8"),
+                        ("az", "<f8"), ("sigma_m", "<f4"), ("sigma_hz", "<f4")])
+WPRED_RX_DTYPE = np.dtype([("flags", "<u2"), ("week", "<i2"), ("t_ms", "<i4"), ("n_have", "u1"), ("n_visible", "u1"), ("n_tracked", "u1"),
+                           ("n_assigned", "u1"), ("n_evicted", "u1"), ("n_dropped", "u1"), ("zero", "<u2"), ("visible_mask", "<u8"), ("have_mask", "<u8"),
+                           ("assigned_mask", "<u8"), ("evicted_mask", "<u8"), ("kept_mask", "<u8"), ("free_mask", "<u8")])
+assert WPRED_CFG_DTYPE.itemsize == 128 and WPRED_DTYPE.itemsize == 64 and WPRED_RX_DTYPE.itemsize == 64
+
+
+def wpred_cfg(ch_per_rx: int, mps_per_hz: float = WVEL_L1CA, el_min_rad: float = 0.0873, max_sigma_m: float = 300.0, max_sigma_hz: float = 12.5,
+              lead_blocks: int = 0, evict_after_blocks: int = 0, handover: int = 1, ion=None) -> np.ndarray:
+    """a gpsx_wpred_cfg_t as a one-element WPRED_CFG_DTYPE array: a banked satellite is a candidate when it stands at least el_min_rad
+    (5 degrees) above the horizon lead_blocks after the filter's rcv_ms and its predicted pseudorange and frequency are known to
+    max_sigma_m and max_sigma_hz (one sigma, from the filter's covariance); handover 1 writes the candidates into free slots"""
+    cfg = np.zeros(1, WPRED_CFG_DTYPE)
+    for name, v in (("mps_per_hz", mps_per_hz), ("el_min_rad", el_min_rad), ("max_sigma_m", max_sigma_m), ("max_sigma_hz", max_sigma_hz),
+                    ("ch_per_rx", ch_per_rx), ("lead_blocks", lead_blocks), ("evict_after_blocks", evict_after_blocks), ("handover", handover)):
+        cfg[name] = v
+    if ion is not None:
+        cfg["ion"][0] = ion
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -490,6 +531,11 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wacq.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p]
     lib.gpsx_wacq_dev.argtypes = lib.gpsx_wacq.argtypes
+    lib.gpsx_wbank.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gpsx_wbank_dev.argtypes = lib.gpsx_wbank.argtypes
+    lib.gpsx_wpred.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gpsx_wpred_dev.argtypes = lib.gpsx_wpred.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1051,6 +1097,38 @@ class Engine:
                                      opt(d_nav_state), opt(d_obs_state), opt(d_eph_state), acq.ctypes.data, det.ctypes.data if want_det else None),
                   "gpsx_wacq")
         return (acq, det) if want_det else acq
+
+    def wbank(self, cfg: np.ndarray, prns, d_sync_state: int, eph: np.ndarray, d_bank: int, want_out: bool = True):
+        """EXTENSION: the ephemeris bank (include/gpsx.h gpsx_wbank) behind a launch's WEPH_DTYPE records eph [n_rx * ch_per_rx] in host
+        memory: the newest VALID record per receiver and PRN of the list prns goes into the WEPH_DTYPE [n_rx, len(prns)] bank at device
+        address d_bank (all zero: empty), and a slot of the WSYNC_STATE_DTYPE states at d_sync_state that tracks a listed PRN without a
+        VALID record of its own gets the bank's in the merged copy; cfg from wbank_cfg.
+        -> (WBANK_DTYPE [n_rx], merged WEPH_DTYPE [n_rx * ch_per_rx]), or the first alone without want_out"""
+        assert cfg.dtype == WBANK_CFG_DTYPE and cfg.size == 1
+        eph = np.ascontiguousarray(eph, WEPH_DTYPE).reshape(-1)
+        prns = np.ascontiguousarray(prns, np.uint8)
+        ch = int(cfg["ch_per_rx"][0])
+        assert ch >= 1 and eph.size % ch == 0
+        n_rx = eph.size // ch
+        rep, out = np.zeros(n_rx, WBANK_DTYPE), np.zeros(eph.size, WEPH_DTYPE)
+        self._chk(self.lib.gpsx_wbank(self.h, cfg.ctypes.data, n_rx, len(prns), prns.ctypes.data, C.c_void_p(d_sync_state), eph.ctypes.data,
+                                      C.c_void_p(d_bank), out.ctypes.data if want_out else None, rep.ctypes.data), "gpsx_wbank")
+        return (rep, out) if want_out else rep
+
+    def wpred(self, cfg: np.ndarray, prns, n_rx: int, d_kf_state: int, d_bank: int, d_sync_state: int, d_lock_state: int | None = None,
+              d_nav_state: int | None = None, d_obs_state: int | None = None, d_eph_state: int | None = None, want_pred: bool = True):
+        """EXTENSION: prediction and hot hand-over (include/gpsx.h gpsx_wpred) from the n_rx WKF_STATE_DTYPE filter states at device
+        address d_kf_state and the WEPH_DTYPE [n_rx, len(prns)] bank at d_bank, on the n_rx * ch_per_rx WSYNC_STATE_DTYPE states at
+        d_sync_state and, where given, the lock, nav, obs and eph states of the same slots; cfg from wpred_cfg.
+        -> (WPRED_RX_DTYPE [n_rx], WPRED_DTYPE [n_rx, n_prn]), or the first alone without want_pred"""
+        assert cfg.dtype == WPRED_CFG_DTYPE and cfg.size == 1
+        prns = np.ascontiguousarray(prns, np.uint8)
+        rx, pred = np.zeros(n_rx, WPRED_RX_DTYPE), np.zeros((n_rx, len(prns)), WPRED_DTYPE)
+        opt = lambda d: C.c_void_p(d) if d else None   # noqa: E731
+        self._chk(self.lib.gpsx_wpred(self.h, cfg.ctypes.data, n_rx, len(prns), prns.ctypes.data, C.c_void_p(d_kf_state), C.c_void_p(d_bank),
+                                      C.c_void_p(d_sync_state), opt(d_lock_state), opt(d_nav_state), opt(d_obs_state), opt(d_eph_state), rx.ctypes.data,
+                                      pred.ctypes.data if want_pred else None), "gpsx_wpred")
+        return (rx, pred) if want_pred else rx
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -726,9 +726,177 @@ int wacq(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g
       });
 }
 
+// ---- the ephemeris bank (host: eph, eph_out and rep are host memory, staged through the arena; the sync states and the bank are device
+//      memory in both variants) ------------------------------------------------------------------------------------------------------
+int wbank(gpsx_ctx *ctx, const gpsx_wbank_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wsync_state_t *d_sync_state,
+          const gpsx_weph_t *eph, gpsx_weph_t *d_bank, gpsx_weph_t *eph_out, gpsx_wbank_t *rep, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !prns || !d_sync_state || !eph || !d_bank || !rep)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->reserved[0] != 0 || cfg->reserved[1] != 0 || cfg->reserved[2] != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (n_prn < 1 || n_prn > 64)
+    return fail(ctx, GPSX_EINVAL, "n_prn must be 1..64");
+  bool listed[GPSX_MAX_PRN + 1] = {};
+  for (int i = 0; i < n_prn; i++) {
+    if (prns[i] < 1 || prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+    if (listed[prns[i]])
+      return fail(ctx, GPSX_EINVAL, "a PRN is listed twice");
+    listed[prns[i]] = true;
+  }
+  if ((reinterpret_cast<uintptr_t>(d_sync_state) & 7u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_sync_state must be 8-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_bank) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_bank must be 16-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(eph) | reinterpret_cast<uintptr_t>(eph_out) | reinterpret_cast<uintptr_t>(rep)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_eph, d_eph_out and d_rep must be 16-byte aligned");
+  size_t sync_bytes = 0, eph_bytes = 0, bank_bytes = 0, rep_bytes = 0;
+  if (records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wsync_state_t), &sync_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_weph_t), &eph_bytes) ||
+      records_overflow((size_t)n_rx, n_prn, sizeof(gpsx_weph_t), &bank_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wbank_t), &rep_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x n_prn records overflow a size");
+  // (host and device addresses share one space here: one list of pairs serves both variants)
+  const struct { const void *p; size_t n; } span[5] = {{d_sync_state, sync_bytes}, {eph, eph_bytes}, {d_bank, bank_bytes}, {eph_out, eph_bytes}, {rep, rep_bytes}};
+  for (int a = 0; a < 5; a++)
+    for (int b = a + 1; b < 5; b++) {
+      const uintptr_t pa = reinterpret_cast<uintptr_t>(span[a].p), pb = reinterpret_cast<uintptr_t>(span[b].p);
+      if (!pa || !pb || (a == 1 && b == 3 && pa == pb))
+        continue;
+      if (pa < pb + span[b].n && pb < pa + span[a].n)
+        return fail(ctx, GPSX_EINVAL, "two arrays overlap (only d_eph_out == d_eph may)");
+    }
+  const size_t n_ch = (size_t)n_rx * (size_t)cfg->ch_per_rx;
+  const gpsx_weph_t *d_eph = eph;
+  gpsx_weph_t *d_out = eph_out;
+  gpsx_wbank_t *d_rep = rep;
+  if (host) {
+    const bool own_out = eph_out && eph_out != eph;
+    if (int rc = arena_reset(ctx, arena_size(eph_bytes) + (own_out ? arena_size(eph_bytes) : 0) + arena_size(rep_bytes))) return rc;
+    if (int rc = stage_in(ctx, eph, n_ch, &d_eph)) return rc;
+    if (eph_out)
+      d_out = own_out ? arena_take<gpsx_weph_t>(ctx, n_ch) : const_cast<gpsx_weph_t *>(d_eph);     // (in place: on the staged copy)
+    d_rep = arena_take<gpsx_wbank_t>(ctx, (size_t)n_rx);
+  }
+  return launch_and_report(
+      ctx, host, "k_wbank", "k_wbank raised the bad-state flag, which it never does",
+      [&](uint32_t *) { launch_wbank(ctx->stream, *cfg, n_rx, n_prn, prns, d_sync_state, d_eph, d_bank, d_out, d_rep); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(rep, d_rep, rep_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (eph_out)
+          HIPCHK(ctx, hipMemcpyAsync(eph_out, d_out, eph_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
+// ---- prediction and hot hand-over (host: rx and pred are host memory, staged through the arena; the filter states, the bank and the
+//      five state arrays are device memory in both variants) ---------------------------------------------------------------------------
+int wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
+          const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+          gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *rx, gpsx_wpred_t *pred, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !prns || !d_kf_state || !d_bank || !d_sync_state || !rx)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  for (double v : cfg->ion)
+    if (!(v - v == 0.0))   // (not finite: the difference is a NaN)
+      return fail(ctx, GPSX_EINVAL, "an ionosphere coefficient is not finite");
+  if (!(cfg->mps_per_hz - cfg->mps_per_hz == 0.0) || cfg->mps_per_hz == 0.0)
+    return fail(ctx, GPSX_EINVAL, "mps_per_hz must be finite and not 0");
+  if (!(std::fabs(cfg->el_min_rad) <= 1.5707963267948966))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "el_min_rad must be finite and within -pi/2..pi/2");
+  if (!(cfg->max_sigma_m - cfg->max_sigma_m == 0.0) || !(cfg->max_sigma_m > 0.0) || !(cfg->max_sigma_hz - cfg->max_sigma_hz == 0.0) ||
+      !(cfg->max_sigma_hz > 0.0))
+    return fail(ctx, GPSX_EINVAL, "max_sigma_m and max_sigma_hz must be finite and above 0");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->lead_blocks < 0 || cfg->lead_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "lead_blocks must be 0..4096");
+  if (cfg->evict_after_blocks < 0 || cfg->evict_after_blocks > (1 << 30))
+    return fail(ctx, GPSX_EINVAL, "evict_after_blocks must be 0..1073741824");
+  if (cfg->handover != 0 && cfg->handover != 1)
+    return fail(ctx, GPSX_EINVAL, "handover must be 0 or 1");
+  if (cfg->reserved[0] != 0 || cfg->reserved[1] != 0 || cfg->reserved[2] != 0 || cfg->reserved[3] != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (cfg->evict_after_blocks != 0 && !d_lock_state)
+    return fail(ctx, GPSX_EINVAL, "evict_after_blocks needs d_lock_state");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (n_prn < 1 || n_prn > 64)
+    return fail(ctx, GPSX_EINVAL, "n_prn must be 1..64");
+  bool listed[GPSX_MAX_PRN + 1] = {};
+  for (int i = 0; i < n_prn; i++) {
+    if (prns[i] < 1 || prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+    if (listed[prns[i]])
+      return fail(ctx, GPSX_EINVAL, "a PRN is listed twice");
+    listed[prns[i]] = true;
+  }
+  if (((reinterpret_cast<uintptr_t>(d_kf_state) | reinterpret_cast<uintptr_t>(d_bank)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_kf_state and d_bank must be 16-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(pred)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_rx and d_pred must be 16-byte aligned");
+  size_t bytes = 0, rx_bytes = 0, pred_bytes = 0;
+  if (records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wsync_state_t), &bytes) ||
+      records_overflow((size_t)n_rx, n_prn, sizeof(gpsx_weph_t), &bytes) || records_overflow((size_t)n_rx, n_prn, sizeof(gpsx_wpred_t), &pred_bytes) ||
+      records_overflow((size_t)n_rx, 1, sizeof(gpsx_wpred_rx_t), &rx_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x n_prn records overflow a size");
+  gpsx_wpred_rx_t *d_rx = rx;
+  gpsx_wpred_t *d_pred = pred;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(rx_bytes) + (pred ? arena_size(pred_bytes) : 0))) return rc;
+    d_rx = arena_take<gpsx_wpred_rx_t>(ctx, (size_t)n_rx);
+    if (pred)
+      d_pred = arena_take<gpsx_wpred_t>(ctx, pred_bytes / sizeof(gpsx_wpred_t));
+  }
+  return launch_and_report(
+      ctx, host, "k_wpred", "k_wpred raised the bad-state flag, which it never does",
+      [&](uint32_t *) {
+        launch_wpred(ctx->stream, *cfg, n_rx, n_prn, prns, d_kf_state, d_bank, d_sync_state, d_lock_state, d_nav_state, d_obs_state, d_eph_state, d_rx,
+                     d_pred);
+      },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(rx, d_rx, rx_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (pred)
+          HIPCHK(ctx, hipMemcpyAsync(pred, d_pred, pred_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wpred_dev(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
+                   const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+                   gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *d_rx, gpsx_wpred_t *d_pred)
+{
+  return wpred(ctx, cfg, n_rx, n_prn, prns, d_kf_state, d_bank, d_sync_state, d_lock_state, d_nav_state, d_obs_state, d_eph_state, d_rx, d_pred, false);
+}
+
+int gpsx_wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
+               const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
+               gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *rx, gpsx_wpred_t *pred)
+{
+  return wpred(ctx, cfg, n_rx, n_prn, prns, d_kf_state, d_bank, d_sync_state, d_lock_state, d_nav_state, d_obs_state, d_eph_state, rx, pred, true);
+}
+
+int gpsx_wbank_dev(gpsx_ctx *ctx, const gpsx_wbank_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wsync_state_t *d_sync_state,
+                   const gpsx_weph_t *d_eph, gpsx_weph_t *d_bank, gpsx_weph_t *d_eph_out, gpsx_wbank_t *d_rep)
+{
+  return wbank(ctx, cfg, n_rx, n_prn, prns, d_sync_state, d_eph, d_bank, d_eph_out, d_rep, false);
+}
+
+int gpsx_wbank(gpsx_ctx *ctx, const gpsx_wbank_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wsync_state_t *d_sync_state,
+               const gpsx_weph_t *eph, gpsx_weph_t *d_bank, gpsx_weph_t *eph_out, gpsx_wbank_t *rep)
+{
+  return wbank(ctx, cfg, n_rx, n_prn, prns, d_sync_state, eph, d_bank, eph_out, rep, true);
+}
 
 int gpsx_wacq_dev(gpsx_ctx *ctx, const gpsx_wacq_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *d_peaks,
                   gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,

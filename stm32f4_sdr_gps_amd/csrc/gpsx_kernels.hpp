@@ -215,6 +215,20 @@ void launch_wkf(hipStream_t s, const gpsx_wkf_cfg_t &cfg, const gpsx_wobs_t *d_o
 void launch_wacq(hipStream_t s, const gpsx_wacq_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, int dopp_min_hz, int dopp_step_hz, int n_dopp,
                  const gpsx_peak_t *d_peaks, gpsx_wsync_state_t *d_sync_st, gpsx_wlock_state_t *d_lock_st, gpsx_wnav_state_t *d_nav_st,
                  gpsx_wobs_state_t *d_obs_st, gpsx_weph_state_t *d_eph_st, gpsx_wacq_t *d_acq, gpsx_wacq_det_t *d_det);
+// extension: gpsx_wbank (k_wbank.hip: k_wbank) -- the ephemeris bank behind gpsx_weph: d_bank [n_rx][n_prn] takes the newest VALID record
+// of d_eph [n_rx * ch_per_rx] per listed PRN (the slots' PRNs from d_sync_st, read only), d_eph_out (may be null, may be d_eph) the
+// records with the bank's where a slot has none of its own, d_rep [n_rx] 32-byte records, every byte written.  A wave per receiver;
+// prns: n_prn (<= 64) PRN numbers in HOST memory, passed by value.  The launcher checks nothing again.
+void launch_wbank(hipStream_t s, const gpsx_wbank_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wsync_state_t *d_sync_st,
+                  const gpsx_weph_t *d_eph, gpsx_weph_t *d_bank, gpsx_weph_t *d_eph_out, gpsx_wbank_t *d_rep);
+// extension: gpsx_wpred (k_wpred.hip: k_wpred) -- prediction and hot hand-over behind gpsx_wkf: from the filter states d_kf_state [n_rx]
+// and the bank d_bank [n_rx][n_prn] (both read only) every listed PRN's elevation, pseudorange, code phase and Doppler lead_blocks after
+// the state's rcv_ms; with cfg.handover the visible, certain and untracked ones go to free slots of the five state arrays (as
+// launch_wacq's: d_lock_st null only with evict_after_blocks == 0; d_nav_st, d_obs_st, d_eph_st may be null).  d_rx [n_rx] and d_pred
+// (may be null) [n_rx][n_prn] 64-byte records, every byte written.  A wave per receiver; prns in HOST memory, by value.  No checks.
+void launch_wpred(hipStream_t s, const gpsx_wpred_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
+                  const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_st, gpsx_wlock_state_t *d_lock_st, gpsx_wnav_state_t *d_nav_st,
+                  gpsx_wobs_state_t *d_obs_st, gpsx_weph_state_t *d_eph_st, gpsx_wpred_rx_t *d_rx, gpsx_wpred_t *d_pred);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

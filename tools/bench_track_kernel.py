@@ -106,7 +106,17 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       gpsx_memcpy_d2h of those records, the first step of the host path it replaces,
                                                       the calls taking turns in one process (a hand-over changes the states, so a
                                                       device-to-device copy puts them back before every timed launch; it is timed alone
-                                                      and subtracted); the lines also go to profiles/r27_weighted_acq_bench.jsonl"""
+                                                      and subtracted); the lines also go to profiles/r27_weighted_acq_bench.jsonl
+  bench_track_kernel.py --weighted-bank [N_RXxN_PRNxCH_PER_RX ...]
+                                                      gpsx_wbank_dev (EXTENSION: the ephemeris bank; k_wbank) at 256, 4096 and 16384
+                                                      receivers x 32 PRNs with 8 and 12 slots: a full bank, three slots of four refresh
+                                                      their entry and the fourth takes the bank's record, beside (1) a device-to-device
+                                                      hipMemcpyAsync of the ephemeris records it reads and (2) gpsx_wkf_dev's update at
+                                                      the same receivers, the calls taking turns in one process; then gpsx_wpred_dev
+                                                      (EXTENSION: prediction and hot hand-over; k_wpred) on the same filter states and
+                                                      bank with half the slots emptied, predicting only and handing over, beside a
+                                                      copy of what it reads and gpsx_wkf_dev; the lines also go to
+                                                      profiles/r28_weighted_pred_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -1164,8 +1174,160 @@ def weighted_acq(shapes, out=ACQ_OUT):
         eng.close()
 
 
+BANK_OUT = os.path.join(ROOT, "profiles", "r28_weighted_pred_bench.jsonl")
+BANK_SHAPES = [(256, 32, 8), (256, 32, 12), (4096, 32, 8), (4096, 32, 12), (16384, 32, 8), (16384, 32, 12)]
+
+
+def weighted_bank(shapes, out=BANK_OUT):
+    """k_wbank at (receivers, PRNs, slots per receiver) on --weighted-kf's records (real ephemerides, every slot on a listed PRN of its
+    own): the steady state of a tracking receiver whose bank is full -- three slots of four offer a set of the bank's own toe (stored
+    again: a refresh), the fourth has no set and takes the bank's.  Such a call leaves the bank as it was, so the timed launches need no
+    copy that puts anything back.  It is timed with the merged copy apart from d_eph and without one (in place a call changes its own
+    input: not timed).  The yardsticks: a device-to-device copy of
+    the ephemeris records the kernel reads, and k_wkf's update at the same receivers on the same records (as --weighted-kf times it:
+    the pair of state copy and update less the state copy); the calls take turns; the lines go to stdout and to `out`.  Behind it, on
+    the same receivers, k_wpred (see the comment there)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fix_cases as W
+    import weighted_kf_cases as K
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0, stream=stream.value)
+    names = sorted(W.SITES)
+    try:
+        for n_rx, n_prn, ch in shapes:
+            pool = [K.track(names[k % len(names)], ch, 3 * k, K.VELOCITY, 1e-6, 2) for k in range(16)]
+            obs0, eph = W.pack([(pool[r % 16][0][0]["obs"], pool[r % 16][1]) for r in range(n_rx)], ch)
+            obs1, _ = W.pack([(pool[r % 16][0][1]["obs"], pool[r % 16][1]) for r in range(n_rx)], ch)
+            n_ch = n_rx * ch
+            prns = np.arange(1, n_prn + 1, dtype=np.uint8)
+            index = (np.arange(n_ch) // ch + np.arange(n_ch) % ch) % n_prn          # receiver r's slot j: PRN index (r + j) mod n_prn
+            sync = np.zeros(n_ch, capi.WSYNC_STATE_DTYPE)
+            sync["loop"]["prn"] = prns[index]
+            bank = np.zeros((n_rx, n_prn), capi.WEPH_DTYPE)
+            bank[np.arange(n_ch) // ch, index] = eph
+            bank["flags"] &= capi.WEPH_FLAG_VALID
+            launch_eph = eph.copy()
+            launch_eph["flags"][3::4] = 0
+            fix_cfg, vel_cfg, kf_cfg, bank_cfg = capi.wfix_cfg(W.OFFSET_MS, ch), capi.wvel_cfg(ch), capi.wkf_cfg(ch), capi.wbank_cfg(ch)
+            state_bytes = n_rx * capi.WKF_STATE_DTYPE.itemsize
+            d_obs0, d_obs1, d_eph, d_leph, d_out, d_copy = (eng.malloc(b) for b in (obs0.nbytes, obs1.nbytes, eph.nbytes, eph.nbytes, eph.nbytes, eph.nbytes))
+            d_fix, d_vel, d_state, d_state0, d_kf = (eng.malloc(b) for b in (n_rx * 128, n_rx * 112, state_bytes, state_bytes, n_rx * capi.WKF_DTYPE.itemsize))
+            d_sync, d_bank, d_rep = eng.malloc(sync.nbytes), eng.malloc(bank.nbytes), eng.malloc(n_rx * capi.WBANK_DTYPE.itemsize)
+            for d, a in ((d_obs0, obs0), (d_obs1, obs1), (d_eph, eph), (d_leph, launch_eph), (d_state0, np.zeros(n_rx, capi.WKF_STATE_DTYPE)), (d_sync, sync),
+                         (d_bank, bank)):
+                eng.h2d(d, a)
+
+            def wkf(d_o, d_st):
+                return eng.lib.gpsx_wkf_dev(eng.h, kf_cfg.ctypes.data, C.c_void_p(d_o), C.c_void_p(d_eph), None, C.c_void_p(d_fix), C.c_void_p(d_vel), n_rx, 1000,
+                                            C.c_void_p(d_st), C.c_void_p(d_kf))
+
+            def restore():
+                return hip.hipMemcpyAsync(d_state, d_state0, state_bytes, 3, stream)
+
+            def restore_and_update():
+                restore()
+                return wkf(d_obs1, d_state)
+
+            def wbank(d_o):
+                return eng.lib.gpsx_wbank_dev(eng.h, bank_cfg.ctypes.data, n_rx, n_prn, prns.ctypes.data, C.c_void_p(d_sync), C.c_void_p(d_leph), C.c_void_p(d_bank),
+                                              None if d_o is None else C.c_void_p(d_o), C.c_void_p(d_rep))
+
+            eng._chk(eng.lib.gpsx_wfix_dev(eng.h, fix_cfg.ctypes.data, C.c_void_p(d_obs0), C.c_void_p(d_eph), None, None, n_rx, C.c_void_p(d_fix), None), "gpsx_wfix_dev")
+            eng._chk(eng.lib.gpsx_wvel_dev(eng.h, vel_cfg.ctypes.data, C.c_void_p(d_obs0), C.c_void_p(d_eph), None, C.c_void_p(d_fix), n_rx, C.c_void_p(d_vel)),
+                     "gpsx_wvel_dev")
+            eng._chk(wkf(d_obs0, d_state0), "gpsx_wkf_dev")      # INIT: what every timed update starts from
+            eng.synchronize()
+            calls = {"d2d_copy_of_the_states": (1, restore),
+                     "d2d_copy_of_the_eph_records": (1, lambda: hip.hipMemcpyAsync(d_copy, d_leph, eph.nbytes, 3, stream)),
+                     "state_copy_then_wkf": (1, restore_and_update),
+                     "wbank_no_merged_copy": (1, lambda: wbank(None)),
+                     "wbank_merged_apart": (1, lambda: wbank(d_out))}
+            med = _timed_rows(eng, calls, {"channels": n_ch, "n_rx": n_rx, "n_prn": n_prn, "ch_per_rx": ch, "eph_bytes": eph.nbytes, "bank_bytes": bank.nbytes},
+                              per_channel_ms=False)
+            rep, kf = np.zeros(n_rx, capi.WBANK_DTYPE), np.zeros(n_rx, capi.WKF_DTYPE)
+            eng.d2h(rep, d_rep)
+            eng.d2h(kf, d_kf)
+            after = np.zeros_like(bank)
+            eng.d2h(after, d_bank)
+            print(json.dumps({"wbank_check": "records after the timed launches", "n_rx": n_rx, "stored_per_rx": [int(rep["n_stored"].min()), int(rep["n_stored"].max())],
+                              "from_bank_per_rx": [int(rep["n_from_bank"].min()), int(rep["n_from_bank"].max())],
+                              "bank_unchanged": bool(after.tobytes() == bank.tobytes()), "wkf_updated": int((kf["flags"] == capi.WKF_FLAG_UPDATED).sum())}), flush=True)
+            own_kf = med["state_copy_then_wkf"] - med["d2d_copy_of_the_states"]
+            own = med["wbank_merged_apart"]
+            print(json.dumps({"ratio": "k_wbank (merged copy apart) over the two yardsticks", "n_rx": n_rx, "n_prn": n_prn, "ch_per_rx": ch, "wbank_us": round(own, 3),
+                              "wbank_no_copy_us": round(med["wbank_no_merged_copy"], 3),
+                              "wkf_us": round(own_kf, 3), "over_d2d_copy_of_the_eph_records": round(own / med["d2d_copy_of_the_eph_records"], 3),
+                              "over_wkf": round(own / own_kf, 3), "ns_per_receiver": round(own / n_rx * 1e3, 2),
+                              "moved_GBps": round((eph.nbytes * 2 + eph.nbytes * 3 // 4 * 2) / own / 1e3, 1)}), flush=True)
+            # -- k_wpred on the same receivers: their initialised filter states and the full bank; half of every receiver's slots emptied,
+            #    so that handover = 1 hands satellites over (a device-to-device copy puts the sync states back before every timed launch;
+            #    it is timed alone and subtracted); max_sigma_hz is wide open, because a freshly initialised filter's drift prior is 500 m/s
+            sync_h = sync.copy()
+            sync_h["loop"]["prn"][1::2] = capi.PRN_NONE
+            d_sync_h, d_sync_h0, d_states_copy = eng.malloc(sync.nbytes), eng.malloc(sync.nbytes), eng.malloc(state_bytes + bank.nbytes)
+            eng.h2d(d_sync_h, sync_h)
+            eng.h2d(d_sync_h0, sync_h)
+            d_prx, d_ppred = eng.malloc(n_rx * capi.WPRED_RX_DTYPE.itemsize), eng.malloc(n_rx * n_prn * capi.WPRED_DTYPE.itemsize)
+            pcfg = {h: capi.wpred_cfg(ch, capi.WVEL_L1CA, max_sigma_m=1e4, max_sigma_hz=1e4, lead_blocks=20, handover=h) for h in (0, 1)}
+
+            def wpred(h, d_s):
+                return eng.lib.gpsx_wpred_dev(eng.h, pcfg[h].ctypes.data, n_rx, n_prn, prns.ctypes.data, C.c_void_p(d_state0), C.c_void_p(d_bank), C.c_void_p(d_s),
+                                              None, None, None, None, C.c_void_p(d_prx), C.c_void_p(d_ppred))
+
+            def restore_slots():
+                return hip.hipMemcpyAsync(d_sync_h, d_sync_h0, sync.nbytes, 3, stream)
+
+            def restore_and_hand_over():
+                restore_slots()
+                return wpred(1, d_sync_h)
+
+            pcalls = {"d2d_copy_of_the_sync_states": (1, restore_slots),
+                      "d2d_copy_of_the_filter_states_and_the_bank": (1, lambda: hip.hipMemcpyAsync(d_states_copy, d_bank, bank.nbytes, 3, stream) or
+                                                                     hip.hipMemcpyAsync(d_states_copy + bank.nbytes, d_state0, state_bytes, 3, stream)),
+                      "state_copy_then_wkf": (1, restore_and_update),
+                      "d2d_copy_of_the_states": (1, restore),
+                      "wpred_predict_only": (1, lambda: wpred(0, d_sync_h0)),
+                      "slot_copy_then_wpred_handover": (1, restore_and_hand_over)}
+            pmed = _timed_rows(eng, pcalls, {"channels": n_ch, "n_rx": n_rx, "n_prn": n_prn, "ch_per_rx": ch, "read_bytes": state_bytes + bank.nbytes},
+                               per_channel_ms=False)
+            prx = np.zeros(n_rx, capi.WPRED_RX_DTYPE)
+            eng.d2h(prx, d_prx)
+            print(json.dumps({"wpred_check": "records after the timed launches", "n_rx": n_rx, "have_per_rx": [int(prx["n_have"].min()), int(prx["n_have"].max())],
+                              "visible_per_rx": [int(prx["n_visible"].min()), int(prx["n_visible"].max())],
+                              "assigned_per_rx": [int(prx["n_assigned"].min()), int(prx["n_assigned"].max())],
+                              "tracked_per_rx": [int(prx["n_tracked"].min()), int(prx["n_tracked"].max())]}), flush=True)
+            own_p = pmed["slot_copy_then_wpred_handover"] - pmed["d2d_copy_of_the_sync_states"]
+            own_k = pmed["state_copy_then_wkf"] - pmed["d2d_copy_of_the_states"]
+            print(json.dumps({"ratio": "k_wpred with handover = 1 (the timed pair less the slot copy) over the two yardsticks", "n_rx": n_rx, "n_prn": n_prn,
+                              "ch_per_rx": ch, "wpred_us": round(own_p, 3), "wpred_predict_only_us": round(pmed["wpred_predict_only"], 3), "wkf_us": round(own_k, 3),
+                              "over_d2d_copy_of_what_it_reads": round(own_p / pmed["d2d_copy_of_the_filter_states_and_the_bank"], 3),
+                              "over_wkf": round(own_p / own_k, 3), "ns_per_receiver": round(own_p / n_rx * 1e3, 2),
+                              "ns_per_satellite_evaluation": round(own_p / max(int(prx["n_have"].sum()) * 3, 1) * 1e3, 3)}), flush=True)
+            for p in (d_sync_h, d_sync_h0, d_states_copy, d_prx, d_ppred):
+                eng.free(p)
+            for p in (d_obs0, d_obs1, d_eph, d_leph, d_out, d_copy, d_fix, d_vel, d_state, d_state0, d_kf, d_sync, d_bank, d_rep):
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-bank" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-bank"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_bank([tuple(int(v) for v in a.split("x")) for a in args] or BANK_SHAPES)
     if "--weighted-acq" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-acq"]
         if "--window-s" in args:
