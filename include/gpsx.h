@@ -1815,6 +1815,123 @@ int gpsx_wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, 
                const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,
                gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *rx, gpsx_wpred_t *pred);
 
+/* ---- EXTENSION, not in the reference: time-of-week aiding of the observables -- the prediction names the millisecond a HOW has not yet ---
+ * gpsx_wobs marks a slot VALID only once a parity-checked HOW of its chain has anchored the time of week: 1.2 .. 7.2 s after the bit
+ * sync of every hand-over, eviction and chain break, and never for a satellite whose words fail parity.  gpsx_wpred's record for that
+ * PRN already holds the transmit millisecond at the same block, good to a few samples, where the question is only "which millisecond"
+ * and a millisecond is 16 368 samples wide.  gpsx_wtow(_dev) sits behind gpsx_wobs_dev and a gpsx_wpred_dev call and anchors, from
+ * that record, the observable state of every slot whose bit chain runs (PHASE and EDGE) but has no TOW; it resolves
+ * GPSX_WOBS_AMBIGUOUS on the way, where the prediction says that the edge block is the other "nearest block start".  A HOW stays the
+ * authority: an anchor it set is never replaced here, and the next real HOW confirms an aided anchor or replaces it with
+ * n_mismatch++, by gpsx_wobs' own rule.  No existing struct, kernel, definition or state rule changes; the aided state uses only flag
+ * bits gpsx_wobs already knows (GPSX_VERSION stays 110).
+ *
+ * THE EPOCHS ARE THE CALLER'S DUTY.  The epoch T of the gpsx_wpred_dev call whose records are read (the filter's rcv_ms + its
+ * lead_blocks) must be the clock's reading of sample 0 of block B, the block the observable states stand at (their blocks_seen).  The
+ * stage cannot check it: a slot's blocks_seen restarts at every hand-over.  Two call orders are valid:
+ *   after gpsx_wkf_dev    ..., gpsx_wobs_dev, ..., gpsx_wkf_dev, gpsx_wpred_dev with lead_blocks = 0, gpsx_wtow_dev: the aided slot counts
+ *                         from the next launch on (d_obs may still be given: the records then say what the next launch will see).
+ *   before gpsx_wkf_dev   ..., gpsx_wobs_dev, gpsx_wpred_dev with lead_blocks = n_blocks on the filter state of the launch before,
+ *                         gpsx_wtow_dev with d_obs, the solvers, gpsx_wkf_dev: with d_obs rewritten the aided slot counts in this launch.
+ *
+ * Definition, per receiver r and slot j, ch = r * ch_per_rx + j, W = 604 800 000; all integers are int64, step 3 is three IEEE double
+ * operations.  The first clause that holds ends the slot with that flag; a flag named in capitals is GPSX_WTOW_<name>.
+ *   0 receiver     d_pred_rx[r].flags lacks GPSX_WPRED_RX_PREDICTED: NO_PRED.  d_tow_rx[r] and every d_tow[ch] are zero but for that
+ *                  flag, no state is read or written.
+ *   1 slot         d_sync_state[ch].loop.prn == GPSX_PRN_NONE: EMPTY.  The PRN is not in the list: UNLISTED; else p is its index.
+ *                  The observable state is one gpsx_wobs calls BAD (its rule, its bounds): BAD, the state stays untouched and the
+ *                  call still returns 0 -- only gpsx_wobs reports it as an error.  The state lacks PHASE or EDGE: WAITING.
+ *                  blocks_seen - last_win_end_p1 > max_age_blocks: STALE (the code phase is older than the prediction may be held against).
+ *   2 prediction   w = d_pred[r][p].  w.flags lacks GPSX_WPRED_PREDICTED, or (double)w.sigma_m > max_sigma_m: UNCERTAIN.
+ *   3 millisecond  d = (double)last_phase - w.code_phase;  k = +1 if d > 8184, -1 if d < -8184, else 0;  rho = d - 16368 k (16368 k
+ *                  is exact).  INCONSISTENT unless |rho| <= (double)max_resid_samples; a NaN fails this test (and is recorded as
+ *                  the quiet NaN 0x7FC00000, whatever its sign and payload).  The loop's code phase and the predicted one are the
+ *                  same edge seen across the ends of the 16 368-sample circle: k is the millisecond between them.
+ *                  tx = (w.tx_ms + k) folded into 0 .. W - 1 (from a w.tx_ms in 0 .. W - 1, which gpsx_wpred writes; any other is
+ *                  taken modulo W first);  Tz' = (tx - ((B mod W) - (Z mod W))) folded into 0 .. W - 1, B = blocks_seen, Z =
+ *                  edge_block, both mods non-negative: the transmit millisecond at the edge of block Z;  m = Tz' mod 20.
+ *   4 grid         a bit edge of this satellite is transmitted on a multiple of 20 ms.  m == 0: s = 0.  m == 1 or m == 19, and
+ *                  AMBIGUOUS is set, and cfg.resolve: s = -1 for m == 1, s = +1 for m == 19, SHIFTED: Z* = Z + s, Tz* = (Tz' + s) mod
+ *                  W, the other choice of "nearest block start".  (Without a shift Z* = Z, Tz* = Tz'.)  Anything else: OFF_GRID, the
+ *                  bit synchroniser's edge is not a bit edge of this satellite, and nothing in the observable state changes; with
+ *                  cfg.rearm and d_sync_state[ch].mode != 0 the sync state gets mode = 0, search_n = 0, prev_best_p1 = 0 (three
+ *                  writes of gpsx_wlock's re-arm: the search starts again) and the record REARMED.
+ *   5 anchor       on the grid.  No TOW: edge_block = Z*, tx_ms_at_edge = Tz*, TOW is set, AMBIGUOUS is cleared if cfg.resolve:
+ *                  AIDED.  TOW and tx_ms_at_edge == Tz*: AGREES; with cfg.resolve edge_block = Z* and AMBIGUOUS is cleared (a
+ *                  HOW-anchored chain whose edge block was chosen wrongly: Tz stays, Z moves).  TOW and they differ: DISAGREES,
+ *                  nothing is written (SHIFTED then only says what step 4 found).  CONFIRMED, the four counters and every other
+ *                  field stay as they are.
+ *   6 observable   d_obs non-NULL and the state changed (AIDED, or AGREES with cfg.resolve from a state with AMBIGUOUS): d_obs[ch].tx_ms
+ *                  = (Tz + B - Z) mod W and .flags = the state's flags | VALID, of the new state -- gpsx_wobs' output clause; PHASE,
+ *                  EDGE and TOW all hold here.  The record's other fields and every other record are untouched.
+ *   7 records      every byte of d_tow and d_tow_rx is written.  A slot's record: flags; prn_index = p, -1 for EMPTY and UNLISTED;
+ *                  tx_ms = tx, resid = (float)rho, both 0 before step 3 (tx_ms also 0 for INCONSISTENT); m, -1 before step 3 and for
+ *                  INCONSISTENT; shift = s.  A receiver's: the masks and their counts over its slots; valid_after: the slots that came
+ *                  past EMPTY, UNLISTED and BAD whose state has PHASE, EDGE and TOW after the call.
+ * A second call on the result finds AGREES where the first found AIDED, and changes nothing.
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written: cfg, prns, d_pred_rx, d_pred, d_sync_state, d_obs_state,
+ * d_tow or d_tow_rx NULL; max_sigma_m not finite or <= 0; max_resid_samples not finite, <= 0 or > 4092; max_age_blocks outside 0 ..
+ * 4096; resolve or rearm not 0 or 1; reserved != 0; ch_per_rx outside 1 .. 64; n_rx outside 1 .. 1 048 576; n_prn outside 1 .. 64; a
+ * PRN outside 1 .. 210 or listed twice; d_pred_rx, d_pred, d_obs_state or d_obs not 16-byte aligned, d_sync_state not 8-byte aligned,
+ * d_tow or d_tow_rx not 16-byte aligned (_dev); size products that overflow; d_tow or d_tow_rx overlapping each other or an input.
+ * _dev only enqueues.  Vector ALU (k_wtow: gpsx_wacq's geometry, a wave per receiver, four receivers per workgroup, lane j is slot j;
+ * no LDS, no barrier; the 80-byte state is read as five 16-byte loads per lane and only the words that change are stored). */
+#define GPSX_WTOW_NO_PRED         1u   /* the receiver has no prediction (step 0) */
+#define GPSX_WTOW_EMPTY           2u
+#define GPSX_WTOW_UNLISTED        4u
+#define GPSX_WTOW_BAD             8u
+#define GPSX_WTOW_WAITING        16u   /* no PHASE or no EDGE yet */
+#define GPSX_WTOW_STALE          32u
+#define GPSX_WTOW_UNCERTAIN      64u
+#define GPSX_WTOW_INCONSISTENT  128u
+#define GPSX_WTOW_OFF_GRID      256u
+#define GPSX_WTOW_REARMED       512u   /* with OFF_GRID: the sync state was sent back to its search */
+#define GPSX_WTOW_SHIFTED      1024u   /* the edge block is the other nearest block start: shift = +-1 */
+#define GPSX_WTOW_AIDED        2048u   /* the anchor was written */
+#define GPSX_WTOW_AGREES       4096u   /* a HOW's anchor says the same millisecond */
+#define GPSX_WTOW_DISAGREES    8192u   /* ... another: the HOW stands */
+#define GPSX_WTOW_RX_NO_PRED      1u
+#define GPSX_WTOW_RX_AIDED        2u   /* n_aided > 0 */
+#define GPSX_WTOW_RX_SHIFTED      4u   /* n_shifted > 0 */
+#define GPSX_WTOW_RX_DISAGREES    8u   /* n_disagrees > 0 */
+#define GPSX_WTOW_RX_OFF_GRID    16u   /* n_off_grid > 0 */
+#define GPSX_WTOW_RX_REARMED     32u   /* a sync state was written */
+
+typedef struct {                 /* 32 bytes */
+  double  max_sigma_m;           /*  0  > 0, finite: a prediction with a greater sigma_m is UNCERTAIN */
+  float   max_resid_samples;     /*  8  > 0 .. 4092: |rho| above it is INCONSISTENT */
+  int32_t ch_per_rx;             /* 12  1 .. 64 */
+  int32_t max_age_blocks;        /* 16  0 .. 4096: blocks_seen - last_win_end_p1 above it is STALE */
+  int32_t resolve;               /* 20  0 / 1: move the edge block of an AMBIGUOUS chain where the prediction says so, clear AMBIGUOUS */
+  int32_t rearm;                 /* 24  0 / 1: send the sync state of an OFF_GRID slot back to its search */
+  int32_t reserved;              /* 28  0 */
+} gpsx_wtow_cfg_t;
+
+typedef struct {                 /* 32 bytes, one per slot */
+  uint32_t flags;  int32_t prn_index;   /*  0  GPSX_WTOW_*; p, or -1 */
+  int64_t  tx_ms;                /*  8  tx, or 0 */
+  float    resid;                /* 16  (float)rho, samples */
+  int32_t  m, shift;             /* 20  Tz' mod 20, or -1; s */
+  uint32_t zero;                 /* 28 */
+} gpsx_wtow_t;
+
+typedef struct {                 /* 64 bytes, one per receiver */
+  uint16_t flags;                /*  0  GPSX_WTOW_RX_* */
+  uint8_t  n_aided, n_agrees, n_disagrees, n_off_grid, n_shifted, n_inconsistent;   /*  2  the popcounts of the first six masks */
+  uint64_t aided_mask, agrees_mask, disagrees_mask, off_grid_mask, shifted_mask, inconsistent_mask;   /*  8  bit j = slot j */
+  uint64_t valid_after_mask;     /* 56  step 7 */
+} gpsx_wtow_rx_t;
+
+/* d_pred_rx [n_rx] and d_pred [n_rx][n_prn]: what gpsx_wpred_dev wrote on the same list prns (n_prn PRN numbers, host memory in both
+ * variants); d_sync_state (written only with cfg.rearm), d_obs_state and d_obs (NULL: no record is patched) [n_rx * ch_per_rx]: device
+ * memory in both variants.  d_tow [n_rx * ch_per_rx], d_tow_rx [n_rx]: device memory; gpsx_wtow takes them in host memory. */
+int gpsx_wtow_dev(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
+                  const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs,
+                  gpsx_wtow_t *d_tow, gpsx_wtow_rx_t *d_tow_rx);
+int gpsx_wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
+              const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs,
+              gpsx_wtow_t *tow, gpsx_wtow_rx_t *tow_rx);
+
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,
  *      with gps_tracking_dll / _pll / _fll / _pll_check :175-393 and gps_nav_data_analyse_new_code, PM/GPS/nav_data.c:46-253)

@@ -134,6 +134,8 @@ def check_no_scratch() -> dict:
     check_wbank()
     # ... and, behind the filter, the prediction and hot hand-over (check_wpred below: FP64, a wave per receiver, the same terms)
     check_wpred()
+    # ... and, behind the observables and the prediction, the time-of-week aiding (check_wtow below: the same terms)
+    check_wtow()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -219,6 +221,12 @@ def check_wpred() -> dict:
     """k_wpred, prediction and hot hand-over (the solvers' shared parts on k_wacq's geometry: an object of its own, exactly one
     instance, no scratch and no LDS)"""
     return check_wsolver("k_wpred.o", "k_wpred", True)
+
+
+def check_wtow() -> dict:
+    """k_wtow, time-of-week aiding of the observables (a mover of a few words per slot on k_wacq's geometry: an object of its own,
+    exactly one instance, no scratch and no LDS)"""
+    return check_wsolver("k_wtow.o", "k_wtow", True)
 
 
 if __name__ == "__main__":

@@ -384,6 +384,32 @@ def wpred_cfg(ch_per_rx: int, mps_per_hz: float = WVEL_L1CA, el_min_rad: float =
     return cfg
 
 
+# gpsx_wtow_cfg_t / gpsx_wtow_t / gpsx_wtow_rx_t (time-of-week aiding of the observable states from gpsx_wpred's records)
+(WTOW_NO_PRED, WTOW_EMPTY, WTOW_UNLISTED, WTOW_BAD, WTOW_WAITING, WTOW_STALE, WTOW_UNCERTAIN, WTOW_INCONSISTENT, WTOW_OFF_GRID, WTOW_REARMED,
+ WTOW_SHIFTED, WTOW_AIDED, WTOW_AGREES, WTOW_DISAGREES) = (1 << i for i in range(14))
+WTOW_RX_NO_PRED, WTOW_RX_AIDED, WTOW_RX_SHIFTED, WTOW_RX_DISAGREES, WTOW_RX_OFF_GRID, WTOW_RX_REARMED = 1, 2, 4, 8, 16, 32
+WTOW_CFG_DTYPE = np.dtype([("max_sigma_m", "<f8"), ("max_resid_samples", "<f4"), ("ch_per_rx", "<i4"), ("max_age_blocks", "<i4"), ("resolve", "<i4"),
+                           ("rearm", "<i4"), ("reserved", "<i4")])
+WTOW_DTYPE = np.dtype([("flags", "<u4"), ("prn_index", "<i4"), ("tx_ms", "<i8"), ("resid", "<f4"), ("m", "<i4"), ("shift", "<i4"), ("zero", "<u4")])
+WTOW_RX_DTYPE = np.dtype([("flags", "<u2"), ("n_aided", "u1"), ("n_agrees", "u1"), ("n_disagrees", "u1"), ("n_off_grid", "u1"), ("n_shifted", "u1"),
+                          ("n_inconsistent", "u1"), ("aided_mask", "<u8"), ("agrees_mask", "<u8"), ("disagrees_mask", "<u8"), ("off_grid_mask", "<u8"),
+                          ("shifted_mask", "<u8"), ("inconsistent_mask", "<u8"), ("valid_after_mask", "<u8")])
+assert WTOW_CFG_DTYPE.itemsize == 32 and WTOW_DTYPE.itemsize == 32 and WTOW_RX_DTYPE.itemsize == 64
+
+
+def wtow_cfg(ch_per_rx: int, max_sigma_m: float = 300.0, max_resid_samples: float = 8.0, max_age_blocks: int = 40, resolve: int = 1,
+             rearm: int = 0) -> np.ndarray:
+    """a gpsx_wtow_cfg_t as a one-element WTOW_CFG_DTYPE array: a slot's time of week is anchored from a prediction known to max_sigma_m
+    (one sigma) whose code phase lies within max_resid_samples of the loop's, that no older than max_age_blocks; resolve 1 moves the
+    edge block of an AMBIGUOUS chain where the prediction says so, rearm 1 sends a slot whose bit edge is off the 20 ms grid back to
+    its search"""
+    cfg = np.zeros(1, WTOW_CFG_DTYPE)
+    for name, v in (("max_sigma_m", max_sigma_m), ("max_resid_samples", max_resid_samples), ("ch_per_rx", ch_per_rx),
+                    ("max_age_blocks", max_age_blocks), ("resolve", resolve), ("rearm", rearm)):
+        cfg[name] = v
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -536,6 +562,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wpred.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gpsx_wpred_dev.argtypes = lib.gpsx_wpred.argtypes
+    lib.gpsx_wtow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p]
+    lib.gpsx_wtow_dev.argtypes = lib.gpsx_wtow.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1129,6 +1158,29 @@ class Engine:
                                       C.c_void_p(d_sync_state), opt(d_lock_state), opt(d_nav_state), opt(d_obs_state), opt(d_eph_state), rx.ctypes.data,
                                       pred.ctypes.data if want_pred else None), "gpsx_wpred")
         return (rx, pred) if want_pred else rx
+
+    def wtow(self, cfg: np.ndarray, prns, n_rx: int, d_pred_rx: int, d_pred: int, d_sync_state: int, d_obs_state: int, d_obs: int | None = None):
+        """EXTENSION: time-of-week aiding (include/gpsx.h gpsx_wtow) of the n_rx * ch_per_rx WOBS_STATE_DTYPE states at device address
+        d_obs_state from the WPRED_RX_DTYPE [n_rx] and WPRED_DTYPE [n_rx, len(prns)] records a gpsx_wpred_dev call left at d_pred_rx and
+        d_pred -- its epoch the block the states stand at: the caller's duty --, the slots' PRNs from the WSYNC_STATE_DTYPE states at
+        d_sync_state; d_obs: that launch's WOBS_DTYPE records, patched where a state changed; cfg from wtow_cfg.
+        -> (WTOW_DTYPE [n_rx * ch_per_rx], WTOW_RX_DTYPE [n_rx])"""
+        assert cfg.dtype == WTOW_CFG_DTYPE and cfg.size == 1
+        prns = np.ascontiguousarray(prns, np.uint8)
+        tow, tow_rx = np.zeros(n_rx * int(cfg["ch_per_rx"][0]), WTOW_DTYPE), np.zeros(n_rx, WTOW_RX_DTYPE)
+        self._chk(self.lib.gpsx_wtow(self.h, cfg.ctypes.data, n_rx, len(prns), prns.ctypes.data, C.c_void_p(d_pred_rx), C.c_void_p(d_pred),
+                                     C.c_void_p(d_sync_state), C.c_void_p(d_obs_state), C.c_void_p(d_obs) if d_obs else None, tow.ctypes.data,
+                                     tow_rx.ctypes.data), "gpsx_wtow")
+        return tow, tow_rx
+
+    def wtow_dev(self, cfg: np.ndarray, prns, n_rx: int, d_pred_rx: int, d_pred: int, d_sync_state: int, d_obs_state: int, d_obs: int | None,
+                 d_tow: int, d_tow_rx: int) -> None:
+        """the same with the two record arrays left in device memory at d_tow and d_tow_rx: enqueues on the context's stream and returns"""
+        assert cfg.dtype == WTOW_CFG_DTYPE and cfg.size == 1
+        prns = np.ascontiguousarray(prns, np.uint8)
+        self._chk(self.lib.gpsx_wtow_dev(self.h, cfg.ctypes.data, n_rx, len(prns), prns.ctypes.data, C.c_void_p(d_pred_rx), C.c_void_p(d_pred),
+                                         C.c_void_p(d_sync_state), C.c_void_p(d_obs_state), C.c_void_p(d_obs) if d_obs else None, C.c_void_p(d_tow),
+                                         C.c_void_p(d_tow_rx)), "gpsx_wtow_dev")
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

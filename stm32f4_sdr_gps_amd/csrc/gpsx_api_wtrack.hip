@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -868,9 +868,96 @@ int wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const
       });
 }
 
+// ---- time-of-week aiding of the observables (host: tow and tow_rx are host memory, staged through the arena; the prediction's records,
+//      the sync and observable states and the observables are device memory in both variants) ------------------------------------------
+int wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
+         const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs, gpsx_wtow_t *tow,
+         gpsx_wtow_rx_t *tow_rx, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !prns || !d_pred_rx || !d_pred || !d_sync_state || !d_obs_state || !tow || !tow_rx)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (!(cfg->max_sigma_m - cfg->max_sigma_m == 0.0) || !(cfg->max_sigma_m > 0.0))   // (not finite: the difference is a NaN)
+    return fail(ctx, GPSX_EINVAL, "max_sigma_m must be finite and above 0");
+  if (!(cfg->max_resid_samples > 0.0f && cfg->max_resid_samples <= 4092.0f))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "max_resid_samples must be finite, above 0 and at most 4092");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->max_age_blocks < 0 || cfg->max_age_blocks > 4096)
+    return fail(ctx, GPSX_EINVAL, "max_age_blocks must be 0..4096");
+  if ((cfg->resolve != 0 && cfg->resolve != 1) || (cfg->rearm != 0 && cfg->rearm != 1))
+    return fail(ctx, GPSX_EINVAL, "resolve and rearm must be 0 or 1");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (n_prn < 1 || n_prn > 64)
+    return fail(ctx, GPSX_EINVAL, "n_prn must be 1..64");
+  bool listed[GPSX_MAX_PRN + 1] = {};
+  for (int i = 0; i < n_prn; i++) {
+    if (prns[i] < 1 || prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+    if (listed[prns[i]])
+      return fail(ctx, GPSX_EINVAL, "a PRN is listed twice");
+    listed[prns[i]] = true;
+  }
+  if (((reinterpret_cast<uintptr_t>(d_pred_rx) | reinterpret_cast<uintptr_t>(d_pred) | reinterpret_cast<uintptr_t>(d_obs_state) |
+        reinterpret_cast<uintptr_t>(d_obs)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_pred_rx, d_pred, d_obs_state and d_obs must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_sync_state) & 7u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_sync_state must be 8-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(tow) | reinterpret_cast<uintptr_t>(tow_rx)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_tow and d_tow_rx must be 16-byte aligned");
+  size_t rx_bytes = 0, pred_bytes = 0, sync_bytes = 0, st_bytes = 0, obs_bytes = 0, tow_bytes = 0, tow_rx_bytes = 0;
+  if (records_overflow((size_t)n_rx, 1, sizeof(gpsx_wpred_rx_t), &rx_bytes) || records_overflow((size_t)n_rx, n_prn, sizeof(gpsx_wpred_t), &pred_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wsync_state_t), &sync_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wobs_state_t), &st_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wobs_t), &obs_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_wtow_t), &tow_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_wtow_rx_t), &tow_rx_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x n_prn records overflow a size");
+  // (host and device addresses share one space here: one list of spans serves both variants)
+  const struct { const void *p; size_t n; } span[7] = {{tow, tow_bytes},           {tow_rx, tow_rx_bytes},    {d_pred_rx, rx_bytes}, {d_pred, pred_bytes},
+                                                      {d_sync_state, sync_bytes}, {d_obs_state, st_bytes}, {d_obs, obs_bytes}};
+  for (int a = 0; a < 2; a++)
+    for (int b = a + 1; b < 7; b++) {
+      const uintptr_t pa = reinterpret_cast<uintptr_t>(span[a].p), pb = reinterpret_cast<uintptr_t>(span[b].p);
+      if (pb && pa < pb + span[b].n && pb < pa + span[a].n)
+        return fail(ctx, GPSX_EINVAL, "d_tow or d_tow_rx overlaps another array");
+    }
+  gpsx_wtow_t *d_tow = tow;
+  gpsx_wtow_rx_t *d_tow_rx = tow_rx;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(tow_bytes) + arena_size(tow_rx_bytes))) return rc;
+    d_tow = arena_take<gpsx_wtow_t>(ctx, tow_bytes / sizeof(gpsx_wtow_t));
+    d_tow_rx = arena_take<gpsx_wtow_rx_t>(ctx, (size_t)n_rx);
+  }
+  return launch_and_report(
+      ctx, host, "k_wtow", "k_wtow raised the bad-state flag, which it never does",
+      [&](uint32_t *) { launch_wtow(ctx->stream, *cfg, n_rx, n_prn, prns, d_pred_rx, d_pred, d_sync_state, d_obs_state, d_obs, d_tow, d_tow_rx); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(tow, d_tow, tow_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(tow_rx, d_tow_rx, tow_rx_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_wtow_dev(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
+                  const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs,
+                  gpsx_wtow_t *d_tow, gpsx_wtow_rx_t *d_tow_rx)
+{
+  return wtow(ctx, cfg, n_rx, n_prn, prns, d_pred_rx, d_pred, d_sync_state, d_obs_state, d_obs, d_tow, d_tow_rx, false);
+}
+
+int gpsx_wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
+              const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs, gpsx_wtow_t *tow,
+              gpsx_wtow_rx_t *tow_rx)
+{
+  return wtow(ctx, cfg, n_rx, n_prn, prns, d_pred_rx, d_pred, d_sync_state, d_obs_state, d_obs, tow, tow_rx, true);
+}
 
 int gpsx_wpred_dev(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
                    const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_state, gpsx_wlock_state_t *d_lock_state, gpsx_wnav_state_t *d_nav_state,

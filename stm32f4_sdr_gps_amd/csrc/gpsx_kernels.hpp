@@ -229,6 +229,14 @@ void launch_wbank(hipStream_t s, const gpsx_wbank_cfg_t &cfg, int n_rx, int n_pr
 void launch_wpred(hipStream_t s, const gpsx_wpred_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,
                   const gpsx_weph_t *d_bank, gpsx_wsync_state_t *d_sync_st, gpsx_wlock_state_t *d_lock_st, gpsx_wnav_state_t *d_nav_st,
                   gpsx_wobs_state_t *d_obs_st, gpsx_weph_state_t *d_eph_st, gpsx_wpred_rx_t *d_rx, gpsx_wpred_t *d_pred);
+// extension: gpsx_wtow (k_wtow.hip: k_wtow) -- time-of-week aiding behind gpsx_wobs and gpsx_wpred: from launch_wpred's records d_pred_rx
+// [n_rx] and d_pred [n_rx][n_prn] (read only) the anchor of every [n_rx * ch_per_rx] observable state d_obs_st whose chain runs without
+// one; d_sync_st is read for the slots' PRNs and written only with cfg.rearm; d_obs (may be null) [n_rx * ch_per_rx]: tx_ms and flags of
+// the slots whose state changed.  d_tow [n_rx * ch_per_rx] 32-byte and d_tow_rx [n_rx] 64-byte records, every byte written.  A wave
+// per receiver; prns in HOST memory, by value.  No checks.
+void launch_wtow(hipStream_t s, const gpsx_wtow_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
+                 const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_st, gpsx_wobs_state_t *d_obs_st, gpsx_wobs_t *d_obs, gpsx_wtow_t *d_tow,
+                 gpsx_wtow_rx_t *d_tow_rx);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

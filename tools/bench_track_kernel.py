@@ -116,7 +116,15 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       (EXTENSION: prediction and hot hand-over; k_wpred) on the same filter states and
                                                       bank with half the slots emptied, predicting only and handing over, beside a
                                                       copy of what it reads and gpsx_wkf_dev; the lines also go to
-                                                      profiles/r28_weighted_pred_bench.jsonl"""
+                                                      profiles/r28_weighted_pred_bench.jsonl
+  bench_track_kernel.py --weighted-tow [N_RXxN_PRNxCH_PER_RX ...]
+                                                      gpsx_wtow_dev (EXTENSION: time-of-week aiding; k_wtow) at the same shapes behind
+                                                      gpsx_wpred_dev's records: every slot anchored (a device-to-device copy puts the
+                                                      observable states back before every timed launch; it is timed alone and
+                                                      subtracted), with and without d_obs, and the steady state in which every slot
+                                                      agrees, beside (1) a device-to-device copy of the bytes it reads and (2)
+                                                      gpsx_wpred_dev predicting only; the lines also go to
+                                                      profiles/r29_weighted_tow_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -1319,8 +1327,132 @@ def weighted_bank(shapes, out=BANK_OUT):
         eng.close()
 
 
+TOW_OUT = os.path.join(ROOT, "profiles", "r29_weighted_tow_bench.jsonl")
+
+
+def weighted_tow(shapes, out=TOW_OUT):
+    """k_wtow at (receivers, PRNs, slots per receiver) behind k_wpred on --weighted-bank's receivers (real ephemerides, initialised filter
+    states, a full bank, every slot on a listed PRN of its own): gpsx_wpred_dev predicts once, and the observable states are made from its
+    records -- a running chain without an anchor in every slot, the loop's phase the predicted one, the edge on the 20 ms grid.  Timed:
+    the call that anchors every slot (a device-to-device copy puts the states back before every timed launch; it is timed alone and
+    subtracted), with and without d_obs, and the steady state behind it (every slot AGREES, nothing is written).  The yardsticks: a
+    device-to-device copy of the bytes the kernel reads (the prediction's records and the observable states), and k_wpred predicting only
+    at the same receivers; the calls take turns; the lines go to stdout and to `out`"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fix_cases as W
+    import weighted_kf_cases as K
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0, stream=stream.value)
+    names = sorted(W.SITES)
+    try:
+        for n_rx, n_prn, ch in shapes:
+            pool = [K.track(names[k % len(names)], ch, 3 * k, K.VELOCITY, 1e-6, 2) for k in range(16)]
+            obs0, eph = W.pack([(pool[r % 16][0][0]["obs"], pool[r % 16][1]) for r in range(n_rx)], ch)
+            n_ch = n_rx * ch
+            prns = np.arange(1, n_prn + 1, dtype=np.uint8)
+            index = (np.arange(n_ch) // ch + np.arange(n_ch) % ch) % n_prn          # receiver r's slot j: PRN index (r + j) mod n_prn
+            sync = np.zeros(n_ch, capi.WSYNC_STATE_DTYPE)
+            sync["loop"]["prn"], sync["mode"] = prns[index], 2
+            bank = np.zeros((n_rx, n_prn), capi.WEPH_DTYPE)
+            bank[np.arange(n_ch) // ch, index] = eph
+            bank["flags"] &= capi.WEPH_FLAG_VALID
+            fix_cfg, vel_cfg, kf_cfg = capi.wfix_cfg(W.OFFSET_MS, ch), capi.wvel_cfg(ch), capi.wkf_cfg(ch)
+            pcfg = capi.wpred_cfg(ch, capi.WVEL_L1CA, max_sigma_m=1e4, max_sigma_hz=1e4, lead_blocks=20, handover=0)
+            tcfg = capi.wtow_cfg(ch, max_sigma_m=1e4, max_resid_samples=8.0, max_age_blocks=40, resolve=1, rearm=0)
+            state_bytes = n_rx * capi.WKF_STATE_DTYPE.itemsize
+            prx_bytes, ppred_bytes = n_rx * capi.WPRED_RX_DTYPE.itemsize, n_rx * n_prn * capi.WPRED_DTYPE.itemsize
+            st_bytes, o_bytes = n_ch * capi.WOBS_STATE_DTYPE.itemsize, n_ch * capi.WOBS_DTYPE.itemsize
+            d_obs0, d_eph, d_fix, d_vel, d_state0, d_kf = (eng.malloc(b) for b in (obs0.nbytes, eph.nbytes, n_rx * 128, n_rx * 112, state_bytes,
+                                                                                   n_rx * capi.WKF_DTYPE.itemsize))
+            d_sync, d_bank, d_prx, d_ppred = (eng.malloc(b) for b in (sync.nbytes, bank.nbytes, prx_bytes, ppred_bytes))
+            d_st, d_st0, d_o, d_tow, d_tow_rx, d_copy = (eng.malloc(b) for b in (st_bytes, st_bytes, o_bytes, n_ch * capi.WTOW_DTYPE.itemsize,
+                                                                               n_rx * capi.WTOW_RX_DTYPE.itemsize, prx_bytes + ppred_bytes + st_bytes))
+            for d, a in ((d_obs0, obs0), (d_eph, eph), (d_state0, np.zeros(n_rx, capi.WKF_STATE_DTYPE)), (d_sync, sync), (d_bank, bank)):
+                eng.h2d(d, a)
+            eng._chk(eng.lib.gpsx_wfix_dev(eng.h, fix_cfg.ctypes.data, C.c_void_p(d_obs0), C.c_void_p(d_eph), None, None, n_rx, C.c_void_p(d_fix), None), "gpsx_wfix_dev")
+            eng._chk(eng.lib.gpsx_wvel_dev(eng.h, vel_cfg.ctypes.data, C.c_void_p(d_obs0), C.c_void_p(d_eph), None, C.c_void_p(d_fix), n_rx, C.c_void_p(d_vel)),
+                     "gpsx_wvel_dev")
+            eng._chk(eng.lib.gpsx_wkf_dev(eng.h, kf_cfg.ctypes.data, C.c_void_p(d_obs0), C.c_void_p(d_eph), None, C.c_void_p(d_fix), C.c_void_p(d_vel), n_rx, 1000,
+                                          C.c_void_p(d_state0), C.c_void_p(d_kf)), "gpsx_wkf_dev")      # INIT
+
+            def wpred():
+                return eng.lib.gpsx_wpred_dev(eng.h, pcfg.ctypes.data, n_rx, n_prn, prns.ctypes.data, C.c_void_p(d_state0), C.c_void_p(d_bank), C.c_void_p(d_sync),
+                                              None, None, None, None, C.c_void_p(d_prx), C.c_void_p(d_ppred))
+            eng._chk(wpred(), "gpsx_wpred_dev")
+            eng.synchronize()
+            pred = np.zeros((n_rx, n_prn), capi.WPRED_DTYPE)
+            eng.d2h(pred, d_ppred)
+            w = pred[np.arange(n_ch) // ch, index]                                 # every slot's record
+            st = np.zeros(n_ch, capi.WOBS_STATE_DTYPE)                              # a running chain without an anchor, the edge on the 20 ms grid
+            st["blocks_seen"], st["last_bit_end_p1"], st["chain_first_p1"], st["last_win_end_p1"] = 25000, 24997, 24597, 24990
+            st["edge_block"] = 25000 - w["tx_ms"] % 20
+            st["last_phase"] = np.minimum(w["code_phase"].astype(np.float32), np.float32(16367.0))
+            st["flags"] = 3                                                          # PHASE | EDGE
+            eng.h2d(d_st0, st)
+            eng.h2d(d_st, st)
+            eng.h2d(d_o, np.zeros(n_ch, capi.WOBS_DTYPE))
+
+            def wtow(d_states, d_obs):
+                return eng.lib.gpsx_wtow_dev(eng.h, tcfg.ctypes.data, n_rx, n_prn, prns.ctypes.data, C.c_void_p(d_prx), C.c_void_p(d_ppred), C.c_void_p(d_sync),
+                                             C.c_void_p(d_states), None if d_obs is None else C.c_void_p(d_obs), C.c_void_p(d_tow), C.c_void_p(d_tow_rx))
+
+            def restore():
+                return hip.hipMemcpyAsync(d_st, d_st0, st_bytes, 3, stream)
+
+            def copy_of_what_it_reads():
+                return (hip.hipMemcpyAsync(d_copy, d_prx, prx_bytes, 3, stream) or hip.hipMemcpyAsync(d_copy + prx_bytes, d_ppred, ppred_bytes, 3, stream) or
+                        hip.hipMemcpyAsync(d_copy + prx_bytes + ppred_bytes, d_st0, st_bytes, 3, stream))
+            eng._chk(wtow(d_st, d_o), "gpsx_wtow_dev")
+            eng.synchronize()
+            first = np.zeros(n_rx, capi.WTOW_RX_DTYPE)
+            eng.d2h(first, d_tow_rx)
+            calls = {"d2d_copy_of_the_obs_states": (1, restore),
+                     "d2d_copy_of_what_it_reads": (1, copy_of_what_it_reads),
+                     "state_copy_then_wtow_aids": (1, lambda: restore() or wtow(d_st, d_o)),
+                     "state_copy_then_wtow_aids_no_obs": (1, lambda: restore() or wtow(d_st, None)),
+                     "wpred_predict_only": (1, wpred)}
+            med = _timed_rows(eng, calls, {"channels": n_ch, "n_rx": n_rx, "n_prn": n_prn, "ch_per_rx": ch, "read_bytes": prx_bytes + ppred_bytes + st_bytes},
+                              per_channel_ms=False)
+            eng._chk(wtow(d_st, d_o), "gpsx_wtow_dev")                              # (the last timed launch aided without d_obs: d_st is anchored)
+            med.update(_timed_rows(eng, {"wtow_agrees": (1, lambda: wtow(d_st, d_o))},
+                                   {"channels": n_ch, "n_rx": n_rx, "n_prn": n_prn, "ch_per_rx": ch, "read_bytes": prx_bytes + ppred_bytes + st_bytes}, per_channel_ms=False))
+            steady = np.zeros(n_rx, capi.WTOW_RX_DTYPE)
+            eng.d2h(steady, d_tow_rx)
+            print(json.dumps({"wtow_check": "records of the first launch and after the timed ones", "n_rx": n_rx,
+                              "aided_per_rx_first": [int(first["n_aided"].min()), int(first["n_aided"].max())],
+                              "agrees_per_rx_steady": [int(steady["n_agrees"].min()), int(steady["n_agrees"].max())],
+                              "aided_steady": int(steady["n_aided"].sum()), "inconsistent_first": int(first["n_inconsistent"].sum())}), flush=True)
+            own = med["state_copy_then_wtow_aids"] - med["d2d_copy_of_the_obs_states"]
+            print(json.dumps({"ratio": "k_wtow anchoring every slot (the timed pair less the state copy) over the two yardsticks", "n_rx": n_rx, "n_prn": n_prn,
+                              "ch_per_rx": ch, "wtow_us": round(own, 3),
+                              "wtow_no_obs_us": round(med["state_copy_then_wtow_aids_no_obs"] - med["d2d_copy_of_the_obs_states"], 3),
+                              "wtow_agrees_us": round(med["wtow_agrees"], 3), "wpred_predict_only_us": round(med["wpred_predict_only"], 3),
+                              "over_d2d_copy_of_what_it_reads": round(own / med["d2d_copy_of_what_it_reads"], 3),
+                              "agrees_over_d2d_copy_of_what_it_reads": round(med["wtow_agrees"] / med["d2d_copy_of_what_it_reads"], 3),
+                              "over_wpred_predict_only": round(own / med["wpred_predict_only"], 3), "ns_per_receiver": round(own / n_rx * 1e3, 2)}), flush=True)
+            for p in (d_obs0, d_eph, d_fix, d_vel, d_state0, d_kf, d_sync, d_bank, d_prx, d_ppred, d_st, d_st0, d_o, d_tow, d_tow_rx, d_copy):
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-tow" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-tow"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_tow([tuple(int(v) for v in a.split("x")) for a in args] or BANK_SHAPES)
     if "--weighted-bank" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-bank"]
         if "--window-s" in args:
