@@ -1932,6 +1932,152 @@ int gpsx_wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, co
               const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs,
               gpsx_wtow_t *tow, gpsx_wtow_rx_t *tow_rx);
 
+/* ---- EXTENSION, not in the reference: almanac, ionosphere and UTC -- subframes 4 and 5 of the words, on the device ------------------
+ * gpsx_weph counts subframes 4 and 5 and drops them; the reference's decoder keeps only their HOW time.  gpsx_walm(_dev) is a stage
+ * behind gpsx_wnav_words_dev, beside gpsx_weph_dev, on the same d_words: it assembles every slot's subframes across launches, keeps
+ * per RECEIVER the newest parity-clean copy of the 32 almanac pages, of subframe 4 page 18 (Klobuchar coefficients, UTC) and of
+ * subframe 5 page 25 (almanac reference week, health summary) in a device-resident bank owned by the caller, and returns per launch the
+ * decoded records: the ion[8] that gpsx_wfix_cfg_t, gpsx_wkf_cfg_t and gpsx_wpred_cfg_t take, GPS - UTC, and the constellation's
+ * coarse orbits.  A slot's PRN plays no part: every satellite sends every page.  It changes no existing struct, kernel or definition
+ * (GPSX_VERSION stays 110).  IS-GPS-200 20.3.3.5 is what the fields mean; the reference has no decoder for these pages, so THIS TEXT is
+ * the definition.
+ *
+ * The channel of receiver r's slot j is r * ch_per_rx + j; d_words is [n_blocks / 600 + 2][n_rx * ch_per_rx].
+ *
+ * Assembly, per slot, on its 64-byte state.  The slots of d_words are read in order.  A record counts only if its flags have
+ * GPSX_WNAV_WORD, 1 <= index <= 10, -600 <= end_block < n_blocks (word 1 of a GPSX_WNAV_SYNC pair ends before its launch may) and,
+ * with E1 = blocks_seen + end_block + 1, E1 >= 1; every other record is skipped.  `passed`: the record has GPSX_WNAV_OK -- and, for
+ * index 2, subframe_id in 1 .. 5 and aux < 100800.  For a record that counts:
+ *   1 word 1       cur_mask = passed, cur_next = 2, cur_id = 0, last_word_end_p1 = E1
+ *   2 the expected word  (index == cur_next and E1 == last_word_end_p1 + 600)  if passed: cur_mask |= 1 << (index - 1); if passed
+ *                  and index is 2: cur_id = subframe_id; if passed and index >= 3: cur[index - 3] = (word >> 6) & 0xFFFFFF.  Then
+ *                  last_word_end_p1 = E1 and cur_next = index == 10 ? 0 : index + 1.  At index 10 with cur_mask == 0x3FF and cur_id
+ *                  4 or 5 the subframe is COMPLETE: it is offered to the bank with cur[] as it stands
+ *   3 anything else  (a gap, a word out of order, a word while waiting for a word 1)  cur_next = 0, cur_mask = 0,
+ *                  last_word_end_p1 = E1
+ * Then blocks_seen += n_blocks.  (Word 10s lie 6000 blocks apart: a slot completes at most one subframe per launch.)  The call must
+ * be made on every launch of a stream, as gpsx_wnav_words must: blocks_seen is the time base.
+ *
+ * Commit, per receiver.  Subframe bit n (0 = the first bit of word 1) lies in word n / 30, and bits 0 .. 23 of a word are d1 .. d24,
+ * d1 first: u(p, l) is the l bits from bit p on, first bit most significant, s(p, l) the same as two's complement.  With data ID =
+ * u(60, 2), s = u(62, 6) and toa = u(90, 8), a COMPLETE subframe goes to bank entry
+ *     cur_id 5, data ID 1, s 1 .. 24,  toa <= 147     s - 1  (almanac of SV s)
+ *     cur_id 4, data ID 1, s 25 .. 32, toa <= 147     s - 1  (almanac of SV s)
+ *     cur_id 4, data ID 1, s 56                       32     (page 18)
+ *     cur_id 5, data ID 1, s 51                       33     (page 25)
+ * and anything else (another data ID, dummy SV 0, another page, an almanac toa beyond 147 * 4096 = 602 112 s) only counts in n_other.
+ * A receiver's commits of one launch apply in ascending slot order: page[e] = cur[0 .. 7], have_mask |= 1 << e, n_stored++ -- the
+ * highest slot's words stand, every commit counts.  Entry e is SEEN in a launch with a commit to it, and NEW if it is SEEN and was not
+ * held before the launch or its eight words after the launch differ from those before it; n_changed += the number of NEW entries.
+ * Nothing is ever cleared.  The counters wrap at 2^32.
+ *
+ * Output, per receiver, from the bank as the launch left it; every byte of d_rx and d_alm is written.  Doubles: the integer converted,
+ * then one IEEE multiply by the scale (an exact power of two), then for semicircles one by 3.1415926535898, no contraction.
+ * Eight-bit weeks (wna, wnt, wn_lsf) are resolved around build week 2290 as gpsx_weph resolves its ten bits:
+ * W = w + (2290 - w + 128) / 256 * 256 in C's integers, 2163 .. 2418.
+ *   d_alm[r][s - 1] from entry s - 1, all zero if it is not held:
+ *     flags   HELD; NEW as above; HEALTHY iff svh == 0; WEEK iff entry 33 is held and its u(68, 8) equals this page's u(90, 8)
+ *     svid u(62, 6) (= s), svh u(136, 8), week = page 25's resolved wna with WEEK, else 0
+ *     e u(68,16) 2^-21;  toas u(90,8) * 4096;  i0 = (0.3 + s(98,16) 2^-19) * pi: the (exact) product, the sum, then the product;
+ *     OMGd s(120,16) 2^-38 pi;  A = rootA * rootA with rootA = u(150,24) 2^-11;  OMG0 s(180,24) 2^-23 pi;  omg s(210,24) 2^-23 pi;
+ *     M0 s(240,24) 2^-23 pi;  f0 = s11(u(270,8) << 3 | u(289,3)) 2^-20;  f1 s(278,11) 2^-38
+ *   d_rx[r]:
+ *     flags   GPSX_WALM_IONUTC iff entry 32 is held, GPSX_WALM_PAGE25 iff entry 33 is held;  n_stored: this launch's commits
+ *     have_mask, new_mask, seen_mask: bit e;  healthy_mask / week_mask: bit s - 1 = the record's HEALTHY / WEEK
+ *     from page 25 (zero without it): toa_s u(68,8) * 4096, wna u(76,8) resolved, p25_unhealthy_mask bit n - 1 iff the six-bit health
+ *       word of SV n (1 .. 24), u(90 + 30 ((n - 1) / 4) + 6 ((n - 1) % 4), 6), is != 0
+ *     from page 18 (zero without it): ion[0 .. 3] = alpha s(68,8) 2^-30, s(76,8) 2^-27, s(90,8) 2^-24, s(98,8) 2^-24; ion[4 .. 7] =
+ *       beta s(106,8) 2^11, s(120,8) 2^14, s(128,8) 2^16, s(136,8) 2^16 (the layout of gpsx_wfix_cfg_t.ion); A1 s(150,24) 2^-50;
+ *       A0 = (int32)(u(180,24) << 8 | u(210,8)) 2^-30; tot_s u(218,8) * 4096; wnt u(226,8) resolved; dt_ls s(240,8); wn_lsf u(248,8)
+ *       resolved; dn u(256,8); dt_lsf s(270,8).  (A page 18 with all-zero alpha and beta gives an all-zero ion[]: the solvers then
+ *       use their default set.)
+ * d_alm NULL: the almanac records are not wanted.
+ *
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written: cfg, d_words, d_slot_state, d_bank or d_rx NULL;
+ * ch_per_rx outside 1 .. 64; a reserved word != 0; n_blocks outside 1 .. 4096; n_rx outside 1 .. 1 048 576; d_words, d_slot_state,
+ * d_bank or (in _dev) d_rx, d_alm not 16-byte aligned; two of the five arrays overlapping; size products that overflow.
+ * A slot is BAD if blocks_seen or last_word_end_p1 lies outside 0 .. 2^62, cur_next is not 0 or 2 .. 10, cur_mask > 0x3FF, cur_id > 5,
+ * a cur word >= 2^24 or reserved != 0: its state stays as it was and it commits nothing; the receiver's other slots are served.  A
+ * bank is BAD if a page word is >= 2^24, have_mask has a bit from 34 on or a reserved word is != 0: the bank AND the receiver's slot
+ * states stay as they were (nothing a slot completed is lost: the launch did not happen for this receiver) and its records are all
+ * zero.  Either way GPSX_EINVAL comes from gpsx_walm after its wait / from the next gpsx_synchronize() after _dev; the other
+ * receivers are served.
+ * _dev only enqueues.  Vector ALU (k_walm: a wave per receiver, four receivers per workgroup, no LDS; lane j is slot j for the
+ * assembly -- the word records' 16-byte loads and the state all in flight before the first is looked at --, lane e is bank entry e
+ * for the commits, which a ballot finds and lane broadcasts apply in ascending slot order; an entry is written back only if it
+ * changed, none is read back; lanes 0 .. 31 decode and store their almanac record).  On one stream: ..., gpsx_wnav_words_dev, then
+ * gpsx_wobs_dev, gpsx_weph_dev and gpsx_walm_dev in any order on the same d_words and n_blocks; the host copies d_rx's ion[] into
+ * the solvers' cfg (eight doubles). */
+#define GPSX_WALM_IONUTC  1u   /* gpsx_walm_rx_t.flags: page 18 is held */
+#define GPSX_WALM_PAGE25  2u   /* gpsx_walm_rx_t.flags: page 25 is held */
+#define GPSX_WALM_HELD    1u   /* gpsx_walm_sv_t.flags: the SV's almanac page is held */
+#define GPSX_WALM_WEEK    2u   /* ... and its toa is page 25's: `week` is its reference week */
+#define GPSX_WALM_HEALTHY 4u   /* ... and its eight-bit health is 0 */
+#define GPSX_WALM_NEW     8u   /* ... and a commit of this launch gave the entry contents it did not have before */
+#define GPSX_WALM_ENTRIES 34   /* almanac pages of SV 1 .. 32, page 18, page 25 */
+
+typedef struct {                 /* 16 bytes */
+  int32_t ch_per_rx;             /* 1 .. 64 */
+  int32_t reserved[3];           /* 0 */
+} gpsx_walm_cfg_t;
+
+typedef struct {                 /* 64 bytes per slot, device resident; all zero = a fresh slot */
+  int64_t  blocks_seen;          /*  0  blocks of all earlier launches */
+  int64_t  last_word_end_p1;     /*  8  absolute last block of the newest word that counted, + 1; 0: none */
+  uint32_t cur[8];               /* 16  d1 .. d24 (d1 in bit 23) of words 3 .. 10 of the subframe being assembled */
+  uint32_t cur_mask;             /* 48  bit w (0 .. 9): word w + 1 of it counted and passed */
+  uint32_t cur_next;             /* 52  index of the word expected next, 2 .. 10; 0: waiting for a word 1 */
+  uint32_t cur_id;               /* 56  from its HOW if that passed: 1 .. 5; else 0 */
+  uint32_t reserved;             /* 60  0 */
+} gpsx_walm_slot_t;
+
+typedef struct {                 /* 1120 bytes per receiver, device resident; all zero = empty */
+  uint32_t page[GPSX_WALM_ENTRIES][8];   /*    0  words 3 .. 10 of the newest copy of every entry */
+  uint64_t have_mask;            /* 1088  bit e: page[e] holds a page */
+  uint32_t n_stored, n_changed, n_other;   /* 1096  commits; entries that became NEW; complete subframes 4 / 5 that went nowhere */
+  uint32_t reserved[3];          /* 1108  0 */
+} gpsx_walm_bank_t;
+
+typedef struct {                 /* 160 bytes, one per receiver and launch */
+  uint32_t flags;                /*   0  GPSX_WALM_IONUTC | GPSX_WALM_PAGE25 */
+  uint32_t n_stored;             /*   4  commits of this launch */
+  uint64_t have_mask, new_mask, seen_mask;   /*   8  bit e = bank entry e */
+  uint32_t healthy_mask, week_mask, p25_unhealthy_mask;   /*  32  bit s - 1 = SV s */
+  int32_t  toa_s, wna;           /*  44  page 25 */
+  int32_t  tot_s, wnt, dt_ls, wn_lsf, dn, dt_lsf;   /*  52  page 18 */
+  uint32_t reserved;             /*  76  0 */
+  double   A0, A1;               /*  80  page 18: UTC polynomial, s and s/s */
+  double   ion[8];               /*  96  page 18: Klobuchar a0..a3, b0..b3, as gpsx_wfix_cfg_t.ion */
+} gpsx_walm_rx_t;
+
+typedef struct {                 /* 96 bytes, d_alm[r][s - 1] */
+  uint32_t flags;                /*  0  GPSX_WALM_HELD | WEEK | HEALTHY | NEW */
+  int32_t  svid, svh, week;      /*  4 */
+  double   toas, e, A, i0, OMG0, omg, M0, OMGd, f0, f1;   /* 16  s, -, m, rad, rad, rad, rad, rad/s, s, s/s */
+} gpsx_walm_sv_t;
+
+/* d_words, d_slot_state [n_rx * ch_per_rx] and d_bank [n_rx]: device memory in both variants.  d_rx [n_rx] and d_alm (NULL: not
+ * wanted) [n_rx][32]: device memory; gpsx_walm takes rx and alm in host memory (staged through the arena; it waits for its kernel). */
+int gpsx_walm_dev(gpsx_ctx *ctx, const gpsx_walm_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx,
+                  gpsx_walm_slot_t *d_slot_state, gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *d_rx, gpsx_walm_sv_t *d_alm);
+int gpsx_walm(gpsx_ctx *ctx, const gpsx_walm_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx,
+              gpsx_walm_slot_t *d_slot_state, gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *rx, gpsx_walm_sv_t *alm);
+
+/* Host only, no GPU.  An almanac record with HELD and WEEK as a GPSX_WEPH_VALID ephemeris record, so that gpsx_weph_to_eph
+ * (include/gpsx_compat.h) and the solvers' satellite position evaluate the almanac orbit unchanged: *out is zeroed, then flags =
+ * GPSX_WEPH_VALID, A, e, i0, OMG0, omg, M0, OMGd, f0, f1, svh and week are the record's, toes = toas, and toe and toc are the
+ * decoder's gps_time(week, toas) (time = 315964800 + 604800 week + (int)toas, sec = toas - (int)toas); every other field (the
+ * harmonic terms, deln, idot, f2, tgd, iode, iodc, ttr, n_sets, have) stays zero.  GPSX_EINVAL for NULL and for a record without HELD
+ * and WEEK (*out is then untouched). */
+int gpsx_walm_to_eph(const gpsx_walm_sv_t *in, gpsx_weph_t *out);
+/* Host only, no GPU.  GPS - UTC at GPS week `week` (full), second tow_s, from a receiver record with GPSX_WALM_IONUTC and dn in 1 .. 7
+ * (IS-GPS-200 20.3.3.5.2.4; the leap second takes effect at the end of day dn of week wn_lsf), in this order of double operations:
+ *   now = (double)week * 604800.0 + tow_s;   then = (double)wn_lsf * 604800.0 + (double)dn * 86400.0
+ *   ls  = now >= then ? dt_lsf : dt_ls
+ *   dt  = ((double)ls + A0) + A1 * ((tow_s - (double)tot_s) + 604800.0 * ((double)week - (double)wnt))
+ * GPSX_EINVAL for NULL, a record without IONUTC, dn outside 1 .. 7 or a tow_s that is not finite (*dt_s is then untouched). */
+int gpsx_walm_gps_minus_utc(const gpsx_walm_rx_t *rx, int week, double tow_s, double *dt_s);
+
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,
  *      with gps_tracking_dll / _pll / _fll / _pll_check :175-393 and gps_nav_data_analyse_new_code, PM/GPS/nav_data.c:46-253)

@@ -136,6 +136,8 @@ def check_no_scratch() -> dict:
     check_wpred()
     # ... and, behind the observables and the prediction, the time-of-week aiding (check_wtow below: the same terms)
     check_wtow()
+    # ... and, beside the ephemeris stage, the almanac, ionosphere and UTC (check_walm below: the same terms)
+    check_walm()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -227,6 +229,12 @@ def check_wtow() -> dict:
     """k_wtow, time-of-week aiding of the observables (a mover of a few words per slot on k_wacq's geometry: an object of its own,
     exactly one instance, no scratch and no LDS)"""
     return check_wsolver("k_wtow.o", "k_wtow", True)
+
+
+def check_walm() -> dict:
+    """k_walm, almanac, ionosphere and UTC from subframes 4 and 5 (k_weph's assembly on k_wbank's geometry: an object of its own,
+    exactly one instance, no scratch and no LDS)"""
+    return check_wsolver("k_walm.o", "k_walm", True)
 
 
 if __name__ == "__main__":

@@ -410,6 +410,57 @@ def wtow_cfg(ch_per_rx: int, max_sigma_m: float = 300.0, max_resid_samples: floa
     return cfg
 
 
+# gpsx_walm_cfg_t / gpsx_walm_slot_t / gpsx_walm_bank_t / gpsx_walm_rx_t / gpsx_walm_sv_t (almanac, ionosphere and UTC from subframes 4, 5)
+WALM_IONUTC, WALM_PAGE25 = 1, 2
+WALM_HELD, WALM_WEEK, WALM_HEALTHY, WALM_NEW = 1, 2, 4, 8
+WALM_ENTRIES = 34
+WALM_CFG_DTYPE = np.dtype([("ch_per_rx", "<i4"), ("reserved", "<i4", (3,))])
+WALM_SLOT_DTYPE = np.dtype([("blocks_seen", "<i8"), ("last_word_end_p1", "<i8"), ("cur", "<u4", (8,)), ("cur_mask", "<u4"), ("cur_next", "<u4"),
+                            ("cur_id", "<u4"), ("reserved", "<u4")])
+WALM_BANK_DTYPE = np.dtype([("page", "<u4", (WALM_ENTRIES, 8)), ("have_mask", "<u8"), ("n_stored", "<u4"), ("n_changed", "<u4"), ("n_other", "<u4"),
+                            ("reserved", "<u4", (3,))])
+WALM_RX_DTYPE = np.dtype([("flags", "<u4"), ("n_stored", "<u4"), ("have_mask", "<u8"), ("new_mask", "<u8"), ("seen_mask", "<u8"), ("healthy_mask", "<u4"),
+                          ("week_mask", "<u4"), ("p25_unhealthy_mask", "<u4"), ("toa_s", "<i4"), ("wna", "<i4"), ("tot_s", "<i4"), ("wnt", "<i4"),
+                          ("dt_ls", "<i4"), ("wn_lsf", "<i4"), ("dn", "<i4"), ("dt_lsf", "<i4"), ("reserved", "<u4"), ("A0", "<f8"), ("A1", "<f8"),
+                          ("ion", "<f8", (8,))])
+WALM_SV_DOUBLES = ("toas", "e", "A", "i0", "OMG0", "omg", "M0", "OMGd", "f0", "f1")
+WALM_SV_DTYPE = np.dtype([("flags", "<u4"), ("svid", "<i4"), ("svh", "<i4"), ("week", "<i4")] + [(k, "<f8") for k in WALM_SV_DOUBLES])
+assert (WALM_CFG_DTYPE.itemsize, WALM_SLOT_DTYPE.itemsize, WALM_BANK_DTYPE.itemsize, WALM_RX_DTYPE.itemsize, WALM_SV_DTYPE.itemsize) == (16, 64, 1120, 160, 96)
+
+
+def walm_cfg(ch_per_rx: int) -> np.ndarray:
+    """a gpsx_walm_cfg_t as a one-element WALM_CFG_DTYPE array"""
+    cfg = np.zeros(1, WALM_CFG_DTYPE)
+    cfg["ch_per_rx"] = ch_per_rx
+    return cfg
+
+
+def walm_to_eph(rec) -> np.ndarray:
+    """one WALM_SV_DTYPE record with WALM_HELD and WALM_WEEK -> a WEPH_FLAG_VALID WEPH_DTYPE [1] record of the almanac orbit (weph_to_eph
+    and the solvers then evaluate it unchanged); GpsxError without the two flags.  Host only."""
+    rec = np.ascontiguousarray(rec, WALM_SV_DTYPE).reshape(-1)
+    if len(rec) != 1:
+        raise GpsxError("walm_to_eph takes one record")
+    out = np.zeros(1, WEPH_DTYPE)
+    rc = load_library().gpsx_walm_to_eph(rec.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise GpsxError(f"gpsx_walm_to_eph -> {rc}: the record is not HELD with WEEK")
+    return out
+
+
+def walm_gps_minus_utc(rx, week: int, tow_s: float) -> float:
+    """GPS - UTC in seconds at GPS week `week`, second tow_s, from one WALM_RX_DTYPE record with WALM_IONUTC; GpsxError without it, with
+    a day number outside 1 .. 7 or a tow_s that is not finite.  Host only."""
+    rx = np.ascontiguousarray(rx, WALM_RX_DTYPE).reshape(-1)
+    if len(rx) != 1:
+        raise GpsxError("walm_gps_minus_utc takes one record")
+    dt = C.c_double(0.0)
+    rc = load_library().gpsx_walm_gps_minus_utc(rx.ctypes.data, int(week), float(tow_s), C.byref(dt))
+    if rc != 0:
+        raise GpsxError(f"gpsx_walm_gps_minus_utc -> {rc}: no page 18, a day number outside 1..7 or a time that is not finite")
+    return dt.value
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -565,6 +616,10 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_wtow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]
     lib.gpsx_wtow_dev.argtypes = lib.gpsx_wtow.argtypes
+    lib.gpsx_walm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gpsx_walm_dev.argtypes = lib.gpsx_walm.argtypes
+    lib.gpsx_walm_to_eph.argtypes = [C.c_void_p, C.c_void_p]
+    lib.gpsx_walm_gps_minus_utc.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1181,6 +1236,23 @@ class Engine:
         self._chk(self.lib.gpsx_wtow_dev(self.h, cfg.ctypes.data, n_rx, len(prns), prns.ctypes.data, C.c_void_p(d_pred_rx), C.c_void_p(d_pred),
                                          C.c_void_p(d_sync_state), C.c_void_p(d_obs_state), C.c_void_p(d_obs) if d_obs else None, C.c_void_p(d_tow),
                                          C.c_void_p(d_tow_rx)), "gpsx_wtow_dev")
+
+    def walm(self, cfg: np.ndarray, d_words: int, n_blocks: int, n_rx: int, d_slot_state: int, d_bank: int, want_alm: bool = True):
+        """EXTENSION: almanac, ionosphere and UTC (include/gpsx.h gpsx_walm) from the WNAV_WORD_DTYPE [n_blocks // 600 + 2, n_rx *
+        ch_per_rx] words at device address d_words that gpsx_wnav_words_dev wrote for n_blocks blocks, on the n_rx * ch_per_rx
+        WALM_SLOT_DTYPE states at d_slot_state and the n_rx WALM_BANK_DTYPE banks at d_bank (all zero: fresh); cfg from walm_cfg.
+        -> (WALM_RX_DTYPE [n_rx], WALM_SV_DTYPE [n_rx, 32]), or the first alone without want_alm"""
+        assert cfg.dtype == WALM_CFG_DTYPE and cfg.size == 1
+        rx, alm = np.zeros(n_rx, WALM_RX_DTYPE), np.zeros((n_rx, 32), WALM_SV_DTYPE)
+        self._chk(self.lib.gpsx_walm(self.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, n_rx, C.c_void_p(d_slot_state), C.c_void_p(d_bank),
+                                     rx.ctypes.data, alm.ctypes.data if want_alm else None), "gpsx_walm")
+        return (rx, alm) if want_alm else rx
+
+    def walm_dev(self, cfg: np.ndarray, d_words: int, n_blocks: int, n_rx: int, d_slot_state: int, d_bank: int, d_rx: int, d_alm: int | None) -> None:
+        """the same with the record arrays left in device memory at d_rx and d_alm (None: not wanted): enqueues and returns"""
+        assert cfg.dtype == WALM_CFG_DTYPE and cfg.size == 1
+        self._chk(self.lib.gpsx_walm_dev(self.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, n_rx, C.c_void_p(d_slot_state), C.c_void_p(d_bank),
+                                         C.c_void_p(d_rx), C.c_void_p(d_alm) if d_alm else None), "gpsx_walm_dev")
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1,6 +1,6 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, each with its _dev twin, and the three
-// host helpers behind them (gpsx_weph_to_eph is gpsx_ephemeris.cpp's, beside the decoder it restates).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, gpsx_walm, each with its _dev twin, and the three
+// host helpers behind them (gpsx_weph_to_eph, gpsx_walm_to_eph and gpsx_walm_gps_minus_utc are gpsx_ephemeris.cpp's, beside the decoder they restate).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
 // waits for its kernel and reports a bad channel itself (flag 0).  Otherwise (_dev) they are device memory, the call returns after
@@ -343,6 +343,58 @@ int weph(gpsx_ctx *ctx, const gpsx_weph_cfg_t *cfg, const gpsx_wnav_word_t *d_wo
       ctx, host, "k_weph", "a channel's ephemeris state is out of range (its state is untouched, its record is zero)",
       [&](uint32_t *flag) { launch_weph(ctx->stream, d_words, n_blocks, d_state, n_ch, d_eph, flag); },
       [&]() -> int { HIPCHK(ctx, hipMemcpyAsync(eph, d_eph, eph_bytes, hipMemcpyDeviceToHost, ctx->stream)); return GPSX_OK; });
+}
+
+// ---- almanac, ionosphere and UTC from the same words (host: rx and alm are host memory, staged through the arena; the words, the slot
+//      states and the banks are device memory in both variants) --------------------------------------------------------------------------
+int walm(gpsx_ctx *ctx, const gpsx_walm_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx, gpsx_walm_slot_t *d_slot_state,
+         gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *rx, gpsx_walm_sv_t *alm, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !d_words || !d_slot_state || !d_bank || !rx)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->ch_per_rx < 1 || cfg->ch_per_rx > 64)
+    return fail(ctx, GPSX_EINVAL, "ch_per_rx must be 1..64");
+  if (cfg->reserved[0] != 0 || cfg->reserved[1] != 0 || cfg->reserved[2] != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (int rc = check_n_blocks(ctx, n_blocks)) return rc;
+  if (n_rx < 1 || n_rx > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_rx must be 1..1048576");
+  if (((reinterpret_cast<uintptr_t>(d_words) | reinterpret_cast<uintptr_t>(d_slot_state) | reinterpret_cast<uintptr_t>(d_bank)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_words, d_slot_state and d_bank must be 16-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(alm)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_rx and d_alm must be 16-byte aligned");
+  size_t words_bytes = 0, slot_bytes = 0, bank_bytes = 0, rx_bytes = 0, alm_bytes = 0;
+  if (records_overflow((size_t)n_rx * (size_t)(n_blocks / 600 + 2), cfg->ch_per_rx, sizeof(gpsx_wnav_word_t), &words_bytes) ||
+      records_overflow((size_t)n_rx, cfg->ch_per_rx, sizeof(gpsx_walm_slot_t), &slot_bytes) ||
+      records_overflow((size_t)n_rx, 1, sizeof(gpsx_walm_bank_t), &bank_bytes) || records_overflow((size_t)n_rx, 1, sizeof(gpsx_walm_rx_t), &rx_bytes) ||
+      records_overflow((size_t)n_rx, 32, sizeof(gpsx_walm_sv_t), &alm_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_rx x ch_per_rx records overflow a size");
+  // (host and device addresses share one space here: one list of pairs serves both variants)
+  const struct { const void *p; size_t n; } span[5] = {{d_words, words_bytes}, {d_slot_state, slot_bytes}, {d_bank, bank_bytes}, {rx, rx_bytes}, {alm, alm_bytes}};
+  for (int a = 0; a < 5; a++)
+    for (int b = a + 1; b < 5; b++) {
+      const uintptr_t pa = reinterpret_cast<uintptr_t>(span[a].p), pb = reinterpret_cast<uintptr_t>(span[b].p);
+      if (pa && pb && pa < pb + span[b].n && pb < pa + span[a].n)
+        return fail(ctx, GPSX_EINVAL, "two arrays overlap");
+    }
+  gpsx_walm_rx_t *d_rx = rx;
+  gpsx_walm_sv_t *d_alm = alm;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(rx_bytes) + (alm ? arena_size(alm_bytes) : 0))) return rc;
+    d_rx = arena_take<gpsx_walm_rx_t>(ctx, (size_t)n_rx);
+    if (alm)
+      d_alm = arena_take<gpsx_walm_sv_t>(ctx, (size_t)n_rx * 32u);
+  }
+  return launch_and_report(
+      ctx, host, "k_walm", "a slot's almanac state or a receiver's almanac bank is out of range (it is untouched, a bad bank's records are zero)",
+      [&](uint32_t *flag) { launch_walm(ctx->stream, *cfg, d_words, n_blocks, n_rx, d_slot_state, d_bank, d_rx, d_alm, flag); },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(rx, d_rx, rx_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (alm)
+          HIPCHK(ctx, hipMemcpyAsync(alm, d_alm, alm_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
 }
 
 // ---- the lock monitor on the sync loop's records (d_rec and all states are device memory in both variants) ----------------------------
@@ -957,6 +1009,18 @@ int gpsx_wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, co
               gpsx_wtow_rx_t *tow_rx)
 {
   return wtow(ctx, cfg, n_rx, n_prn, prns, d_pred_rx, d_pred, d_sync_state, d_obs_state, d_obs, tow, tow_rx, true);
+}
+
+int gpsx_walm_dev(gpsx_ctx *ctx, const gpsx_walm_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx,
+                  gpsx_walm_slot_t *d_slot_state, gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *d_rx, gpsx_walm_sv_t *d_alm)
+{
+  return walm(ctx, cfg, d_words, n_blocks, n_rx, d_slot_state, d_bank, d_rx, d_alm, false);
+}
+
+int gpsx_walm(gpsx_ctx *ctx, const gpsx_walm_cfg_t *cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx,
+              gpsx_walm_slot_t *d_slot_state, gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *rx, gpsx_walm_sv_t *alm)
+{
+  return walm(ctx, cfg, d_words, n_blocks, n_rx, d_slot_state, d_bank, rx, alm, true);
 }
 
 int gpsx_wpred_dev(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wkf_state_t *d_kf_state,

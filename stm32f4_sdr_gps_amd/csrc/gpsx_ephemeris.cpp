@@ -196,3 +196,36 @@ extern "C" int gpsx_weph_to_eph(const gpsx_weph_t *in, int prn, eph_t *out)
   e.f0 = in->f0; e.f1 = in->f1; e.f2 = in->f2; e.tgd[0] = in->tgd;
   return GPSX_OK;
 }
+
+// An almanac record of gpsx_walm with HELD and WEEK as a VALID record of gpsx_weph (include/gpsx.h): the Kepler terms, the clock's two
+// terms, health and week; toe = toc = the decoder's gps_time(week, toas); every other field zero.
+extern "C" int gpsx_walm_to_eph(const gpsx_walm_sv_t *in, gpsx_weph_t *out)
+{
+  const uint32_t need = GPSX_WALM_HELD | GPSX_WALM_WEEK;
+  if (!in || !out || (in->flags & need) != need)
+    return GPSX_EINVAL;
+  std::memset(out, 0, sizeof *out);
+  out->flags = GPSX_WEPH_VALID;
+  out->svh = in->svh;
+  out->week = in->week;
+  out->A = in->A; out->e = in->e; out->i0 = in->i0; out->OMG0 = in->OMG0; out->omg = in->omg; out->M0 = in->M0; out->OMGd = in->OMGd;
+  out->toes = in->toas;
+  out->f0 = in->f0; out->f1 = in->f1;
+  const gtime_t t = gps_time(in->week, in->toas);
+  out->toe_time = (int64_t)t.time; out->toe_sec = t.sec;
+  out->toc_time = (int64_t)t.time; out->toc_sec = t.sec;
+  return GPSX_OK;
+}
+
+// GPS - UTC from page 18 of a receiver record of gpsx_walm, in include/gpsx.h's order of double operations (-ffp-contract=off).
+extern "C" int gpsx_walm_gps_minus_utc(const gpsx_walm_rx_t *rx, int week, double tow_s, double *dt_s)
+{
+  if (!rx || !dt_s || !(rx->flags & GPSX_WALM_IONUTC) || rx->dn < 1 || rx->dn > 7 || !(__builtin_fabs(tow_s) <= 1.7976931348623157e308))
+    return GPSX_EINVAL;
+  const double now = (double)week * 604800.0 + tow_s;
+  const double then = (double)rx->wn_lsf * 604800.0 + (double)rx->dn * 86400.0;
+  const int ls = now >= then ? rx->dt_lsf : rx->dt_ls;
+  const double since = (tow_s - (double)rx->tot_s) + 604800.0 * ((double)week - (double)rx->wnt);
+  *dt_s = ((double)ls + rx->A0) + rx->A1 * since;
+  return GPSX_OK;
+}

@@ -237,6 +237,12 @@ void launch_wpred(hipStream_t s, const gpsx_wpred_cfg_t &cfg, int n_rx, int n_pr
 void launch_wtow(hipStream_t s, const gpsx_wtow_cfg_t &cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
                  const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_st, gpsx_wobs_state_t *d_obs_st, gpsx_wobs_t *d_obs, gpsx_wtow_t *d_tow,
                  gpsx_wtow_rx_t *d_tow_rx);
+// extension: gpsx_walm (k_walm.hip: k_walm) -- almanac, ionosphere and UTC behind gpsx_wnav_words, beside launch_weph on the same word
+// records d_words [n_blocks / 600 + 2][n_rx * ch_per_rx]: a resident 64-byte state per slot in d_slot_st [n_rx * ch_per_rx], a
+// resident 1120-byte bank per receiver in d_bank [n_rx]; d_rx [n_rx] 160-byte and d_alm (may be null) [n_rx][32] 96-byte records,
+// every byte of them written.  A wave per receiver.  A slot state or a bank that is out of range raises *d_bad_state.  No checks.
+void launch_walm(hipStream_t s, const gpsx_walm_cfg_t &cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx, gpsx_walm_slot_t *d_slot_st,
+                 gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *d_rx, gpsx_walm_sv_t *d_alm, uint32_t *d_bad_state);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

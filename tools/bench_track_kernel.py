@@ -124,7 +124,16 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       subtracted), with and without d_obs, and the steady state in which every slot
                                                       agrees, beside (1) a device-to-device copy of the bytes it reads and (2)
                                                       gpsx_wpred_dev predicting only; the lines also go to
-                                                      profiles/r29_weighted_tow_bench.jsonl"""
+                                                      profiles/r29_weighted_tow_bench.jsonl
+  bench_track_kernel.py --weighted-alm [N_RXxCH_PER_RX ...]
+                                                      gpsx_walm_dev (EXTENSION: almanac, ionosphere and UTC; k_walm) on gpsx_weph's and
+                                                      gpsx_wbank's shapes (53248 x 4; 256, 4096 and 16384 receivers x 8 and 12 slots),
+                                                      4000-block launches in which every slot receives words 5 .. 10 of a subframe: of a
+                                                      subframe 2 (no page), of an almanac page in slot 0 (a page per receiver) and in
+                                                      every slot (a page per slot), with and without d_alm, beside (1) gpsx_weph_dev on
+                                                      the same words and (2) a device-to-device copy of the bytes touched (a copy puts
+                                                      the states back before every timed launch; it is timed alone and subtracted); the
+                                                      lines also go to profiles/r30_weighted_alm_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -1444,8 +1453,124 @@ def weighted_tow(shapes, out=TOW_OUT):
         eng.close()
 
 
+ALM_OUT = os.path.join(ROOT, "profiles", "r30_weighted_alm_bench.jsonl")
+ALM_SHAPES = [(53248, 4), (256, 8), (256, 12), (4096, 8), (4096, 12), (16384, 8), (16384, 12)]
+
+
+def weighted_alm(shapes, out=ALM_OUT, n_blocks=4000):
+    """k_walm at (receivers, slots per receiver): every slot stands behind word 4 of a subframe and the launch's word records bring its
+    words 5 .. 10 -- six records that count, the subframe completes.  Three loads: `none` (every slot assembles a subframe 2: nothing is
+    offered to the bank), `per_rx` (slot 0 of every receiver completes an almanac page), `per_slot` (every slot completes the page of an
+    SV of its own).  After the first launch the bank holds these very words, so a timed launch commits (SEEN) without writing an entry
+    back: the steady state of a receiver that hears the same almanac from every satellite.  A device-to-device copy puts the slot states
+    back before every timed launch; it is timed alone and subtracted, for k_weph on the same words and 192-byte states likewise.  The
+    other yardstick: a device-to-device copy of half the bytes k_walm touches (read plus written); the calls take turns; the lines go to
+    stdout and to `out`"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_alm_cases as A
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0, stream=stream.value)
+    rng = np.random.default_rng(30)
+    pages = np.array([A.random_almanac(rng, sv, toa=31) for sv in range(1, 25)], np.uint32)      # [24][8]
+    other = np.array(rng.integers(0, 1 << 24, 8), np.uint32)
+    word_slots, seen0 = capi.wnav_word_slots(n_blocks), 60000
+    ecfg = np.zeros(1, capi.WEPH_CFG_DTYPE)
+    try:
+        for n_rx, ch in shapes:
+            n_ch = n_rx * ch
+            rx_of, slot_of = np.arange(n_ch) // ch, np.arange(n_ch) % ch
+            first_end = 37 + (53 * np.arange(n_ch)) % 900                           # word 5 ends at this block of the launch
+            cfg = capi.walm_cfg(ch)
+            slot_bytes, est_bytes, bank_bytes = n_ch * 64, n_ch * 192, n_rx * 1120
+            rx_bytes, alm_bytes, words_bytes = n_rx * 160, n_rx * 32 * 96, word_slots * n_ch * 16
+            d_words, d_slots, d_slots0, d_est, d_est0, d_bank = (eng.malloc(b) for b in (words_bytes, slot_bytes, slot_bytes, est_bytes, est_bytes, bank_bytes))
+            d_rx, d_alm, d_eph = eng.malloc(rx_bytes), eng.malloc(alm_bytes), eng.malloc(n_ch * 256)
+            for mode in ("none", "per_rx", "per_slot"):
+                paged = {"none": np.zeros(n_ch, bool), "per_rx": slot_of == 0, "per_slot": np.ones(n_ch, bool)}[mode]
+                sv = (rx_of + slot_of) % 24
+                w8 = np.where(paged[:, None], pages[sv], other[None, :])             # [n_ch][8]: words 3 .. 10 of every slot's subframe
+                slots = np.zeros(n_ch, capi.WALM_SLOT_DTYPE)
+                slots["blocks_seen"], slots["last_word_end_p1"] = seen0, seen0 + first_end + 1 - 600
+                slots["cur"][:, :2], slots["cur_mask"], slots["cur_next"], slots["cur_id"] = w8[:, :2], 0xF, 5, np.where(paged, 5, 2)
+                est = np.zeros(n_ch, capi.WEPH_STATE_DTYPE)
+                for k in ("blocks_seen", "last_word_end_p1", "cur", "cur_mask", "cur_next", "cur_id"):
+                    est[k] = slots[k]
+                est["cur_tow"] = 1000
+                words = np.zeros((word_slots, n_ch), capi.WNAV_WORD_DTYPE)
+                words["end_block"] = -1
+                for k in range(6):
+                    words["end_block"][k], words["word"][k], words["index"][k] = first_end + 600 * k, w8[:, 2 + k] << 6, 5 + k
+                    words["flags"][k], words["subframe_id"][k] = capi.WNAV_FLAG_WORD | capi.WNAV_FLAG_OK, np.where(paged, 5, 2)
+                for d, a in ((d_words, words), (d_slots0, slots), (d_slots, slots), (d_est0, est), (d_est, est), (d_bank, np.zeros(n_rx, capi.WALM_BANK_DTYPE))):
+                    eng.h2d(d, a)
+                touched = words_bytes + 2 * slot_bytes + bank_bytes + rx_bytes + alm_bytes
+                d_src, d_dst = eng.malloc(touched // 2), eng.malloc(touched // 2)
+
+                def restore():
+                    return hip.hipMemcpyAsync(d_slots, d_slots0, slot_bytes, 3, stream)
+
+                def restore_eph():
+                    return hip.hipMemcpyAsync(d_est, d_est0, est_bytes, 3, stream)
+
+                def walm(with_alm):
+                    return eng.lib.gpsx_walm_dev(eng.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, n_rx, C.c_void_p(d_slots), C.c_void_p(d_bank),
+                                                 C.c_void_p(d_rx), C.c_void_p(d_alm) if with_alm else None)
+
+                def weph():
+                    return eng.lib.gpsx_weph_dev(eng.h, ecfg.ctypes.data, C.c_void_p(d_words), n_blocks, C.c_void_p(d_est), n_ch, C.c_void_p(d_eph))
+                eng._chk(walm(True), "gpsx_walm_dev")                                # the first launch fills the bank
+                eng.synchronize()
+                first = np.zeros(n_rx, capi.WALM_RX_DTYPE)
+                eng.d2h(first, d_rx)
+                calls = {"d2d_copy_of_the_slot_states": (1, restore),
+                         "d2d_copy_of_the_eph_states": (1, restore_eph),
+                         "d2d_copy_of_half_the_bytes_touched": (1, lambda: hip.hipMemcpyAsync(d_dst, d_src, touched // 2, 3, stream)),
+                         "slot_copy_then_walm": (1, lambda: restore() or walm(True)),
+                         "slot_copy_then_walm_no_alm": (1, lambda: restore() or walm(False)),
+                         "state_copy_then_weph": (1, lambda: restore_eph() or weph())}
+                extra = {"channels": n_ch, "n_rx": n_rx, "ch_per_rx": ch, "pages": mode, "n_blocks": n_blocks, "bytes_touched": touched}
+                med = _timed_rows(eng, calls, extra, per_channel_ms=False)
+                steady, bank = np.zeros(n_rx, capi.WALM_RX_DTYPE), np.zeros(n_rx, capi.WALM_BANK_DTYPE)
+                eng.d2h(steady, d_rx)
+                eng.d2h(bank, d_bank)
+                print(json.dumps({"walm_check": "records of the first launch and after the timed ones", "n_rx": n_rx, "ch_per_rx": ch, "pages": mode,
+                                  "stored_per_rx_first": [int(first["n_stored"].min()), int(first["n_stored"].max())], "new_first": int((first["new_mask"] != 0).sum()),
+                                  "stored_per_rx_steady": [int(steady["n_stored"].min()), int(steady["n_stored"].max())], "new_steady": int((steady["new_mask"] != 0).sum()),
+                                  "held_per_rx": [int(min(bin(int(m)).count("1") for m in bank["have_mask"])), int(max(bin(int(m)).count("1") for m in bank["have_mask"]))],
+                                  "sync_code": int(eng.lib.gpsx_synchronize(eng.h))}), flush=True)
+                own = med["slot_copy_then_walm"] - med["d2d_copy_of_the_slot_states"]
+                own_no = med["slot_copy_then_walm_no_alm"] - med["d2d_copy_of_the_slot_states"]
+                own_e = med["state_copy_then_weph"] - med["d2d_copy_of_the_eph_states"]
+                print(json.dumps({"ratio": "k_walm (the timed pair less the slot copy) over the two yardsticks", "n_rx": n_rx, "ch_per_rx": ch, "pages": mode,
+                                  "walm_us": round(own, 3), "walm_no_alm_us": round(own_no, 3), "weph_us": round(own_e, 3),
+                                  "over_weph": round(own / own_e, 3), "no_alm_over_weph": round(own_no / own_e, 3),
+                                  "over_d2d_copy_of_the_bytes_touched": round(own / med["d2d_copy_of_half_the_bytes_touched"], 3),
+                                  "touched_GBps": round(touched / own / 1e3, 1), "ns_per_receiver": round(own / n_rx * 1e3, 2)}), flush=True)
+                eng.free(d_src)
+                eng.free(d_dst)
+            for p in (d_words, d_slots, d_slots0, d_est, d_est0, d_bank, d_rx, d_alm, d_eph):
+                eng.free(p)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-alm" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-alm"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_alm([tuple(int(v) for v in a.split("x")) for a in args] or ALM_SHAPES)
     if "--weighted-tow" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-tow"]
         if "--window-s" in args:
