@@ -2078,6 +2078,99 @@ int gpsx_walm_to_eph(const gpsx_walm_sv_t *in, gpsx_weph_t *out);
  * GPSX_EINVAL for NULL, a record without IONUTC, dn outside 1 .. 7 or a tow_s that is not finite (*dt_s is then untouched). */
 int gpsx_walm_gps_minus_utc(const gpsx_walm_rx_t *rx, int week, double tow_s, double *dt_s);
 
+/* ---- EXTENSION, not in the reference: the weighted grid in a WINDOW around each predicted satellite ---------------------------------
+ * gpsx_wpred hands a satellite straight to a slot only when its prediction is CERTAIN (3 samples, 12.5 Hz); everything else used to go
+ * through a full grid of n_prn x n_dopp x 16 368 hypotheses per receiver, although the chain often knows the answer to a few dozen
+ * samples and a few hertz: a filter just after INIT, an outage of more than a few seconds, a bank entry that came from an almanac
+ * (gpsx_walm_to_eph: the orbit is good to about a kilometre, some 70 samples).  gpsx_acq_window_weighted(_dev) takes gpsx_wpred's records
+ * where they lie and searches, per (receiver, PRN index), the 2 W + 1 code phases and the at most 2 D + 1 Doppler bins around the
+ * prediction only.  It answers in the grids' record format, so that gpsx_wacq decides and hands over unchanged.  No existing struct,
+ * kernel or definition changes (GPSX_VERSION stays 110).
+ *
+ * g is the descriptor a gpsx_acq_grid_weighted_hyb call would be given: n_search = n_rx (search r is receiver r), search_stride_blocks
+ * the multi loop's rx_stride_blocks, the Doppler lattice dopp_min_hz + d x dopp_step_hz for d in [0, n_dopp), weights either mode.
+ * g->prns is a HOST pointer to THE SAME LIST gpsx_wpred was called with, index for index: d_pred[r][p] is read as the prediction for
+ * PRN g->prns[p].  The device cannot check this; it is the caller's duty.
+ *
+ * Definition, per (receiver r, PRN index p), rec = d_pred[r][p]; W = half_width, D = half_bins:
+ *   0 selection  SKIPPED unless (rec.flags & need_flags) == need_flags and (rec.flags & skip_flags) == 0.  BAD if selected but
+ *                code_phase is not finite or lies outside [0, 16368], or f_hz is not finite.  In both cases every record of the row
+ *                d_peaks[r][p][*] is zero and the report has zeros beside its flag.
+ *   1 centre     c = (int)rint(code_phase) in double, ties to even; c == 16368 becomes 0.  The window is the 2 W + 1 phases
+ *                (c + j) mod 16368, j = -W .. W.
+ *   2 bins       x = (f_hz - (double)dopp_min_hz) / (double)dopp_step_hz: one subtraction, one division, uncontracted.  |x| > 2^30:
+ *                OFF_LATTICE.  Otherwise dc = (int)rint(x), d0 = max(dc - D, 0), d1 = min(dc + D, n_dopp - 1); d0 > d1: OFF_LATTICE
+ *                (zero row, the report has zeros beside that flag).  Otherwise SEARCHED, with CLIPPED if dc - D < 0 or dc + D >
+ *                n_dopp - 1; the report has first_bin = d0, n_bins = d1 - d0 + 1, centre = c.
+ *   3 energy     for each bin d in d0 .. d1, E_d(tau) is exactly gpsx_acq_grid_weighted_hyb's E(tau) for search r, PRN prns[p], bin
+ *                d, n_coh, n_seg: segment j's blocks are r x stride + j x n_coh + b, the NCO runs from 0 at each segment's first
+ *                block and is chained through its blocks, the sixteen unmixed samples weigh 0, the roots are exact.  It is
+ *                evaluated at the window's phases only.
+ *   4 record     d_peaks[r][p][d]: max_val = max E_d over the window; phase = the numerically smallest tau of the window that
+ *                reaches it (the grids' rule and the grids' key: a window across the seam answers with its low taus), 0 when max_val
+ *                is 0.  sum is the noise floor in the grids' units: F = the window's phases whose circular distance from `phase`
+ *                exceeds guard (|F| >= 2 because guard < W), S_far = the sum of E_d over F, sum = the low 32 bits of
+ *                floor(S_far x 16368 / |F|) in uint64 (S_far < 2^40: the product stays below 2^54); avr = sum / 16368.  With this
+ *                sum gpsx_wacq's step 2 reads unchanged -- peak over the mean of the window's far phases >= det_num / det_den; the
+ *                floor makes sum / 16368 SMALLER than the true mean by less than one part in 16 368 x mean, so it errs, if at all,
+ *                towards a detection.  The grids' mod 2^32 condition carries over word for word: the mean must stay below 2^18.
+ *   5 coverage   every other record of the row is all zero.  Every byte of d_peaks[n_rx][n_prn][n_dopp] is written by the call, and
+ *                so is every byte of d_rep[n_rx][n_prn] unless it is NULL.
+ * The call needs (n_search - 1) x search_stride_blocks + n_coh x n_seg <= n_blocks.
+ *
+ * The identity that ties it to the grids: for every searched (r, p, d), if the phase of gpsx_acq_grid_weighted_hyb's record for the
+ * same (search, PRN, bin) lies in the window, then max_val and phase are that record's.
+ *
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written, checked in this order: g, cfg, g->prns, pred, blocks or
+ * peaks NULL; n_coh outside 1 .. 20; n_seg outside 1 .. 128; half_width outside 1 .. 2047; half_bins outside 0 .. 32; guard outside
+ * 0 .. half_width - 1; a bit outside the seven GPSX_WPRED_* in need_flags or skip_flags; need_flags without GPSX_WPRED_PREDICTED;
+ * reserved != 0; unknown weights; dopp_step_hz < 1; n_search outside 1 .. 1 048 576; n_prn outside 1 .. 64; n_dopp outside
+ * 1 .. 1 048 576; search_stride_blocks < 0; a PRN outside 1 .. 210 or listed twice; the lattice's last bin outside int32; too few
+ * blocks; d_pred or d_rep not 16-byte aligned (_dev); size products that overflow.
+ *
+ * _dev only enqueues; gpsx_last_kernel says k_acq_win.  Vector ALU, exact in integers (k_acq_win: a workgroup of 256 threads per
+ * (receiver, PRN index, bin of the 2 D + 1); the grids' pre-sum into LDS per segment, v_dot2_i32_i16 against the PRN's chip pairs at
+ * the window's phases, E in LDS; no HBM scratch, no global atomics).
+ *
+ * For the caller.  On one stream: gpsx_wkf_dev; gpsx_wpred_dev (with handover = 1 the CERTAIN satellites go straight to slots and
+ * carry ASSIGNED, which the intended skip_flags leave out); this call on the blocks that BEGIN AT THE PREDICTION'S EPOCH BLOCK;
+ * gpsx_wacq_dev with the same g and lead_blocks = n_coh x n_seg; the next loop launch.  Matching the prediction's epoch (the filter's
+ * rcv_ms + lead_blocks) to the first block is the caller's duty, as in gpsx_wtow.  The intended masks are need_flags = PREDICTED |
+ * VISIBLE, skip_flags = TRACKED | ASSIGNED.  An almanac warm start fills bank entries with gpsx_walm_to_eph records on the host.
+ * Step the lattice by about 500 / n_coh Hz.  The code slides about 3 samples per 100 ms at 5 kHz of Doppler: choose W over the
+ * prediction's error plus that slide. */
+#define GPSX_ACQ_WINDOW_SEARCHED     1u
+#define GPSX_ACQ_WINDOW_SKIPPED      2u
+#define GPSX_ACQ_WINDOW_BAD          4u
+#define GPSX_ACQ_WINDOW_OFF_LATTICE  8u
+#define GPSX_ACQ_WINDOW_CLIPPED     16u
+
+typedef struct {                 /* 32 bytes */
+  int32_t  n_coh;                /*  0  1 .. 20 blocks per coherent segment */
+  int32_t  n_seg;                /*  4  1 .. 128 segments, their magnitudes summed */
+  int32_t  half_width;           /*  8  W: 1 .. 2047 samples */
+  int32_t  half_bins;            /* 12  D: 0 .. 32 bins */
+  int32_t  guard;                /* 16  0 .. W - 1: phases within guard of the peak do not count as noise */
+  uint32_t need_flags;           /* 20  GPSX_WPRED_* bits a record must have; must contain GPSX_WPRED_PREDICTED */
+  uint32_t skip_flags;           /* 24  GPSX_WPRED_* bits a record must not have */
+  int32_t  reserved;             /* 28  0 */
+} gpsx_acq_window_t;
+
+typedef struct {                 /* 16 bytes, one per (receiver, PRN index) */
+  uint32_t flags;                /*  0  GPSX_ACQ_WINDOW_*: SEARCHED (with or without CLIPPED), or SKIPPED, BAD, OFF_LATTICE alone */
+  int32_t  first_bin;            /*  4  d0 */
+  int32_t  n_bins;               /*  8  d1 - d0 + 1 */
+  int32_t  centre;               /* 12  c */
+} gpsx_acq_window_rep_t;
+
+/* d_pred [n_rx][n_prn], d_if_blocks_2bit (n_blocks 4092-byte blocks), d_peaks [n_rx][n_prn][n_dopp] and d_rep (NULL: not wanted)
+ * [n_rx][n_prn]: device memory; gpsx_acq_window_weighted takes all four in host memory (staged through the arena; it waits for its
+ * kernel). */
+int gpsx_acq_window_weighted_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const gpsx_acq_window_t *cfg, const gpsx_wpred_t *d_pred,
+                                 const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks, gpsx_acq_window_rep_t *d_rep);
+int gpsx_acq_window_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const gpsx_acq_window_t *cfg, const gpsx_wpred_t *pred,
+                             const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks, gpsx_acq_window_rep_t *rep);
+
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,
  *      with gps_tracking_dll / _pll / _fll / _pll_check :175-393 and gps_nav_data_analyse_new_code, PM/GPS/nav_data.c:46-253)

@@ -138,6 +138,8 @@ def check_no_scratch() -> dict:
     check_wtow()
     # ... and, beside the ephemeris stage, the almanac, ionosphere and UTC (check_walm below: the same terms)
     check_walm()
+    # ... and, between the prediction and the acquisition decisions, the grid in a window (check_wwin below: no scratch, its LDS as planned)
+    check_wwin()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -235,6 +237,21 @@ def check_walm() -> dict:
     """k_walm, almanac, ionosphere and UTC from subframes 4 and 5 (k_weph's assembly on k_wbank's geometry: an object of its own,
     exactly one instance, no scratch and no LDS)"""
     return check_wsolver("k_walm.o", "k_walm", True)
+
+
+# k_acq_win's LDS: the planes (2 x 16 x 1024 int8), the two int16 rows (2 x 1028 dwords), the chip pairs (512 dwords), E (4096 dwords),
+# the four waves' keys, far sums (8 bytes each) and far counts
+WWIN_LDS_BYTES = 2 * 16 * 1024 + 2 * 1028 * 4 + 512 * 4 + 4096 * 4 + 4 * (8 + 8 + 4)
+
+
+def check_wwin() -> dict:
+    """k_acq_win, the weighted grid in a window around each prediction (the coherent grids' parts on one PRN and a slice of the phases:
+    an object of its own, exactly one instance, no scratch, and the LDS it was planned with -- two workgroups per compute unit)"""
+    found = check_wsolver("k_acq_win.o", "k_acq_win", False)
+    bad = {k: v for k, v in found.items() if v["lds_bytes"] != WWIN_LDS_BYTES}
+    if bad:
+        raise RuntimeError(f"k_acq_win's LDS is not the planned {WWIN_LDS_BYTES} bytes: {bad}")
+    return found
 
 
 if __name__ == "__main__":

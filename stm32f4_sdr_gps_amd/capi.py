@@ -461,6 +461,26 @@ def walm_gps_minus_utc(rx, week: int, tow_s: float) -> float:
     return dt.value
 
 
+# gpsx_acq_window_t / gpsx_acq_window_rep_t (the weighted grid in a window around each of gpsx_wpred's predictions)
+ACQ_WINDOW_SEARCHED, ACQ_WINDOW_SKIPPED, ACQ_WINDOW_BAD, ACQ_WINDOW_OFF_LATTICE, ACQ_WINDOW_CLIPPED = 1, 2, 4, 8, 16
+ACQ_WINDOW_CFG_DTYPE = np.dtype([("n_coh", "<i4"), ("n_seg", "<i4"), ("half_width", "<i4"), ("half_bins", "<i4"), ("guard", "<i4"),
+                                 ("need_flags", "<u4"), ("skip_flags", "<u4"), ("reserved", "<i4")])
+ACQ_WINDOW_REP_DTYPE = np.dtype([("flags", "<u4"), ("first_bin", "<i4"), ("n_bins", "<i4"), ("centre", "<i4")])
+assert ACQ_WINDOW_CFG_DTYPE.itemsize == 32 and ACQ_WINDOW_REP_DTYPE.itemsize == 16
+
+
+def acq_window_cfg(n_coh: int, n_seg: int, half_width: int, half_bins: int, guard: int, need_flags: int = WPRED_PREDICTED | WPRED_VISIBLE,
+                   skip_flags: int = WPRED_TRACKED | WPRED_ASSIGNED) -> np.ndarray:
+    """a gpsx_acq_window_t as a one-element ACQ_WINDOW_CFG_DTYPE array: n_seg coherent segments of n_coh blocks, the half_width samples
+    and half_bins Doppler bins either side of each prediction that has need_flags and none of skip_flags; phases within guard of the
+    peak do not count as noise"""
+    cfg = np.zeros(1, ACQ_WINDOW_CFG_DTYPE)
+    for name, v in (("n_coh", n_coh), ("n_seg", n_seg), ("half_width", half_width), ("half_bins", half_bins), ("guard", guard),
+                    ("need_flags", need_flags), ("skip_flags", skip_flags)):
+        cfg[name] = v
+    return cfg
+
+
 def wlock_cfg(epoch_search, epoch_lock, code_min, car_min, snr_min, n_good, n_bad, rearm=0, patience=0) -> np.ndarray:
     """a gpsx_wlock_cfg_t as a one-element WLOCK_CFG_DTYPE array"""
     cfg = np.zeros(1, WLOCK_CFG_DTYPE)
@@ -620,6 +640,8 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_walm_dev.argtypes = lib.gpsx_walm.argtypes
     lib.gpsx_walm_to_eph.argtypes = [C.c_void_p, C.c_void_p]
     lib.gpsx_walm_gps_minus_utc.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
+    lib.gpsx_acq_window_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.gpsx_acq_window_weighted_dev.argtypes = lib.gpsx_acq_window_weighted.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.gps_tracking_words_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int]
     lib.gpsx_loop_state_from_channel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1253,6 +1275,35 @@ class Engine:
         assert cfg.dtype == WALM_CFG_DTYPE and cfg.size == 1
         self._chk(self.lib.gpsx_walm_dev(self.h, cfg.ctypes.data, C.c_void_p(d_words), n_blocks, n_rx, C.c_void_p(d_slot_state), C.c_void_p(d_bank),
                                          C.c_void_p(d_rx), C.c_void_p(d_alm) if d_alm else None), "gpsx_walm_dev")
+
+    def acq_window(self, cfg: np.ndarray, pred: np.ndarray, blocks_2bit: np.ndarray, prns, dopp_min_hz: int, dopp_step_hz: int, n_dopp: int,
+                   use_magnitude: bool = True, stride_blocks: int | None = None, want_rep: bool = True):
+        """EXTENSION: the weighted grid in a window around each prediction (include/gpsx.h gpsx_acq_window_weighted): pred is gpsx_wpred's
+        WPRED_DTYPE [n_rx, len(prns)] in host memory, prns THE SAME LIST that call was given; receiver r reads blocks r * stride_blocks
+        .. + n_coh * n_seg - 1 (the stride defaults to n_coh * n_seg); cfg from acq_window_cfg.
+        -> (PEAK_DTYPE [n_rx, n_prn, n_dopp], ACQ_WINDOW_REP_DTYPE [n_rx, n_prn]), or the first alone without want_rep"""
+        assert cfg.dtype == ACQ_WINDOW_CFG_DTYPE and cfg.size == 1
+        pred = np.ascontiguousarray(pred, WPRED_DTYPE)
+        prns = np.ascontiguousarray(prns, np.uint8)
+        assert pred.ndim == 2 and pred.shape[1] == len(prns)
+        blocks = np.ascontiguousarray(blocks_2bit, np.uint8).reshape(-1, BYTES_PER_MS_2BIT)
+        n_rx = pred.shape[0]
+        stride = int(cfg["n_coh"][0]) * int(cfg["n_seg"][0]) if stride_blocks is None else stride_blocks
+        g = AcqWeightedT(n_rx, stride, len(prns), prns.ctypes.data_as(C.POINTER(C.c_uint8)), dopp_min_hz, dopp_step_hz, n_dopp, 1 if use_magnitude else 0)
+        peaks, rep = np.zeros((n_rx, len(prns), n_dopp), PEAK_DTYPE), np.zeros((n_rx, len(prns)), ACQ_WINDOW_REP_DTYPE)
+        self._chk(self.lib.gpsx_acq_window_weighted(self.h, C.addressof(g), cfg.ctypes.data, pred.ctypes.data, blocks.ctypes.data, len(blocks),
+                                                    peaks.ctypes.data, rep.ctypes.data if want_rep else None), "gpsx_acq_window_weighted")
+        return (peaks, rep) if want_rep else peaks
+
+    def acq_window_dev(self, cfg: np.ndarray, d_pred: int, d_blocks: int, n_blocks: int, n_rx: int, prns, dopp_min_hz: int, dopp_step_hz: int,
+                       n_dopp: int, d_peaks: int, d_rep: int | None, use_magnitude: bool = True, stride_blocks: int | None = None) -> None:
+        """the same with the predictions, the blocks, the records and the reports (None: not wanted) in device memory: enqueues and returns"""
+        assert cfg.dtype == ACQ_WINDOW_CFG_DTYPE and cfg.size == 1
+        prns = np.ascontiguousarray(prns, np.uint8)
+        stride = int(cfg["n_coh"][0]) * int(cfg["n_seg"][0]) if stride_blocks is None else stride_blocks
+        g = AcqWeightedT(n_rx, stride, len(prns), prns.ctypes.data_as(C.POINTER(C.c_uint8)), dopp_min_hz, dopp_step_hz, n_dopp, 1 if use_magnitude else 0)
+        self._chk(self.lib.gpsx_acq_window_weighted_dev(self.h, C.addressof(g), cfg.ctypes.data, C.c_void_p(d_pred), C.c_void_p(d_blocks), n_blocks,
+                                                        C.c_void_p(d_peaks), C.c_void_p(d_rep) if d_rep else None), "gpsx_acq_window_weighted_dev")
 
     def set_loop_schedule(self, schedule: int) -> None:
         """SCHED_EVERY_MS or SCHED_MUX17 (the reference's four-channel 17 ms multiplex) for this context's track_loop launches"""

@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, gpsx_walm, each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, gpsx_walm, gpsx_acq_window_weighted (the grid in a window around gpsx_wpred's records: it stands in the chain, between the prediction and gpsx_wacq), each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph, gpsx_walm_to_eph and gpsx_walm_gps_minus_utc are gpsx_ephemeris.cpp's, beside the decoder they restate).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -993,9 +993,105 @@ int wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const u
       });
 }
 
+// ---- the weighted grid in a window around each prediction (host: pred, the blocks, peaks and rep are host memory, staged through the
+//      arena) ---------------------------------------------------------------------------------------------------------------------------
+int acq_window(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const gpsx_acq_window_t *cfg, const gpsx_wpred_t *pred, const void *if_blocks_2bit,
+               int n_blocks, gpsx_peak_t *peaks, gpsx_acq_window_rep_t *rep, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!g || !cfg || !g->prns || !pred || !if_blocks_2bit || !peaks)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  if (cfg->n_coh < 1 || cfg->n_coh > 20)
+    return fail(ctx, GPSX_EINVAL, "n_coh outside 1..20");
+  if (cfg->n_seg < 1 || cfg->n_seg > 128)
+    return fail(ctx, GPSX_EINVAL, "n_seg outside 1..128");
+  if (cfg->half_width < 1 || cfg->half_width > 2047)
+    return fail(ctx, GPSX_EINVAL, "half_width must be 1..2047");
+  if (cfg->half_bins < 0 || cfg->half_bins > 32)
+    return fail(ctx, GPSX_EINVAL, "half_bins must be 0..32");
+  if (cfg->guard < 0 || cfg->guard > cfg->half_width - 1)
+    return fail(ctx, GPSX_EINVAL, "guard must be 0..half_width - 1");
+  if (((cfg->need_flags | cfg->skip_flags) & ~0x7Fu) != 0)
+    return fail(ctx, GPSX_EINVAL, "need_flags and skip_flags must be GPSX_WPRED_* bits");
+  if ((cfg->need_flags & GPSX_WPRED_PREDICTED) == 0)
+    return fail(ctx, GPSX_EINVAL, "need_flags must contain GPSX_WPRED_PREDICTED");
+  if (cfg->reserved != 0)
+    return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (g->weights != GPSX_WEIGHTS_SIGN_ONLY && g->weights != GPSX_WEIGHTS_SIGN_MAGNITUDE)
+    return fail(ctx, GPSX_EINVAL, "unknown weights");
+  if (g->dopp_step_hz < 1)
+    return fail(ctx, GPSX_EINVAL, "dopp_step_hz must be at least 1");
+  if (g->n_search < 1 || g->n_search > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_search must be 1..1048576");
+  if (g->n_prn < 1 || g->n_prn > 64)
+    return fail(ctx, GPSX_EINVAL, "n_prn must be 1..64");
+  if (g->n_dopp < 1 || g->n_dopp > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_dopp must be 1..1048576");
+  if (g->search_stride_blocks < 0)
+    return fail(ctx, GPSX_EINVAL, "search_stride_blocks must be at least 0");
+  bool listed[GPSX_MAX_PRN + 1] = {};
+  for (int i = 0; i < g->n_prn; i++) {
+    if (g->prns[i] < 1 || g->prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+    if (listed[g->prns[i]])
+      return fail(ctx, GPSX_EINVAL, "a PRN is listed twice");
+    listed[g->prns[i]] = true;
+  }
+  const long long f_last = (long long)g->dopp_min_hz + (long long)(g->n_dopp - 1) * (long long)g->dopp_step_hz;
+  if (f_last > 2147483647ll)
+    return fail(ctx, GPSX_EINVAL, "a Doppler bin lies outside int32");
+  if (n_blocks < 1 || (long long)(g->n_search - 1) * g->search_stride_blocks + (long long)cfg->n_coh * cfg->n_seg > n_blocks)
+    return fail(ctx, GPSX_EINVAL, "not enough blocks for the searches");
+  if (!host && ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(rep)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_pred and d_rep must be 16-byte aligned");
+  size_t peak_bytes = 0, pred_bytes = 0, rep_bytes = 0, if_bytes = 0;
+  if (records_overflow((size_t)g->n_search * (size_t)g->n_prn, g->n_dopp, sizeof(gpsx_peak_t), &peak_bytes) ||
+      records_overflow((size_t)g->n_search, g->n_prn, sizeof(gpsx_wpred_t), &pred_bytes) ||
+      records_overflow((size_t)g->n_search, g->n_prn, sizeof(gpsx_acq_window_rep_t), &rep_bytes) ||
+      records_overflow((size_t)n_blocks, 1, (size_t)GPSX_BYTES_PER_MS_2BIT, &if_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_search x n_prn x n_dopp records overflow a size");
+  const size_t n_rows = (size_t)g->n_search * (size_t)g->n_prn;
+  const gpsx_wpred_t *d_pred = pred;
+  const uint8_t *d_if = static_cast<const uint8_t *>(if_blocks_2bit);
+  gpsx_peak_t *d_peaks = peaks;
+  gpsx_acq_window_rep_t *d_rep = rep;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(pred_bytes) + arena_size(if_bytes) + arena_size(peak_bytes) + (rep ? arena_size(rep_bytes) : 0))) return rc;
+    if (int rc = stage_in(ctx, pred, n_rows, &d_pred)) return rc;
+    if (int rc = stage_in(ctx, static_cast<const uint8_t *>(if_blocks_2bit), if_bytes, &d_if)) return rc;
+    d_peaks = arena_take<gpsx_peak_t>(ctx, peak_bytes / sizeof(gpsx_peak_t));
+    if (rep)
+      d_rep = arena_take<gpsx_acq_window_rep_t>(ctx, n_rows);
+  }
+  return launch_and_report(
+      ctx, host, "k_acq_win", "k_acq_win raised the bad-state flag, which it never does",
+      [&](uint32_t *) {
+        launch_acq_win(ctx->stream, *cfg, d_if, g->n_search, g->search_stride_blocks, g->n_prn, g->prns, ctx->d_chips_all, ctx->if_hz, g->dopp_min_hz,
+                       g->dopp_step_hz, g->n_dopp, g->weights == GPSX_WEIGHTS_SIGN_MAGNITUDE, d_pred, d_peaks, d_rep);
+      },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(peaks, d_peaks, peak_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (rep)
+          HIPCHK(ctx, hipMemcpyAsync(rep, d_rep, rep_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpsx_acq_window_weighted_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const gpsx_acq_window_t *cfg, const gpsx_wpred_t *d_pred,
+                                 const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks, gpsx_acq_window_rep_t *d_rep)
+{
+  return acq_window(ctx, g, cfg, d_pred, d_if_blocks_2bit, n_blocks, d_peaks, d_rep, false);
+}
+
+int gpsx_acq_window_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const gpsx_acq_window_t *cfg, const gpsx_wpred_t *pred,
+                             const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks, gpsx_acq_window_rep_t *rep)
+{
+  return acq_window(ctx, g, cfg, pred, if_blocks_2bit, n_blocks, peaks, rep, true);
+}
 
 int gpsx_wtow_dev(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
                   const gpsx_wpred_t *d_pred, gpsx_wsync_state_t *d_sync_state, gpsx_wobs_state_t *d_obs_state, gpsx_wobs_t *d_obs,

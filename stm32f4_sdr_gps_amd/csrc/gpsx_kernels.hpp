@@ -243,6 +243,14 @@ void launch_wtow(hipStream_t s, const gpsx_wtow_cfg_t &cfg, int n_rx, int n_prn,
 // every byte of them written.  A wave per receiver.  A slot state or a bank that is out of range raises *d_bad_state.  No checks.
 void launch_walm(hipStream_t s, const gpsx_walm_cfg_t &cfg, const gpsx_wnav_word_t *d_words, int n_blocks, int n_rx, gpsx_walm_slot_t *d_slot_st,
                  gpsx_walm_bank_t *d_bank, gpsx_walm_rx_t *d_rx, gpsx_walm_sv_t *d_alm, uint32_t *d_bad_state);
+// extension: gpsx_acq_window_weighted (k_acq_win.hip: k_acq_win) -- the weighted grid's energy in a window around each prediction: from
+// launch_wpred's records d_pred [n_rx][n_prn] (read only) and the receivers' blocks (receiver r from block r * stride_blocks, cfg.n_coh *
+// cfg.n_seg of them) the records d_peaks [n_rx][n_prn][n_dopp] and the reports d_rep (may be null) [n_rx][n_prn], every byte of them
+// written.  A workgroup per (receiver, PRN index, bin of the 2 * half_bins + 1), receivers in chunks where a launch would count more
+// than 2^32 - 1 threads (2^24 - 1 workgroups); prns: n_prn (<= 64) PRN numbers in HOST memory, passed by value.  No HBM scratch.  The launcher checks nothing again.
+void launch_acq_win(hipStream_t s, const gpsx_acq_window_t &cfg, const uint8_t *d_if_blocks, int n_rx, int stride_blocks, int n_prn,
+                    const uint8_t *prns, const uint8_t *d_chips_all, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp, int use_magnitude,
+                    const gpsx_wpred_t *d_pred, gpsx_peak_t *d_peaks, gpsx_acq_window_rep_t *d_rep);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

@@ -133,7 +133,14 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       every slot (a page per slot), with and without d_alm, beside (1) gpsx_weph_dev on
                                                       the same words and (2) a device-to-device copy of the bytes touched (a copy puts
                                                       the states back before every timed launch; it is timed alone and subtracted); the
-                                                      lines also go to profiles/r30_weighted_alm_bench.jsonl"""
+                                                      lines also go to profiles/r30_weighted_alm_bench.jsonl
+  bench_track_kernel.py --weighted-win [N_RXxN_COHxN_SEGxW ...]
+                                                      gpsx_acq_window_weighted_dev (EXTENSION: the weighted grid in a window around
+                                                      each prediction; k_acq_win) on 12 PRNs per receiver, D = 2, every record
+                                                      searched on all five bins (256 and 4096 receivers; 10 x 8 and 20 x 4 blocks; W =
+                                                      128 and 1024), beside gpsx_acq_grid_weighted_hyb_dev on the same receivers, PRNs,
+                                                      blocks and five bins -- the cheapest way the grids answer the same question; the
+                                                      calls take turns; the lines also go to profiles/r31_weighted_win_bench.jsonl"""
 import ctypes as C
 import json
 import os
@@ -1562,8 +1569,80 @@ def weighted_alm(shapes, out=ALM_OUT, n_blocks=4000):
         eng.close()
 
 
+WIN_OUT = os.path.join(ROOT, "profiles", "r31_weighted_win_bench.jsonl")
+WIN_SHAPES = [(n_rx, n_coh, n_seg, w) for n_rx in (256, 4096) for n_coh, n_seg in ((10, 8), (20, 4)) for w in (128, 1024)]
+WIN_PRNS, WIN_D = 12, 2
+
+
+def weighted_win(shapes, out=WIN_OUT):
+    """k_acq_win at (receivers, n_coh, n_seg, W) on WIN_PRNS PRNs per receiver, D = WIN_D: every prediction selected, its centre anywhere,
+    its Doppler on the middle of a five-bin lattice (step 500 / n_coh Hz), so that the window call and the hybrid grid call search the
+    same 2 D + 1 bins of the same receivers and PRNs on the same blocks.  Receiver r reads blocks r .. r + n_coh n_seg - 1 of one random
+    stream (stride 1: every receiver's samples differ, the stream stays a few megabytes).  The two calls take turns; the lines go to
+    stdout and to `out`.  From the counts: products per (receiver, PRN, bin, segment) -- the pre-sum's 16352 x n_coh weighted samples in
+    two streams, the window's (2 W + 1) x 1023 x 2 chip products -- beside the kernel time"""
+    from stm32f4_sdr_gps_amd import capi
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0)
+    prns = np.arange(1, WIN_PRNS + 1, dtype=np.uint8)
+    n_dopp = 2 * WIN_D + 1
+    try:
+        for n_rx, n_coh, n_seg, w in shapes:
+            span, step = n_coh * n_seg, max(1, 500 // n_coh)
+            rng = np.random.default_rng(31)
+            blocks = rng.integers(0, 256, (n_rx - 1 + span, 4092), dtype=np.uint8)
+            pred = np.zeros((n_rx, WIN_PRNS), capi.WPRED_DTYPE)
+            pred["flags"], pred["slot"] = capi.WPRED_HAVE_EPH | capi.WPRED_PREDICTED | capi.WPRED_VISIBLE, -1
+            pred["code_phase"], pred["f_hz"] = rng.uniform(0.0, 16368.0, pred.shape), rng.uniform(-0.4 * step, 0.4 * step, pred.shape)
+            cfg = capi.acq_window_cfg(n_coh, n_seg, w, WIN_D, min(32, w - 1))
+            g = capi.AcqWeightedT(n_rx, 1, WIN_PRNS, prns.ctypes.data_as(C.POINTER(C.c_uint8)), -WIN_D * step, step, n_dopp, 1)
+            n_peaks = n_rx * WIN_PRNS * n_dopp
+            d_if, d_pred, d_pk, d_pk2, d_rep = (eng.malloc(b) for b in (blocks.nbytes + 2, pred.nbytes, n_peaks * 16, n_peaks * 16, n_rx * WIN_PRNS * 16))
+            eng.h2d(d_if, blocks)
+            eng.h2d(d_pred, pred)
+
+            def win():
+                return eng.lib.gpsx_acq_window_weighted_dev(eng.h, C.addressof(g), cfg.ctypes.data, C.c_void_p(d_pred), C.c_void_p(d_if), len(blocks),
+                                                            C.c_void_p(d_pk), C.c_void_p(d_rep))
+
+            def grid():
+                return eng.lib.gpsx_acq_grid_weighted_hyb_dev(eng.h, C.addressof(g), n_coh, n_seg, C.c_void_p(d_if), len(blocks), C.c_void_p(d_pk2))
+            eng._chk(grid(), "gpsx_acq_grid_weighted_hyb_dev")
+            grid_kernel = eng.lib.gpsx_last_kernel(eng.h).decode()
+            eng._chk(win(), "gpsx_acq_window_weighted_dev")
+            eng.synchronize()
+            rep, pk, pk2 = np.zeros((n_rx, WIN_PRNS), capi.ACQ_WINDOW_REP_DTYPE), np.zeros(n_peaks, capi.PEAK_DTYPE), np.zeros(n_peaks, capi.PEAK_DTYPE)
+            eng.d2h(rep, d_rep)
+            eng.d2h(pk, d_pk)
+            eng.d2h(pk2, d_pk2)
+            extra = {"channels": n_rx * WIN_PRNS, "n_rx": n_rx, "n_prn": WIN_PRNS, "n_coh": n_coh, "n_seg": n_seg, "half_width": w, "half_bins": WIN_D,
+                     "n_dopp": n_dopp, "dopp_step_hz": step, "grid_kernel": grid_kernel}
+            med = _timed_rows(eng, {"window": (1, win), "grid_restricted_to_the_bins": (1, grid)}, extra, per_channel_ms=False)
+            units = n_rx * WIN_PRNS * n_dopp * n_seg
+            print(json.dumps({"ratio": "k_acq_win over the hybrid grid restricted to the same bins", **extra, "window_us": round(med["window"], 1),
+                              "grid_us": round(med["grid_restricted_to_the_bins"], 1), "window_over_grid": round(med["window"] / med["grid_restricted_to_the_bins"], 4),
+                              "searched": int((rep["flags"] == capi.ACQ_WINDOW_SEARCHED).sum()), "bins_searched": int(rep["n_bins"].sum()),
+                              "same_record_where_the_grids_phase_is_in_the_window": int(((pk["max_val"] == pk2["max_val"]) & (pk["phase"] == pk2["phase"])).sum()),
+                              "presum_samples_per_us": round(units * 2 * 16352 * n_coh / med["window"], 1),
+                              "chip_products_per_us": round(units * (2 * w + 1) * 1023 * 2 / med["window"], 1),
+                              "ns_per_unit_segment": round(med["window"] / units * 1e3, 2), "sync_code": int(eng.lib.gpsx_synchronize(eng.h))}), flush=True)
+            for p_ in (d_if, d_pred, d_pk, d_pk2, d_rep):
+                eng.free(p_)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-win" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-win"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_win([tuple(int(v) for v in a.split("x")) for a in args] or WIN_SHAPES)
     if "--weighted-alm" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-alm"]
         if "--window-s" in args:
