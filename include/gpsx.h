@@ -2137,6 +2137,7 @@ int gpsx_walm_gps_minus_utc(const gpsx_walm_rx_t *rx, int week, double tow_s, do
  * gpsx_wacq_dev with the same g and lead_blocks = n_coh x n_seg; the next loop launch.  Matching the prediction's epoch (the filter's
  * rcv_ms + lead_blocks) to the first block is the caller's duty, as in gpsx_wtow.  The intended masks are need_flags = PREDICTED |
  * VISIBLE, skip_flags = TRACKED | ASSIGNED.  An almanac warm start fills bank entries with gpsx_walm_to_eph records on the host.
+ * The same bank feeds gpsx_wsnap (below).
  * Step the lattice by about 500 / n_coh Hz.  The code slides about 3 samples per 100 ms at 5 kHz of Doppler: choose W over the
  * prediction's error plus that slide. */
 #define GPSX_ACQ_WINDOW_SEARCHED     1u
@@ -2170,6 +2171,147 @@ int gpsx_acq_window_weighted_dev(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, co
                                  const void *d_if_blocks_2bit, int n_blocks, gpsx_peak_t *d_peaks, gpsx_acq_window_rep_t *d_rep);
 int gpsx_acq_window_weighted(gpsx_ctx *ctx, const gpsx_acq_weighted_t *g, const gpsx_acq_window_t *cfg, const gpsx_wpred_t *pred,
                              const uint8_t *if_blocks_2bit, int n_blocks, gpsx_peak_t *peaks, gpsx_acq_window_rep_t *rep);
+
+/* ---- EXTENSION, not in the reference: snapshot fixes -- a weighted grid's records, a bank and a coarse prior to a position -----------
+ * A grid record becomes a position today only through a slot, bit sync, a HOW and 18 .. 30 s of subframes.  A capture of a few
+ * milliseconds carries no navigation data; with the orbits from elsewhere (a gpsx_wbank bank, gpsx_walm_to_eph, another receiver of
+ * the launch) and a prior that knows where and when to within a cell and a minute it can still be positioned: coarse-time navigation,
+ * five unknowns (position, a common bias, the error of the time tag).  gpsx_wsnap(_dev) is a STATELESS stage behind any weighted grid
+ * call (gpsx_acq_grid_weighted{,_ms,_coh,_hyb}, gpsx_acq_window_weighted): per receiver it reads the grid's records where they lie,
+ * an ephemeris bank and a prior, and writes a position, the bias and a corrected time of week.  Nothing crosses to the host in
+ * between.  No existing struct, kernel or definition changes (GPSX_VERSION stays 110).  The same bank that feeds gpsx_wpred and the
+ * windowed grid feeds this stage.
+ *
+ * g is the description the grid call was given (gpsx_wacq's reading of it: search s IS receiver s, prns a HOST pointer, PRN index p
+ * its position in the list).  THIS TEXT is the definition.  Decisions are integers where they can be; everything else is IEEE
+ * double, uncontracted, with gpsx_wkf's constants (c, ms = 299792.458 m, we, Re) and the sum orders given here.
+ *   0 prior        d_prior[r] = {flags, week, rr[3], tow_s, reserved}: where the receiver roughly is (ECEF, m) and the GPS week and
+ *                  time of week of the search's first sample.  Without GPSX_WSNAP_PRIOR_HAVE, with a flag bit beyond it, with a
+ *                  reserved word != 0, with an rr or tow_s that is not finite, a tow_s outside 0 <= tow_s < 604800 or a week outside
+ *                  0 .. 32767: NO_PRIOR -- d_snap[r] and every d_sv[r][p] are zero but for that flag, and the call still returns 0.
+ *   1 detection    gpsx_wacq's steps 1 and 2, word for word: per PRN index p the best record is the LOWEST bin of the row's
+ *                  greatest max_val, M that max_val, S that record's sum, tau_p that record's phase, f_p = dopp_min_hz + bin x
+ *                  dopp_step_hz; DETECTED iff M >= max(min_peak, 1) and (uint64)M x 16368 x det_den >= (uint64)det_num x S.
+ *   2 satellites   the bank record of (r, p) is d_bank[r x bank_stride + p], bank_stride either n_prn (gpsx_wbank's layout) or 0 (one
+ *                  row of n_prn records for every receiver).  A record with GPSX_WEPH_VALID has HAVE_EPH.  EVAL(x, t), for a record
+ *                  with HAVE_EPH and svh == 0, is gpsx_wpred's step 2 at the point x with clock term 0 and receive time t in double
+ *                  seconds, that step's T being the double 1000 t: pr_0 = 72 ms; pass k = 0, 1, 2: t_sv = (T - pr_k / ms) / 1000; the
+ *                  satellite at its clock's reading t_sv (ps, vs,
+ *                  d', dts, svar; the pass fails if |tk| > 7201, A <= 0 or Kepler's iteration needs 30 steps); l = ps - x, range =
+ *                  |l|; the pass fails if range == 0, |ps| < Re or rho = range + we (ps_x x_1 - ps_y x_0) / c <= 0; e = l / range;
+ *                  az, el at ecef2pos(x); dion = Klobuchar(cfg.ion or the default set where cfg's are all 0, tow = T / 1000), dtrp =
+ *                  Saastamoinen(0.7), var = gpsx_wfix's variance of the row (measurement, svar, ionosphere, troposphere);
+ *                  pr_(k+1) = (rho + dion + dtrp - c dts) + c tgd.  The last pass's values count: pr = pr_3, e, el, az, var and
+ *                  rd = e . vs + k (vs_x x_1 - vs_y x_0) - c d', k = we / c, the pseudorange's rate (gpsx_wpred step 3's second
+ *                  bracket).  EVAL is GOOD iff no pass failed and pr, el, az, rd and var are finite and |pr| < 1e12.
+ *                  t0 = tow_s + epoch_offset_s (one addition; epoch_offset_s: half the search's span, because a non-coherent
+ *                  sum's phase belongs to the middle of its blocks).  A CANDIDATE is DETECTED, has HAVE_EPH and svh == 0, EVAL(prior
+ *                  rr, t0) is GOOD and its el >= el_min_rad.  Fewer than min_sats candidates: TOO_FEW (n_iter = 0).
+ *   3 milliseconds the REFERENCE is the candidate of greatest el; at equal el the lower index.  With s_p = (double)tau_p / 16368 and
+ *                  pr_p of step 2:  N_ref = rint(pr_ref / ms - s_ref);  b0 = (N_ref + s_ref) x ms - pr_ref;  for every candidate
+ *                  (the reference too)  N_p = rint((pr_p + b0) / ms - s_p),  z_p = (N_p + s_p) x ms.  Every operation single, in the
+ *                  order written, ties to even.  The N_p are fixed from here on (they resolve while the prior's combined error in
+ *                  a range DIFFERENCE stays under half a millisecond, 150 km: position error x up to 2 plus 800 m/s x the time error).
+ *   4 iteration    unknowns (x, y, z, b in metres, dt in seconds) from (prior rr, 0, 0).  Per pass every candidate runs
+ *                  EVAL((x, y, z), t0 + dt) -- T = 1000 ((tow_s + epoch_offset_s) + dt).  It has a ROW iff that is GOOD and its el >= 0.  The row
+ *                  is h = (-e_x, -e_y, -e_z, 1, rd), v = z_p - (pr + b), sig = sqrt(var), a = h / sig (a_3 = 1 / sig), y = v / sig.
+ *                  The 15 + 5 sums N_ij = sum a_i a_j (i >= j), g_i = sum a_i y run over the 64 lanes of a wave (a lane without a
+ *                  row adds zeros) as a butterfly: six rounds, in round m = 1, 2, 4, 8, 16, 32 lane l adds lane l ^ m's value.
+ *                  Fewer than min_sats rows: TOO_FEW.  A sum not finite: NONFINITE.  Cholesky N = L L^T row by row as gpsx_wfix's:
+ *                  p_j = N_jj - l_j0^2 - .. - l_j(j-1)^2, l_jj = sqrt(p_j), l_ij = (N_ij - l_i0 l_j0 - .. - l_i(j-1) l_j(j-1)) / l_jj;
+ *                  p_0 <= 0 or p_k <= 1e-10 N_kk: SINGULAR.  M = L^-1: m_jj = 1 / l_jj, m_ij = -(l_ij m_jj + .. + l_i(i-1) m_(i-1)j)
+ *                  / l_ii; w_i = m_i0 g_0 + .. + m_ii g_i; dx_j = m_jj w_j + .. + m_4j w_4 (sums left to right).  A dx not finite:
+ *                  NONFINITE.  The unknowns += dx; converged when dx_0^2 + dx_1^2 + dx_2^2 + dx_3^2 + (1000 dx_4)^2 < 1e-8 (left
+ *                  to right).  Ten passes at most, then NO_CONV.  n_iter counts the passes, n_used and used_mask are the last
+ *                  pass's rows, qr the first three unknowns' block of M^T M of the converging pass in gpsx_wfix's order.
+ *   5 check        one more EVAL at the final unknowns; over the rows of it that are in used_mask: resid_m_p = v_p,
+ *                  resid_rms_m = sqrt(sum v^2 / n_used) (the butterfly's sum, unweighted); geo = ecef2pos of the final point.  A
+ *                  wrong millisecond is 300 km: resid_rms_m > max_resid_m gives RESID, not FIX; the numbers stay in the record.
+ *                  Anything of the record not finite (rr, b_m, dt_s, tow_s, geo, the float qr, the rms), or a tow_s that step 6's
+ *                  single fold leaves outside 0 <= tow_s < 604800 (|dt_s| beyond a week: a solve that ran away): NONFINITE instead,
+ *                  with zeros.
+ *   6 records      d_snap[r]: flags is exactly one of FIX / RESID / TOO_FEW / SINGULAR / NO_CONV / NONFINITE / NO_PRIOR; the
+ *                  counts, ref and used_mask as far as the receiver came (ref = -1 before step 3); rr .. resid_rms_m only with
+ *                  FIX or RESID.  tow_s = the prior's tow_s + dt_s, week the prior's; tow_s >= 604800: tow_s -= 604800, week += 1;
+ *                  tow_s < 0: tow_s += 604800, week -= 1 (with FIX or RESID; otherwise the prior's own).  d_sv[r][p] (unless NULL):
+ *                  flags DETECTED, HAVE_EPH, CANDIDATE, USED (bit p of used_mask), REFERENCE; phase = tau_p and dopp_hz = f_p
+ *                  always; n_ms = N_p of a candidate (once step 3 ran), el and az of step 2 for a candidate; resid_m with FIX or
+ *                  RESID for a USED row of step 5.  Every byte of both is written; nothing non-finite is ever written.
+ * Errors, each GPSX_EINVAL with a gpsx_last_error text and nothing written: cfg, g, g->prns, the peaks, d_bank, d_prior or d_snap
+ * NULL; an ion[] not finite; el_min_rad not finite or outside +-pi/2; epoch_offset_s not finite or outside 0 .. 4.096; max_resid_m
+ * not finite or <= 0; det_num, det_den outside 1 .. 1024 or det_num < det_den; min_sats outside 5 .. 64; a reserved word != 0; n_search
+ * outside 1 .. 1 048 576; n_prn outside 1 .. 64; n_dopp outside 1 .. 1 048 576; a PRN outside 1 .. 210 or listed twice; a Doppler bin
+ * outside int32; bank_stride neither 0 nor n_prn; d_bank not 16-byte aligned, (_dev) d_peaks not 4-byte, d_prior not 8-byte, d_snap or
+ * d_sv not 16-byte aligned; (_dev) d_snap or d_sv overlapping each other or one of the three inputs; size products that overflow.
+ * _dev only enqueues on the context's stream: the grid call, then gpsx_wsnap_dev on its d_peaks.  Vector ALU, FP64 (k_wsnap: a wave
+ * per receiver, four receivers per workgroup, no LDS; step 1 is k_wacq's strided rows and 64-bit keys; from step 2 on lane p is PRN
+ * index p, one satellite evaluation per lane and pass; the reference by ballots and shuffles; the twenty sums under wave-uniform
+ * control flow, the 5 x 5 factorisation in every lane's registers). */
+#define GPSX_WSNAP_FIX          1u
+#define GPSX_WSNAP_RESID        2u   /* converged, but resid_rms_m > max_resid_m: a wrong millisecond, a wrong prior */
+#define GPSX_WSNAP_TOO_FEW      4u
+#define GPSX_WSNAP_SINGULAR     8u
+#define GPSX_WSNAP_NO_CONV     16u
+#define GPSX_WSNAP_NONFINITE   32u
+#define GPSX_WSNAP_NO_PRIOR    64u
+#define GPSX_WSNAP_PRIOR_HAVE   1u   /* gpsx_wsnap_prior_t.flags */
+#define GPSX_WSNAP_SV_DETECTED  1u
+#define GPSX_WSNAP_SV_HAVE_EPH  2u
+#define GPSX_WSNAP_SV_CANDIDATE 4u
+#define GPSX_WSNAP_SV_USED      8u
+#define GPSX_WSNAP_SV_REFERENCE 16u
+
+typedef struct {                 /* 128 bytes */
+  double   ion[8];               /*   0  as gpsx_wfix_cfg_t's; all 0: the default set */
+  double   el_min_rad;           /*  64  finite, -pi/2 .. pi/2 */
+  double   epoch_offset_s;       /*  72  0 .. 4.096: from the search's first sample to the instant its phases belong to */
+  double   max_resid_m;          /*  80  > 0 */
+  int32_t  det_num, det_den;     /*  88  as gpsx_wacq_cfg_t's: 1 .. 1024, det_num >= det_den */
+  uint32_t min_peak;             /*  96  as gpsx_wacq_cfg_t's */
+  int32_t  min_sats;             /* 100  5 .. 64 */
+  int32_t  reserved[6];          /* 104  0 */
+} gpsx_wsnap_cfg_t;
+
+typedef struct {                 /* 48 bytes, one per receiver */
+  uint32_t flags;  int32_t week; /*   0  GPSX_WSNAP_PRIOR_HAVE; 0 .. 32767 */
+  double   rr[3];                /*   8  ECEF, m */
+  double   tow_s;                /*  32  of the search's first sample, 0 <= tow_s < 604800 */
+  uint32_t reserved[2];          /*  40  0 */
+} gpsx_wsnap_prior_t;
+
+typedef struct {                 /* 128 bytes, one per receiver */
+  uint32_t flags;  int32_t week; /*   0  GPSX_WSNAP_*; the week of tow_s */
+  uint8_t  n_detected, n_candidates, n_used, n_iter;   /*   8 */
+  int32_t  ref;                  /*  12  the reference's PRN index, -1: none */
+  uint64_t used_mask;            /*  16  bit p = PRN index p */
+  double   rr[3];                /*  24  ECEF, m */
+  double   b_m;                  /*  48  the common bias */
+  double   dt_s;                 /*  56  what the prior's tow_s was off by */
+  double   tow_s;                /*  64  the prior's + dt_s, inside the week */
+  double   geo[3];               /*  72  lat, lon (rad), height (m) */
+  double   resid_rms_m;          /*  96 */
+  float    qr[6];                /* 104  as gpsx_wfix_t's */
+} gpsx_wsnap_t;
+
+typedef struct {                 /* 48 bytes, one per (receiver, PRN index) */
+  uint32_t flags;  int32_t n_ms; /*   0  GPSX_WSNAP_SV_*; N_p */
+  uint32_t phase;  int32_t dopp_hz;   /*   8  tau_p, f_p */
+  double   el, az, resid_m;      /*  16 */
+  uint32_t reserved[2];          /*  40  0 */
+} gpsx_wsnap_sv_t;
+
+/* d_peaks [n_search][n_prn][n_dopp], d_bank [n_search][n_prn] or (bank_stride 0) [n_prn], d_prior [n_search], d_snap [n_search],
+ * d_sv (NULL: not wanted) [n_search][n_prn]: device memory.  gpsx_wsnap takes peaks, prior, snap and sv in host memory (staged
+ * through the arena; it waits for its kernel); the bank is device memory in both variants, as gpsx_wpred's. */
+int gpsx_wsnap_dev(gpsx_ctx *ctx, const gpsx_wsnap_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *d_peaks,
+                   const gpsx_weph_t *d_bank, int bank_stride, const gpsx_wsnap_prior_t *d_prior, gpsx_wsnap_t *d_snap,
+                   gpsx_wsnap_sv_t *d_sv);
+int gpsx_wsnap(gpsx_ctx *ctx, const gpsx_wsnap_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *peaks,
+               const gpsx_weph_t *d_bank, int bank_stride, const gpsx_wsnap_prior_t *prior, gpsx_wsnap_t *snap, gpsx_wsnap_sv_t *sv);
+/* Host only, no GPU.  A snapshot with FIX as the gpsx_wfix_t fields gpsx_wkf's INIT reads (flags = GPSX_WFIX_FIX, rr, dtr_s = b_m / c,
+ * rx_tow_s = tow_s + dtr_s, week) and what else the two records share (n_used, n_iter, ref_slot = ref, used_mask, geo, qr,
+ * resid_rms_m); so a snapshot can start the filter 30 s before the first subframe.  GPSX_EINVAL: a NULL, a record without FIX. */
+int gpsx_wsnap_to_fix(const gpsx_wsnap_t *in, gpsx_wfix_t *out);
 
 /* ---- the tracking LOOPS on the device: correlators + DLL / PLL / FLL + false-lock check + SNR + 20 ms bit synchroniser,
  *      K milliseconds per launch, channel state resident in HBM  (gps_tracking_data_process, PM/GPS/tracking.c:92-170,

@@ -140,6 +140,8 @@ def check_no_scratch() -> dict:
     check_walm()
     # ... and, between the prediction and the acquisition decisions, the grid in a window (check_wwin below: no scratch, its LDS as planned)
     check_wwin()
+    # ... and, behind any weighted grid, the snapshot fixes (check_wsnap below: FP64, a wave per receiver, no scratch, no LDS)
+    check_wsnap()
     # ... and the word layer behind it (k_wnav_words: two register sets of eight slots' bit words, the frame state)
     wnav = {k: v for k, v in kernel_resources(os.path.join(PKG, "build", "k_wnav_words.o")).items() if "k_wnav_words" in k}
     if len(wnav) != 1:
@@ -237,6 +239,12 @@ def check_walm() -> dict:
     """k_walm, almanac, ionosphere and UTC from subframes 4 and 5 (k_weph's assembly on k_wbank's geometry: an object of its own,
     exactly one instance, no scratch and no LDS)"""
     return check_wsolver("k_walm.o", "k_walm", True)
+
+
+def check_wsnap() -> dict:
+    """k_wsnap, snapshot fixes from a weighted grid's records, a bank and a prior (the solvers' shared parts on k_wacq's geometry, a
+    5 x 5 system in every lane's registers: an object of its own, exactly one instance, no scratch and no LDS)"""
+    return check_wsolver("k_wsnap.o", "k_wsnap", True)
 
 
 # k_acq_win's LDS: the planes (2 x 16 x 1024 int8), the two int16 rows (2 x 1028 dwords), the chip pairs (512 dwords), E (4096 dwords),

@@ -384,6 +384,43 @@ def wpred_cfg(ch_per_rx: int, mps_per_hz: float = WVEL_L1CA, el_min_rad: float =
     return cfg
 
 
+# gpsx_wsnap_cfg_t / gpsx_wsnap_prior_t / gpsx_wsnap_t / gpsx_wsnap_sv_t (snapshot fixes from a weighted grid's records, a bank and a prior)
+WSNAP_FIX, WSNAP_RESID, WSNAP_TOO_FEW, WSNAP_SINGULAR, WSNAP_NO_CONV, WSNAP_NONFINITE, WSNAP_NO_PRIOR = 1, 2, 4, 8, 16, 32, 64
+WSNAP_PRIOR_HAVE = 1
+WSNAP_SV_DETECTED, WSNAP_SV_HAVE_EPH, WSNAP_SV_CANDIDATE, WSNAP_SV_USED, WSNAP_SV_REFERENCE = 1, 2, 4, 8, 16
+WSNAP_CFG_DTYPE = np.dtype([("ion", "<f8", (8,)), ("el_min_rad", "<f8"), ("epoch_offset_s", "<f8"), ("max_resid_m", "<f8"), ("det_num", "<i4"),
+                            ("det_den", "<i4"), ("min_peak", "<u4"), ("min_sats", "<i4"), ("reserved", "<i4", (6,))])
+WSNAP_PRIOR_DTYPE = np.dtype([("flags", "<u4"), ("week", "<i4"), ("rr", "<f8", (3,)), ("tow_s", "<f8"), ("reserved", "<u4", (2,))])
+WSNAP_DTYPE = np.dtype([("flags", "<u4"), ("week", "<i4"), ("n_detected", "u1"), ("n_candidates", "u1"), ("n_used", "u1"), ("n_iter", "u1"),
+                        ("ref", "<i4"), ("used_mask", "<u8"), ("rr", "<f8", (3,)), ("b_m", "<f8"), ("dt_s", "<f8"), ("tow_s", "<f8"),
+                        ("geo", "<f8", (3,)), ("resid_rms_m", "<f8"), ("qr", "<f4", (6,))])
+WSNAP_SV_DTYPE = np.dtype([("flags", "<u4"), ("n_ms", "<i4"), ("phase", "<u4"), ("dopp_hz", "<i4"), ("el", "<f8"), ("az", "<f8"), ("resid_m", "<f8"),
+                           ("reserved", "<u4", (2,))])
+assert WSNAP_CFG_DTYPE.itemsize == 128 and WSNAP_PRIOR_DTYPE.itemsize == 48 and WSNAP_DTYPE.itemsize == 128 and WSNAP_SV_DTYPE.itemsize == 48
+
+
+def wsnap_cfg(epoch_offset_s: float, el_min_rad: float = 0.0873, max_resid_m: float = 1000.0, det=(4, 1), min_peak: int = 0, min_sats: int = 5,
+              ion=None) -> np.ndarray:
+    """a gpsx_wsnap_cfg_t as a one-element WSNAP_CFG_DTYPE array: a PRN counts when its best record is detected as gpsx_wacq detects
+    (det, min_peak) and it stands at least el_min_rad above the prior's horizon; epoch_offset_s is half the search's span; a
+    converged solution whose residuals' rms is above max_resid_m (a wrong millisecond is 300 km) is flagged RESID, not FIX"""
+    cfg = np.zeros(1, WSNAP_CFG_DTYPE)
+    for name, v in (("el_min_rad", el_min_rad), ("epoch_offset_s", epoch_offset_s), ("max_resid_m", max_resid_m), ("det_num", det[0]),
+                    ("det_den", det[1]), ("min_peak", min_peak), ("min_sats", min_sats)):
+        cfg[name] = v
+    if ion is not None:
+        cfg["ion"][0] = ion
+    return cfg
+
+
+def wsnap_prior(rr, week, tow_s) -> np.ndarray:
+    """gpsx_wsnap_prior_t records with HAVE from rr [n, 3] (ECEF, m), the GPS week and the time of week of the search's first sample"""
+    rr = np.asarray(rr, np.float64).reshape(-1, 3)
+    out = np.zeros(len(rr), WSNAP_PRIOR_DTYPE)
+    out["flags"], out["week"], out["rr"], out["tow_s"] = WSNAP_PRIOR_HAVE, week, rr, tow_s
+    return out
+
+
 # gpsx_wtow_cfg_t / gpsx_wtow_t / gpsx_wtow_rx_t (time-of-week aiding of the observable states from gpsx_wpred's records)
 (WTOW_NO_PRED, WTOW_EMPTY, WTOW_UNLISTED, WTOW_BAD, WTOW_WAITING, WTOW_STALE, WTOW_UNCERTAIN, WTOW_INCONSISTENT, WTOW_OFF_GRID, WTOW_REARMED,
  WTOW_SHIFTED, WTOW_AIDED, WTOW_AGREES, WTOW_DISAGREES) = (1 << i for i in range(14))
@@ -640,6 +677,9 @@ def load_library(lab: bool | None = None) -> C.CDLL:
     lib.gpsx_walm_dev.argtypes = lib.gpsx_walm.argtypes
     lib.gpsx_walm_to_eph.argtypes = [C.c_void_p, C.c_void_p]
     lib.gpsx_walm_gps_minus_utc.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
+    lib.gpsx_wsnap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gpsx_wsnap_dev.argtypes = lib.gpsx_wsnap.argtypes
+    lib.gpsx_wsnap_to_fix.argtypes = [C.c_void_p, C.c_void_p]
     lib.gpsx_acq_window_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.gpsx_acq_window_weighted_dev.argtypes = lib.gpsx_acq_window_weighted.argtypes
     lib.gpsx_wlock_cn0_dbhz.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -1235,6 +1275,44 @@ class Engine:
                                       C.c_void_p(d_sync_state), opt(d_lock_state), opt(d_nav_state), opt(d_obs_state), opt(d_eph_state), rx.ctypes.data,
                                       pred.ctypes.data if want_pred else None), "gpsx_wpred")
         return (rx, pred) if want_pred else rx
+
+    def _wsnap_grid(self, n_rx, prns, dopp_min_hz, dopp_step_hz, n_dopp):
+        prns = np.ascontiguousarray(prns, np.uint8)
+        return prns, AcqWeightedT(n_rx, 0, len(prns), prns.ctypes.data_as(C.POINTER(C.c_uint8)), dopp_min_hz, dopp_step_hz, n_dopp, 1)
+
+    def wsnap(self, cfg: np.ndarray, peaks: np.ndarray, prns, dopp_min_hz: int, dopp_step_hz: int, d_bank: int, bank_stride: int, prior: np.ndarray,
+              want_sv: bool = True):
+        """EXTENSION: snapshot fixes (include/gpsx.h gpsx_wsnap) from a weighted grid's records, PEAK_DTYPE [n_rx, n_prn, n_dopp] in host
+        memory (search s is receiver s; prns and the Doppler grid are the grid call's), the WEPH_DTYPE bank at device address d_bank
+        ([n_rx, n_prn] with bank_stride n_prn, one shared row [n_prn] with 0) and the WSNAP_PRIOR_DTYPE [n_rx] priors (wsnap_prior); cfg
+        from wsnap_cfg.  -> (WSNAP_DTYPE [n_rx], WSNAP_SV_DTYPE [n_rx, n_prn]), or the first alone without want_sv"""
+        assert cfg.dtype == WSNAP_CFG_DTYPE and cfg.size == 1
+        peaks = np.ascontiguousarray(peaks, PEAK_DTYPE)
+        assert peaks.ndim == 3 and peaks.shape[1] == len(prns)
+        n_rx, n_prn, n_dopp = peaks.shape
+        prior = np.ascontiguousarray(prior, WSNAP_PRIOR_DTYPE).reshape(n_rx)
+        prns, g = self._wsnap_grid(n_rx, prns, dopp_min_hz, dopp_step_hz, n_dopp)
+        snap, sv = np.zeros(n_rx, WSNAP_DTYPE), np.zeros((n_rx, n_prn), WSNAP_SV_DTYPE)
+        self._chk(self.lib.gpsx_wsnap(self.h, cfg.ctypes.data, C.addressof(g), peaks.ctypes.data, C.c_void_p(d_bank), bank_stride, prior.ctypes.data,
+                                      snap.ctypes.data, sv.ctypes.data if want_sv else None), "gpsx_wsnap")
+        return (snap, sv) if want_sv else snap
+
+    def wsnap_dev(self, cfg: np.ndarray, d_peaks: int, n_rx: int, prns, dopp_min_hz: int, dopp_step_hz: int, n_dopp: int, d_bank: int, bank_stride: int,
+                  d_prior: int, d_snap: int, d_sv: int | None = None) -> None:
+        """EXTENSION: gpsx_wsnap_dev on the records a weighted grid call left at device address d_peaks, enqueued behind it on the
+        engine's stream: WSNAP_DTYPE [n_rx] to d_snap and, where given, WSNAP_SV_DTYPE [n_rx, len(prns)] to d_sv; nothing is read back"""
+        assert cfg.dtype == WSNAP_CFG_DTYPE and cfg.size == 1
+        prns, g = self._wsnap_grid(n_rx, prns, dopp_min_hz, dopp_step_hz, n_dopp)
+        self._chk(self.lib.gpsx_wsnap_dev(self.h, cfg.ctypes.data, C.addressof(g), C.c_void_p(d_peaks), C.c_void_p(d_bank), bank_stride,
+                                          C.c_void_p(d_prior), C.c_void_p(d_snap), C.c_void_p(d_sv) if d_sv else None), "gpsx_wsnap_dev")
+
+    def wsnap_to_fix(self, snap: np.ndarray) -> np.ndarray:
+        """EXTENSION: gpsx_wsnap_to_fix per record: WSNAP_DTYPE [n] -> WFIX_DTYPE [n]; a record without FIX gives an all-zero one"""
+        snap = np.ascontiguousarray(snap, WSNAP_DTYPE).reshape(-1)
+        fix = np.zeros(len(snap), WFIX_DTYPE)
+        for k in range(len(snap)):
+            self.lib.gpsx_wsnap_to_fix(snap[k:k + 1].ctypes.data, fix[k:k + 1].ctypes.data)
+        return fix
 
     def wtow(self, cfg: np.ndarray, prns, n_rx: int, d_pred_rx: int, d_pred: int, d_sync_state: int, d_obs_state: int, d_obs: int | None = None):
         """EXTENSION: time-of-week aiding (include/gpsx.h gpsx_wtow) of the n_rx * ch_per_rx WOBS_STATE_DTYPE states at device address

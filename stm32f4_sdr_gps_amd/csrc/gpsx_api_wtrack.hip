@@ -1,5 +1,5 @@
 // gpsx_api_wtrack.hip -- the C ABI of the weighted two-bit tracking chain (include/gpsx.h): gpsx_track_epl_weighted,
-// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, gpsx_walm, gpsx_acq_window_weighted (the grid in a window around gpsx_wpred's records: it stands in the chain, between the prediction and gpsx_wacq), each with its _dev twin, and the three
+// gpsx_track_loop_weighted, gpsx_track_loop_weighted_sync (and the carrier-aided form of each, _aided), gpsx_track_loop_weighted_sync_multi, gpsx_wnav_words, gpsx_wobs, gpsx_weph, gpsx_wlock, gpsx_wfix, gpsx_wfde, gpsx_wvel, gpsx_wkf, gpsx_wacq, gpsx_wbank, gpsx_wpred, gpsx_wtow, gpsx_walm, gpsx_wsnap, gpsx_acq_window_weighted (the grid in a window around gpsx_wpred's records: it stands in the chain, between the prediction and gpsx_wacq), each with its _dev twin, and the three
 // host helpers behind them (gpsx_weph_to_eph, gpsx_walm_to_eph and gpsx_walm_gps_minus_utc are gpsx_ephemeris.cpp's, beside the decoder they restate).  Host code only, like gpsx_api.hip; it reads no lab knob, so lib/libgpsx_lab.so links this object as it is.
 //
 // A pair is ONE function with a `bool host`.  host: the capture and the results are host memory, staged through the arena; the call
@@ -920,6 +920,100 @@ int wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, const
       });
 }
 
+// ---- snapshot fixes (host: peaks, prior, snap and sv are host memory, staged through the arena; the bank is device memory in both
+//      variants) ------------------------------------------------------------------------------------------------------------------------
+int wsnap(gpsx_ctx *ctx, const gpsx_wsnap_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *peaks, const gpsx_weph_t *d_bank,
+          int bank_stride, const gpsx_wsnap_prior_t *prior, gpsx_wsnap_t *snap, gpsx_wsnap_sv_t *sv, bool host)
+{
+  if (int rc = use_device(ctx)) return rc;
+  if (!cfg || !g || !g->prns || !peaks || !d_bank || !prior || !snap)
+    return fail(ctx, GPSX_EINVAL, "null argument");
+  for (double v : cfg->ion)
+    if (!(v - v == 0.0))   // (not finite: the difference is a NaN)
+      return fail(ctx, GPSX_EINVAL, "an ionosphere coefficient is not finite");
+  if (!(std::fabs(cfg->el_min_rad) <= 1.5707963267948966))   // (a NaN fails it)
+    return fail(ctx, GPSX_EINVAL, "el_min_rad must be finite and within -pi/2..pi/2");
+  if (!(cfg->epoch_offset_s >= 0.0 && cfg->epoch_offset_s <= 4.096))
+    return fail(ctx, GPSX_EINVAL, "epoch_offset_s must be finite and 0..4.096");
+  if (!(cfg->max_resid_m - cfg->max_resid_m == 0.0) || !(cfg->max_resid_m > 0.0))
+    return fail(ctx, GPSX_EINVAL, "max_resid_m must be finite and above 0");
+  if (cfg->det_num < 1 || cfg->det_num > 1024 || cfg->det_den < 1 || cfg->det_den > 1024 || cfg->det_num < cfg->det_den)
+    return fail(ctx, GPSX_EINVAL, "det_num and det_den must be 1..1024, det_num >= det_den");
+  if (cfg->min_sats < 5 || cfg->min_sats > 64)
+    return fail(ctx, GPSX_EINVAL, "min_sats must be 5..64");
+  for (int32_t v : cfg->reserved)
+    if (v != 0)
+      return fail(ctx, GPSX_EINVAL, "reserved must be 0");
+  if (g->n_search < 1 || g->n_search > (1 << 20))
+    return fail(ctx, GPSX_EINVAL, "n_search must be 1..1048576");
+  if (g->n_prn < 1 || g->n_prn > 64)
+    return fail(ctx, GPSX_EINVAL, "n_prn must be 1..64");
+  if (g->n_dopp < 1 || g->n_dopp > (1 << 20))   // (the kernel counts bins in int32, four turns of 64 ahead)
+    return fail(ctx, GPSX_EINVAL, "n_dopp must be 1..1048576");
+  bool listed[GPSX_MAX_PRN + 1] = {};
+  for (int i = 0; i < g->n_prn; i++) {
+    if (g->prns[i] < 1 || g->prns[i] > GPSX_MAX_PRN)
+      return fail(ctx, GPSX_EINVAL, "PRN outside 1..210");
+    if (listed[g->prns[i]])
+      return fail(ctx, GPSX_EINVAL, "a PRN is listed twice");
+    listed[g->prns[i]] = true;
+  }
+  const long long f_first = g->dopp_min_hz, f_last = f_first + (long long)(g->n_dopp - 1) * (long long)g->dopp_step_hz;
+  if (f_last < -2147483647ll - 1 || f_last > 2147483647ll)
+    return fail(ctx, GPSX_EINVAL, "a Doppler bin lies outside int32");
+  if (bank_stride != 0 && bank_stride != g->n_prn)
+    return fail(ctx, GPSX_EINVAL, "bank_stride must be 0 or n_prn");
+  if ((reinterpret_cast<uintptr_t>(d_bank) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_bank must be 16-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(peaks) & 3u) != 0 || (reinterpret_cast<uintptr_t>(prior) & 7u) != 0))
+    return fail(ctx, GPSX_EINVAL, "d_peaks must be 4-byte and d_prior 8-byte aligned");
+  if (!host && ((reinterpret_cast<uintptr_t>(snap) | reinterpret_cast<uintptr_t>(sv)) & 15u) != 0)
+    return fail(ctx, GPSX_EINVAL, "d_snap and d_sv must be 16-byte aligned");
+  size_t peak_bytes = 0, bank_bytes = 0, prior_bytes = 0, snap_bytes = 0, sv_bytes = 0;
+  if (records_overflow((size_t)g->n_search * (size_t)g->n_prn, g->n_dopp, sizeof(gpsx_peak_t), &peak_bytes) ||
+      records_overflow((size_t)(bank_stride ? g->n_search : 1), g->n_prn, sizeof(gpsx_weph_t), &bank_bytes) ||
+      records_overflow((size_t)g->n_search, 1, sizeof(gpsx_wsnap_prior_t), &prior_bytes) ||
+      records_overflow((size_t)g->n_search, 1, sizeof(gpsx_wsnap_t), &snap_bytes) ||
+      records_overflow((size_t)g->n_search, g->n_prn, sizeof(gpsx_wsnap_sv_t), &sv_bytes))
+    return fail(ctx, GPSX_EINVAL, "n_search x n_prn x n_dopp records overflow a size");
+  if (!host) {
+    // (the two outputs against each other and against the three inputs)
+    const struct { const void *p; size_t n; } span[5] = {{snap, snap_bytes}, {sv, sv_bytes}, {peaks, peak_bytes}, {d_bank, bank_bytes}, {prior, prior_bytes}};
+    for (int a = 0; a < 2; a++)
+      for (int b = a + 1; b < 5; b++) {
+        const uintptr_t pa = reinterpret_cast<uintptr_t>(span[a].p), pb = reinterpret_cast<uintptr_t>(span[b].p);
+        if (!pa || !pb)
+          continue;
+        if (pa < pb + span[b].n && pb < pa + span[a].n)
+          return fail(ctx, GPSX_EINVAL, "d_snap or d_sv overlaps another array");
+      }
+  }
+  const gpsx_peak_t *d_peaks = peaks;
+  const gpsx_wsnap_prior_t *d_prior = prior;
+  gpsx_wsnap_t *d_snap = snap;
+  gpsx_wsnap_sv_t *d_sv = sv;
+  if (host) {
+    if (int rc = arena_reset(ctx, arena_size(peak_bytes) + arena_size(prior_bytes) + arena_size(snap_bytes) + (sv ? arena_size(sv_bytes) : 0))) return rc;
+    if (int rc = stage_in(ctx, peaks, peak_bytes / sizeof(gpsx_peak_t), &d_peaks)) return rc;
+    if (int rc = stage_in(ctx, prior, (size_t)g->n_search, &d_prior)) return rc;
+    d_snap = arena_take<gpsx_wsnap_t>(ctx, (size_t)g->n_search);
+    if (sv)
+      d_sv = arena_take<gpsx_wsnap_sv_t>(ctx, sv_bytes / sizeof(gpsx_wsnap_sv_t));
+  }
+  return launch_and_report(
+      ctx, host, "k_wsnap", "k_wsnap raised the bad-state flag, which it never does",
+      [&](uint32_t *) {
+        launch_wsnap(ctx->stream, *cfg, g->n_search, g->n_prn, g->dopp_min_hz, g->dopp_step_hz, g->n_dopp, d_peaks, d_bank, bank_stride, d_prior, d_snap,
+                     d_sv);
+      },
+      [&]() -> int {
+        HIPCHK(ctx, hipMemcpyAsync(snap, d_snap, snap_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (sv)
+          HIPCHK(ctx, hipMemcpyAsync(sv, d_sv, sv_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return GPSX_OK;
+      });
+}
+
 // ---- time-of-week aiding of the observables (host: tow and tow_rx are host memory, staged through the arena; the prediction's records,
 //      the sync and observable states and the observables are device memory in both variants) ------------------------------------------
 int wtow(gpsx_ctx *ctx, const gpsx_wtow_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wpred_rx_t *d_pred_rx,
@@ -1131,6 +1225,44 @@ int gpsx_wpred(gpsx_ctx *ctx, const gpsx_wpred_cfg_t *cfg, int n_rx, int n_prn, 
                gpsx_wobs_state_t *d_obs_state, gpsx_weph_state_t *d_eph_state, gpsx_wpred_rx_t *rx, gpsx_wpred_t *pred)
 {
   return wpred(ctx, cfg, n_rx, n_prn, prns, d_kf_state, d_bank, d_sync_state, d_lock_state, d_nav_state, d_obs_state, d_eph_state, rx, pred, true);
+}
+
+int gpsx_wsnap_dev(gpsx_ctx *ctx, const gpsx_wsnap_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *d_peaks, const gpsx_weph_t *d_bank,
+                   int bank_stride, const gpsx_wsnap_prior_t *d_prior, gpsx_wsnap_t *d_snap, gpsx_wsnap_sv_t *d_sv)
+{
+  return wsnap(ctx, cfg, g, d_peaks, d_bank, bank_stride, d_prior, d_snap, d_sv, false);
+}
+
+int gpsx_wsnap(gpsx_ctx *ctx, const gpsx_wsnap_cfg_t *cfg, const gpsx_acq_weighted_t *g, const gpsx_peak_t *peaks, const gpsx_weph_t *d_bank,
+               int bank_stride, const gpsx_wsnap_prior_t *prior, gpsx_wsnap_t *snap, gpsx_wsnap_sv_t *sv)
+{
+  return wsnap(ctx, cfg, g, peaks, d_bank, bank_stride, prior, snap, sv, true);
+}
+
+// host only: a snapshot with FIX as the gpsx_wfix_t record gpsx_wkf's INIT reads
+int gpsx_wsnap_to_fix(const gpsx_wsnap_t *in, gpsx_wfix_t *out)
+{
+  if (!in || !out || in->flags != GPSX_WSNAP_FIX)
+    return GPSX_EINVAL;
+  gpsx_wfix_t f;
+  std::memset(&f, 0, sizeof f);
+  f.flags = GPSX_WFIX_FIX;
+  f.n_used = in->n_used;
+  f.n_iter = in->n_iter;
+  f.ref_slot = in->ref;
+  f.used_mask = in->used_mask;
+  f.dtr_s = in->b_m / 299792458.0;
+  f.rx_tow_s = in->tow_s + f.dtr_s;
+  f.week = in->week;
+  for (int i = 0; i < 3; i++) {
+    f.rr[i] = in->rr[i];
+    f.geo[i] = in->geo[i];
+  }
+  for (int i = 0; i < 6; i++)
+    f.qr[i] = in->qr[i];
+  f.resid_rms_m = in->resid_rms_m;
+  *out = f;
+  return GPSX_OK;
 }
 
 int gpsx_wbank_dev(gpsx_ctx *ctx, const gpsx_wbank_cfg_t *cfg, int n_rx, int n_prn, const uint8_t *prns, const gpsx_wsync_state_t *d_sync_state,

@@ -251,6 +251,13 @@ void launch_walm(hipStream_t s, const gpsx_walm_cfg_t &cfg, const gpsx_wnav_word
 void launch_acq_win(hipStream_t s, const gpsx_acq_window_t &cfg, const uint8_t *d_if_blocks, int n_rx, int stride_blocks, int n_prn,
                     const uint8_t *prns, const uint8_t *d_chips_all, int if_hz, int dopp_min_hz, int dopp_step_hz, int n_dopp, int use_magnitude,
                     const gpsx_wpred_t *d_pred, gpsx_peak_t *d_peaks, gpsx_acq_window_rep_t *d_rep);
+// extension: gpsx_wsnap (k_wsnap.hip: k_wsnap) -- snapshot fixes behind a weighted grid: from the records d_peaks [n_rx][n_prn][n_dopp], the
+// bank d_bank (record (r, p) at r * bank_stride + p; bank_stride n_prn or 0) and the priors d_prior [n_rx] (all read only) a position, a
+// common bias and a corrected time of week per receiver: d_snap [n_rx] 128-byte and d_sv (may be null) [n_rx][n_prn] 48-byte records,
+// every byte of them written.  A wave per receiver, no state of its own.  cfg and the grid as the host checked them.  No checks.
+void launch_wsnap(hipStream_t s, const gpsx_wsnap_cfg_t &cfg, int n_rx, int n_prn, int dopp_min_hz, int dopp_step_hz, int n_dopp,
+                  const gpsx_peak_t *d_peaks, const gpsx_weph_t *d_bank, int bank_stride, const gpsx_wsnap_prior_t *d_prior, gpsx_wsnap_t *d_snap,
+                  gpsx_wsnap_sv_t *d_sv);
 // GPSX_DRAWS_LIBC (include/gpsx.h): a channel's false-lock jump reported by the first pass / its carrier candidate for the second
 // (ms_from: the millisecond of the launch at which the channel's state in HBM is valid -- 0, or, under the multiplex, the first
 //  millisecond of the slot it stopped in: its earlier slots of the launch were stored when they ended -- the replay starts there)

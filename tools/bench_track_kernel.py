@@ -134,6 +134,9 @@ the per-millisecond tracking step is the kernel and what part the PCIe round tri
                                                       the same words and (2) a device-to-device copy of the bytes touched (a copy puts
                                                       the states back before every timed launch; it is timed alone and subtracted); the
                                                       lines also go to profiles/r30_weighted_alm_bench.jsonl
+  bench_track_kernel.py --weighted-snap [N_RXxN_PRN ...]   k_wsnap (snapshot fixes from grid records, a bank and a prior) at 21 bins, beside a
+                                                      device-to-device copy of what it reads, k_wfix on as many rows, and the host path
+                                                      (records copied back, the CPU restatement): profiles/r32_weighted_snap_bench.jsonl
   bench_track_kernel.py --weighted-win [N_RXxN_COHxN_SEGxW ...]
                                                       gpsx_acq_window_weighted_dev (EXTENSION: the weighted grid in a window around
                                                       each prediction; k_acq_win) on 12 PRNs per receiver, D = 2, every record
@@ -1634,8 +1637,112 @@ def weighted_win(shapes, out=WIN_OUT):
         eng.close()
 
 
+SNAP_OUT = os.path.join(ROOT, "profiles", "r32_weighted_snap_bench.jsonl")
+SNAP_SHAPES = [(256, 12), (256, 32), (4096, 12), (4096, 32), (16384, 12), (16384, 32)]
+SNAP_BINS = 21
+
+
+def weighted_snap(shapes, out=SNAP_OUT):
+    """k_wsnap at (receivers, PRNs) x 21 bins: sixteen receivers (the four sites under skies of twelve satellites, the prior up to 30 km
+    and 20 s off, whole-sample phases from the restatement's model; tests/weighted_snap_cases.py) tiled over the launch, every one a
+    FIX in four or five passes.  The yardsticks, taking turns with it: a device-to-device copy of the records it reads (peaks, bank,
+    priors), and k_wfix on as many rows (the same skies' twelve satellites per receiver as observables).  Behind them, timed on the
+    host clock: the parent's only way to the same answer -- the records copied back and the CPU restatement run on them (the
+    restatement on at most 256 receivers, scaled).  The lines go to stdout and to `out`"""
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import weighted_fix_cases as W
+    import weighted_snap_cases as K
+    import weighted_snap_ref as S
+    from stm32f4_sdr_gps_amd import capi
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    tee = sys.stdout = _Tee(out)
+    eng = capi.Engine(0, stream=stream.value)
+    names = sorted(W.SITES)
+    try:
+        for n_rx, n_prn in shapes:
+            rng = np.random.default_rng(n_prn)
+            pool = []
+            for k in range(16):
+                site = names[k % len(names)]
+                bank = np.zeros(n_prn, S.EPH_DTYPE)
+                for (raw, _), p in zip(W.sky(site, 12, 3 * k), rng.permutation(n_prn)[:12]):
+                    bank[p] = W.eph_record(raw)[0]
+                rr = np.asarray(W.site_ecef(site), np.float64)
+                d = rng.normal(0.0, 1.0, 3)
+                pool.append((K.receiver(bank, rr, W.TOW, rr + d / np.linalg.norm(d) * float(rng.uniform(0.0, 30000.0)), W.TOW + float(rng.uniform(-20.0, 20.0)),
+                                        seed=k, n_dopp=SNAP_BINS), W.receiver(site, 12, 3 * k)))
+            peaks = np.stack([pool[r % 16][0]["peaks"] for r in range(n_rx)])
+            bank = np.stack([pool[r % 16][0]["bank"] for r in range(n_rx)])
+            prior = np.array([pool[r % 16][0]["prior"] for r in range(n_rx)], S.PRIOR_DTYPE)
+            obs, eph = W.pack([pool[r % 16][1] for r in range(n_rx)], 12)
+            prns = np.arange(1, n_prn + 1, dtype=np.uint8)
+            cfg, fix_cfg = capi.wsnap_cfg(K.EPOCH_S), capi.wfix_cfg(W.OFFSET_MS, 12)
+            read_bytes = peaks.nbytes + bank.nbytes + prior.nbytes
+            d_peaks, d_bank, d_prior, d_copy = (eng.malloc(b) for b in (peaks.nbytes, bank.nbytes, prior.nbytes, read_bytes))
+            d_snap, d_sv, d_obs, d_eph, d_fix = (eng.malloc(b) for b in (n_rx * 128, n_rx * n_prn * 48, obs.nbytes, eph.nbytes, n_rx * 128))
+            for d, a in ((d_peaks, peaks), (d_bank, bank), (d_prior, prior), (d_obs, obs), (d_eph, eph)):
+                eng.h2d(d, a)
+            g = capi.AcqWeightedT(n_rx, 0, n_prn, prns.ctypes.data_as(C.POINTER(C.c_uint8)), K.DOPP_MIN_HZ, K.DOPP_STEP_HZ, SNAP_BINS, 1)
+
+            def wsnap(want_sv):
+                return eng.lib.gpsx_wsnap_dev(eng.h, cfg.ctypes.data, C.addressof(g), C.c_void_p(d_peaks), C.c_void_p(d_bank), n_prn, C.c_void_p(d_prior),
+                                              C.c_void_p(d_snap), C.c_void_p(d_sv) if want_sv else None)
+
+            def copy():
+                return (hip.hipMemcpyAsync(d_copy, d_peaks, peaks.nbytes, 3, stream) or hip.hipMemcpyAsync(d_copy + peaks.nbytes, d_bank, bank.nbytes, 3, stream) or
+                        hip.hipMemcpyAsync(d_copy + peaks.nbytes + bank.nbytes, d_prior, prior.nbytes, 3, stream))
+
+            calls = {"d2d_copy_of_the_records_read": (1, copy),
+                     "wfix_on_as_many_rows": (1, lambda: eng.lib.gpsx_wfix_dev(eng.h, fix_cfg.ctypes.data, C.c_void_p(d_obs), C.c_void_p(d_eph), None, None, n_rx,
+                                                                               C.c_void_p(d_fix), None)),
+                     "wsnap": (1, lambda: wsnap(True)),
+                     "wsnap_without_d_sv": (1, lambda: wsnap(False))}
+            med = _timed_rows(eng, calls, {"channels": n_rx * 12, "n_rx": n_rx, "n_prn": n_prn, "n_dopp": SNAP_BINS, "read_bytes": read_bytes}, per_channel_ms=False)
+            snap = np.zeros(n_rx, capi.WSNAP_DTYPE)
+            eng.d2h(snap, d_snap)
+            back = np.empty_like(peaks)
+            d2h = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                eng.d2h(back, d_peaks)
+                d2h.append((time.perf_counter() - t0) * 1e6)
+            n_host = min(n_rx, 256)
+            t0 = time.perf_counter()
+            want, _ = S.snap(cfg, prns, K.DOPP_MIN_HZ, K.DOPP_STEP_HZ, back[:n_host], bank[:n_host], n_prn, prior[:n_host], want_sv=False)
+            host_us = (time.perf_counter() - t0) * 1e6 * n_rx / n_host
+            err = np.array([np.linalg.norm(snap["rr"][r] - pool[r % 16][0]["rr"]) for r in range(min(n_rx, 16))])
+            print(json.dumps({"wsnap_check": "records after the timed launches", "n_rx": n_rx, "fix": int((snap["flags"] == capi.WSNAP_FIX).sum()),
+                              "n_iter": [int(snap["n_iter"].min()), int(snap["n_iter"].max())], "n_used": [int(snap["n_used"].min()), int(snap["n_used"].max())],
+                              "largest_error_m": round(float(err.max()), 2), "flags_equal_the_restatement": bool((want["flags"] == snap["flags"][:n_host]).all())}), flush=True)
+            own = med["wsnap"]
+            print(json.dumps({"ratio": "k_wsnap over the yardsticks", "n_rx": n_rx, "n_prn": n_prn, "n_dopp": SNAP_BINS, "wsnap_us": round(own, 3),
+                              "wsnap_without_d_sv_us": round(med["wsnap_without_d_sv"], 3), "wfix_us": round(med["wfix_on_as_many_rows"], 3),
+                              "over_d2d_copy_of_the_records_read": round(own / med["d2d_copy_of_the_records_read"], 3),
+                              "over_wfix": round(own / med["wfix_on_as_many_rows"], 3), "ns_per_receiver": round(own / n_rx * 1e3, 2),
+                              "host_path_d2h_us_median": round(float(np.median(d2h)), 1), "host_path_restatement_us": round(host_us, 1),
+                              "host_path_restatement_receivers_timed": n_host, "host_path_over_wsnap": round((float(np.median(d2h)) + host_us) / own, 1)}), flush=True)
+            for d in (d_peaks, d_bank, d_prior, d_copy, d_snap, d_sv, d_obs, d_eph, d_fix):
+                eng.free(d)
+    finally:
+        sys.stdout = tee.out
+        tee.file.close()
+        eng.close()
+
+
 def main():
     global WINDOW_S
+    if "--weighted-snap" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--weighted-snap"]
+        if "--window-s" in args:
+            at = args.index("--window-s")
+            WINDOW_S = float(args.pop(at + 1))
+            args.pop(at)
+        return weighted_snap([tuple(int(v) for v in a.split("x")) for a in args] or SNAP_SHAPES)
     if "--weighted-win" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--weighted-win"]
         if "--window-s" in args:
