@@ -170,6 +170,22 @@ def test_host_entry_warm_start_in_place_and_no_pr(eng):
             run.free()
 
 
+def test_host_entry_without_lock_prev_and_pr(eng):
+    """(e') gpsx_wfde (host arrays) with lock, prev and pr_m NULL: the records equal gpsx_wfde_dev's without lock records byte for byte,
+    and the restatement's without them as weighted_fde_cases.compare orders it"""
+    ch, n_rx = 8, 2
+    case = X.launch_case(ch, n_rx)
+    run = _Launch(eng, case["cfg"], case["obs"], case["eph"], n_rx)
+    try:
+        fix, fde, pr = run.run()
+        host = eng.wfde(case["cfg"], case["obs"], case["eph"], n_rx)
+        assert eng.lib.gpsx_last_kernel(eng.h) == b"k_wfde"
+    finally:
+        run.free()
+    assert len(host) == 2 and host[0].tobytes() == fix.tobytes() and host[1].tobytes() == fde.tobytes()
+    print("parity no lock", X.compare(fix, fde, pr, *D.run(case["cfg"], case["obs"], case["eph"], n_rx)[:3]))
+
+
 def test_every_refusal_returns_einval_and_writes_nothing(eng):
     """(f) every error clause of the header but the size overflow: GPSX_EINVAL with a text, canaries and prefill intact, and the
     context works afterwards"""

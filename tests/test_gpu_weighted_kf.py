@@ -133,6 +133,26 @@ def test_host_arrays_and_the_binding_equal_device_arrays(eng):
         assert (nofix[0][-1]["flags"][fresh] == R.F_NOT_INIT).all() and (full[0][-1]["flags"][fresh] == R.F_INIT).all()
 
 
+def test_host_arrays_without_fix_equal_device_arrays(eng):
+    """gpsx_wkf (host arrays) with fix NULL from the second launch on, lock and vel given: records and states equal gpsx_wkf_dev's with
+    d_fix NULL byte for byte, and the restatement's without the records"""
+    ch, n_rx = 8, 2
+    case = K.launch_case(ch, n_rx)
+    dev = _sequence(eng, case, n_rx, fix_until=1)
+    host = _sequence(eng, case, n_rx, dev=False, fix_until=1)
+    assert dev[2] == host[2]
+    state = np.zeros(n_rx, R.STATE_DTYPE)
+    for k in range(K.N_LAUNCH):
+        assert dev[0][k].tobytes() == host[0][k].tobytes() and dev[1][k].tobytes() == host[1][k].tobytes()
+        if k == K.N_LAUNCH - 1:
+            for r, fields in case["poke"].items():
+                for name, val in fields.items():
+                    state[name][r] = val
+        want, state, _ = R.run(case["cfg"], case["obs"][k], case["eph"], state, n_rx, case["n_blocks"], case["lock"], case["fix"][k] if k < 1 else None,
+                               case["vel"])
+        K.compare(dev[0][k], want)
+
+
 def test_every_refusal_returns_einval_and_writes_nothing(eng):
     """every error clause of the header but the size overflow (which no n_rx <= 2^20 x ch_per_rx <= 64 can reach on a 64-bit size_t),
     each with its text, in both variants; then the context still works"""
