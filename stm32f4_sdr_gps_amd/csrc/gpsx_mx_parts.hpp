@@ -120,6 +120,20 @@ struct MxFold {
   v4i lut[2][32];                        // [late][plane bits 4 j - 2 .. 4 j + 2] -> the pairs of q = 4 j .. 4 j + 3, q >= 2
 };
 
+// The single-block form alone: the chip operand of a lane -- chips_a[kappa][h][PRN] of its own (PRN, h), kappa < kMxChipsResident --
+// in registers for the whole cluster.  With the transposed tile a lane's B operand is 32 chips of ONE PRN and K half per kappa: the
+// same 4 dwords in the anchor pass and in all fifteen recurrence passes, of every tile and both streams.  The anchor pass reads
+// them from LDS as it always did, a step ahead of their first MFMA (mx_anchor_step), and they stay; the recurrence passes read no
+// chips (mx_pass_step<.., RES>).  k[] IS the a[] of the passes' steps: an entry at or beyond kMxChipsResident is requested by every
+// pass a step ahead of its use, as in the other forms, and lives no longer than that.  The passes are unrolled over the
+// anti-diagonal, so every k[] is indexed by a constant: registers, never memory.
+// 16 = all of them: k_acq_mx<0> at 16 compiles without scratch inside the 256 registers that two waves per SIMD leave a wave.
+constexpr int kMxChipsResident = 16;
+static_assert(kMxChipsResident >= 0 && kMxChipsResident <= 16 && kMxChipsResident % 4 == 0, "whole quads of kappa");
+struct MxChipRegs {
+  v4i k[16];
+};
+
 __device__ __forceinline__ v8i widen(v4i x) { return v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0}; }
 
 __device__ __forceinline__ u32 lds_byte(const u32 *words, int byte_index)
@@ -479,20 +493,21 @@ __device__ __forceinline__ v16f mx_mfma(v4i chips, v4i frag, v16f acc, u32 scale
   else
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(widen(chips), widen(frag), acc, 4, 4, 0, SCALE_C, 0, scale_f);
 }
-// (FOLD is the single-block form's instantiation, and the transposed one)
-template <int S, int NT, u32 SCALE_A = kScaleA, bool FOLD = false>
+// (FOLD is the single-block form's instantiation, and the transposed one; RES: a[] is MxChipRegs::k, filled for kappa < RES)
+template <int S, int NT, u32 SCALE_A = kScaleA, bool FOLD = false, int RES = 0>
 __device__ __forceinline__ void mx_pass_step(lds_cu32 *wi, lds_cu32 *wq, const v4i *ca, v4i (&a)[16], v4i &fi, v4i &fq,
                                              v16f (&acc)[2][NT], u32 scale_b, MxFoldRegs *fold = nullptr)
 {
   constexpr int kSteps = 16 + NT - 1;
   constexpr bool more = S + 1 < kSteps;
   constexpr bool pair_next = FOLD && more && S + 1 >= 15, patched = FOLD && S >= 15;
+  constexpr bool chips_next = more && S + 1 < 16 && S + 1 >= RES;
   v4i fi_next = fi, fq_next = fq;
   u32 pi_next = 0, pq_next = 0;
   if constexpr (more) {
     fi_next = lds_frag(wi, 8 * (S + 1));
     fq_next = lds_frag(wq, 8 * (S + 1));
-    if constexpr (S + 1 < 16)
+    if constexpr (chips_next)
       a[S + 1] = ca[(S + 1) * 64];                         // chips_a[S + 1][h][n]
     if constexpr (pair_next) {
       pi_next = fold->w[64 * (S + 1 - 15)];
@@ -512,7 +527,7 @@ __device__ __forceinline__ void mx_pass_step(lds_cu32 *wi, lds_cu32 *wq, const v
     acc[1][j_lo] = mx_mfma<FOLD, SCALE_A>(a[15], fq, acc[1][j_lo], scale_b);
   }
   if constexpr (more) {
-    __builtin_amdgcn_sched_group_barrier(0x100, (S + 1 < 16 ? 5 : 4) + (pair_next ? 2 : 0), 0);   // DS reads
+    __builtin_amdgcn_sched_group_barrier(0x100, (chips_next ? 5 : 4) + (pair_next ? 2 : 0), 0);   // DS reads
     if constexpr (patched) {
       __builtin_amdgcn_sched_group_barrier(0x008, 2 * (j_hi - j_lo), 0);    // MFMAs of the tiles below kappa = 15
       __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);                    // the two patches
@@ -529,7 +544,7 @@ __device__ __forceinline__ void mx_pass_step(lds_cu32 *wi, lds_cu32 *wq, const v
     fold->pq = pq_next;
   }
   if constexpr (more)
-    mx_pass_step<S + 1, NT, SCALE_A, FOLD>(wi, wq, ca, a, fi, fq, acc, scale_b, fold);
+    mx_pass_step<S + 1, NT, SCALE_A, FOLD, RES>(wi, wq, ca, a, fi, fq, acc, scale_b, fold);
 }
 
 // The same without a second set of fragment registers (the walk forms, whose prefetched sums leave none): the I fragment of the
@@ -572,11 +587,14 @@ __device__ __forceinline__ void mx_pass_step_inplace(lds_cu32 *wi, lds_cu32 *wq,
 // NT = q-tiles of this call (q0_tile + 2 j, j < NT): four everywhere but in the byte-phase form, which works in tile pairs
 // SCALE_A: the A operand's block scale (the weighted extension keeps plain integers in its accumulators: 2^0; AHEAD only)
 // FOLD: no extra K step; with_corr says whether the pairs of fold_pair (MxFold::pair[buf]) are patched in (mx_pass_step)
-template <bool AHEAD, int NT, u32 SCALE_A = kScaleA, bool FOLD = false>
+// RES > 0 (the single-block form): the steps' a[] is chips->k, filled for kappa < RES; the pass reads the others from LDS as it goes
+template <bool AHEAD, int NT, u32 SCALE_A = kScaleA, bool FOLD = false, int RES = 0>
 __device__ __forceinline__ void mx_pass(const MxSharedCore &sh, int buf, int lane, int q0_tile, v16f (&acc)[2][NT],
-                                        u32 scale_b, v4i a_corr, bool with_corr, const u32 *fold_pair = nullptr)
+                                        u32 scale_b, v4i a_corr, bool with_corr, const u32 *fold_pair = nullptr,
+                                        MxChipRegs *chips = nullptr)
 {
   static_assert(!FOLD || (AHEAD && NT == kMxTiles), "the fold is the single-block form's");
+  static_assert(RES == 0 || (FOLD && RES <= kMxChipsResident), "resident chips are the single-block form's");
   const int n = lane & 31, h = lane >> 5;
   const u32 *e8 = &sh.e8[buf][0][0][0];
   lds_cu32 *wi = lds_opaque(e8 + (n & 7) * kCopyDwords + 4 * (q0_tile + h) + (n >> 3));
@@ -585,10 +603,14 @@ __device__ __forceinline__ void mx_pass(const MxSharedCore &sh, int buf, int lan
   v4i a[16];
   if constexpr (AHEAD) {
     v4i fi = lds_frag(wi, 0), fq = lds_frag(wq, 0);
-    a[0] = ca[0];
+    if constexpr (RES == 0)
+      a[0] = ca[0];
     if constexpr (FOLD) {
       MxFoldRegs fold{lds_opaque(fold_pair + 32 * q0_tile + n), h && with_corr ? kGpsxFoldMask : 0u, 0u, 0u};
-      mx_pass_step<0, NT, SCALE_A, true>(wi, wq, ca, a, fi, fq, acc, scale_b, &fold);
+      if constexpr (RES > 0)
+        mx_pass_step<0, NT, SCALE_A, true, RES>(wi, wq, ca, chips->k, fi, fq, acc, scale_b, &fold);
+      else
+        mx_pass_step<0, NT, SCALE_A, true>(wi, wq, ca, a, fi, fq, acc, scale_b, &fold);
     } else {
       mx_pass_step<0, NT, SCALE_A>(wi, wq, ca, a, fi, fq, acc, scale_b);
     }

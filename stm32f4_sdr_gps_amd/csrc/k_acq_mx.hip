@@ -168,18 +168,20 @@ __device__ __forceinline__ void mx_anchor_step(lds_cu32 *wi, lds_cu32 *wq, const
     mx_anchor_step<S + 1, NT>(wi, wq, ca, a, fi, fq, acc, shift);
   }
 }
+// The chips it reads -- every kappa, each a step ahead of its first MFMA -- are the lane's for the whole cluster: they go into
+// `chips`, where the recurrence passes find those of kappa < kMxChipsResident (MxChipRegs).
 template <int NT>
-__device__ __forceinline__ void mx_anchor_pass(const MxSharedCore &sh, const u32 *anchor, int lane, int q0_tile, v16f (&acc)[2][NT])
+__device__ __forceinline__ void mx_anchor_pass(const MxSharedCore &sh, const u32 *anchor, int lane, int q0_tile, v16f (&acc)[2][NT],
+                                               MxChipRegs &chips)
 {
   const int n = lane & 31, h = lane >> 5;
   const u32 shift = (u32)(6 * n) & 31u;
   lds_cu32 *wi = lds_opaque(anchor + 6 * (q0_tile + h) + ((6 * n) >> 5));
   lds_cu32 *wq = lds_opaque(anchor + kAnchorDwords + 6 * (q0_tile + h) + ((6 * n) >> 5));
   const v4i *ca = &sh.chips_a[0][h][n];
-  v4i a[16];
   v8i fi = mx_anchor_frag(mx_anchor_raw(wi, 0), shift), fq = mx_anchor_frag(mx_anchor_raw(wq, 0), shift);
-  a[0] = ca[0];
-  mx_anchor_step<0, NT>(wi, wq, ca, a, fi, fq, acc, shift);
+  chips.k[0] = ca[0];
+  mx_anchor_step<0, NT>(wi, wq, ca, chips.k, fi, fq, acc, shift);
 }
 
 // ---- the two vectors of a DIRECT start at sample offset t0s, in one phase ---------------------------------------------------
@@ -969,7 +971,8 @@ __device__ __forceinline__ void mx_single(MxSingleShared &shs, const AcqParams &
       mxt_half_switch_build(sh, shs.hs, opaque(tid) & 255, 256);
       mxt_init_acc(sh.ones, opaque(lane), q0_tile, acc, prm.win_start, prm.win_stop, kGpsxAnchorPassBias);
     }
-    mx_anchor_pass(sh, &sh.e8[0][0][0][0], lane, q0_tile, acc);
+    MxChipRegs chips;              // (filled by the anchor pass, read by every pass after it)
+    mx_anchor_pass(sh, &sh.e8[0][0][0][0], lane, q0_tile, acc, chips);
     bool hot = false;              // (the epilogues' predictor: per wave, clear for its first one)
     if (!role)                     // half step 1 of role 0, under role 1's pass
       mxt_epilogue(part, lane, q0_tile, 0, acc, hot);
@@ -989,8 +992,8 @@ __device__ __forceinline__ void mx_single(MxSingleShared &shs, const AcqParams &
       //  the compiler schedules the kernel differently: 7728 instructions against 7732)
       const int p = (x >> 1) + 1;
       if (active && (x & 1) == 0) {
-        mx_pass<true, kMxTiles, kScaleA, true>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne, v4i{0, 0, 0, 0},
-                                               p >= 2 && p != 9, &fold.pair[p & 1][0][0]);
+        mx_pass<true, kMxTiles, kScaleA, true, kMxChipsResident>(sh, p & 1, lane, q0_tile, acc, p == 1 ? kScaleEight : kScaleOne,
+                                                                 v4i{0, 0, 0, 0}, p >= 2 && p != 9, &fold.pair[p & 1][0][0], &chips);
         if (p == 9)
           mxt_half_switch(sh, shs.hs, lane, q0_tile, acc, prm.win_start, prm.win_stop);
       }
